@@ -17,6 +17,11 @@ really has, test/helpers/helpers.js:147-149).
 under a launcher: every rank runs its own batches -- batch-level data parallelism, no data-path collective (DESIGN.md
 "Multi-GPU") -- and the value is all ranks' transactions over the max-over-ranks time ("scaling": "weak"); the same line carries
 BASELINE config 4, ONE batch sharded by transaction index with its single all_gather, as `shard_tx` (strong scaling).
+
+A plain run sets up, warms up, times `--steps` steps and prints the headline line (`value`, `ms_per_step`, ...). `--full` adds
+everything else the line used to carry: the parity checks against the builder, per-kernel times and rooflines, `value_e2e`,
+`value_node`, the export, deep-state, latency and occupancy figures, and the tx-sharded, withdraw, Poseidon and CPU-baseline lines.
+`--dump-outputs DIR` writes what the last timed step computed (hashGlobalInputs and a seeded witness sample per batch) as .npy files.
 """
 import argparse
 import ctypes
@@ -800,6 +805,31 @@ def doubled_sources(L, torch, src_ptr, n, pbytes):
     return pin2, dev
 
 
+DUMP_BLOCK = 64   # --dump-outputs: the witness sample is runs of this many consecutive elements
+
+
+def dump_outputs(path, ctx, n_inst):
+    """--dump-outputs: what the last timed step handed its caller, read from the context that ran it -- hashGlobalInputs of every
+    batch of the launch, and the same fixed sample of every batch's witness (runs of DUMP_BLOCK elements at offsets drawn from SEED:
+    identical from run to run for the same arguments). Field elements as eight little-endian 32-bit limbs in float64 (exact);
+    at most 48 MB in all."""
+    import random
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    n = ctx.witness_len()
+    blocks = max(1, min(64, (48 << 20) // (n_inst * DUMP_BLOCK * 64), n // DUMP_BLOCK))
+    starts = sorted(DUMP_BLOCK * b for b in random.Random(SEED).sample(range(n // DUMP_BLOCK), blocks))
+
+    def limbs(raw):
+        return np.frombuffer(raw, dtype="<u4").reshape(-1, 8).astype(np.float64)
+    hgi = ctx.lookup("main.hashGlobalInputs")
+    out = {"hash_global_inputs": np.stack([limbs(ctx.read_bytes(hgi, 1, b))[0] for b in range(n_inst)]),
+           "witness_sample": np.stack([np.concatenate([limbs(ctx.read_bytes(s, DUMP_BLOCK, b)) for s in starts]) for b in range(n_inst)]),
+           "witness_sample_index": np.concatenate([np.arange(s, s + DUMP_BLOCK) for s in starts]).astype(np.float64)}
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def respawn(args):
     """`python bench.py --gpus N` outside a launcher: start the N ranks (one process per GPU) and hand over."""
     s = socket.socket()
@@ -861,11 +891,21 @@ def main():
                          "calibrates the FETCH_SIZE / WRITE_SIZE counters of a rocprofv3 --pmc pass (tools/profile.sh)")
     ap.add_argument("--shard-timeout", type=int, default=240, help="N > 1: seconds the tx-sharded secondary line may take before it is given up")
     ap.add_argument("--shard-tx", action="store_true", help="only the tx-sharded line (BASELINE config 4) as the main line")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the parity checks against the builder's hashGlobalInputs, per-kernel times and the "
+                         "rooflines, value_e2e / value_node, export, deep state, latency and occupancy sweeps, the tx-sharded, withdraw, Poseidon "
+                         "and CPU-baseline lines (each still subject to its --no-* switch). Without it a run sets up, warms up, times the steps "
+                         "and prints the headline line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float64): hashGlobalInputs of "
+                         "every batch of that launch and a fixed, seeded sample of each batch's witness, field elements as eight 32-bit limbs")
     args = ap.parse_args()
+    if args.dump_outputs and (args.workload != "rollup-main" or args.shard_tx or args.steps < 1):
+        ap.error("--dump-outputs needs the rollup-main batch loop and --steps >= 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         respawn(args)
-    if (args.gpus <= 1 and "WORLD_SIZE" not in os.environ and not args.gpu_worker and not args.no_node and not args.no_e2e
+    if (args.full and args.gpus <= 1 and "WORLD_SIZE" not in os.environ and not args.gpu_worker and not args.no_node and not args.no_e2e
             and args.workload == "rollup-main" and not args.shard_tx):
         return with_node_host(args)
     D = Dist()
@@ -980,15 +1020,17 @@ def main():
     dsrc = None if args.no_rotate else dsrc_t.data_ptr()
     R = Rotation(ctxs, streams, Bp, n_distinct, pbytes, expected, pin2, dsrc)
     R.load()   # inputs resident in HBM before the timed region (round 0 in the witness layout, every batch in packed form)
-    # one checked pass per context: parity of every batch's public output with the builder's independently computed value
-    ctxs[0].set_profiling(True)
+    # one checked pass per context (--full: parity of every batch's public output with the builder's independently computed value)
+    if args.full:
+        ctxs[0].set_profiling(True)
     for k in range(inflight):
         R.enqueue(k)
         ctxs[k].check()
-    if not args.no_verify:
-        R.verify("first pass")
-    full_bytes = {name: by for name, _ms, by, _u in ctxs[0].profile()}   # a fresh buffer holds nothing: every signal was stored
-    ctxs[0].set_profiling(False)
+    if args.full:
+        if not args.no_verify:
+            R.verify("first pass")
+        full_bytes = {name: by for name, _ms, by, _u in ctxs[0].profile()}   # a fresh buffer holds nothing: every signal was stored
+        ctxs[0].set_profiling(False)
 
     def upload(k):
         for b in range(Bp):
@@ -1008,6 +1050,45 @@ def main():
             R.stage(k, dsrc)
     R.go(max(args.warmup, inflight if dsrc else 0), dsrc)
     dt = D.timed(lambda: R.go(args.steps, dsrc))
+    if args.dump_outputs and rank == 0:   # (before drain(): the witness buffers still hold the timed steps' batches)
+        dump_outputs(args.dump_outputs, ctxs[(args.steps - 1) % inflight], Bp)
+    witness_bytes = ctxs[0].witness_len() * 32
+
+    def headline():
+        return {
+            "metric": "rollup-main tx-witnesses/sec (nTx=%d, nLevels=%d)" % (nTx, lv),
+            "value": round(nTx * Bp * args.steps * world / dt, 1), "unit": "tx-witnesses/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": DTYPE, "data": "synthetic",
+            "config": {"workload": "rollup-main nTx=%d nLevels=%d maxL1Tx=%d maxFeeTx=%d" % (nTx, lv, m1, F), "batches_per_launch": Bp, "contexts_in_flight": inflight,
+                       "distinct_batches": n_distinct,
+                       "rotation": ("none (--no-rotate): every step re-evaluates the inputs its instances hold" if args.no_rotate else
+                                    "every step a new round: instance b of context k holds batch (k * %d + b + round) mod %d; the round's packed inputs (resident in HBM) are "
+                                    "scattered into the witness layout inside the timed region; hashGlobalInputs of the last round checked after it (--full)" % (Bp, n_distinct)),
+                       "constant_marks": os.environ.get("HZ_NO_ZMARK") is None, "state_accounts": n_acc, "l1_txs": nTx - n_l2, "l2_signed_txs": n_l2, "parallelism": "batch-dp%d" % world,
+                       "world_size": world, "backend": D.backend if world > 1 else None,
+                       "witness_bytes_per_batch": witness_bytes, "batch_build_s": round(t_build, 1),
+                       "batch_builder": ({"kind": "native (libhz_host.so hzb_batch_build_begin / _finish) + hz_poseidon_dag", "batches": len(all_seeds),
+                                          "pipelined": "the device evaluates batch i's Merkle hashes (a worker thread) while the host walks batch i + 1",
+                                          "hashes": builder_stats["jobs"], "dag_segments": builder_stats["segments"], "device_ms": round(builder_stats["device_ms"], 1),
+                                          "walk_and_sign_s": round(builder_stats["walk_s"], 2), "evaluator_s": round(builder_stats["eval_s"], 2),
+                                          "state_s": round(builder_stats["state_s"], 2), "batch_s": round(builder_stats["batch_s"], 2),
+                                          "phases_ms_per_batch": {k: round(1e3 * v / max(1, len(all_seeds)), 2) for k, v in builder_stats.get("phases_s", {}).items()},
+                                          "recipe": "native (hzb_batch_add_synthetic: the reference generator's recipe inside libhz_host.so)",
+                                          "ms_per_batch": round(1e3 * builder_stats["batch_s"] / max(1, len(all_seeds)), 1),
+                                          "sign_ms_per_batch": round(1e3 * builder_stats["sign_s"] / max(1, len(all_seeds)), 1),
+                                          "ms_per_batch_without_signing": round(1e3 * (builder_stats["batch_s"] - builder_stats["sign_s"]) / max(1, len(all_seeds)), 1),
+                                          "builder_tx_per_s": round(nTx * len(all_seeds) / builder_stats["batch_s"], 1),
+                                          "builder_tx_per_s_without_signing": round(nTx * len(all_seeds) / max(1e-9, builder_stats["batch_s"] - builder_stats["sign_s"]), 1),
+                                          "pipeline_ratio": round(nTx * len(all_seeds) / builder_stats["batch_s"] / (nTx * Bp * args.steps * world / dt), 4),
+                                          "note": "one host process; from the seed to the packed inputs in pinned memory (transactions, walk, signing, Merkle hashing as one "
+                                                  "DAG on the GPU, packing); signing is a wallet's work in production; pipeline_ratio = builder_tx_per_s / value"}
+                                         if builder_stats else {"kind": "python (circuits_amd/builder.py), host hashing, process pool", "batches": len(all_seeds)})},
+        }
+    if not args.full:   # the headline alone: no checks, no secondary figures
+        if rank == 0:
+            print(json.dumps(headline()))
+        return D.close()
     R.drain()
     if not args.no_verify:
         R.verify("after the timed region", instances=(0, Bp // 2, Bp - 1))
@@ -1060,7 +1141,6 @@ def main():
             e1.record()
         torch.cuda.synchronize()
         upload_ms = e0.elapsed_time(e1) / Bp
-    witness_bytes = ctxs[0].witness_len() * 32
     export = None
     if world == 1 and not args.no_export:
         try:
@@ -1270,35 +1350,9 @@ def main():
                              "source": "SQ_INSTS_VALU of %s (%s), x %.1f cycles per wave-instruction of this mix (profiles/r03_instbench.txt), "
                                        "/ (SIMDs x clock x the step time of THIS run)" % (vmeta.get("source_file", "?") if vmeta else "?", vmeta.get("command", "?") if vmeta else "?", VALU_CYCLES_PER_INST)}
         bound = "valu" if (frac_valu or 0) > frac_hbm else "hbm"
-        out = {
-            "metric": "rollup-main tx-witnesses/sec (nTx=%d, nLevels=%d)" % (nTx, lv),
-            "value": round(value, 1), "unit": "tx-witnesses/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": DTYPE, "data": "synthetic",
-            "config": {"workload": "rollup-main nTx=%d nLevels=%d maxL1Tx=%d maxFeeTx=%d" % (nTx, lv, m1, F), "batches_per_launch": Bp, "contexts_in_flight": inflight,
-                       "distinct_batches": n_distinct,
-                       "rotation": ("none (--no-rotate): every step re-evaluates the inputs its instances hold" if args.no_rotate else
-                                    "every step a new round: instance b of context k holds batch (k * %d + b + round) mod %d; the round's packed inputs (resident in HBM) are "
-                                    "scattered into the witness layout inside the timed region; hashGlobalInputs of the last round checked after it" % (Bp, n_distinct)),
-                       "constant_marks": os.environ.get("HZ_NO_ZMARK") is None, "state_accounts": n_acc, "l1_txs": nTx - n_l2, "l2_signed_txs": n_l2, "parallelism": "batch-dp%d" % world,
-                       "world_size": world, "backend": D.backend if world > 1 else None,
-                       "witness_bytes_per_batch": witness_bytes, "step_latency_ms": round(single_ms, 3), "batch_build_s": round(t_build, 1),
-                       "batch_builder": ({"kind": "native (libhz_host.so hzb_batch_build_begin / _finish) + hz_poseidon_dag", "batches": len(all_seeds),
-                                          "pipelined": "the device evaluates batch i's Merkle hashes (a worker thread) while the host walks batch i + 1",
-                                          "hashes": builder_stats["jobs"], "dag_segments": builder_stats["segments"], "device_ms": round(builder_stats["device_ms"], 1),
-                                          "walk_and_sign_s": round(builder_stats["walk_s"], 2), "evaluator_s": round(builder_stats["eval_s"], 2),
-                                          "state_s": round(builder_stats["state_s"], 2), "batch_s": round(builder_stats["batch_s"], 2),
-                                          "phases_ms_per_batch": {k: round(1e3 * v / max(1, len(all_seeds)), 2) for k, v in builder_stats.get("phases_s", {}).items()},
-                                          "recipe": "native (hzb_batch_add_synthetic: the reference generator's recipe inside libhz_host.so)",
-                                          "ms_per_batch": round(1e3 * builder_stats["batch_s"] / max(1, len(all_seeds)), 1),
-                                          "sign_ms_per_batch": round(1e3 * builder_stats["sign_s"] / max(1, len(all_seeds)), 1),
-                                          "ms_per_batch_without_signing": round(1e3 * (builder_stats["batch_s"] - builder_stats["sign_s"]) / max(1, len(all_seeds)), 1),
-                                          "builder_tx_per_s": round(nTx * len(all_seeds) / builder_stats["batch_s"], 1),
-                                          "builder_tx_per_s_without_signing": round(nTx * len(all_seeds) / max(1e-9, builder_stats["batch_s"] - builder_stats["sign_s"]), 1),
-                                          "pipeline_ratio": round(nTx * len(all_seeds) / builder_stats["batch_s"] / value, 4),
-                                          "note": "one host process; from the seed to the packed inputs in pinned memory (transactions, walk, signing, Merkle hashing as one "
-                                                  "DAG on the GPU, packing); signing is a wallet's work in production; pipeline_ratio = builder_tx_per_s / value"}
-                                         if builder_stats else {"kind": "python (circuits_amd/builder.py), host hashing, process pool", "batches": len(all_seeds)})},
+        out = headline()
+        out["config"]["step_latency_ms"] = round(single_ms, 3)
+        out.update({
             "roofline": {"bound": bound, "kernel": dk, "launch": dname, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBS, 5), "frac_hbm": round(frac_hbm, 5), "frac_valu": round(frac_valu, 5) if frac_valu else None,
                          "traffic": measured_traffic(dk, Bp)[0],
@@ -1322,7 +1376,7 @@ def main():
                            "frac": round(algorithmic_bytes_per_tx(lv, F) * value / world / 1e9 / HBM_PEAK_GBS, 5)},
             "kernels_ms": {k: round(v[0], 3) for k, v in acc.items()},
             "kernels_GBs": {k: round(v[1] / (v[0] * 1e-3) / 1e9, 1) for k, v in acc.items() if v[0] > 0},
-        }
+        })
         if roofline_valu is not None:
             out["roofline_valu"] = roofline_valu
         if single is not None:

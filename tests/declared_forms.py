@@ -1,20 +1,21 @@
-"""tests/golden/declared_forms.json.gz (the reference's own wiring and constraints, recorded by extract_declared_forms.py) as a checker:
+"""tests/golden/declared_forms/<main>.json.xz (the reference's own wiring and constraints, recorded by extract_declared_forms.py) as a checker:
 values for every signal name from a witness that holds only SOME of them, the constraint check, and the same system written as the
 files a circom compile would hand over (.sym + .r1cs, unreduced: every signal a variable of its own)."""
 import gzip
 import json
+import lzma
 import os
 import struct
 
 P = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_DATA = None
+_DATA = {}
 
 
 def load(key):
-    global _DATA
-    if _DATA is None:
-        _DATA = json.loads(gzip.open(os.path.join(_HERE, "golden", "declared_forms.json.gz")).read())
+    if key not in _DATA:
+        with lzma.open(os.path.join(_HERE, "golden", "declared_forms", key + ".json.xz")) as f:
+            _DATA[key] = json.loads(f.read())
     return _DATA[key]
 
 

@@ -2,7 +2,7 @@
 """Records, from the reference's own circuit sources, HOW every signal that is not a product or a hint is wired: a symbolic run of
 the templates under /root/reference/src (a small interpreter for the circom subset they use: templates, functions, var, for, if,
 signal / component arrays, <== ==> <-- --> ===) in which every signal is its own symbol, as in an unreduced compile. Output:
-tests/golden/declared_forms.json.gz -- per main template and shape
+tests/golden/declared_forms/<main>.json.xz -- per main template and shape (one file each: every one stays below 1 MiB)
 
     forms   {signal name: [constant, [[coefficient, signal name], ...]]}   (field elements as decimal strings, those above r / 2 as negative
             numbers) every `x <== linear expression` of the sources, one level at a time (the right-hand names are signals again: of the same template, inputs of a sub-component, outputs of one)
@@ -24,8 +24,8 @@ evaluated on the oracle's witness.
 
     python tests/golden/extract_declared_forms.py [/root/reference]        (run in the build container; the reference does not travel)
 """
-import gzip
 import json
+import lzma
 import os
 import re
 import sys
@@ -1535,7 +1535,7 @@ def load_defs(ref):
 
 
 def build(defs, tmpl, args, **models):
-    """the recorded system of `tmpl(args)` as `component main` (the object stored per main in declared_forms.json.gz)"""
+    """the recorded system of `tmpl(args)` as `component main` (the object stored per main in declared_forms/<main>.json.xz)"""
     r = Run(defs, **models)
     r.instantiate(tmpl, args, "main")
     # outputs of black boxes and everything else a form refers to without defining it
@@ -1556,10 +1556,15 @@ def main():
                              smt_model=key in ("fee-tx", "rollup-tx", "withdraw"), eddsa_model=key in ("rollup-tx", "ay-sign-2-ax"))
         print("%-28s %6d forms, %6d product / === constraints, %6d bases, %6d declared" % ("%s(%s)" % (tmpl, ",".join(map(str, args))), len(m["forms"]), len(m["quads"]),
                                                                                              len(m["bases"]), len(m["declared"])))
-    dst = os.path.join(os.path.dirname(os.path.abspath(__file__)), "declared_forms.json.gz")
-    with gzip.GzipFile(dst, "wb", mtime=0) as g:
-        g.write(json.dumps(out, sort_keys=True, separators=(",", ":")).encode())
-    print("-> %s (%d bytes)" % (dst, os.path.getsize(dst)))
+    # the COMPLETE RollupMain(3,16,2,1): every circomlib model on but Sha256's inside (tests/test_declared_signals.py test_complete_rollup_main*)
+    out["rollup-main-complete"] = build(defs, "RollupMain", [3, 16, 2, 1], pos_model=True, smt_model=True, eddsa_model=True, sha_model=False)
+    dst_dir = os.path.join(os.path.dirname(os.path.abspath(__file__)), "declared_forms")
+    os.makedirs(dst_dir, exist_ok=True)
+    for key, m in sorted(out.items()):
+        dst = os.path.join(dst_dir, key + ".json.xz")
+        with open(dst, "wb") as f:
+            f.write(lzma.compress(json.dumps(m, sort_keys=True, separators=(",", ":")).encode(), preset=9 | lzma.PRESET_EXTREME))
+        print("-> %s (%d bytes)" % (dst, os.path.getsize(dst)))
 
 
 if __name__ == "__main__":

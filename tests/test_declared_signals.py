@@ -1,6 +1,6 @@
 """The reference's own wiring and constraints against the witness.
 
-tests/golden/declared_forms.json.gz is a symbolic run of /root/reference/src/*.circom (tests/golden/extract_declared_forms.py): every
+tests/golden/declared_forms/*.json.xz is a symbolic run of the reference's src/*.circom (tests/golden/extract_declared_forms.py): every
 `x <== linear expression` as a form, every product and `===` line as A * B = C, every declared signal by name -- each signal a symbol
 of its own, as in the unreduced compile the reference's suites use (reference test/rollup-main.test.js:52 reduceConstraints:false).
 Here:
@@ -151,22 +151,13 @@ def test_oracle_rejects_whatever_violates_a_recorded_constraint(key, shape, gen)
     assert stat[(False, False)] >= 1 and stat[(True, True)] + stat["not bits"] >= 1, stat   # both kinds occur
 
 
-def test_complete_rollup_main_when_the_reference_is_at_hand():
-    """RollupMain with EVERY circomlib model on (Poseidon, SMTProcessor, EdDSAPoseidonVerifier, Bits2Point_Strict; Sha256 -- a million
-    signals -- only on request) is too large to commit as a fixture; where the reference's sources are present (the build
-    container) the system is recorded on the spot: the main-level wiring together with every component, 4 x 10^5 constraints, all
-    satisfied by the oracle's witness of a synthetic batch."""
-    ref = "/root/reference"
-    if not os.path.isdir(os.path.join(ref, "src")):
-        pytest.skip("the reference's sources are not here")
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("extract_declared_forms", os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "extract_declared_forms.py"))
-    X = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(X)
-    shape = (3, 16, 2, 1)   # (the bit string SHA-256 hashes must be whole bytes for hashlib: (2 nTx + maxFeeTx) * nLevels a multiple of 8)
-    # HZ_FULL_SYSTEM=1 turns the Sha256 model on as well (nothing opaque at all: 1.4 x 10^6 signals, 90 s; it passes -- the Withdraw
-    # fixture holds the same Sha256 model in every run)
-    m = X.build(X.load_defs(ref), "RollupMain", list(shape), pos_model=True, smt_model=True, eddsa_model=True, sha_model=os.environ.get("HZ_FULL_SYSTEM") == "1")
+def test_complete_rollup_main_from_the_recorded_system():
+    """RollupMain with EVERY circomlib model on (Poseidon, SMTProcessor, EdDSAPoseidonVerifier, Bits2Point_Strict; Sha256's inside
+    opaque), as extract_declared_forms.py records it (tests/golden/declared_forms/rollup-main-complete.json.xz): the main-level wiring
+    together with every component, 4 x 10^5 constraints, all satisfied by the oracle's witness of a synthetic batch."""
+    m = DF.load("rollup-main-complete")
+    shape = tuple(m["args"])   # (3, 16, 2, 1): the bit string SHA-256 hashes must be whole bytes for hashlib, (2 nTx + maxFeeTx) * nLevels a multiple of 8
+    assert shape == (3, 16, 2, 1)
     assert len(m["quads"]) > 100000 and len(m["forms"]) > 300000
     bb = B.synthetic_batch(*shape, n_accounts=5, exits=1, seed=3)
     o = OracleCtx("rollup-main", *shape)
@@ -326,9 +317,8 @@ def test_hip_complete_rollup_main(hz):
     full = os.path.exists(path)
     if not full:
         path = os.path.join(gen, "rollup_main_3_16_2_1.json.gz")
-    if not os.path.exists(path):
-        pytest.skip("tests/_generated/ was not built (the reference's sources were not present at build time)")
-    m = DF.load_file(path)
+    # without tests/_generated/ (build() records it only where the reference's sources are present): the committed system, Sha256 opaque
+    m = DF.load_file(path) if os.path.exists(path) else DF.load("rollup-main-complete")
     shape = tuple(m["args"])
     bb = B.synthetic_batch(*shape, n_accounts=5, exits=1, seed=3)
     inp = bb.get_input()

@@ -374,7 +374,7 @@ def test_bench_gpus8_eight_ranks_on_one_gpu(hz):
     env = dict(os.environ, HZ_BENCH_DEVICE="0", HZ_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--nTx", "40", "--nLevels", "16", "--maxL1Tx", "8", "--maxFeeTx", "4",
-           "--batches-per-launch", "2", "--inflight", "1", "--steps", "2", "--warmup", "1", "--cpu-sample", "0", "--build-workers", "1", "--no-e2e"]
+           "--batches-per-launch", "2", "--inflight", "1", "--steps", "2", "--warmup", "1", "--cpu-sample", "0", "--build-workers", "1", "--no-e2e", "--full"]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -413,7 +413,7 @@ def test_bench_gpus2_spawns_two_ranks_and_exchanges_real_records(hz):
     env = dict(os.environ, HZ_BENCH_DEVICE="0", HZ_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--nTx", "40", "--nLevels", "16", "--maxL1Tx", "8", "--maxFeeTx", "4",
-           "--batches-per-launch", "2", "--inflight", "1", "--steps", "2", "--warmup", "1", "--cpu-sample", "0", "--build-workers", "1"]
+           "--batches-per-launch", "2", "--inflight", "1", "--steps", "2", "--warmup", "1", "--cpu-sample", "0", "--build-workers", "1", "--full"]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -7,7 +7,7 @@ out=gpurun_out/ab_latency_$(echo $vs | tr ' ' '_').txt; : > $out
 for r in $(seq 1 $rounds); do
   for name in $vs base; do
     lib=$PWD/variants/libhz_$name.so; [ "$name" = "base" ] && lib=$PWD/circuits_amd/libhermez_witness.so
-    HZ_WITNESS_LIB=$lib timeout 900 python bench.py --steps 12 --warmup 3 --cpu-sample 0 --no-withdraw --no-e2e --no-poseidon --no-export --no-deep-state 2>/dev/null | grep '^{"metric"' | tail -1 | python -c "
+    HZ_WITNESS_LIB=$lib timeout 900 python bench.py --full --steps 12 --warmup 3 --cpu-sample 0 --no-withdraw --no-e2e --no-poseidon --no-export --no-deep-state 2>/dev/null | grep '^{"metric"' | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 s = d['single_batch_latency_ms']

@@ -2,7 +2,7 @@
 # plain (unpartitioned) contexts whose internal streams each own a hardware queue (HZ_DEDICATED_QUEUES=1: CU mask of every CU) against
 # the default (streams share the process's hardware queues)
 cd $GRAFT_REPO_ROOT
-B="python bench.py --cpu-sample 0 --no-withdraw --no-e2e --no-poseidon --no-export --no-node --no-deep-state --no-sweep --no-shard --no-verify --distinct-batches 4"
+B="python bench.py --full --cpu-sample 0 --no-withdraw --no-e2e --no-poseidon --no-export --no-node --no-deep-state --no-sweep --no-shard --no-verify --distinct-batches 4"
 for cfg in "32 2 6" "16 2 8" "8 2 10" "1 2 12"; do
   set -- $cfg
   for v in 0 1 1e 0 1; do

@@ -4,7 +4,7 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/fl_tl; rm -rf $OUT; mkdir -p $OUT; cd $R
 I=${1:-2}
-timeout 600 rocprofv3 --kernel-trace --output-format csv -d $OUT -o run -- python bench.py --steps 12 --warmup 3 --cpu-sample 0 --no-verify --no-poseidon --no-export --no-withdraw --no-e2e --no-deep-state --no-sweep --no-node --batches-per-launch 1 --inflight $I --latency-scheduling --distinct-batches 4 > $OUT/bench.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --output-format csv -d $OUT -o run -- python bench.py --full --steps 12 --warmup 3 --cpu-sample 0 --no-verify --no-poseidon --no-export --no-withdraw --no-e2e --no-deep-state --no-sweep --no-node --batches-per-launch 1 --inflight $I --latency-scheduling --distinct-batches 4 > $OUT/bench.log 2>&1
 tail -1 $OUT/bench.log | cut -c1-200
 f=$(find $OUT -name "*kernel_trace.csv" | head -1)
 python - "$f" > $R/gpurun_out/flagged_gantt.txt <<'PY'

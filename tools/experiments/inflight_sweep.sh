@@ -9,7 +9,7 @@ common="--steps 12 --warmup 3 --no-sweep --no-deep-state --no-node --no-export -
 for r in $(seq 1 ${1:-2}); do
   for cfg in "2 32" "3 21" "4 16"; do
     set -- $cfg
-    line=$(timeout 600 python bench.py --inflight $1 --batches-per-launch $2 $common 2>/dev/null | grep '^{"metric"' | tail -1)
+    line=$(timeout 600 python bench.py --full --inflight $1 --batches-per-launch $2 $common 2>/dev/null | grep '^{"metric"' | tail -1)
     python - "$1" "$2" <<PY >> $out
 import json, sys
 d = json.loads('''$line''' or '{}')

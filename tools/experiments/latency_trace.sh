@@ -3,7 +3,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/lat; rm -rf $OUT; mkdir -p $OUT
 cd $R
-timeout 600 rocprofv3 --kernel-trace --output-format csv -d $OUT -o run -- python bench.py --steps 3 --warmup 1 --cpu-sample 0 --no-verify --no-poseidon --no-withdraw --no-e2e --no-shard --distinct-batches 1 --inflight 1 --batches-per-launch 1 "$@" > $OUT/bench.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --output-format csv -d $OUT -o run -- python bench.py --full --steps 3 --warmup 1 --cpu-sample 0 --no-verify --no-poseidon --no-withdraw --no-e2e --no-shard --distinct-batches 1 --inflight 1 --batches-per-launch 1 "$@" > $OUT/bench.log 2>&1
 tail -1 $OUT/bench.log | cut -c1-200
 f=$(find $OUT -name "*kernel_trace.csv" | head -1)
 python - "$f" > $OUT/last_step.txt <<'PY'

@@ -2,7 +2,7 @@
 # HZ_LDS_PAD (unused dynamic LDS per wavefront: at most 160 KB / pad wavefronts per compute unit, whatever kernels they belong to) against
 # the CU partition of HZ_FLAG_LATENCY contexts, in the latency regime
 cd $GRAFT_REPO_ROOT   # (needs the hz_lds_pad() launch-site patch of this experiment: see profiles/r05_latency_regime.txt)
-B="python bench.py --cpu-sample 0 --no-withdraw --no-e2e --no-poseidon --no-export --no-node --no-deep-state --no-sweep --no-shard --no-verify --distinct-batches 4"
+B="python bench.py --full --cpu-sample 0 --no-withdraw --no-e2e --no-poseidon --no-export --no-node --no-deep-state --no-sweep --no-shard --no-verify --distinct-batches 4"
 for cfg in ${POINTS:-"1 1" "1 2" "1 4" "2 2" "2 4" "4 2" "4 4" "8 2"}; do
   set -- $cfg
   for v in 0 40960 20480 flag; do

@@ -1,7 +1,7 @@
 #!/bin/bash
 # headline step: default queues against GPU_MAX_HW_QUEUES=16 and / or a hardware queue of its own for the ladder stream (HZ_DEDICATED_QUEUES=1e)
 cd $GRAFT_REPO_ROOT
-B="python bench.py --steps 6 --warmup 2 --cpu-sample 0 --no-withdraw --no-e2e --no-poseidon --no-export --no-node --no-deep-state --no-sweep --no-shard --no-verify --distinct-batches 4"
+B="python bench.py --full --steps 6 --warmup 2 --cpu-sample 0 --no-withdraw --no-e2e --no-poseidon --no-export --no-node --no-deep-state --no-sweep --no-shard --no-verify --distinct-batches 4"
 for i in 1 2 3; do
 for v in base q16 ded both; do
   unset GPU_MAX_HW_QUEUES HZ_DEDICATED_QUEUES

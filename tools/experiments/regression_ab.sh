@@ -7,7 +7,7 @@ cd $GRAFT_REPO_ROOT
 OUT=$GRAFT_REPO_ROOT/gpurun_out/ab; mkdir -p $OUT
 LOG=$OUT/regression_ab.txt; : > $LOG
 STEPS=${STEPS:-20}
-want="--steps $STEPS --warmup 3 --cpu-sample 0 --no-node --no-e2e --no-withdraw --no-poseidon --no-sweep --no-deep-state --no-export"
+want="--full --steps $STEPS --warmup 3 --cpu-sample 0 --no-node --no-e2e --no-withdraw --no-poseidon --no-sweep --no-deep-state --no-export"
 line='import sys,json; d=json.loads(sys.stdin.read()); k=d["kernels_ms"]; print("%.0f tx/s  %.3f ms/step  smt %.2f front %.2f hash4 %.2f eddsa %.2f fix %.2f hi %.2f%s" % (d["value"], d["ms_per_step"], k.get("smt",0), k.get("front",0), k.get("hash4",0), k.get("eddsa",0), k.get("eddsa_fix",0), k.get("hash_inputs",0), (" fee_acc %.2f" % k["fee_acc"]) if "fee_acc" in k else ""))'
 run() {   # run <label> <dir> [env / extra args...]
   local label=$1 dir=$2; shift 2

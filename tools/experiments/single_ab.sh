@@ -3,7 +3,7 @@
 # (A build that piped the SHA-256 block expansion over the fee stream for partitioned contexts too measured 9.10-9.15 ms against 7.86-7.89:
 # not in the tree.)
 cd $GRAFT_REPO_ROOT
-B="python bench.py --cpu-sample 0 --no-withdraw --no-e2e --no-poseidon --no-export --no-node --no-deep-state --no-sweep --no-shard --distinct-batches 2 --batches-per-launch 1 --inflight 1 --latency-scheduling --solo --steps 40 --warmup 5"
+B="python bench.py --full --cpu-sample 0 --no-withdraw --no-e2e --no-poseidon --no-export --no-node --no-deep-state --no-sweep --no-shard --distinct-batches 2 --batches-per-launch 1 --inflight 1 --latency-scheduling --solo --steps 40 --warmup 5"
 for i in 1 2; do
 for v in base nosplit; do
   unset HZ_ED_NO_PRE_SPLIT

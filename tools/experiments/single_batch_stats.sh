@@ -3,10 +3,10 @@
 # usage (GPU box): bash tools/experiments/single_batch_stats.sh -> gpurun_out/single_batch_kernel_stats.csv
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/sb; rm -rf $OUT; mkdir -p $OUT; cd $R
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o run -- python bench.py --steps 16 --warmup 3 --cpu-sample 0 --no-verify --no-poseidon --no-export --no-withdraw --no-e2e --no-deep-state --no-sweep --no-node --batches-per-launch 1 --inflight 1 --latency-scheduling --distinct-batches 4 > $OUT/bench.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o run -- python bench.py --full --steps 16 --warmup 3 --cpu-sample 0 --no-verify --no-poseidon --no-export --no-withdraw --no-e2e --no-deep-state --no-sweep --no-node --batches-per-launch 1 --inflight 1 --latency-scheduling --distinct-batches 4 > $OUT/bench.log 2>&1
 tail -1 $OUT/bench.log | cut -c1-160
 f=$(find $OUT -name "*kernel_stats.csv" | head -1)
-{ echo "# rocprofv3 --kernel-trace --stats -- python bench.py --batches-per-launch 1 --inflight 1 --latency-scheduling --steps 16 ... (round 6, final kernels): ONE 2048-transaction batch alone on the device, HZ_FLAG_LATENCY"; python - "$f" <<'PY'
+{ echo "# rocprofv3 --kernel-trace --stats -- python bench.py --full --batches-per-launch 1 --inflight 1 --latency-scheduling --steps 16 ... (round 6, final kernels): ONE 2048-transaction batch alone on the device, HZ_FLAG_LATENCY"; python - "$f" <<'PY'
 import csv, sys
 rows = list(csv.DictReader(open(sys.argv[1])))
 print("name,calls,average_us,total_us,percentage")

@@ -7,7 +7,7 @@ OUT=$R/gpurun_out/diag; rm -rf $OUT; mkdir -p $OUT
 cd $R
 T=${PMC_TIMEOUT:-240}
 ( rocprofv3 -L || rocprofv3 --list-avail ) > $OUT/counters_list.txt 2>&1
-ARGS="--steps 2 --warmup 1 --cpu-sample 0 --no-e2e --no-withdraw --distinct-batches 4 ${DIAG_BENCH_ARGS}"
+ARGS="--full --steps 2 --warmup 1 --cpu-sample 0 --no-e2e --no-withdraw --distinct-batches 4 ${DIAG_BENCH_ARGS}"
 python - "$OUT" > $OUT/groups.txt <<'PY'
 import re, sys
 txt = open(sys.argv[1] + "/counters_list.txt").read()
@@ -50,7 +50,7 @@ for f in glob.glob(out + "/p*/**/*counter_collection.csv", recursive=True):
         acc[k][r["Counter_Name"]] += float(r["Counter_Value"]); n[k][r["Counter_Name"]].add(r["Dispatch_Id"])
 names = sorted({c for k in acc for c in acc[k]})
 with open(out + "/diag_summary.csv", "w") as o:
-    o.write("# per-dispatch means over the largest-grid dispatches of each kernel; separate --pmc passes of: python bench.py --steps 2 --warmup 1 --cpu-sample 0 --no-e2e --no-withdraw --distinct-batches 4\n")
+    o.write("# per-dispatch means over the largest-grid dispatches of each kernel; separate --pmc passes of: python bench.py --full --steps 2 --warmup 1 --cpu-sample 0 --no-e2e --no-withdraw --distinct-batches 4\n")
     o.write("kernel,grid," + ",".join(names) + "\n")
     for k in sorted(acc, key=lambda k: -acc[k].get("SQ_WAVE_CYCLES", 0) / max(1, len(n[k].get("SQ_WAVE_CYCLES", [1])))):
         o.write(k + "," + str(grid[k]) + "," + ",".join(("%.4g" % (acc[k][c] / len(n[k][c]))) if c in acc[k] else "" for c in names) + "\n")

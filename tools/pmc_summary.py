@@ -47,7 +47,7 @@ def valu():
             e["insts_valu_per_step"] += sum(x[1] for x in v) / steps
             e["insts_valu_largest_grid_mean"] = max(e["insts_valu_largest_grid_mean"], sum(big) / len(big))
             e["dispatches"] += len(v)
-        json.dump({"command": "python bench.py --steps 2 --warmup 1 --cpu-sample 0 --no-sweep " + " ".join(__import__("sys").argv[1:]), "steps_enqueued": steps,
+        json.dump({"command": "python bench.py --full --steps 2 --warmup 1 --cpu-sample 0 --no-sweep " + " ".join(__import__("sys").argv[1:]), "steps_enqueued": steps,
                    "insts_valu_per_step": sum(e["insts_valu_per_step"] for e in kernels.values()),
                    "note": "SQ_INSTS_VALU (wave-instructions), rocprofv3 --pmc pass of its own; per step = all dispatches / k_main_front dispatches; largest_grid_mean = mean over the dispatches with the most waves (the transaction launch)",
                    "kernels": kernels}, open(out + "/valu_counters.json", "w"), indent=1)

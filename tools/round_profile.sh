@@ -7,7 +7,7 @@ export HZ_ROUND=6
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/round; rm -rf $OUT; mkdir -p $OUT
 cd $R
-( time timeout 900 python bench.py ) > $OUT/bench_default.log 2>&1
+( time timeout 900 python bench.py --full ) > $OUT/bench_default.log 2>&1
 grep '^{' $OUT/bench_default.log | tail -1 > $OUT/bench_line.json
 bash tools/profile.sh > $OUT/profile.log 2>&1
 cp gpurun_out/prof/kernel_stats.csv gpurun_out/prof/hbm_counters.csv gpurun_out/prof/hbm_counters.json $OUT/ 2>/dev/null
