@@ -193,6 +193,14 @@ def oracle_failures(parts):
     return out
 
 
+def constraint_name(cid):
+    import ctypes
+    from oracle_binding import Oracle
+    f = Oracle().c.orc_constraint_name
+    f.restype = ctypes.c_char_p
+    return f(cid).decode()
+
+
 def set_all_inputs(g, cases):
     """every input of every instance of a product context, one call per signal (instance = -1)"""
     for name, _ in g.input_names():
@@ -224,16 +232,41 @@ def compare_instanced(g, parts, n, rows_per_chunk=512):
                     r0 + r, name, lo + k, int.from_bytes(a[r, lo + k].tobytes(), "little"), int.from_bytes(b[r, k].tobytes(), "little")))
 
 
-def check_failures(g, parts, run_error):
-    """the product's per-instance first-failure records == the oracle's, and the launch-wide report == the lowest of them"""
+def compare_replicated(g, o, n_gpu, n_dist, which, rows_per_chunk=256):
+    """Instanced template (one section, physical layout [signal][instance]): instance k of the GPU context holds the inputs of the
+    oracle's instance which[k] (o: one oracle context, or run_oracle_threads' slices); whole physical buffers, a few hundred signal
+    rows at a time."""
+    parts = o if isinstance(o, list) else [(o, 0, n_dist)]
+    wl = g.witness_len()
+    assert g.total() == wl * n_gpu and sum(cnt for _, _, cnt in parts) == n_dist
+    assert all(p.witness_len() == wl and p.total() == wl * cnt for p, _, cnt in parts) and [lo for _, lo, _ in parts] == [sum(c for _, _, c in parts[:i]) for i in range(len(parts))]
+    idx = np.asarray(which)
+    assert idx.shape == (n_gpu,)
+    for r0 in range(0, wl, rows_per_chunk):
+        rows = min(rows_per_chunk, wl - r0)
+        a = np.frombuffer(g.read_raw_bytes(r0 * n_gpu, rows * n_gpu), dtype=np.uint8).reshape(rows, n_gpu, 32)
+        b = np.concatenate([np.frombuffer(p.read_raw_bytes(r0 * cnt, rows * cnt), dtype=np.uint8).reshape(rows, cnt, 32) for p, _, cnt in parts], axis=1)[:, idx, :]
+        if not np.array_equal(a, b):
+            r, k = np.argwhere((a != b).any(axis=2))[0]
+            raise AssertionError("witness differs at signal row %d, instance %d (oracle instance %d): gpu=%d oracle=%d" % (
+                r0 + r, k, which[k], int.from_bytes(a[r, k].tobytes(), "little"), int.from_bytes(b[r, k].tobytes(), "little")))
+
+
+def check_failures(g, parts, run_error, which=None):
+    """the product's per-instance first-failure records == the oracle's, and the launch-wide report == the lowest of them. Returns the
+    number of rejected instances. which: instance k of the product holds the oracle's case which[k] (a replicated launch; every one of
+    the len(which) instances is compared); None: instance k is case k."""
     exp = oracle_failures(parts)
+    if which is not None:
+        assert len(which) == g.n_instances
+        exp = {k: exp[d] for k, d in enumerate(which) if d in exp}
     got = {f[0]: (f[1], f[2], f[4], f[5]) for f in g.failures()}
     if got != exp:
         for i in sorted(set(got) | set(exp)):
             if got.get(i) != exp.get(i):
-                from oracle_binding import Oracle
-                nm = lambda r: None if r is None else (r[0], Oracle().c.orc_constraint_name(r[1]).decode(), r[2], r[3])   # noqa: E731
-                raise AssertionError("first failure of instance %d: gpu %r, oracle %r" % (i, nm(got.get(i)), nm(exp.get(i))))
+                nm = lambda r: None if r is None else (r[0], constraint_name(r[1]), r[2], r[3])   # noqa: E731
+                raise AssertionError("first failure of instance %d%s: gpu %r, oracle %r" % (
+                    i, "" if which is None else " (case %d)" % which[i], nm(got.get(i)), nm(exp.get(i))))
     if exp:
         i0 = min(exp)
         assert run_error is not None, "the oracle rejects instance %d, the HIP path accepted the launch" % i0
@@ -347,3 +380,195 @@ def rollup_main_cases(n, shape, seed):
     bits = [(f, (i,)) for f in ("onChain", "newAccount", "isOld0_1", "isOld0_2", "newExit") for i in range(nTx)] + [("fromBjjCompressed", (i, rng.randrange(256))) for i in range(nTx)]
     keys = [(f, (i,)) for f in ("auxFromIdx", "auxToIdx", "oldKey1", "oldKey2") for i in range(nTx)]
     return [mutate(rng, valid[rng.randrange(len(valid))], sibling_fields=sib, key_fields=keys, key_bits=L, bit_fields=bits) for _ in range(n)]
+
+
+# ---- signature edges -------------------------------------------------------------------------------------------------------------
+# Baby Jubjub (circomlib babyjub.circom): a x^2 + y^2 = 1 + d x^2 y^2 over F_P, group order 8 l, B8 of order l.
+BJJ_A, BJJ_D = 168700, 168696
+
+
+def bjj_add(p, q):
+    (x1, y1), (x2, y2) = p, q
+    t = BJJ_D * x1 * x2 * y1 * y2 % P
+    return ((x1 * y2 + y1 * x2) * pow(1 + t, -1, P) % P, (y1 * y2 - BJJ_A * x1 * x2) * pow(1 - t, -1, P) % P)
+
+
+def bjj_mul(p, k):
+    r = (0, 1)
+    while k:
+        if k & 1:
+            r = bjj_add(r, p)
+        p = bjj_add(p, p)
+        k >>= 1
+    return r
+
+
+def bjj_on_curve(p):
+    x2, y2 = p[0] * p[0] % P, p[1] * p[1] % P
+    return (BJJ_A * x2 + y2 - 1 - BJJ_D * x2 * y2) % P == 0
+
+
+def fr_sqrt(n):
+    """a square root of n mod P (Tonelli-Shanks: P - 1 = 2^28 * odd), None for a non-residue"""
+    n %= P
+    if n == 0:
+        return 0
+    if pow(n, (P - 1) // 2, P) != 1:
+        return None
+    q, s = P - 1, 0
+    while q % 2 == 0:
+        q, s = q // 2, s + 1
+    z = 2
+    while pow(z, (P - 1) // 2, P) == 1:
+        z += 1
+    m, c, t, r = s, pow(z, q, P), pow(n, q, P), pow(n, (q + 1) // 2, P)
+    while t != 1:
+        i, t2 = 0, t
+        while t2 != 1:
+            t2, i = t2 * t2 % P, i + 1
+        b = pow(c, 1 << (m - i - 1), P)
+        m, c, t, r = i, b * b % P, t * b * b % P, r * b % P
+    return r
+
+
+def bjj_x_of(y):
+    """an x with (x, y) on the curve, None where there is none (an `ay` AySign2Ax finds no point for)"""
+    y2 = y * y % P
+    den = (BJJ_A - BJJ_D * y2) % P
+    return None if den == 0 else fr_sqrt((1 - y2) * pow(den, -1, P))
+
+
+_ORDER8 = []
+
+
+def bjj_order8_point():
+    """a point of order exactly 8: l times a curve point outside the subgroup, the first small y that gives one"""
+    from circuits_amd.builder import SUBORDER
+    y = 2
+    while not _ORDER8:
+        x = bjj_x_of(y)
+        if x is not None:
+            q = bjj_mul((x, y), SUBORDER)
+            if bjj_mul(q, 4) != (0, 1):
+                _ORDER8.append(q)
+        y += 1
+    return _ORDER8[0]
+
+
+def signature_edge_cases(valid_l2_input, other_l2_input=None, l1_create_input=None):
+    """[(label, input object)]: one valid signed L2 RollupTx input with its signature inputs moved to the edges of
+    EdDSAPoseidonVerifier (circomlib eddsaposeidon.circom) and AySign2Ax (reference src/lib/utils-bjj.circom) --
+
+      s          0, 1, l - 1, l, l + 1, s + k l while < 2^253 (the same point S * B8: only CompConstant rejects it, the malleability
+                 guard), 2^253 - 1, 2^253 and s + 2^253 (Num2Bits(253) fails), P - 1
+      (r8x, r8y) the neutral point (0, 1), the order-2 point (0, P - 1), (0, 0), the order-4 points (+-1 / sqrt(a), 0), -R8, the R8 of
+                 another transaction (other_l2_input; 2 * R8 without one), an off-curve point
+      ay1, sign1 ay1 = 0, 1, P - 1, 2 (no x: (1 - ay^2) / (a - d ay^2) is a non-residue), 5 (a point outside the subgroup), sign1 flipped, sign1 = 2, a key of order 8
+
+    -- each of them also with fromIdx = 0 and with onChain = 1 (verifier disabled: the witness is still written, the verifier reports
+    nothing), and, with l1_create_input (an account-creating L1 transaction), the key edges in its fromBjjCompressed bits. The first
+    entry is the unmodified input. Labels are unique."""
+    from circuits_amd.builder import SUBORDER as l
+    base = {k: _copy(v) for k, v in valid_l2_input.items()}
+    assert not base["onChain"] and base["fromIdx"], "needs a signed L2 transaction"
+    s, r8 = base["s"], (base["r8x"], base["r8y"])
+    inv_sqrt_a = pow(fr_sqrt(BJJ_A), -1, P)
+    o8 = bjj_order8_point()
+    edges = [("s=0", {"s": 0}), ("s=1", {"s": 1}), ("s=l-1", {"s": l - 1}), ("s=l", {"s": l}), ("s=l+1", {"s": l + 1})]
+    k = 1
+    while s + k * l < (1 << 253):
+        edges.append(("s=s+%dl" % k, {"s": s + k * l}))
+        k += 1
+    edges += [("s=2^253-1", {"s": (1 << 253) - 1}), ("s=2^253", {"s": 1 << 253}), ("s=s+2^253", {"s": s + (1 << 253)}), ("s=p-1", {"s": P - 1})]
+    other = (other_l2_input["r8x"], other_l2_input["r8y"]) if other_l2_input is not None else bjj_add(r8, r8)
+    assert other != r8
+    off = (r8[0] + 1) % P, r8[1]
+    assert not bjj_on_curve(off) and bjj_on_curve((inv_sqrt_a, 0)) and bjj_mul((inv_sqrt_a, 0), 2) == (0, P - 1)
+    for label, (x, y) in (("r8=(0,1)", (0, 1)), ("r8=(0,p-1)", (0, P - 1)), ("r8=(0,0)", (0, 0)), ("r8=(1/sqrt(a),0)", (inv_sqrt_a, 0)),
+                          ("r8=(-1/sqrt(a),0)", (P - inv_sqrt_a, 0)), ("r8=-R8", (P - r8[0], r8[1])), ("r8=other", other), ("r8=off-curve", off)):
+        edges.append((label, {"r8x": x, "r8y": y}))
+    assert bjj_x_of(2) is None and bjj_x_of(5) is not None
+    keys = [("ay1=0", {"ay1": 0}), ("ay1=1", {"ay1": 1}), ("ay1=p-1", {"ay1": P - 1}), ("ay1=2", {"ay1": 2}), ("ay1=5", {"ay1": 5}), ("sign1^1", {"sign1": 1 - base["sign1"]}),
+            ("sign1=2", {"sign1": 2}), ("key=order8", {"ay1": o8[1], "sign1": 1 if o8[0] > (P - 1) // 2 else 0})]
+    edges += keys
+    out = [("valid", base)]
+    for label, edit in edges:
+        for gate, extra in (("", {}), (" & fromIdx=0", {"fromIdx": 0}), (" & onChain=1", {"onChain": 1})):
+            d = {k: _copy(v) for k, v in base.items()}
+            d.update(edit)
+            d.update(extra)
+            out.append((label + gate, d))
+    if l1_create_input is not None:
+        c = l1_create_input
+        assert c["onChain"] and c["newAccount"], "needs an account-creating L1 transaction"
+        for label, edit in keys:
+            ay = edit.get("ay1", sum(b << i for i, b in enumerate(c["fromBjjCompressed"][:255])))
+            sign = edit.get("sign1", c["fromBjjCompressed"][255])
+            d = {k: _copy(v) for k, v in c.items()}
+            d["fromBjjCompressed"] = [(ay >> i) & 1 for i in range(255)] + [sign]
+            out.append(("create," + label.replace("ay1", "ay").replace("sign1", "sign"), d))
+    assert len({lb for lb, _ in out}) == len(out)
+    return out
+
+
+def rollup_main_signature_edges(main_input, labels=None):
+    """[(label, input object)]: a valid RollupMain input in which the first signed L2 transaction carries one of signature_edge_cases'
+    edges (those of s, r8x, r8y, ay1, sign1; `labels` selects some). RollupMain takes fromIdx from txCompressedData: the two gated
+    variants of every edge belong to the standalone RollupTx and are left out here."""
+    n_tx = len(main_input["onChain"])
+    tx = next(i for i in range(n_tx) if not main_input["onChain"][i] and (main_input["txCompressedData"][i] >> 48) & ((1 << 48) - 1))
+    fields = ("s", "r8x", "r8y", "ay1", "sign1")
+    single = {f: main_input[f][tx] for f in fields}
+    single.update(onChain=0, fromIdx=(main_input["txCompressedData"][tx] >> 48) & ((1 << 48) - 1))
+    other = next(({f: main_input[f][i] for f in fields} for i in range(tx + 1, n_tx) if not main_input["onChain"][i] and main_input["r8x"][i] and
+                  main_input["r8x"][i] != single["r8x"]), None)
+    out = []
+    for label, e in signature_edge_cases(single, other)[1:]:
+        if " & " in label or (labels is not None and label not in labels):
+            continue
+        d = {k: _copy(v) for k, v in main_input.items()}
+        for f in fields:
+            d[f][tx] = e[f]
+        out.append(("tx %d: %s" % (tx, label), d))
+    assert labels is None or len(out) == len(labels)
+    return out
+
+
+def signature_form_tx_cases(n_levels, max_fee, seed, n_bases, n_garbage):
+    """(labels, cases) of standalone RollupTx inputs for the launches that compare the forms of the signature kernels: the transactions
+    of a synthetic batch as they are, signature_edge_cases of `n_bases` of its signed L2 transactions (another transaction's R8 and an
+    account-creating L1 transaction beside each), `n_garbage` rollup_tx_cases"""
+    from circuits_amd import builder as B
+    bb = B.synthetic_batch(40, n_levels, 6, max_fee, n_accounts=12, exits=3, seed=seed)
+    ins = [bb.get_single_tx_input(i)[0] for i in range(bb.nTx)]
+    l2 = [i for i, d in enumerate(ins) if not d["onChain"] and d["fromIdx"]]
+    l1c = [i for i, d in enumerate(ins) if d["onChain"] and d["newAccount"]]
+    assert len(l2) >= n_bases and l1c
+    out = [("valid tx %d" % i, d) for i, d in enumerate(ins)]
+    for j, i in enumerate(l2[:n_bases]):
+        edges = signature_edge_cases(ins[i], ins[l2[(j + 1) % len(l2)]], ins[l1c[j]] if j < len(l1c) else None)
+        out += [("tx %d: %s" % (i, lb), d) for lb, d in edges[1:]]
+    out += [("garbage %d" % k, d) for k, d in enumerate(rollup_tx_cases(n_garbage, n_levels, max_fee, seed + 1))]
+    return [lb for lb, _ in out], [d for _, d in out]
+
+
+def place_replicas(g, cases, which):
+    """Inputs of a replicated launch: instance k of the product context gets cases[which[k]]. Every distinct case is uploaded once, to
+    the first instance that holds it, and copied on the device to the others (copy_instance_inputs)."""
+    home = {}
+    for k, d in enumerate(which):
+        if d not in home:
+            home[d] = k
+            g.set_inputs(cases[d], instance=k)
+    for k, d in enumerate(which):
+        if home[d] != k:
+            g.copy_instance_inputs(home[d], k)
+
+
+def lane_units(n, per_lane):
+    """The signatures of every lane of the throughput kernels (eddsa_kernels.hip k_eddsa_seg<G> / k_eddsa_fix<G> `mk_io`): lane li of
+    nl = ceil(n / G) lanes holds units li, li + nl, li + 2 nl, ... -- slot g of every lane is the g-th nl-long stretch of the launch,
+    the units of a lane are NOT consecutive -- and a slot past the end (ragged launch) repeats the lane's first unit. Returns
+    [[unit of slot 0, ...] per lane], padding slots left out."""
+    nl = (n + per_lane - 1) // per_lane
+    return [[li + g * nl for g in range(per_lane) if li + g * nl < n] for li in range(nl)]

@@ -35,9 +35,9 @@ def test_oracle_on_garbage_threads_equal_serial(template, shape, gen):
 
 
 # ---- GPU ---------------------------------------------------------------------------------------------------------------------------
-def _fuzz(hz, template, shape, gen, n_total, chunk, ctx_kw):
+def _fuzz(hz, template, shape, gen, n_total, chunk, ctx_kw, flags=0):
     from circuits_amd import ConstraintError
-    g = hz.ctx(template, n_instances=chunk, **ctx_kw)
+    g = hz.ctx(template, n_instances=chunk, flags=flags, **ctx_kw)
     rejected = 0
     cids = set()
     for c0 in range(0, n_total, chunk):
@@ -62,6 +62,8 @@ def _fuzz(hz, template, shape, gen, n_total, chunk, ctx_kw):
                         assert g.read_bytes(first, c, lo + k) == o.read_bytes(first, c, k), "instance %d, elements from %d" % (c0 + lo + k, first)
         else:
             FZ.compare_instanced(g, parts, chunk)
+    if flags:
+        g.close()   # flagged contexts one after the other: how many are alive decides the form of their chain kernel (ctx.hip enqueue_smt_chain)
     return rejected, cids
 
 
@@ -96,3 +98,45 @@ def test_hip_adversarial_fuzz_rollup_main(hz):
     rejected, cids = _fuzz(hz, "rollup-main", shape, lambda n, s: FZ.rollup_main_cases(n, shape, 11000 + s), 1024, 512,
                            dict(nTx=4, nLevels=16, maxL1Tx=2, maxFeeTx=2))
     assert 450 < rejected < 1024 and len(cids) >= 6
+
+
+def _with_signature_edges(cases, edges, seed):
+    """`cases` with the first len(edges) of them replaced by the signature edges, in a seeded order"""
+    import random
+    assert len(edges) < len(cases) // 2
+    out = list(edges) + cases[len(edges):]
+    random.Random(seed).shuffle(out)
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("flags", [2, 2 | 4], ids=["latency", "latency-solo"])
+@pytest.mark.parametrize("template,shape,n_total", [("rollup-tx", (0, 32, 0, 64), 2048), ("rollup-main", (4, 16, 2, 2), 512)], ids=["rollup-tx", "rollup-main"])
+def test_hip_adversarial_fuzz_flagged(hz, template, shape, n_total, flags):
+    """Garbage and the signature edges (fuzz_common.signature_edge_cases) through contexts created with HZ_FLAG_LATENCY (2) and
+    HZ_FLAG_LATENCY | HZ_FLAG_SOLO (6, include/hermez_witness.h), one launch each, the same requirements as the plain rows above.
+    Which kernels that selects (ctx.hip hz_ctx_create / enqueue_smt_chain; the profile names do not tell the forms apart, so the
+    rule is stated here): a RollupMain context with HZ_FLAG_LATENCY runs its chains on four CU-masked streams -- the split signature
+    kernels (k_eddsa_pre_a beside the front kernel, k_eddsa_pre_b, k_eddsa_ladder<1>, k_eddsa_fix<1>, k_eddsa_final), k_main_feeacc
+    behind the fixed-base kernel -- and, with at most 2 048 transactions per launch (512 x 4 here) and at most two such contexts alive
+    on the device, k_smt<true> (a quad of lanes per chain); HZ_FLAG_SOLO keeps k_smt<true> whatever else is alive. A RollupTx
+    context has no partition: HZ_FLAG_LATENCY alone leaves it the plain schedule, HZ_FLAG_SOLO gives it k_smt<true> (2 048
+    instances: the limit). Every context here is closed before the next one is made."""
+    nTx, L, m1, F = shape
+    if template == "rollup-tx":
+        def gen(n, s):
+            labels, cases = FZ.signature_form_tx_cases(L, F, 12000 + s, n_bases=4, n_garbage=n)
+            edges = [d for lb, d in zip(labels, cases) if lb.startswith("tx ")]
+            return _with_signature_edges(cases[len(cases) - n:], edges, 12500 + s)
+        kw = {"nLevels": L, "maxFeeTx": F}
+    else:
+        def gen(n, s):
+            from circuits_amd import builder as B
+            edges = []
+            for b in range(4):
+                inp = B.synthetic_batch(nTx, L, m1, F, n_accounts=4 + b, exits=1, seed=13500 + s + b).get_input()
+                edges += [d for _, d in FZ.rollup_main_signature_edges(inp)]
+            return _with_signature_edges(FZ.rollup_main_cases(n, shape, 13000 + s), edges, 13900 + s)
+        kw = dict(nTx=nTx, nLevels=L, maxL1Tx=m1, maxFeeTx=F)
+    rejected, cids = _fuzz(hz, template, shape, gen, n_total, n_total, kw, flags=flags)
+    assert n_total // 2 < rejected < n_total and len(cids) >= (4 if template == "rollup-tx" else 6)

@@ -2,6 +2,7 @@
 witness buffer (every stored signal), on seeded inputs built by the batch builder."""
 import pytest
 
+import fuzz_common as FZ
 from oracle_binding import OracleCtx
 
 P = 21888242871839275222246405745257275088548364400416034343698204186575808495617
@@ -87,24 +88,6 @@ def test_rollup_tx_config2_bit_exact(hz, batch):
         assert g.read(g.lookup("main.accFeeOut[0]"), 4, i) == exp["accFeeOut"]
 
 
-
-def _compare_replicated(g, o, n_gpu, n_dist, which, rows_per_chunk=256):
-    """Instanced template (one section, physical layout [signal][instance]): instance k of the GPU context holds the inputs of the
-    oracle's instance which[k]; whole physical buffers, a few hundred signal rows at a time."""
-    import numpy as np
-    wl = g.witness_len()
-    assert wl == o.witness_len() and g.total() == wl * n_gpu and o.total() == wl * n_dist
-    idx = np.asarray(which)
-    for r0 in range(0, wl, rows_per_chunk):
-        rows = min(rows_per_chunk, wl - r0)
-        a = np.frombuffer(g.read_raw_bytes(r0 * n_gpu, rows * n_gpu), dtype=np.uint8).reshape(rows, n_gpu, 32)
-        b = np.frombuffer(o.read_raw_bytes(r0 * n_dist, rows * n_dist), dtype=np.uint8).reshape(rows, n_dist, 32)[:, idx, :]
-        if not np.array_equal(a, b):
-            r, k = np.argwhere((a != b).any(axis=2))[0]
-            raise AssertionError("witness differs at signal row %d, instance %d (oracle instance %d): gpu=%d oracle=%d" % (
-                r0 + r, k, which[k], int.from_bytes(a[r, k].tobytes(), "little"), int.from_bytes(b[r, k].tobytes(), "little")))
-
-
 @pytest.mark.parametrize("L,F,N", [(16, 4, 16384 + 67)])   # (32, 64) ran here too: same kernels and forms, 29 s of a ten-minute suite; that shape
 # runs the throughput forms whole in test_headline_launch_whole_buffer
 def test_throughput_signature_kernels_bit_exact(hz, L, F, N):
@@ -128,7 +111,7 @@ def test_throughput_signature_kernels_bit_exact(hz, L, F, N):
         g.copy_instance_inputs(which[k], k)
     g.run()
     assert o.run() is None
-    _compare_replicated(g, o, N, D, which)
+    FZ.compare_replicated(g, o, N, D, which)
     # a bad signature in the ragged last wavefront is reported for exactly that instance, by the verifier's own constraint
     from circuits_amd import ConstraintError
     i_l2 = next(i for i in range(D) if not bb.get_single_tx_input(i)[0]["onChain"] and bb.get_single_tx_input(i)[0]["fromIdx"])
@@ -138,6 +121,29 @@ def test_throughput_signature_kernels_bit_exact(hz, L, F, N):
     with pytest.raises(ConstraintError) as e:
         g.run()
     assert e.value.instance == N - 2 and "sigVerifier" in e.value.name
+    # s + l (l: the subgroup order) is the same point S * B8 -- both equality checks pass, CompConstant alone rejects it (the
+    # malleability guard): in the last instance AND in slot 0 of a lane whose three other signatures are valid (lane li of
+    # nl = ceil(N / 4) holds instances li, li + nl, li + 2 nl, li + 3 nl: k_eddsa_seg). Reported for exactly these instances, by that
+    # constraint; the whole buffer against the oracle's again.
+    li = 1000
+    mall = dict(bb.get_single_tx_input(i_l2)[0])
+    mall["s"] = mall["s"] + B.SUBORDER
+    assert mall["s"] < (1 << 253) and li + 3 * ((N + 3) // 4) < N - 2
+    o2 = OracleCtx("rollup-tx", nLevels=L, maxFeeTx=F, n_instances=2)
+    o2.set_inputs(bad, instance=0)
+    o2.set_inputs(mall, instance=1)
+    r2 = o2.run()
+    assert r2 is not None and r2[0] == 0
+    for k in (N - 1, li):
+        g.set_inputs(mall, instance=k)
+        which[k] = D + 1
+    which[N - 2] = D
+    with pytest.raises(ConstraintError) as e:
+        g.run()
+    assert e.value.instance == li and e.value.name == "rollupTx.sigVerifier: compConstant.out*enabled === 0"
+    assert [(f[0], f[3]) for f in g.failures()] == [(li, e.value.name), (N - 2, r2[3]), (N - 1, e.value.name)]
+    assert FZ.check_failures(g, [(o, 0, D), (o2, D, 2)], e.value, which=which) == 3
+    FZ.compare_replicated(g, [(o, 0, D), (o2, D, 2)], N, D + 2, which)
 
 
 def test_throughput_rollup_main_many_batches(hz):
