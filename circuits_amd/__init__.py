@@ -11,6 +11,7 @@ from .capi import (  # noqa: F401
     ConstraintError,
     Lib,
     Ctx,
+    State,
     lib,
     lib_path,
     fr_to_bytes,

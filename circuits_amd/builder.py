@@ -265,6 +265,30 @@ class DenseState:
             levels[d] = np.frombuffer(hash_rows(3, n, rows.tobytes()), dtype=np.uint8).reshape(n, 32)
         return DenseState(k, first_idx, seed, n_keys, key_idx, mant, expo, levels, value)
 
+    def leaf_fields(self):
+        """the four leaf fields of every account as [N, 32] arrays (e0, balance, ay, ethAddr): what State.load takes"""
+        import numpy as np
+
+        def col(vals):
+            return np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in vals), dtype=np.uint8).reshape(-1, 32)
+        keys = self.keys()
+        ki = np.asarray(self.key_idx)
+        bal = col([int(m) * 10 ** int(e) for m, e in zip(np.asarray(self.mant).tolist(), np.asarray(self.expo).tolist())])
+        return col([1 + (a.sign << 72) for a in keys])[ki], bal, col([a.ay for a in keys])[ki], col([a.eth_addr for a in keys])[ki]
+
+    def to_device(self, lib, device=0):
+        """this state as a capi.State: the tree rebuilt on the device from the leaf fields"""
+        st = lib.state(self.k, first_idx=self.first_idx, device=device)
+        st.load(*self.leaf_fields())
+        return st
+
+    @staticmethod
+    def from_device(state, like):
+        """the consolidated arrays of a capi.State as a DenseState (for hzb_db_set_base, or save). `like`: the DenseState the device
+        state was made from; its account recipe (keys, balances) is carried over as it is -- the device holds hashes, not fields."""
+        levels, value = state.download()
+        return DenseState(state.k, state.first_idx, like.seed, like.n_keys, like.key_idx, like.mant, like.expo, levels, value)
+
     def save(self, path):
         import numpy as np
         arrs = {"meta": np.array([self.k, self.first_idx, self.seed, self.n_keys], dtype=np.int64), "key_idx": self.key_idx, "mant": self.mant,

@@ -67,6 +67,7 @@ EXPORTS = [
     "hz_symmap_from_index", "hz_component_major_index", "hz_symmap_upload", "hz_witness_export_dev", "hz_witness_export_range_dev", "hz_witness_export_host", "hz_symmap_dev_index", "hz_witness_derive_dev",
     "hz_symbol_count", "hz_symbol_get", "hz_symbol_lookup", "hz_constraint_name", "hz_poseidon_batch",
     "hz_poseidon_batch_dev", "hz_shard_range", "hz_set_inputs_json", "hz_witness_write_json", "hz_witness_write_wtns", "hz_symbols_write_sym", "hz_fr_ops", "hz_poseidon_dag",
+    "hz_state_create", "hz_state_destroy", "hz_state_load", "hz_state_root", "hz_state_apply", "hz_state_proofs", "hz_state_download", "hz_state_device_ms",
 ]
 
 
@@ -178,6 +179,17 @@ class Lib:
         c.hz_ctx_set_profiling.argtypes = [vp, ctypes.c_int32]
         c.hz_profile_count.argtypes = [vp]
         c.hz_profile_get.argtypes = [vp, ctypes.c_int32, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(u64), ctypes.POINTER(u64)]
+        sz = ctypes.c_size_t
+        c.hz_state_create.argtypes = [ctypes.c_int32, ctypes.c_int32, u64, ctypes.POINTER(vp)]
+        c.hz_state_destroy.argtypes = [vp]
+        c.hz_state_destroy.restype = None
+        c.hz_state_load.argtypes = [vp, vp, vp, vp, vp]
+        c.hz_state_root.argtypes = [vp, vp]
+        c.hz_state_apply.argtypes = [vp, sz, vp, vp, sz, vp, vp, vp, vp]
+        c.hz_state_proofs.argtypes = [vp, sz, vp, sz, vp, vp]
+        c.hz_state_download.argtypes = [vp, ctypes.POINTER(vp), vp]
+        c.hz_state_device_ms.argtypes = [vp]
+        c.hz_state_device_ms.restype = ctypes.c_double
 
     def _check(self, st):
         if st != 0:
@@ -238,6 +250,9 @@ class Lib:
 
     def ctx(self, template, **kw):
         return Ctx(self, template, **kw)
+
+    def state(self, k, first_idx=256, device=0):
+        return State(self, k, first_idx=first_idx, device=device)
 
     def host_alloc(self, nbytes):
         """pinned host memory for hz_inputs_upload (address as int); free with host_free"""
@@ -540,6 +555,83 @@ class Ctx:
         s = hz_symbol()
         self.L._check(self.L.c.hz_symbol_get(self.h, i, ctypes.byref(s)))
         return s.name.decode(), s.index
+
+
+class State:
+    """hz_state: the account tree of N = 2^k consecutive accounts resident on the device (builder.DenseState's geometry). Field elements
+    cross as numpy uint8 arrays of 32-byte little-endian canonical integers."""
+
+    def __init__(self, L, k, first_idx=256, device=0):
+        self.L = L
+        self.h = ctypes.c_void_p()
+        L._check(L.c.hz_state_create(device, k, first_idx, ctypes.byref(self.h)))
+        self.k, self.N, self.first_idx = k, 1 << k, first_idx
+
+    def close(self):
+        if self.h:
+            self.L.c.hz_state_destroy(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _fr(a, shape):
+        import numpy as np
+        a = np.ascontiguousarray(a, dtype=np.uint8)
+        if a.shape != shape:
+            raise ValueError("expected an array of shape %s, got %s" % (shape, a.shape))
+        return a
+
+    def load(self, e0, balance, ay, eth_addr):
+        """the four leaf fields as [N, 32] arrays indexed by account idx - first_idx; builds the whole tree on the device"""
+        cols = [self._fr(a, (self.N, 32)) for a in (e0, balance, ay, eth_addr)]
+        self.L._check(self.L.c.hz_state_load(self.h, *[a.ctypes.data for a in cols]))
+
+    def root(self):
+        out = (ctypes.c_uint8 * 32)()
+        self.L._check(self.L.c.hz_state_root(self.h, out))
+        return int.from_bytes(bytes(out), "little")
+
+    def apply(self, idx, fields, n_sib=None):
+        """m ordered updates of existing accounts: idx [m] integers, fields [m, 4, 32] (e0, balance, ay, ethAddr). Returns a dictionary of
+        numpy arrays: siblings [m, n_sib, 32] (root side first, zero beyond depth k), old_value / old_root / new_root [m, 32]."""
+        import numpy as np
+        n_sib = self.k if n_sib is None else n_sib
+        idx = np.ascontiguousarray(idx, dtype=np.uint64)
+        m = idx.size
+        fields = self._fr(fields, (m, 4, 32))
+        out = {"siblings": np.zeros((m, max(n_sib, 0), 32), dtype=np.uint8), "old_value": np.zeros((m, 32), dtype=np.uint8),
+               "old_root": np.zeros((m, 32), dtype=np.uint8), "new_root": np.zeros((m, 32), dtype=np.uint8)}
+        self.L._check(self.L.c.hz_state_apply(self.h, m, idx.ctypes.data, fields.ctypes.data, n_sib, out["siblings"].ctypes.data,
+                                              out["old_value"].ctypes.data, out["old_root"].ctypes.data, out["new_root"].ctypes.data))
+        return out
+
+    def proofs(self, idx, n_sib=None):
+        """membership proofs against the current root -> (siblings [n, n_sib, 32], state hashes [n, 32])"""
+        import numpy as np
+        n_sib = self.k if n_sib is None else n_sib
+        idx = np.ascontiguousarray(idx, dtype=np.uint64)
+        sib = np.zeros((idx.size, max(n_sib, 0), 32), dtype=np.uint8)
+        val = np.zeros((idx.size, 32), dtype=np.uint8)
+        self.L._check(self.L.c.hz_state_proofs(self.h, idx.size, idx.ctypes.data, n_sib, sib.ctypes.data, val.ctypes.data))
+        return sib, val
+
+    def download(self):
+        """(levels, value) in DenseState's layout: levels[d] is [2^d, 32], value [N, 32]"""
+        import numpy as np
+        levels = [np.zeros((1 << d, 32), dtype=np.uint8) for d in range(self.k + 1)]
+        value = np.zeros((self.N, 32), dtype=np.uint8)
+        ptrs = (ctypes.c_void_p * (self.k + 1))(*[a.ctypes.data for a in levels])
+        self.L._check(self.L.c.hz_state_download(self.h, ptrs, value.ctypes.data))
+        return levels, value
+
+    def device_ms(self):
+        """device time of the last load / apply"""
+        return self.L.c.hz_state_device_ms(self.h)
 
 
 class SymMap:

@@ -58,4 +58,24 @@ __device__ __forceinline__ Fr poseidon3_quad(const Fr& in0, const Fr& in1, const
     return quad_bcast<0x00>(st);
 }
 
+// The same walk for a consumer that wants the digest alone (the device-resident account tree, state.hip): no witness, so the S-box
+// stays in Montgomery form -- three products, three reductions -- and every column of the mix takes M1.
+__device__ __forceinline__ Fr poseidon3_quad_digest(const Fr& in0, const Fr& in1, const Pos3Dense& K, uint32_t lane_in_quad) {
+    const uint32_t j = lane_in_quad < 3 ? lane_in_quad : 0u;
+    Fr st = j == 0 ? fr_zero() : j == 1 ? in0 : in1;
+    const Fr row[3] = {K.M1[j * 3], K.M1[j * 3 + 1], K.M1[j * 3 + 2]};
+#pragma unroll 1
+    for (int r = 0; r < 65; r++) {
+        st = fr_add(st, K.C[r * 3 + j]);
+        if (r < 4 || r >= 61 || j == 0) {
+            const Fr x2 = fr_sqr(st);
+            const Fr x4 = fr_sqr(x2);
+            st = fr_mul(x4, st);
+        }
+        const Fr v[3] = {quad_bcast<0x00>(st), quad_bcast<0x55>(st), quad_bcast<0xAA>(st)};
+        st = fr_dot<3>(row, v);
+    }
+    return quad_bcast<0x00>(st);
+}
+
 }  // namespace hz

@@ -314,6 +314,42 @@ const char* hz_constraint_name(int32_t constraint_id);
 hz_status hz_poseidon_dag(int32_t device, uint8_t* vals, uint64_t n_vals, const uint32_t* job_in, const uint32_t* job_out, uint64_t n_jobs,
                           const uint32_t* seg_t, const uint64_t* seg_first, const uint64_t* seg_count, uint32_t n_segs, double* device_ms);
 
+/* Device-resident account tree: the pre-populated state of a rollup kept, updated and proven in HBM (the role RollupDB's state tree
+ * plays behind @hermeznetwork/commonjs BatchBuilder, reference test/helpers/helpers.js:46,148; leaf = src/lib/hash-state.circom:14-40).
+ * An hz_state is a perfect binary tree of depth k over the N = 2^k consecutive accounts first_idx .. first_idx + N - 1, the geometry of
+ * circuits_amd/builder.py DenseState: node (d, p) covers the keys = p (mod 2^d), its children are (d + 1, p) and (d + 1, p + 2^d),
+ * leaves sit at depth k, key bits LSB first as in circomlib. The k + 1 level arrays and the N state hashes stay on the device.
+ *   hz_state_create / _destroy   4 <= k <= 24; a failed allocation is HZ_ERR_HIP with the runtime's text in hz_last_error
+ *   hz_state_load       builds the whole tree on the device from four host arrays of [N][32] leaf fields (e0 = tokenID + nonce * 2^32 +
+ *                       sign * 2^72, balance, ay, ethAddr), indexed by account j = idx - first_idx: state hash Poseidon(5), leaf hash
+ *                       Poseidon(4) of (idx, state hash, 1), k levels of Poseidon(3): one upload, k + 2 launches, no level returns to the host
+ *   hz_state_root       the current root
+ *   hz_state_apply      m ORDERED updates of EXISTING accounts (m <= 65536; idx[m], fields[m][4][32] as above), sequential semantics: update j
+ *                       sees the tree as updates 0 .. j - 1 left it; an account may appear any number of times. Outputs in host memory,
+ *                       each may be NULL: siblings_out [m][n_sib][32] (root side first, zero beyond depth k; n_sib >= k, the circuits
+ *                       want nLevels + 1), old_value_out [m][32] (the leaf's state hash before update j), old_root_out / new_root_out
+ *                       [m][32] (the root before / after update j): with oldKey = newKey = idx and fnc = (0, 1) the inputs of
+ *                       circomlib's SMTProcessor. The tree is updated in place; the next call sees the consolidated state. An idx outside
+ *                       the state is HZ_ERR_ARG and leaves the tree untouched. The dependent work is k + 2 launches whatever m is (node
+ *                       versions, DESIGN.md "Device-resident account tree").
+ *   hz_state_proofs     membership proofs against the current root (SMTVerifier's inputs): siblings_out [n][n_sib][32], value_out
+ *                       [n][32] state hashes; a gather on the device
+ *   hz_state_download   the arrays in DenseState's layout: levels_out[d] receives the 2^d digests of level d (d = 0 .. k; a NULL entry is
+ *                       skipped), value_out the N state hashes -- what hzb_db_set_base (hz_host.h) takes as a base
+ *   hz_state_device_ms  device time of the last load / apply (first kernel to write-back, HIP events)
+ * OUT OF SCOPE: inserts and new accounts (a deposit that creates a leaf changes the tree's shape), the exit tree, transaction semantics
+ * (balances, nonces, fees: the batch builder's), more than one device per state. A state is used by one thread at a time. */
+typedef struct hz_state hz_state;
+hz_status hz_state_create(int32_t device, int32_t k, uint64_t first_idx, hz_state** out);
+void hz_state_destroy(hz_state* st);
+hz_status hz_state_load(hz_state* st, const uint8_t* e0, const uint8_t* balance, const uint8_t* ay, const uint8_t* eth_addr);
+hz_status hz_state_root(hz_state* st, uint8_t* out32);
+hz_status hz_state_apply(hz_state* st, size_t m, const uint64_t* idx, const uint8_t* fields, size_t n_sib, uint8_t* siblings_out,
+                         uint8_t* old_value_out, uint8_t* old_root_out, uint8_t* new_root_out);
+hz_status hz_state_proofs(hz_state* st, size_t n, const uint64_t* idx, size_t n_sib, uint8_t* siblings_out, uint8_t* value_out);
+hz_status hz_state_download(hz_state* st, uint8_t* const* levels_out, uint8_t* value_out);
+double hz_state_device_ms(const hz_state* st);
+
 /* Poseidon batch: n independent permutations of width t = n_inputs + 1 (2..7). ----------------
  * `in`  : [n][t-1] canonical elements; `out`: [n] digests (state[0] after the last round).
  * If `sbox_witness` is non-NULL it receives the S-box signals (in2,in4,out per S-box, the
