@@ -487,9 +487,13 @@ def sha256_bits(bits):
     return b"".join(x.to_bytes(4, "big") for x in h)
 
 
+def leaf_fields(st):
+    """the four elements a leaf's state hash is taken of: (e0, balance, ay, ethAddr)"""
+    return [st["tokenID"] + (st["nonce"] << 32) + (st["sign"] << 72), st["balance"], st["ay"], st["ethAddr"]]
+
+
 def hash_state(st, hasher=None):
-    e0 = st["tokenID"] + (st["nonce"] << 32) + (st["sign"] << 72)
-    return (hasher or host()).poseidon([e0, st["balance"], st["ay"], st["ethAddr"]])
+    return (hasher or host()).poseidon(leaf_fields(st))
 
 
 def build_tx_compressed_data(tx, chain_id):
@@ -927,24 +931,58 @@ def withdraw_input(batch, idx, n_levels):
     return inp, int.from_bytes(hashlib.sha256(by).digest(), "big") % P
 
 
+class DeviceSMT:
+    """The read side of SMT (root, find) over a capi.SparseTree: what withdraw_input() needs of an exit tree that lives on the device."""
+
+    def __init__(self, tree):
+        self.tree = tree
+
+    @property
+    def root(self):
+        return self.tree.root()
+
+    def find(self, key):
+        p = self.tree.proofs([key])
+        sib = [int.from_bytes(r.tobytes(), "little") for r in p["siblings"][0]]
+        while sib and sib[-1] == 0:
+            sib.pop()
+        if p["found"][0]:
+            return {"found": True, "siblings": sib, "foundValue": int.from_bytes(p["value"][0].tobytes(), "little"), "isOld0": False}
+        return {"found": False, "siblings": sib, "notFoundKey": int(p["not_found_key"][0]),
+                "notFoundValue": int.from_bytes(p["not_found_value"][0].tobytes(), "little"), "isOld0": bool(p["is_old0"][0])}
+
+
 class ExitTreeFixture:
     """An exit tree built directly (what a batch of `n_leaves` exits leaves behind; reference test/withdraw.test.js:39-157 reaches it
-    through four exit transactions): exit_tree / exit_leaves as withdraw_input() reads them. device=N hashes the tree on GPU N."""
+    through four exit transactions): exit_tree / exit_leaves as withdraw_input() reads them. device=N hashes the tree on GPU N.
+    sparse_tree: a capi.SparseTree -- the tree is built ON the device instead (reset, then the leaves as ordered inserts of one
+    hz_smt_apply per 65536) and stays there; exit_tree is then a DeviceSMT over it. The tree names its own device and hashes there, so
+    device / dag_evaluator (the deferred-hash path of the host tree) cannot be given with it."""
 
-    def __init__(self, n_leaves, seed=0x57495448, first_idx=256, n_keys=8, device=None, dag_evaluator=None):
+    def __init__(self, n_leaves, seed=0x57495448, first_idx=256, n_keys=8, device=None, dag_evaluator=None, sparse_tree=None):
         import random
+        import numpy as np
+        if sparse_tree is not None and (device is not None or dag_evaluator is not None):
+            raise ValueError("ExitTreeFixture: sparse_tree= builds the tree on the SparseTree's own device; device= / dag_evaluator= do not apply")
         rng = random.Random(seed)
         lazy = device is not None or dag_evaluator is not None
         hasher = DagHasher(dag_evaluator or _device_dag_evaluator(device)) if lazy else host()
         keys = [Account(seed * 1000 + i) for i in range(n_keys)]
-        self.exit_tree, self.exit_leaves = SMT(hasher), {}
+        self.exit_tree, self.exit_leaves = SMT(hasher) if sparse_tree is None else DeviceSMT(sparse_tree), {}
         for i in range(n_leaves):
             a = keys[rng.randrange(n_keys)]
             st = {"tokenID": rng.randrange(1, 1 << 32), "nonce": 0, "sign": a.sign, "balance": rng.randrange(1, 1 << 192), "ay": a.ay, "ethAddr": a.eth_addr}
-            self.exit_tree.insert(first_idx + i, hash_state(st, hasher))
+            if sparse_tree is None:
+                self.exit_tree.insert(first_idx + i, hash_state(st, hasher))
             self.exit_leaves[first_idx + i] = st
         if lazy:
             self.exit_tree.rekey(hasher.resolve())
+        if sparse_tree is not None:
+            sparse_tree.reset()
+            idxs = list(self.exit_leaves)
+            for at in range(0, len(idxs), 65536):
+                rows = b"".join(int(x).to_bytes(32, "little") for i in idxs[at:at + 65536] for x in leaf_fields(self.exit_leaves[i]))
+                sparse_tree.apply(idxs[at:at + 65536], np.frombuffer(rows, dtype=np.uint8).reshape(-1, 4, 32))
 
 
 def synthetic_batch(n_tx, n_levels, max_l1, max_fee, seed=0x48455A31, n_accounts=None, n_keys=8, exits=0, device=None, dag_evaluator=None, first_idx=256,

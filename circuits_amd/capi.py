@@ -68,6 +68,7 @@ EXPORTS = [
     "hz_symbol_count", "hz_symbol_get", "hz_symbol_lookup", "hz_constraint_name", "hz_poseidon_batch",
     "hz_poseidon_batch_dev", "hz_shard_range", "hz_set_inputs_json", "hz_witness_write_json", "hz_witness_write_wtns", "hz_symbols_write_sym", "hz_fr_ops", "hz_poseidon_dag",
     "hz_state_create", "hz_state_destroy", "hz_state_load", "hz_state_root", "hz_state_apply", "hz_state_proofs", "hz_state_download", "hz_state_device_ms",
+    "hz_smt_create", "hz_smt_destroy", "hz_smt_reset", "hz_smt_root", "hz_smt_size", "hz_smt_device_ms", "hz_smt_apply", "hz_smt_proofs", "hz_smt_plan",
 ]
 
 
@@ -190,6 +191,18 @@ class Lib:
         c.hz_state_download.argtypes = [vp, ctypes.POINTER(vp), vp]
         c.hz_state_device_ms.argtypes = [vp]
         c.hz_state_device_ms.restype = ctypes.c_double
+        c.hz_smt_create.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(vp)]
+        c.hz_smt_destroy.argtypes = [vp]
+        c.hz_smt_destroy.restype = None
+        c.hz_smt_reset.argtypes = [vp]
+        c.hz_smt_root.argtypes = [vp, vp]
+        c.hz_smt_size.argtypes = [vp]
+        c.hz_smt_size.restype = u64
+        c.hz_smt_device_ms.argtypes = [vp]
+        c.hz_smt_device_ms.restype = ctypes.c_double
+        c.hz_smt_apply.argtypes = [vp, sz, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp]
+        c.hz_smt_proofs.argtypes = [vp, sz, vp, sz, vp, vp, vp, vp, vp, vp]
+        c.hz_smt_plan.argtypes = [sz, vp, sz, vp, vp, vp, vp]
 
     def _check(self, st):
         if st != 0:
@@ -253,6 +266,21 @@ class Lib:
 
     def state(self, k, first_idx=256, device=0):
         return State(self, k, first_idx=first_idx, device=device)
+
+    def smt(self, n_sib_max, device=0):
+        return SparseTree(self, n_sib_max, device=device)
+
+    def smt_plan(self, keys, n_sib):
+        """hz_smt_plan, a diagnostic: the host planner alone on an empty tree (integers only, no device needed) -> dictionary of numpy
+        arrays depth (of each op's leaf), fnc (1 insert, 0 update), old_key, is_old0"""
+        import numpy as np
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        m = keys.size
+        out = {"depth": np.zeros(m, dtype=np.uint32), "fnc": np.zeros(m, dtype=np.uint8), "old_key": np.zeros(m, dtype=np.uint64),
+               "is_old0": np.zeros(m, dtype=np.uint8)}
+        self._check(self.c.hz_smt_plan(m, keys.ctypes.data, n_sib, out["depth"].ctypes.data, out["fnc"].ctypes.data, out["old_key"].ctypes.data,
+                                       out["is_old0"].ctypes.data))
+        return out
 
     def host_alloc(self, nbytes):
         """pinned host memory for hz_inputs_upload (address as int); free with host_free"""
@@ -632,6 +660,76 @@ class State:
     def device_ms(self):
         """device time of the last load / apply"""
         return self.L.c.hz_state_device_ms(self.h)
+
+
+class SparseTree:
+    """hz_smt: a circomlib sparse Merkle tree resident on the device that accepts inserts and updates (the exit tree; the state tree under
+    create-account deposits). Field elements cross as numpy uint8 arrays of 32-byte little-endian canonical integers."""
+
+    def __init__(self, L, n_sib_max, device=0):
+        self.L = L
+        self.h = ctypes.c_void_p()
+        L._check(L.c.hz_smt_create(device, n_sib_max, ctypes.byref(self.h)))
+        self.n_sib_max = n_sib_max
+
+    def close(self):
+        if self.h:
+            self.L.c.hz_smt_destroy(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        """the empty tree again; the device pools are kept"""
+        self.L._check(self.L.c.hz_smt_reset(self.h))
+
+    def root(self):
+        out = (ctypes.c_uint8 * 32)()
+        self.L._check(self.L.c.hz_smt_root(self.h, out))
+        return int.from_bytes(bytes(out), "little")
+
+    def size(self):
+        """keys held"""
+        return self.L.c.hz_smt_size(self.h)
+
+    def apply(self, keys, fields, n_sib=None):
+        """m ordered ops, each an insert (key absent) or an update (key present): keys [m] integers, fields [m, 4, 32] (e0, balance, ay,
+        ethAddr). Returns a dictionary of numpy arrays, the inputs of SMTProcessor(n_sib) per op: siblings [m, n_sib, 32] (zero-padded),
+        old_key [m], old_value [m, 32], is_old0 [m], fnc [m] (1 insert: fnc = [1, 0]; 0 update: fnc = [0, 1]), old_root / new_root [m, 32]."""
+        import numpy as np
+        n_sib = self.n_sib_max if n_sib is None else n_sib
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        m = keys.size
+        fields = State._fr(fields, (m, 4, 32))
+        out = {"siblings": np.zeros((m, min(max(n_sib, 0), 64), 32), dtype=np.uint8), "old_key": np.zeros(m, dtype=np.uint64),
+               "old_value": np.zeros((m, 32), dtype=np.uint8), "is_old0": np.zeros(m, dtype=np.uint8), "fnc": np.zeros(m, dtype=np.uint8),
+               "old_root": np.zeros((m, 32), dtype=np.uint8), "new_root": np.zeros((m, 32), dtype=np.uint8)}
+        self.L._check(self.L.c.hz_smt_apply(self.h, m, keys.ctypes.data, fields.ctypes.data, n_sib, out["siblings"].ctypes.data, out["old_key"].ctypes.data,
+                                            out["old_value"].ctypes.data, out["is_old0"].ctypes.data, out["fnc"].ctypes.data,
+                                            out["old_root"].ctypes.data, out["new_root"].ctypes.data))
+        return out
+
+    def proofs(self, keys, n_sib=None):
+        """membership / non-membership proofs against the current root (SMTVerifier's inputs) -> dictionary of numpy arrays: siblings
+        [n, n_sib, 32], found [n], value [n, 32] (found keys), not_found_key [n], not_found_value [n, 32], is_old0 [n] (absent keys)"""
+        import numpy as np
+        n_sib = self.n_sib_max if n_sib is None else n_sib
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        n = keys.size
+        out = {"siblings": np.zeros((n, min(max(n_sib, 0), 64), 32), dtype=np.uint8), "found": np.zeros(n, dtype=np.uint8),
+               "value": np.zeros((n, 32), dtype=np.uint8), "not_found_key": np.zeros(n, dtype=np.uint64),
+               "not_found_value": np.zeros((n, 32), dtype=np.uint8), "is_old0": np.zeros(n, dtype=np.uint8)}
+        self.L._check(self.L.c.hz_smt_proofs(self.h, n, keys.ctypes.data, n_sib, out["siblings"].ctypes.data, out["found"].ctypes.data, out["value"].ctypes.data,
+                                             out["not_found_key"].ctypes.data, out["not_found_value"].ctypes.data, out["is_old0"].ctypes.data))
+        return out
+
+    def device_ms(self):
+        """device time of the last apply"""
+        return self.L.c.hz_smt_device_ms(self.h)
 
 
 class SymMap:

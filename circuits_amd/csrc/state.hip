@@ -24,6 +24,7 @@
 #include "hostutil.h"
 #include "kernels.h"
 #include "poseidon_quad.h"
+#include "state_dev.h"
 
 #define HZ_STATE_MIN_K 4
 #define HZ_STATE_MAX_K 24
@@ -38,18 +39,7 @@ __global__ __launch_bounds__(256) void k_state_value(const uint8_t* __restrict__
                                                       uint8_t* __restrict__ out, uint32_t n) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    Fr x[4];
-#pragma unroll
-    for (int f = 0; f < 4; f++) x[f] = fr_from_canon(load_fr(fields + ((size_t)i * elem_stride + (size_t)f * field_stride) * 32));
-    NoSink sink;
-    store_fr(out + (size_t)i * 32, fr_to_canon(poseidon_hash<5>(x, poseidon_consts<5>(), sink)));
-}
-
-// leaf hash: Poseidon(4) of (key, value, 1) (circomlib SMTHash1)
-__device__ __forceinline__ Fc state_leaf_hash(uint64_t key, const Fc& value) {
-    const Fr x[3] = {fr_from_u64(key), fr_from_canon(value), fr_one()};
-    NoSink sink;
-    return fr_to_canon(poseidon_hash<4>(x, poseidon_consts<4>(), sink));
+    store_fr(out + (size_t)i * 32, state_value_hash(fields + (size_t)i * elem_stride * 32, field_stride));
 }
 
 // load: the leaf of residue p belongs to account (p - first_idx) mod N

@@ -350,6 +350,50 @@ hz_status hz_state_proofs(hz_state* st, size_t n, const uint64_t* idx, size_t n_
 hz_status hz_state_download(hz_state* st, uint8_t* const* levels_out, uint8_t* value_out);
 double hz_state_device_ms(const hz_state* st);
 
+/* Sparse device-resident Merkle tree: a circomlib SMT in HBM that accepts INSERTS as well as updates -- the exit tree of a batch (empty at
+ * its start, filled by inserts and updates), the state tree under create-account deposits (idx = lastIdx + 1), membership proofs for
+ * Withdraw. Keys are below 2^48, bits LSB first; the value of a leaf is the state hash Poseidon(5) of its four fields (e0, balance, ay,
+ * ethAddr, as hz_state_load), its hash Poseidon(4) of (key, value, 1). The digests live in device pools that grow on demand; the host
+ * keeps the shape as integers (no field arithmetic and no hash there), DESIGN.md 8b.
+ *   hz_smt_create / _destroy   an empty tree; n_sib_max (1 .. 64) bounds the n_sib of later calls. A failed allocation, here or when a
+ *                       pool grows, is HZ_ERR_HIP
+ *   hz_smt_reset        the empty tree again, pools kept: the exit tree of the next batch
+ *   hz_smt_root / _size the current root (0 for the empty tree); the number of keys held
+ *   hz_smt_apply        m ORDERED operations (m <= 65536; key[m], fields[m][4][32]) with sequential semantics: operation j inserts its key
+ *                       when the tree as operations 0 .. j - 1 left it does not hold it, and updates it otherwise. Outputs in host
+ *                       memory, each may be NULL, are the inputs of circomlib's SMTProcessor(n_sib) for operation j with newKey = key[j]
+ *                       and newValue = the state hash: siblings_out [m][n_sib][32] (root side first, zero-padded), old_key_out [m],
+ *                       old_value_out [m][32], is_old0_out [m] (an insert into an empty slot: old key = key, old value 0; an insert
+ *                       that meets another leaf reports that leaf's key and value; an update its own key and previous value),
+ *                       fnc_out [m] (0 update: fnc = [0, 1]; 1 insert: fnc = [1, 0]), old_root_out / new_root_out [m][32]. The
+ *                       dependent device work is max depth + 2 launches whatever m is
+ *   hz_smt_proofs       proofs against the current root (SMTVerifier's inputs, fnc 0 where found_out[i] and fnc 1 otherwise):
+ *                       siblings_out [n][n_sib][32], value_out [n][32] (found keys), not_found_key_out [n] / not_found_value_out [n][32]
+ *                       / is_old0_out [n] (absent keys: the leaf the lookup met, or the key itself, 0 and is_old0 = 1 at an empty slot);
+ *                       n <= 2^20; a gather on the device
+ *   hz_smt_plan         DIAGNOSTIC: the host planner alone on an empty tree -- integers only, works without a device: the depth of each
+ *                       operation's leaf, fnc, old key and is_old0 as hz_smt_apply would report them
+ *   hz_smt_device_ms    device time of the last apply (first kernel to write-back, HIP events)
+ * A failing call names the offending operation in hz_last_error and leaves the tree untouched: root, size and later results are as if
+ * it had not been made; a refused hz_smt_proofs writes to none of its outputs. The one exception is a HIP failure reported AFTER a
+ * call's write-back was queued (the copies out, the final synchronise): the pools may then hold part of that call, so the shape is
+ * rolled back and every later apply / proofs / root answers HZ_ERR_HIP until hz_smt_reset. No failing call leaves work in flight. HZ_ERR_ARG: null arguments, m over the cap, n_sib outside 1 .. 64 or above n_sib_max. HZ_ERR_INPUT: a key >=
+ * 2^48, a field >= r, an operation whose leaf would sit at depth >= n_sib (an insert SMTProcessor(n_sib) cannot express; a proof that
+ * needs n_sib or more siblings likewise).
+ * OUT OF SCOPE: transaction semantics, deletes (Hermez never deletes), more than one device per tree. One thread at a time. */
+typedef struct hz_smt hz_smt;
+hz_status hz_smt_create(int32_t device, int32_t n_sib_max, hz_smt** out);
+void hz_smt_destroy(hz_smt* t);
+hz_status hz_smt_reset(hz_smt* t);
+hz_status hz_smt_root(hz_smt* t, uint8_t* out32);
+uint64_t hz_smt_size(const hz_smt* t);
+double hz_smt_device_ms(const hz_smt* t);
+hz_status hz_smt_apply(hz_smt* t, size_t m, const uint64_t* key, const uint8_t* fields, size_t n_sib, uint8_t* siblings_out, uint64_t* old_key_out,
+                       uint8_t* old_value_out, uint8_t* is_old0_out, uint8_t* fnc_out, uint8_t* old_root_out, uint8_t* new_root_out);
+hz_status hz_smt_proofs(hz_smt* t, size_t n, const uint64_t* key, size_t n_sib, uint8_t* siblings_out, uint8_t* found_out, uint8_t* value_out,
+                        uint64_t* not_found_key_out, uint8_t* not_found_value_out, uint8_t* is_old0_out);
+hz_status hz_smt_plan(size_t m, const uint64_t* key, size_t n_sib, uint32_t* depth_out, uint8_t* fnc_out, uint64_t* old_key_out, uint8_t* is_old0_out);
+
 /* Poseidon batch: n independent permutations of width t = n_inputs + 1 (2..7). ----------------
  * `in`  : [n][t-1] canonical elements; `out`: [n] digests (state[0] after the last round).
  * If `sbox_witness` is non-NULL it receives the S-box signals (in2,in4,out per S-box, the
