@@ -282,6 +282,12 @@ class DenseState:
         st.load(*self.leaf_fields())
         return st
 
+    def to_ledger(self, lib, device=0):
+        """this state as a capi.Ledger: tree and leaf fields resident on the device"""
+        lg = lib.ledger(self.k, first_idx=self.first_idx, device=device)
+        lg.load(*self.leaf_fields())
+        return lg
+
     @staticmethod
     def from_device(state, like):
         """the consolidated arrays of a capi.State as a DenseState (for hzb_db_set_base, or save). `like`: the DenseState the device
@@ -911,6 +917,71 @@ class BatchBuilder:
                "newStateRoot": self.tx_meta[i]["stateRoot"], "newExitRoot": self.tx_meta[i]["exitRoot"],
                "isAmountNullified": self.tx_meta[i]["isAmountNullified"]}
         return r, out
+
+
+# RollupMain's state-dependent inputs of an all-L2-transfer batch, and where hz_ledger_apply_l2 leaves each (array, first row, rows)
+def l2_state_signals(n_tx, max_fee):
+    sig = {f + n: (f + n, 0, n_tx if n != "3" else max_fee) for n in "123" for f in ("tokenID", "nonce", "sign", "balance", "ay", "ethAddr", "siblings")}
+    sig.update({"imStateRoot": ("state_root_after", 0, n_tx - 1), "imAccFeeOut": ("acc_fee_after", 0, n_tx - 1),
+                "imInitStateRootFee": ("state_root_after", n_tx - 1, 1), "imStateRootFee": ("state_root_after_fee", 0, max_fee - 1),
+                "imFinalAccFee": ("final_acc_fee", 0, max_fee), "oldStateRoot": ("old_root", 0, 1)})
+    return sig
+
+
+def l2_batch_inputs(ledger, db_like, txs, n_tx, n_levels, max_l1, max_fee, fee_tokens, fee_idxs, chain_id, host_outputs=True):
+    """The complete RollupMain(n_tx, n_levels, max_l1, max_fee) input dictionary of a batch of L2 transfers between existing accounts:
+    the transaction-only signals from this module's helpers, every state-dependent signal from capi.Ledger.apply_l2 (which also applies
+    the batch to the ledger), the exit-side signals zero. db_like: anything with last_idx and num_batch (a RollupDB, or a namespace);
+    num_batch is advanced. txs: transaction dictionaries (fromIdx, toIdx, amount or amountF, tokenID, userFee, nonce, optionally signer or
+    r8x / r8y / s); fewer than n_tx are padded with NOPs. host_outputs=False: the state-dependent signals stay on the device -- they
+    are left out of the dictionary, and the second value returned maps each to (device pointer, elements) for hz_set_input_dev.
+    -> (inputs, device signals or None)"""
+    if len(txs) > n_tx:
+        raise ValueError("batch full")
+    txs = [dict(t) for t in txs]
+    for t in txs:
+        if "amountF" not in t or "amount" in t:
+            t["amountF"] = fix2float(t.get("amount", 0))
+    plan = list(fee_tokens) + [0] * (max_fee - len(fee_tokens))
+    idxs = list(fee_idxs) + [0] * (max_fee - len(fee_idxs))
+    padded = txs + [{}] * (n_tx - len(txs))
+    out = ledger.apply_l2(padded, plan, idxs, n_sib=n_levels + 1, outputs=host_outputs)
+    inp = {"oldLastIdx": db_like.last_idx, "globalChainID": chain_id, "currentNumBatch": db_like.num_batch + 1, "feePlanTokens": plan, "feeIdxs": idxs}
+    db_like.num_batch += 1
+    names = ("txCompressedData amountF txCompressedDataV2 fromIdx auxFromIdx toIdx auxToIdx toBjjAy toEthAddr maxNumBatch onChain newAccount "
+             "rqOffset rqTxCompressedDataV2 rqToEthAddr rqToBjjAy s r8x r8y loadAmountF fromEthAddr fromBjjCompressed isOld0_1 oldKey1 oldValue1 "
+             "newExit isOld0_2 oldKey2 oldValue2").split()
+    for k in names:
+        inp[k] = []
+    for t in padded:
+        sig = {"r8x": 0, "r8y": 0, "s": 0}
+        if t.get("fromIdx", 0):
+            sig = t["signer"].sign_msg(build_hash_sig(t, chain_id)) if "signer" in t else {k: t.get(k, 0) for k in ("r8x", "r8y", "s")}
+        vals = {"txCompressedData": build_tx_compressed_data(t, chain_id), "amountF": t.get("amountF", 0), "txCompressedDataV2": build_tx_compressed_data_v2(t),
+                "fromIdx": t.get("fromIdx", 0), "toIdx": t.get("toIdx", 0), "toBjjAy": t.get("toBjjAy", 0), "toEthAddr": t.get("toEthAddr", 0),
+                "maxNumBatch": t.get("maxNumBatch", 0), "s": sig["s"], "r8x": sig["r8x"], "r8y": sig["r8y"], "fromBjjCompressed": [0] * 256}
+        for k in names:
+            inp[k].append(vals.get(k, 0))
+    for k in ("imOnChain", "imExitRoot"):
+        inp[k] = [0] * (n_tx - 1)
+    inp["imOutIdx"] = [db_like.last_idx] * (n_tx - 1)
+    sigs = l2_state_signals(n_tx, max_fee)
+    if not host_outputs:
+        dev = ledger.outputs_dev()
+        devsig = {}
+        for name, (arr, first, rows) in sigs.items():
+            width = {"siblings": n_levels + 1, "imAccFeeOut": max_fee}.get(name.rstrip("123"), 1)
+            devsig[name] = (dev[arr] + first * width * 32, rows * width)
+        return inp, devsig
+
+    def ints(a):
+        if a.ndim == 2:
+            return [int.from_bytes(r.tobytes(), "little") for r in a]
+        return [ints(r) for r in a]
+    for name, (arr, first, rows) in sigs.items():
+        v = ints(out[arr][first:first + rows])
+        inp[name] = v[0] if name in ("imInitStateRootFee", "oldStateRoot") else v
+    return inp, None
 
 
 def withdraw_input(batch, idx, n_levels):

@@ -69,7 +69,32 @@ EXPORTS = [
     "hz_poseidon_batch_dev", "hz_shard_range", "hz_set_inputs_json", "hz_witness_write_json", "hz_witness_write_wtns", "hz_symbols_write_sym", "hz_fr_ops", "hz_poseidon_dag",
     "hz_state_create", "hz_state_destroy", "hz_state_load", "hz_state_root", "hz_state_apply", "hz_state_proofs", "hz_state_download", "hz_state_device_ms",
     "hz_smt_create", "hz_smt_destroy", "hz_smt_reset", "hz_smt_root", "hz_smt_size", "hz_smt_device_ms", "hz_smt_apply", "hz_smt_proofs", "hz_smt_plan",
+    "hz_ledger_create", "hz_ledger_destroy", "hz_ledger_load", "hz_ledger_root", "hz_ledger_accounts", "hz_ledger_tree", "hz_ledger_apply_l2",
+    "hz_ledger_outputs_dev", "hz_ledger_plan_l2", "hz_ledger_device_ms", "hz_ledger_semantic_ms",
 ]
+
+
+class hz_l2tx(ctypes.Structure):
+    _fields_ = [("from_idx", ctypes.c_uint64), ("to_idx", ctypes.c_uint64), ("amount_f", ctypes.c_uint64), ("nonce", ctypes.c_uint64),
+                ("token_id", ctypes.c_uint32), ("user_fee", ctypes.c_uint8)]
+
+
+# hz_ledger_out's arrays in order: (name, rows per "tx" / "fee" / "one", columns "sib" / "fee" / None)
+LEDGER_ARRAYS = (
+    [(f + "1", "tx", None) for f in ("tokenID", "nonce", "sign", "balance", "ay", "ethAddr")] + [("siblings1", "tx", "sib")] +
+    [(f + "2", "tx", None) for f in ("tokenID", "nonce", "sign", "balance", "ay", "ethAddr")] + [("siblings2", "tx", "sib")] +
+    [("state_root_after", "tx", None), ("acc_fee_after", "tx", "fee")] +
+    [(f + "3", "fee", None) for f in ("tokenID", "nonce", "sign", "balance", "ay", "ethAddr")] + [("siblings3", "fee", "sib")] +
+    [("state_root_after_fee", "fee", None), ("final_acc_fee", "fee", None), ("old_root", "one", None), ("new_root", "one", None)])
+
+
+def l2tx_array(txs):
+    """[{fromIdx, toIdx, amountF, nonce, tokenID, userFee}] (builder's transaction dictionaries; missing keys are 0) -> hz_l2tx array"""
+    arr = (hz_l2tx * max(len(txs), 1))()
+    for i, t in enumerate(txs):
+        arr[i] = hz_l2tx(t.get("fromIdx", 0), t.get("toIdx", 0), t.get("amountF", 0), t.get("nonce", 0), t.get("tokenID", 0), t.get("userFee", 0))
+    return arr
+
 
 
 class Lib:
@@ -203,6 +228,20 @@ class Lib:
         c.hz_smt_apply.argtypes = [vp, sz, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp]
         c.hz_smt_proofs.argtypes = [vp, sz, vp, sz, vp, vp, vp, vp, vp, vp]
         c.hz_smt_plan.argtypes = [sz, vp, sz, vp, vp, vp, vp]
+        c.hz_ledger_create.argtypes = [ctypes.c_int32, ctypes.c_int32, u64, ctypes.POINTER(vp)]
+        c.hz_ledger_destroy.argtypes = [vp]
+        c.hz_ledger_destroy.restype = None
+        c.hz_ledger_load.argtypes = [vp, vp, vp, vp, vp]
+        c.hz_ledger_root.argtypes = [vp, vp]
+        c.hz_ledger_accounts.argtypes = [vp, sz, vp, vp]
+        c.hz_ledger_tree.argtypes = [vp]
+        c.hz_ledger_tree.restype = vp
+        c.hz_ledger_apply_l2.argtypes = [vp, sz, vp, sz, vp, vp, sz, vp]
+        c.hz_ledger_outputs_dev.argtypes = [vp, vp]
+        c.hz_ledger_plan_l2.argtypes = [sz, vp, sz, vp, vp, ctypes.c_int32, u64, vp, vp, vp, vp, ctypes.POINTER(sz), vp, vp]
+        for f in ("hz_ledger_device_ms", "hz_ledger_semantic_ms"):
+            getattr(c, f).argtypes = [vp]
+            getattr(c, f).restype = ctypes.c_double
 
     def _check(self, st):
         if st != 0:
@@ -280,6 +319,29 @@ class Lib:
                "is_old0": np.zeros(m, dtype=np.uint8)}
         self._check(self.c.hz_smt_plan(m, keys.ctypes.data, n_sib, out["depth"].ctypes.data, out["fnc"].ctypes.data, out["old_key"].ctypes.data,
                                        out["is_old0"].ctypes.data))
+        return out
+
+    def ledger(self, k, first_idx=256, device=0):
+        return Ledger(self, k, first_idx=first_idx, device=device)
+
+    def ledger_plan_l2(self, txs, fee_plan_tokens, fee_idxs, k, first_idx=256):
+        """hz_ledger_plan_l2, a diagnostic: the host planner alone (integers only, no device needed). txs: transaction dictionaries or an
+        hz_l2tx array. -> dictionary of numpy arrays: ev_sender / ev_receiver / fee_slot / last_event [m] (-1: none), account / prev_same
+        [events]"""
+        import numpy as np
+        arr = txs if isinstance(txs, ctypes.Array) else l2tx_array(txs)
+        m = len(txs)
+        plan = np.ascontiguousarray(fee_plan_tokens, dtype=np.uint32)
+        idxs = np.ascontiguousarray(fee_idxs, dtype=np.uint64)
+        F = plan.size
+        if idxs.size != F:
+            raise ValueError("fee_plan_tokens and fee_idxs differ in length")
+        out = {n: np.zeros(m, dtype=np.int32) for n in ("ev_sender", "ev_receiver", "fee_slot", "last_event")}
+        acct, prev, n_ev = np.zeros(2 * m + F, dtype=np.uint64), np.zeros(2 * m + F, dtype=np.int32), ctypes.c_size_t(0)
+        self._check(self.c.hz_ledger_plan_l2(m, ctypes.addressof(arr), F, plan.ctypes.data, idxs.ctypes.data, k, first_idx, out["ev_sender"].ctypes.data,
+                                             out["ev_receiver"].ctypes.data, out["fee_slot"].ctypes.data, out["last_event"].ctypes.data, ctypes.byref(n_ev),
+                                             acct.ctypes.data, prev.ctypes.data))
+        out["account"], out["prev_same"] = acct[:n_ev.value], prev[:n_ev.value]
         return out
 
     def host_alloc(self, nbytes):
@@ -392,6 +454,10 @@ class Ctx:
     def set_inputs(self, d, instance=0):
         for k, v in d.items():
             self.set_input(k, v, instance)
+
+    def set_input_dev(self, name, d_vals, count, instance=0, stream=None):
+        """hz_set_input_dev: `count` canonical 32-byte elements that already lie in device memory (an address)"""
+        self.L._check(self.L.c.hz_set_input_dev(self.h, instance, name.encode(), d_vals, count, stream))
 
     def packed_layout(self):
         """(total bytes, [(name, byte offset, element bytes, flat length)]) of the bulk-upload buffer of one instance"""
@@ -660,6 +726,103 @@ class State:
     def device_ms(self):
         """device time of the last load / apply"""
         return self.L.c.hz_state_device_ms(self.h)
+
+
+class _BorrowedState(State):
+    """the hz_state inside a Ledger: proofs / download / root work on it; the ledger owns it"""
+
+    def __init__(self, L, h, k, first_idx):
+        self.L, self.h = L, ctypes.c_void_p(h)
+        self.k, self.N, self.first_idx = k, 1 << k, first_idx
+
+    def close(self):
+        self.h = ctypes.c_void_p()
+
+
+class Ledger:
+    """hz_ledger: an hz_state plus the resident leaf fields; L2 transfers and the batch's fee transactions computed and applied on the
+    device. Field elements cross as numpy uint8 arrays of 32-byte little-endian canonical integers."""
+
+    def __init__(self, L, k, first_idx=256, device=0):
+        self.L = L
+        self.h = ctypes.c_void_p()
+        L._check(L.c.hz_ledger_create(device, k, first_idx, ctypes.byref(self.h)))
+        self.k, self.N, self.first_idx = k, 1 << k, first_idx
+
+    def close(self):
+        if self.h:
+            self.L.c.hz_ledger_destroy(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def load(self, e0, balance, ay, eth_addr):
+        cols = [State._fr(a, (self.N, 32)) for a in (e0, balance, ay, eth_addr)]
+        self.L._check(self.L.c.hz_ledger_load(self.h, *[a.ctypes.data for a in cols]))
+
+    def root(self):
+        out = (ctypes.c_uint8 * 32)()
+        self.L._check(self.L.c.hz_ledger_root(self.h, out))
+        return int.from_bytes(bytes(out), "little")
+
+    def accounts(self, idx):
+        """the resident leaf fields (e0, balance, ay, ethAddr) of the accounts idx -> [n, 4, 32]"""
+        import numpy as np
+        idx = np.ascontiguousarray(idx, dtype=np.uint64)
+        out = np.zeros((idx.size, 4, 32), dtype=np.uint8)
+        self.L._check(self.L.c.hz_ledger_accounts(self.h, idx.size, idx.ctypes.data, out.ctypes.data))
+        return out
+
+    def tree(self):
+        """the tree as a capi.State, borrowed: proofs / download / root"""
+        return _BorrowedState(self.L, self.L.c.hz_ledger_tree(self.h), self.k, self.first_idx)
+
+    @staticmethod
+    def shapes(m, F, n_sib):
+        rows = {"tx": m, "fee": F, "one": 1}
+        cols = {"sib": n_sib, "fee": F}
+        return [(name, (rows[r], 32) if c is None else (rows[r], cols[c], 32)) for name, r, c in LEDGER_ARRAYS]
+
+    def apply_l2(self, txs, fee_plan_tokens, fee_idxs, n_sib=None, outputs=True, into=None):
+        """txs: transaction dictionaries (fromIdx, toIdx, amountF, nonce, tokenID, userFee) or an hz_l2tx array; fee_plan_tokens /
+        fee_idxs: [F]. Returns a dictionary of numpy arrays named as hz_ledger_out's members (outputs=False: nothing is copied to the
+        host, outputs_dev has them; into: a dictionary of arrays to fill instead of fresh ones)."""
+        import numpy as np
+        n_sib = self.k if n_sib is None else n_sib
+        arr = txs if isinstance(txs, ctypes.Array) else l2tx_array(txs)
+        m = len(txs)
+        plan = np.ascontiguousarray(fee_plan_tokens, dtype=np.uint32)
+        idxs = np.ascontiguousarray(fee_idxs, dtype=np.uint64)
+        F = plan.size
+        if idxs.size != F:
+            raise ValueError("fee_plan_tokens and fee_idxs differ in length")
+        out, ptrs = {}, (ctypes.c_void_p * len(LEDGER_ARRAYS))()
+        if outputs:
+            for i, (name, shape) in enumerate(self.shapes(m, F, min(max(n_sib, 0), 64))):
+                out[name] = into[name] if into is not None else np.zeros(shape, dtype=np.uint8)
+                assert out[name].shape == shape and out[name].dtype == np.uint8 and out[name].flags.c_contiguous
+                ptrs[i] = out[name].ctypes.data
+        self.L._check(self.L.c.hz_ledger_apply_l2(self.h, m, ctypes.addressof(arr), F, plan.ctypes.data, idxs.ctypes.data, n_sib,
+                                                  ctypes.addressof(ptrs) if outputs else None))
+        return out
+
+    def outputs_dev(self):
+        """device pointers of the last successful apply_l2's arrays, by name; valid until the ledger's next call"""
+        ptrs = (ctypes.c_void_p * len(LEDGER_ARRAYS))()
+        self.L._check(self.L.c.hz_ledger_outputs_dev(self.h, ctypes.addressof(ptrs)))
+        return {name: ptrs[i] for i, (name, _, _) in enumerate(LEDGER_ARRAYS)}
+
+    def device_ms(self):
+        """device time of the last apply_l2"""
+        return self.L.c.hz_ledger_device_ms(self.h)
+
+    def semantic_ms(self):
+        """device time of the last apply_l2's semantic kernels alone (first kernel to the failure-word read)"""
+        return self.L.c.hz_ledger_semantic_ms(self.h)
 
 
 class SparseTree:

@@ -1,0 +1,642 @@
+// hz_ledger: an hz_state plus the resident leaf fields, and L2 transfers computed and applied on the device.
+//
+// The split is the library's: the host does integer work on indices only (ledger_plan.h: events, their grouping by account, fee slots),
+// the device everything that touches a 256-bit value. One call is
+//   k_ledger_tx        a lane per transaction: float40 -> amount, fee = amount x table[selector] (>> 60 below 192), the signed deltas
+//                      of its sender and receiver events
+//   k_ledger_fee_sum / k_ledger_fee_scan   the accumulated fees after every transaction, per slot: chunk sums, then a lane per
+//                      (chunk, slot) walks its chunk; the last row is the delta of the fee events
+//   k_ledger_scan      balances and nonces with sequential semantics: the events of an account lie behind each other (grouped order)
+//                      and one lane carries balance and e0 through them, checks token, nonce, underflow and overflow, lowers the failure
+//                      word with atomicMin, and writes every event's leaf before and after
+//   -- one synchronise: the failure word. A refused batch ends here; nothing resident has been written --
+//   k_ledger_pack      the before-fields of every transaction and fee slot into the output arrays
+//   the tree update    state_apply_launch (state.hip): the body of hz_state_apply on the records k_ledger_scan wrote
+//   k_ledger_gather    events back to transactions: siblings1/2/3, the root after each transaction and fee slot
+//   k_ledger_writeback the last leaf of every touched account into the resident planes
+// Values are plain 256-bit integers in eight 32-bit limbs (the Fc container of fr.h, nothing is reduced modulo r); deltas are
+// two's complement: every true prefix is below 2^220 in magnitude, so a set top bit means "negative".
+#define HZ_FR_INLINE 1
+#include <hip/hip_runtime.h>
+#include <string.h>
+#include <memory>
+#include <vector>
+#include "../../include/hermez_witness.h"
+#include "devcommon.h"
+#include "hostutil.h"
+#include "ledger_plan.h"
+#include "state_internal.h"
+
+#define HZ_LEDGER_MAX_EVENTS 65536u
+#define HZ_LEDGER_MAX_TX (1u << 20)
+#define HZ_LEDGER_MAX_F 64u
+#define HZ_LEDGER_CHUNK 64u   // transactions per lane of the fee scan
+
+namespace hz {
+
+// ---- 256-bit integers -----------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ Fc u256_zero() {
+    Fc r;
+#pragma unroll
+    for (int i = 0; i < 8; i++) r.v[i] = 0u;
+    return r;
+}
+__device__ __forceinline__ Fc u256_add(const Fc& a, const Fc& b) {
+    Fc r;
+    uint64_t c = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        c += (uint64_t)a.v[i] + b.v[i];
+        r.v[i] = (uint32_t)c;
+        c >>= 32;
+    }
+    return r;
+}
+__device__ __forceinline__ Fc u256_neg(const Fc& a) {
+    Fc r;
+    uint64_t c = 1;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        c += (uint64_t)(~a.v[i]);
+        r.v[i] = (uint32_t)c;
+        c >>= 32;
+    }
+    return r;
+}
+__device__ __forceinline__ Fc u256_mul_u32(const Fc& a, uint32_t w) {
+    Fc r;
+    uint64_t c = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        c += (uint64_t)a.v[i] * w;
+        r.v[i] = (uint32_t)c;
+        c >>= 32;
+    }
+    return r;
+}
+__device__ __forceinline__ Fc u256_mul_u64(const Fc& a, uint64_t t) {
+    const Fc lo = u256_mul_u32(a, (uint32_t)t), hi = u256_mul_u32(a, (uint32_t)(t >> 32));
+    Fc sh;
+    sh.v[0] = 0u;
+#pragma unroll
+    for (int i = 1; i < 8; i++) sh.v[i] = hi.v[i - 1];
+    return u256_add(lo, sh);
+}
+__device__ __forceinline__ Fc u256_shr60(const Fc& a) {
+    Fc r;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const uint32_t lo = i + 1 < 8 ? a.v[i + 1] : 0u, hi = i + 2 < 8 ? a.v[i + 2] : 0u;
+        r.v[i] = (lo >> 28) | (hi << 4);
+    }
+    return r;
+}
+__device__ __forceinline__ Fc u256_u64(uint64_t x) {
+    Fc r = u256_zero();
+    r.v[0] = (uint32_t)x;
+    r.v[1] = (uint32_t)(x >> 32);
+    return r;
+}
+
+// the 27 output arrays in hz_ledger_out's order, as device pointers
+struct LedgerOutDev {
+    uint8_t* a[HZ_LEDGER_ARRAYS];
+};
+enum { LO_TX1 = 0, LO_SIB1 = 6, LO_TX2 = 7, LO_SIB2 = 13, LO_ROOT_AFTER = 14, LO_ACC_FEE = 15, LO_TX3 = 16, LO_SIB3 = 22, LO_ROOT_FEE = 23,
+       LO_FINAL_FEE = 24, LO_OLD_ROOT = 25, LO_NEW_ROOT = 26 };
+
+// one event in grouped order
+struct LedgerPos {
+    uint32_t ev, unit, kind, acct;
+};
+
+// ---- kernels ----------------------------------------------------------------------------------------------------------------------------
+// amount = mantissa x 10^exponent (src/lib/decode-float.circom), fee (src/compute-fee.circom); deltas at the events' grouped positions
+__global__ __launch_bounds__(64) void k_ledger_tx(const hz_l2tx* __restrict__ txs, const int32_t* __restrict__ pos_s, const int32_t* __restrict__ pos_r,
+                                                  uint8_t* __restrict__ fee_out, uint8_t* __restrict__ delta, uint32_t m) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    Fc fee = u256_zero();
+    if (txs[i].from_idx != 0) {
+        const uint64_t af = txs[i].amount_f;
+        Fc amount = u256_u64(af & ((1ull << 35) - 1));
+        const uint32_t e = (uint32_t)(af >> 35) & 31u;
+        for (uint32_t s = 0; s < e; s++) amount = u256_mul_u32(amount, 10u);
+        const uint32_t sel = txs[i].user_fee;
+        fee = u256_mul_u64(amount, HZ_FEE_TABLE[sel]);
+        if (sel < 192u) fee = u256_shr60(fee);
+        store_fr(delta + (size_t)pos_s[i] * 32, u256_neg(u256_add(amount, fee)));
+        if (pos_r[i] >= 0) store_fr(delta + (size_t)pos_r[i] * 32, amount);
+    }
+    store_fr(fee_out + (size_t)i * 32, fee);
+}
+
+// fee of slot j summed over the transactions of chunk c
+__global__ __launch_bounds__(64) void k_ledger_fee_sum(const uint8_t* __restrict__ fee, const int32_t* __restrict__ slot, uint8_t* __restrict__ chunk_sum,
+                                                       uint32_t m, uint32_t F) {
+    const uint32_t c = blockIdx.x, j = threadIdx.x;
+    if (j >= F) return;
+    Fc acc = u256_zero();
+    const uint32_t end = min(m, (c + 1) * HZ_LEDGER_CHUNK);
+    for (uint32_t i = c * HZ_LEDGER_CHUNK; i < end; i++)
+        if (slot[i] == (int32_t)j) acc = u256_add(acc, load_fr(fee + (size_t)i * 32));
+    store_fr(chunk_sum + ((size_t)c * F + j) * 32, acc);
+}
+
+// accumulated fee j after every transaction of chunk c; the last chunk leaves the final fees and the fee events' deltas
+__global__ __launch_bounds__(64) void k_ledger_fee_scan(const uint8_t* __restrict__ fee, const int32_t* __restrict__ slot, const uint8_t* __restrict__ chunk_sum,
+                                                        const int32_t* __restrict__ pos_fee, uint8_t* __restrict__ acc_after, uint8_t* __restrict__ final_fee,
+                                                        uint8_t* __restrict__ delta, uint32_t m, uint32_t F, uint32_t n_chunks) {
+    const uint32_t c = blockIdx.x, j = threadIdx.x;
+    if (j >= F) return;
+    Fc acc = u256_zero();
+    for (uint32_t b = 0; b < c; b++) acc = u256_add(acc, load_fr(chunk_sum + ((size_t)b * F + j) * 32));
+    const uint32_t end = min(m, (c + 1) * HZ_LEDGER_CHUNK);
+    for (uint32_t i = c * HZ_LEDGER_CHUNK; i < end; i++) {
+        if (slot[i] == (int32_t)j) acc = u256_add(acc, load_fr(fee + (size_t)i * 32));
+        store_fr(acc_after + ((size_t)i * F + j) * 32, acc);
+    }
+    if (c + 1 == n_chunks) {
+        store_fr(final_fee + (size_t)j * 32, acc);
+        if (pos_fee[j] >= 0) store_fr(delta + (size_t)pos_fee[j] * 32, acc);
+    }
+}
+
+__device__ __forceinline__ void ledger_fail(uint32_t* word, uint32_t unit, uint32_t reason) { atomicMin(word, (unit << 8) | reason); }
+
+// a lane per account group: the leaf before and after every event of the account, in order
+__global__ __launch_bounds__(64) void k_ledger_scan(const LedgerPos* __restrict__ pos, const uint32_t* __restrict__ seg_start, const hz_l2tx* __restrict__ txs,
+                                                    const uint32_t* __restrict__ plan_tok, const uint8_t* __restrict__ delta, const uint8_t* __restrict__ planes,
+                                                    uint8_t* __restrict__ before, uint8_t* __restrict__ records, uint32_t* __restrict__ fail_word, uint32_t N,
+                                                    uint32_t G, uint32_t m) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= G) return;
+    const uint32_t p0 = seg_start[g], p1 = seg_start[g + 1];
+    const uint32_t acct = pos[p0].acct;
+    Fc e0 = load_fr(planes + (size_t)acct * 32);
+    Fc bal = load_fr(planes + ((size_t)N + acct) * 32);
+    const Fc ay = load_fr(planes + ((size_t)2 * N + acct) * 32);
+    const Fc eth = load_fr(planes + ((size_t)3 * N + acct) * 32);
+    for (uint32_t p = p0; p < p1; p++) {
+        const LedgerPos ev = pos[p];
+        store_fr(before + (size_t)ev.ev * 64, e0);
+        store_fr(before + (size_t)ev.ev * 64 + 32, bal);
+        const bool sender = ev.kind == LEDGER_EV_SENDER, fee = ev.kind == LEDGER_EV_FEE;
+        const uint32_t tok = fee ? plan_tok[ev.unit - m] : txs[ev.unit].token_id;
+        if (e0.v[0] != tok) ledger_fail(fail_word, ev.unit, sender ? 1u : fee ? 6u : 4u);
+        if (sender) {
+            const uint64_t nonce = (uint64_t)e0.v[1] | ((uint64_t)(e0.v[2] & 0xFFu) << 32);
+            if (nonce != txs[ev.unit].nonce) ledger_fail(fail_word, ev.unit, 2u);
+            const uint64_t next = (nonce + 1) & ((1ull << 40) - 1);
+            e0.v[1] = (uint32_t)next;
+            e0.v[2] = (e0.v[2] & ~0xFFu) | (uint32_t)(next >> 32);
+        }
+        bal = u256_add(bal, load_fr(delta + (size_t)p * 32));
+        if (bal.v[7] >> 31)
+            ledger_fail(fail_word, ev.unit, 3u);
+        else if ((bal.v[6] | bal.v[7]) != 0u)
+            ledger_fail(fail_word, ev.unit, 5u);
+        uint8_t* rec = records + (size_t)ev.ev * 128;
+        store_fr(rec, e0);
+        store_fr(rec + 32, bal);
+        store_fr(rec + 64, ay);
+        store_fr(rec + 96, eth);
+    }
+}
+
+// tokenID, nonce, sign, balance, ay, ethAddr of the leaf event `ev` found, into six arrays at row `row`; ev < 0: zeros, tokenID = tok
+__device__ __forceinline__ void ledger_put_leaf(const LedgerOutDev& o, int base, uint32_t row, int32_t ev, uint32_t tok, const uint32_t* __restrict__ ev_acct,
+                                                const uint8_t* __restrict__ before, const uint8_t* __restrict__ planes, uint32_t N) {
+    Fc f[6];
+#pragma unroll
+    for (int q = 0; q < 6; q++) f[q] = u256_zero();
+    f[0].v[0] = tok;
+    if (ev >= 0) {
+        const Fc e0 = load_fr(before + (size_t)ev * 64);
+        const uint32_t acct = ev_acct[ev];
+        f[0].v[0] = e0.v[0];
+        f[1].v[0] = e0.v[1];
+        f[1].v[1] = e0.v[2] & 0xFFu;
+        f[2].v[0] = (e0.v[2] >> 8) & 1u;
+        f[3] = load_fr(before + (size_t)ev * 64 + 32);
+        f[4] = load_fr(planes + ((size_t)2 * N + acct) * 32);
+        f[5] = load_fr(planes + ((size_t)3 * N + acct) * 32);
+    }
+#pragma unroll
+    for (int q = 0; q < 6; q++) store_fr(o.a[base + q] + (size_t)row * 32, f[q]);
+}
+
+// a lane per transaction, then a lane per fee slot
+__global__ __launch_bounds__(64) void k_ledger_pack(const LedgerOutDev o, const hz_l2tx* __restrict__ txs, const int32_t* __restrict__ ev_s,
+                                                    const int32_t* __restrict__ ev_r, const int32_t* __restrict__ ev_fee, const uint32_t* __restrict__ ev_acct,
+                                                    const uint8_t* __restrict__ before, const uint8_t* __restrict__ planes, uint32_t N, uint32_t m, uint32_t F) {
+    const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= m + F) return;
+    if (u < m) {
+        const bool active = txs[u].from_idx != 0;
+        ledger_put_leaf(o, LO_TX1, u, ev_s[u], 0u, ev_acct, before, planes, N);
+        ledger_put_leaf(o, LO_TX2, u, ev_r[u], active ? txs[u].token_id : 0u, ev_acct, before, planes, N);
+    } else {
+        ledger_put_leaf(o, LO_TX3, u - m, ev_fee[u - m], 0u, ev_acct, before, planes, N);
+    }
+}
+
+// thread (unit u, d): sibling d of the unit's events (d < n_sib), or the root after the unit (d == n_sib)
+__global__ __launch_bounds__(256) void k_ledger_gather(const LedgerOutDev o, const int32_t* __restrict__ ev_s, const int32_t* __restrict__ ev_r,
+                                                       const int32_t* __restrict__ ev_fee, const int32_t* __restrict__ last_ev, const uint8_t* __restrict__ sib,
+                                                       const uint8_t* __restrict__ new_root, const uint8_t* __restrict__ root0, uint32_t k, uint32_t n_sib,
+                                                       uint32_t m, uint32_t F) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (size_t)(m + F) * (n_sib + 1)) return;
+    const uint32_t u = (uint32_t)(t / (n_sib + 1)), d = (uint32_t)(t - (size_t)u * (n_sib + 1));
+    if (d == n_sib) {
+        const int32_t le = last_ev[u];   // [m] of the transactions, then [F] of the fee slots
+        uint8_t* dst = u < m ? o.a[LO_ROOT_AFTER] + (size_t)u * 32 : o.a[LO_ROOT_FEE] + (size_t)(u - m) * 32;
+        store_fr(dst, le >= 0 ? load_fr(new_root + (size_t)le * 32) : load_fr(root0));
+        return;
+    }
+    if (u < m) {
+        const int32_t a = ev_s[u], b = ev_r[u];
+        store_fr(o.a[LO_SIB1] + ((size_t)u * n_sib + d) * 32, a >= 0 && d < k ? load_fr(sib + ((size_t)a * n_sib + d) * 32) : u256_zero());
+        store_fr(o.a[LO_SIB2] + ((size_t)u * n_sib + d) * 32, b >= 0 && d < k ? load_fr(sib + ((size_t)b * n_sib + d) * 32) : u256_zero());
+    } else {
+        const int32_t a = ev_fee[u - m];
+        store_fr(o.a[LO_SIB3] + ((size_t)(u - m) * n_sib + d) * 32, a >= 0 && d < k ? load_fr(sib + ((size_t)a * n_sib + d) * 32) : u256_zero());
+    }
+}
+
+// the leaf the last event of every group left, into the resident planes (ay and ethAddr never change)
+__global__ __launch_bounds__(64) void k_ledger_writeback(const LedgerPos* __restrict__ pos, const uint32_t* __restrict__ seg_start, const uint8_t* __restrict__ records,
+                                                         uint8_t* __restrict__ planes, uint32_t N, uint32_t G) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= G) return;
+    const LedgerPos ev = pos[seg_start[g + 1] - 1];
+    store_fr(planes + (size_t)ev.acct * 32, load_fr(records + (size_t)ev.ev * 128));
+    store_fr(planes + ((size_t)N + ev.acct) * 32, load_fr(records + (size_t)ev.ev * 128 + 32));
+}
+
+// thread (i, f): field f of account i
+__global__ __launch_bounds__(256) void k_ledger_accounts(const uint32_t* __restrict__ acct, const uint8_t* __restrict__ planes, uint8_t* __restrict__ out, uint32_t N,
+                                                         uint32_t n) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= 4 * n) return;
+    store_fr(out + (size_t)t * 32, load_fr(planes + ((size_t)(t & 3u) * N + acct[t >> 2]) * 32));
+}
+
+static hipError_t grow_dev(DevBuf& b, size_t bytes) { return b.bytes >= bytes ? hipSuccess : b.alloc(bytes + bytes / 2); }
+
+static size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+static const char* const LEDGER_REASON[7] = {"", "the sender's token is not the transaction's", "the nonce is not the sender's current nonce",
+                                             "the sender's balance is below amount + fee", "the receiver's token is not the transaction's",
+                                             "a new balance reaches 2^192", "the fee account's token is not the slot's plan token"};
+
+}  // namespace hz
+
+using namespace hz;
+
+struct hz_ledger {
+    int32_t device = 0;
+    uint32_t k = 0, N = 0;
+    uint64_t first_idx = 0;
+    hz_state* tree = nullptr;
+    DevBuf planes;             // resident: e0 | balance | ay | ethAddr, [N][32] each
+    DevBuf ints, work, outs;   // per call, grown on demand
+    void* h_ints = nullptr;    // pinned
+    size_t h_ints_bytes = 0;
+    uint32_t* h_fail = nullptr;   // pinned
+    LedgerPlan plan;
+    LedgerOutDev out_dev{};
+    bool have_outputs = false;
+    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
+    double device_ms = 0.0, semantic_ms = 0.0;
+    ~hz_ledger() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        if (e2) (void)hipEventDestroy(e2);
+        if (h_ints) (void)hipHostFree(h_ints);
+        if (h_fail) (void)hipHostFree(h_fail);
+        if (tree) hz_state_destroy(tree);
+    }
+};
+
+static hz_status ledger_ready(const hz_ledger* l, const char* who) {
+    if (!l) return set_err(HZ_ERR_ARG, "%s: null ledger", who);
+    if (!state_loaded(l->tree)) return set_err(HZ_ERR_ARG, "%s: the ledger holds no accounts yet (hz_ledger_load)", who);
+    return HZ_OK;
+}
+
+static bool ledger_has(uint64_t first_idx, uint64_t N, uint64_t idx) { return idx >= first_idx && idx - first_idx < N; }
+
+// the argument checks hz_ledger_apply_l2 and hz_ledger_plan_l2 share; on success the plan is made
+static hz_status ledger_check_plan(const char* who, size_t m, const hz_l2tx* txs, size_t F, const uint32_t* plan_tokens, const uint64_t* fee_idxs, uint32_t k,
+                                   uint64_t first_idx, LedgerPlan& plan) {
+    if ((m && !txs) || (F && (!plan_tokens || !fee_idxs))) return set_err(HZ_ERR_ARG, "%s: null argument", who);
+    if (F > HZ_LEDGER_MAX_F) return set_err(HZ_ERR_ARG, "%s: F = %zu fee slots (at most %u)", who, F, HZ_LEDGER_MAX_F);
+    if (m > HZ_LEDGER_MAX_TX) return set_err(HZ_ERR_ARG, "%s: %zu transactions in one call (at most %u)", who, m, HZ_LEDGER_MAX_TX);
+    const uint64_t N = 1ull << k, last = first_idx + N - 1;
+    for (size_t i = 0; i < m; i++) {
+        const hz_l2tx& t = txs[i];
+        if (t.from_idx == 0) continue;
+        if (!ledger_has(first_idx, N, t.from_idx))
+            return set_err(HZ_ERR_ARG, "%s: tx %zu: from_idx = %llu is outside the state (%llu .. %llu)", who, i, (unsigned long long)t.from_idx,
+                           (unsigned long long)first_idx, (unsigned long long)last);
+        if (t.to_idx <= 1)
+            return set_err(HZ_ERR_ARG, "%s: tx %zu: to_idx = %llu (%s) is not supported yet", who, i, (unsigned long long)t.to_idx,
+                           t.to_idx ? "an exit" : "a transfer to an address");
+        if (!ledger_has(first_idx, N, t.to_idx))
+            return set_err(HZ_ERR_ARG, "%s: tx %zu: to_idx = %llu is outside the state (%llu .. %llu)", who, i, (unsigned long long)t.to_idx,
+                           (unsigned long long)first_idx, (unsigned long long)last);
+        if (t.amount_f >> 40) return set_err(HZ_ERR_ARG, "%s: tx %zu: amount_f has more than 40 bits", who, i);
+    }
+    for (size_t j = 0; j < F; j++)
+        if (fee_idxs[j] != 0 && !ledger_has(first_idx, N, fee_idxs[j]))
+            return set_err(HZ_ERR_ARG, "%s: fee_idxs[%zu] = %llu is outside the state (%llu .. %llu)", who, j, (unsigned long long)fee_idxs[j],
+                           (unsigned long long)first_idx, (unsigned long long)last);
+    size_t events = 0;
+    for (size_t i = 0; i < m; i++)
+        if (txs[i].from_idx != 0) events += 1 + (ledger_mantissa(txs[i].amount_f) != 0);
+    for (size_t j = 0; j < F; j++) events += fee_idxs[j] != 0;
+    if (events > HZ_LEDGER_MAX_EVENTS) return set_err(HZ_ERR_ARG, "%s: %zu updates in one call (at most %u)", who, events, HZ_LEDGER_MAX_EVENTS);
+    ledger_plan_l2(m, txs, F, plan_tokens, fee_idxs, plan);
+    return HZ_OK;
+}
+
+extern "C" hz_status hz_ledger_plan_l2(size_t m, const hz_l2tx* txs, size_t F, const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs, int32_t k,
+                                       uint64_t first_idx, int32_t* ev_sender_out, int32_t* ev_receiver_out, int32_t* fee_slot_out, int32_t* last_event_out,
+                                       size_t* n_events_out, uint64_t* ev_account_out, int32_t* ev_prev_out) {
+    if (k < 4 || k > 24) return set_err(HZ_ERR_ARG, "hz_ledger_plan_l2: k = %d (4 .. 24)", k);
+    LedgerPlan p;
+    if (hz_status e = ledger_check_plan("hz_ledger_plan_l2", m, txs, F, fee_plan_tokens, fee_idxs, (uint32_t)k, first_idx, p)) return e;
+    for (size_t i = 0; i < m; i++) {
+        if (ev_sender_out) ev_sender_out[i] = p.ev_sender[i];
+        if (ev_receiver_out) ev_receiver_out[i] = p.ev_receiver[i];
+        if (fee_slot_out) fee_slot_out[i] = p.fee_slot[i];
+        if (last_event_out) last_event_out[i] = p.last_event[i];
+    }
+    if (n_events_out) *n_events_out = p.account.size();
+    for (size_t e = 0; e < p.account.size(); e++) {
+        if (ev_account_out) ev_account_out[e] = p.account[e];
+        if (ev_prev_out) ev_prev_out[e] = p.prev_same[e];
+    }
+    return HZ_OK;
+}
+
+extern "C" hz_status hz_ledger_create(int32_t device, int32_t k, uint64_t first_idx, hz_ledger** out) {
+    if (!out) return set_err(HZ_ERR_ARG, "hz_ledger_create: null argument");
+    *out = nullptr;
+    std::unique_ptr<hz_ledger> l(new hz_ledger);
+    if (hz_status e = hz_state_create(device, k, first_idx, &l->tree)) return e;
+    l->device = device;
+    l->k = (uint32_t)k;
+    l->N = 1u << k;
+    l->first_idx = first_idx;
+    HZ_HIP(hipSetDevice(device));
+    HZ_HIP(l->planes.alloc((size_t)4 * l->N * 32));
+    HZ_HIP(hipHostMalloc((void**)&l->h_fail, 64, hipHostMallocDefault));
+    HZ_HIP(hipEventCreate(&l->e0));
+    HZ_HIP(hipEventCreate(&l->e1));
+    HZ_HIP(hipEventCreate(&l->e2));
+    *out = l.release();
+    return HZ_OK;
+}
+
+extern "C" void hz_ledger_destroy(hz_ledger* l) {
+    if (!l) return;
+    (void)hipSetDevice(l->device);
+    (void)hipStreamSynchronize(state_stream(l->tree));
+    delete l;
+}
+
+extern "C" hz_status hz_ledger_load(hz_ledger* l, const uint8_t* e0, const uint8_t* balance, const uint8_t* ay, const uint8_t* eth_addr) {
+    if (!l || !e0 || !balance || !ay || !eth_addr) return set_err(HZ_ERR_ARG, "hz_ledger_load: null argument");
+    l->have_outputs = false;
+    if (hz_status e = hz_state_load(l->tree, e0, balance, ay, eth_addr)) return e;   // checks every field < r
+    const uint8_t* src[4] = {e0, balance, ay, eth_addr};
+    hipStream_t s = state_stream(l->tree);
+    HZ_HIP(hipSetDevice(l->device));
+    for (int f = 0; f < 4; f++) HZ_HIP(hipMemcpyAsync((uint8_t*)l->planes.p + (size_t)f * l->N * 32, src[f], (size_t)l->N * 32, hipMemcpyHostToDevice, s));
+    HZ_HIP(hipStreamSynchronize(s));
+    return HZ_OK;
+}
+
+extern "C" hz_status hz_ledger_root(hz_ledger* l, uint8_t* out32) {
+    if (hz_status e = ledger_ready(l, "hz_ledger_root")) return e;
+    return hz_state_root(l->tree, out32);
+}
+
+extern "C" hz_state* hz_ledger_tree(hz_ledger* l) { return l ? l->tree : nullptr; }
+extern "C" double hz_ledger_device_ms(const hz_ledger* l) { return l ? l->device_ms : 0.0; }
+extern "C" double hz_ledger_semantic_ms(const hz_ledger* l) { return l ? l->semantic_ms : 0.0; }
+
+extern "C" hz_status hz_ledger_accounts(hz_ledger* l, size_t n, const uint64_t* idx, uint8_t* fields_out) {
+    if (hz_status e = ledger_ready(l, "hz_ledger_accounts")) return e;
+    if (n == 0) return HZ_OK;
+    if (!idx || !fields_out) return set_err(HZ_ERR_ARG, "hz_ledger_accounts: null argument");
+    if (n > l->N) return set_err(HZ_ERR_ARG, "hz_ledger_accounts: %zu accounts in one call (the state holds %u)", n, l->N);
+    std::vector<uint32_t> acct(n);
+    for (size_t i = 0; i < n; i++) {
+        if (!ledger_has(l->first_idx, l->N, idx[i]))
+            return set_err(HZ_ERR_ARG, "hz_ledger_accounts: idx[%zu] = %llu is outside the state", i, (unsigned long long)idx[i]);
+        acct[i] = (uint32_t)(idx[i] - l->first_idx);
+    }
+    HZ_HIP(hipSetDevice(l->device));
+    l->have_outputs = false;   // the call's buffers are reused
+    hipStream_t s = state_stream(l->tree);
+    HZ_HIP(grow_dev(l->ints, n * 4));
+    HZ_HIP(grow_dev(l->work, n * 128));
+    HZ_HIP(hipMemcpyAsync(l->ints.p, acct.data(), n * 4, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_ledger_accounts, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, s, (const uint32_t*)l->ints.p, (const uint8_t*)l->planes.p,
+                       (uint8_t*)l->work.p, l->N, (uint32_t)n);
+    HZ_HIP(hipGetLastError());
+    HZ_HIP(hipMemcpyAsync(fields_out, l->work.p, n * 128, hipMemcpyDeviceToHost, s));
+    HZ_HIP(hipStreamSynchronize(s));
+    return HZ_OK;
+}
+
+extern "C" hz_status hz_ledger_outputs_dev(hz_ledger* l, hz_ledger_out* dev) {
+    if (!l || !dev) return set_err(HZ_ERR_ARG, "hz_ledger_outputs_dev: null argument");
+    if (!l->have_outputs) return set_err(HZ_ERR_ARG, "hz_ledger_outputs_dev: no successful hz_ledger_apply_l2 since the ledger's last other call");
+    uint8_t** d = (uint8_t**)dev;
+    for (int a = 0; a < HZ_LEDGER_ARRAYS; a++) d[a] = l->out_dev.a[a];
+    return HZ_OK;
+}
+
+extern "C" hz_status hz_ledger_apply_l2(hz_ledger* l, size_t m, const hz_l2tx* txs, size_t F, const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs,
+                                        size_t n_sib, const hz_ledger_out* out) {
+    static_assert(sizeof(hz_ledger_out) == HZ_LEDGER_ARRAYS * sizeof(uint8_t*), "hz_ledger_out is an array of pointers");
+    if (hz_status e = ledger_ready(l, "hz_ledger_apply_l2")) return e;
+    const uint32_t k = l->k, N = l->N;
+    if (n_sib < k || n_sib > 64) return set_err(HZ_ERR_ARG, "hz_ledger_apply_l2: n_sib = %zu (%u .. 64)", n_sib, k);
+    LedgerPlan& p = l->plan;
+    if (hz_status e = ledger_check_plan("hz_ledger_apply_l2", m, txs, F, fee_plan_tokens, fee_idxs, k, l->first_idx, p)) return e;
+    l->have_outputs = false;
+    const uint32_t m32 = (uint32_t)m, F32 = (uint32_t)F, S = (uint32_t)n_sib;
+    const uint32_t M = (uint32_t)p.account.size(), G = (uint32_t)p.seg_start.size() - 1;
+    const uint32_t n_chunks = m32 ? (m32 + HZ_LEDGER_CHUNK - 1) / HZ_LEDGER_CHUNK : 1u;
+    HZ_HIP(hipSetDevice(l->device));
+    hipStream_t s = state_stream(l->tree);
+
+    // ---- integer tables, one pinned block
+    size_t o = 0;
+    auto take = [&](size_t bytes) {
+        const size_t at = o;
+        o = align16(o + bytes);
+        return at;
+    };
+    const size_t o_tx = take(m * sizeof(hz_l2tx)), o_pos_s = take(m * 4), o_pos_r = take(m * 4), o_ev_s = take(m * 4), o_ev_r = take(m * 4),
+                 o_slot = take(m * 4), o_last = take((m + F) * 4), o_ev_fee = take(F * 4), o_pos_fee = take(F * 4), o_plan = take(F * 4),
+                 o_acct = take((size_t)M * 4), o_pos = take((size_t)M * sizeof(LedgerPos)), o_seg = take(((size_t)G + 1) * 4);
+    const size_t ints_bytes = o ? o : 16;
+    if (l->h_ints_bytes < ints_bytes) {
+        if (l->h_ints) (void)hipHostFree(l->h_ints);
+        l->h_ints = nullptr;
+        l->h_ints_bytes = 0;
+        HZ_HIP(hipHostMalloc(&l->h_ints, ints_bytes + ints_bytes / 2, hipHostMallocDefault));
+        l->h_ints_bytes = ints_bytes + ints_bytes / 2;
+    }
+    uint8_t* hb = (uint8_t*)l->h_ints;
+    std::vector<uint32_t> pos_of(M);
+    for (uint32_t q = 0; q < M; q++) pos_of[p.perm[q]] = q;
+    if (m) memcpy(hb + o_tx, txs, m * sizeof(hz_l2tx));
+    for (size_t i = 0; i < m; i++) {
+        ((int32_t*)(hb + o_pos_s))[i] = p.ev_sender[i] >= 0 ? (int32_t)pos_of[p.ev_sender[i]] : -1;
+        ((int32_t*)(hb + o_pos_r))[i] = p.ev_receiver[i] >= 0 ? (int32_t)pos_of[p.ev_receiver[i]] : -1;
+        ((int32_t*)(hb + o_ev_s))[i] = p.ev_sender[i];
+        ((int32_t*)(hb + o_ev_r))[i] = p.ev_receiver[i];
+        ((int32_t*)(hb + o_slot))[i] = p.fee_slot[i];
+        ((int32_t*)(hb + o_last))[i] = p.last_event[i];
+    }
+    for (size_t j = 0; j < F; j++) {
+        ((int32_t*)(hb + o_last))[m + j] = p.last_event_fee[j];
+        ((int32_t*)(hb + o_ev_fee))[j] = p.ev_fee[j];
+        ((int32_t*)(hb + o_pos_fee))[j] = p.ev_fee[j] >= 0 ? (int32_t)pos_of[p.ev_fee[j]] : -1;
+        ((uint32_t*)(hb + o_plan))[j] = fee_plan_tokens[j];
+    }
+    for (uint32_t e = 0; e < M; e++) ((uint32_t*)(hb + o_acct))[e] = (uint32_t)(p.account[e] - l->first_idx);
+    for (uint32_t q = 0; q < M; q++) {
+        const uint32_t e = p.perm[q];
+        ((LedgerPos*)(hb + o_pos))[q] = LedgerPos{e, p.unit[e], p.kind[e], (uint32_t)(p.account[e] - l->first_idx)};
+    }
+    for (uint32_t g = 0; g <= G; g++) ((uint32_t*)(hb + o_seg))[g] = p.seg_start[g];
+
+    // ---- device buffers: work = fee[m] | chunk sums | delta[M] | before[M][2] | failure word; outs = the 27 arrays
+    size_t w = 0;
+    const size_t w_fee = w;
+    w += (size_t)(m32 ? m32 : 1) * 32;
+    const size_t w_chunk = w;
+    w += (size_t)n_chunks * (F32 ? F32 : 1) * 32;
+    const size_t w_delta = w;
+    w += (size_t)(M ? M : 1) * 32;
+    const size_t w_before = w;
+    w += (size_t)(M ? M : 1) * 64;
+    const size_t w_fail = w;
+    w += 64;
+    size_t elems[HZ_LEDGER_ARRAYS];
+    for (int a = 0; a < HZ_LEDGER_ARRAYS; a++) elems[a] = a < LO_TX3 ? m : F;
+    elems[LO_SIB1] = elems[LO_SIB2] = m * n_sib;
+    elems[LO_ACC_FEE] = m * F;
+    elems[LO_SIB3] = F * n_sib;
+    elems[LO_OLD_ROOT] = elems[LO_NEW_ROOT] = 1;
+    size_t out_bytes = 0;
+    for (int a = 0; a < HZ_LEDGER_ARRAYS; a++) out_bytes += elems[a] * 32;
+    HZ_HIP(grow_dev(l->ints, ints_bytes));
+    HZ_HIP(grow_dev(l->work, w));
+    HZ_HIP(grow_dev(l->outs, out_bytes));
+    LedgerOutDev od;
+    {
+        uint8_t* at = (uint8_t*)l->outs.p;
+        for (int a = 0; a < HZ_LEDGER_ARRAYS; a++) {
+            od.a[a] = at;
+            at += elems[a] * 32;
+        }
+    }
+    uint8_t* db = (uint8_t*)l->ints.p;
+    uint8_t* wb = (uint8_t*)l->work.p;
+    const hz_l2tx* d_txs = (const hz_l2tx*)(db + o_tx);
+    const LedgerPos* d_pos = (const LedgerPos*)(db + o_pos);
+    const uint32_t* d_seg = (const uint32_t*)(db + o_seg);
+    uint32_t* d_fail = (uint32_t*)(wb + w_fail);
+
+    StateCallBufs tb{};
+    if (M)
+        if (hz_status e = state_apply_prepare(l->tree, M, p.account.data(), S, &tb)) return e;
+    HZ_HIP(hipMemcpyAsync(l->ints.p, l->h_ints, ints_bytes, hipMemcpyHostToDevice, s));
+    HZ_HIP(hipMemsetAsync(d_fail, 0xFF, 4, s));
+
+    // ---- the semantic kernels
+    HZ_HIP(hipEventRecord(l->e0, s));
+    if (m32) {
+        hipLaunchKernelGGL(k_ledger_tx, dim3((m32 + 63) / 64), dim3(64), 0, s, d_txs, (const int32_t*)(db + o_pos_s), (const int32_t*)(db + o_pos_r), wb + w_fee,
+                           wb + w_delta, m32);
+        HZ_HIP(hipGetLastError());
+    }
+    if (F32) {
+        hipLaunchKernelGGL(k_ledger_fee_sum, dim3(n_chunks), dim3(64), 0, s, (const uint8_t*)(wb + w_fee), (const int32_t*)(db + o_slot), wb + w_chunk, m32, F32);
+        HZ_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_ledger_fee_scan, dim3(n_chunks), dim3(64), 0, s, (const uint8_t*)(wb + w_fee), (const int32_t*)(db + o_slot),
+                           (const uint8_t*)(wb + w_chunk), (const int32_t*)(db + o_pos_fee), od.a[LO_ACC_FEE], od.a[LO_FINAL_FEE], wb + w_delta, m32, F32, n_chunks);
+        HZ_HIP(hipGetLastError());
+    }
+    if (G) {
+        hipLaunchKernelGGL(k_ledger_scan, dim3((G + 63) / 64), dim3(64), 0, s, d_pos, d_seg, d_txs, (const uint32_t*)(db + o_plan), (const uint8_t*)(wb + w_delta),
+                           (const uint8_t*)l->planes.p, wb + w_before, tb.fields, d_fail, N, G, m32);
+        HZ_HIP(hipGetLastError());
+    }
+    HZ_HIP(hipEventRecord(l->e1, s));
+    HZ_HIP(hipMemcpyAsync(l->h_fail, d_fail, 4, hipMemcpyDeviceToHost, s));
+    HZ_HIP(hipStreamSynchronize(s));   // the one round trip: nothing resident has been written yet
+    const uint32_t word = *l->h_fail;
+    if (word != 0xFFFFFFFFu) {
+        const uint32_t unit = word >> 8, reason = word & 0xFFu;
+        if (unit >= m32)
+            return set_err(HZ_ERR_INPUT, "hz_ledger_apply_l2: refused at index %u (fee slot %u), reason %u: %s", unit, unit - m32, reason,
+                           LEDGER_REASON[reason < 7 ? reason : 0]);
+        return set_err(HZ_ERR_INPUT, "hz_ledger_apply_l2: refused at index %u (transaction %u), reason %u: %s", unit, unit, reason,
+                       LEDGER_REASON[reason < 7 ? reason : 0]);
+    }
+
+    // ---- outputs, tree, resident planes
+    if (m32 + F32) {
+        hipLaunchKernelGGL(k_ledger_pack, dim3((m32 + F32 + 63) / 64), dim3(64), 0, s, od, d_txs, (const int32_t*)(db + o_ev_s), (const int32_t*)(db + o_ev_r),
+                           (const int32_t*)(db + o_ev_fee), (const uint32_t*)(db + o_acct), (const uint8_t*)(wb + w_before), (const uint8_t*)l->planes.p, N, m32, F32);
+        HZ_HIP(hipGetLastError());
+    }
+    const uint8_t* root0 = state_root_dev(l->tree);
+    if (M) {
+        if (hz_status e = state_apply_launch(l->tree, M, S, false)) return e;
+        root0 = tb.old_root;
+    }
+    HZ_HIP(hipMemcpyAsync(od.a[LO_OLD_ROOT], root0, 32, hipMemcpyDeviceToDevice, s));
+    HZ_HIP(hipMemcpyAsync(od.a[LO_NEW_ROOT], M ? tb.new_root + (size_t)(M - 1) * 32 : root0, 32, hipMemcpyDeviceToDevice, s));
+    if (m32 + F32) {
+        const size_t threads = (size_t)(m32 + F32) * (S + 1);
+        hipLaunchKernelGGL(k_ledger_gather, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, od, (const int32_t*)(db + o_ev_s), (const int32_t*)(db + o_ev_r),
+                           (const int32_t*)(db + o_ev_fee), (const int32_t*)(db + o_last), (const uint8_t*)tb.siblings, (const uint8_t*)tb.new_root, root0, k, S, m32,
+                           F32);
+        HZ_HIP(hipGetLastError());
+    }
+    if (G) {
+        hipLaunchKernelGGL(k_ledger_writeback, dim3((G + 63) / 64), dim3(64), 0, s, d_pos, d_seg, (const uint8_t*)tb.fields, (uint8_t*)l->planes.p, N, G);
+        HZ_HIP(hipGetLastError());
+    }
+    HZ_HIP(hipEventRecord(l->e2, s));
+    if (out) {
+        uint8_t* const* h = (uint8_t* const*)out;
+        for (int a = 0; a < HZ_LEDGER_ARRAYS; a++)
+            if (h[a] && elems[a]) HZ_HIP(hipMemcpyAsync(h[a], od.a[a], elems[a] * 32, hipMemcpyDeviceToHost, s));
+    }
+    if (M) {
+        if (hz_status e = state_apply_finish(l->tree)) return e;
+    } else {
+        HZ_HIP(hipStreamSynchronize(s));
+    }
+    float ms = 0;
+    HZ_HIP(hipEventElapsedTime(&ms, l->e0, l->e1));
+    l->semantic_ms = ms;
+    HZ_HIP(hipEventElapsedTime(&ms, l->e0, l->e2));
+    l->device_ms = ms;
+    l->out_dev = od;
+    l->have_outputs = true;
+    return HZ_OK;
+}

@@ -1,0 +1,100 @@
+// hz_ledger's host planner: the integer work of a batch of L2 transfers -- which update events the batch makes, on which accounts,
+// in which order, and where each fee goes. No field arithmetic, no hash, no HIP: hz_ledger_plan_l2 runs it without a device and the
+// CPU suite checks it against a Python restatement.
+//
+// Events. Active transaction i (from_idx != 0) makes a SENDER event and, when its amount is not zero (the float40's 35-bit mantissa is
+// not zero: integer work), a RECEIVER event right after it; after the last transaction every fee slot j with fee_idxs[j] != 0 makes a
+// FEE event, in slot order. The events in that order are the updates of one hz_state apply. Events of one account are grouped, in order
+// (perm / seg_start): a device lane walks a group and carries the account's balance and nonce through it.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include <vector>
+#include "../../include/hermez_witness.h"
+
+namespace hz {
+
+enum : uint8_t { LEDGER_EV_SENDER = 0, LEDGER_EV_RECEIVER = 1, LEDGER_EV_FEE = 2 };
+
+struct LedgerPlan {
+    // per transaction
+    std::vector<int32_t> ev_sender, ev_receiver;   // event numbers, -1: none
+    std::vector<int32_t> fee_slot;                  // first slot whose plan token is the transaction's, -1: none (or a NOP)
+    std::vector<int32_t> last_event;                // the last event made by transactions 0 .. i, -1: none yet
+    // per fee slot
+    std::vector<int32_t> ev_fee, last_event_fee;    // the slot's event (-1: fee_idxs[j] == 0); the last event up to and including slot j
+    // per event
+    std::vector<uint64_t> account;
+    std::vector<int32_t> prev_same;                 // the previous event on the same account, -1: none
+    std::vector<uint32_t> unit;                     // transaction i, or m + j for the event of fee slot j
+    std::vector<uint8_t> kind;
+    // grouping: the events of group g are perm[seg_start[g] .. seg_start[g + 1]), ascending
+    std::vector<uint32_t> perm, seg_start;
+};
+
+inline uint64_t ledger_mantissa(uint64_t amount_f) { return amount_f & ((1ull << 35) - 1); }
+
+inline void ledger_plan_l2(size_t m, const hz_l2tx* txs, size_t F, const uint32_t* plan_tokens, const uint64_t* fee_idxs, LedgerPlan& p) {
+    p.ev_sender.assign(m, -1);
+    p.ev_receiver.assign(m, -1);
+    p.fee_slot.assign(m, -1);
+    p.last_event.assign(m, -1);
+    p.ev_fee.assign(F, -1);
+    p.last_event_fee.assign(F, -1);
+    p.account.clear();
+    p.unit.clear();
+    p.kind.clear();
+    auto event = [&](uint64_t account, size_t unit, uint8_t kind) {
+        p.account.push_back(account);
+        p.unit.push_back((uint32_t)unit);
+        p.kind.push_back(kind);
+        return (int32_t)(p.account.size() - 1);
+    };
+    for (size_t i = 0; i < m; i++) {
+        const hz_l2tx& t = txs[i];
+        if (t.from_idx != 0) {
+            p.ev_sender[i] = event(t.from_idx, i, LEDGER_EV_SENDER);
+            if (ledger_mantissa(t.amount_f) != 0) p.ev_receiver[i] = event(t.to_idx, i, LEDGER_EV_RECEIVER);
+            for (size_t s = 0; s < F; s++)
+                if (plan_tokens[s] == t.token_id) {
+                    p.fee_slot[i] = (int32_t)s;
+                    break;
+                }
+        }
+        p.last_event[i] = (int32_t)p.account.size() - 1;
+    }
+    for (size_t j = 0; j < F; j++) {
+        if (fee_idxs[j] != 0) p.ev_fee[j] = event(fee_idxs[j], m + j, LEDGER_EV_FEE);
+        p.last_event_fee[j] = (int32_t)p.account.size() - 1;
+    }
+
+    // stable grouping by account: open addressing account -> group, groups numbered by first appearance
+    const uint32_t M = (uint32_t)p.account.size();
+    uint32_t cap = 16;
+    while (cap < 2 * M) cap <<= 1;
+    std::vector<uint64_t> key(cap, ~0ull);
+    std::vector<uint32_t> group(cap), ev_group(M), tail;
+    p.prev_same.assign(M, -1);
+    p.seg_start.assign(1, 0);
+    for (uint32_t e = 0; e < M; e++) {
+        uint32_t s = (uint32_t)((p.account[e] * 0x9E3779B97F4A7C15ull) >> 40) & (cap - 1);
+        while (key[s] != ~0ull && key[s] != p.account[e]) s = (s + 1) & (cap - 1);
+        if (key[s] == ~0ull) {
+            key[s] = p.account[e];
+            group[s] = (uint32_t)tail.size();
+            tail.push_back(e);
+            p.seg_start.push_back(0);
+        } else {
+            p.prev_same[e] = (int32_t)tail[group[s]];
+            tail[group[s]] = e;
+        }
+        ev_group[e] = group[s];
+        p.seg_start[ev_group[e] + 1]++;
+    }
+    for (size_t g = 1; g < p.seg_start.size(); g++) p.seg_start[g] += p.seg_start[g - 1];
+    std::vector<uint32_t> at(p.seg_start.begin(), p.seg_start.end() - 1);
+    p.perm.resize(M);
+    for (uint32_t e = 0; e < M; e++) p.perm[at[ev_group[e]]++] = e;
+}
+
+}  // namespace hz

@@ -25,6 +25,7 @@
 #include "kernels.h"
 #include "poseidon_quad.h"
 #include "state_dev.h"
+#include "state_internal.h"
 
 #define HZ_STATE_MIN_K 4
 #define HZ_STATE_MAX_K 24
@@ -288,19 +289,13 @@ extern "C" hz_status hz_state_root(hz_state* st, uint8_t* out32) {
 
 extern "C" double hz_state_device_ms(const hz_state* st) { return st ? st->device_ms : 0.0; }
 
-extern "C" hz_status hz_state_apply(hz_state* st, size_t m, const uint64_t* idx, const uint8_t* fields, size_t n_sib, uint8_t* siblings_out,
-                                    uint8_t* old_value_out, uint8_t* old_root_out, uint8_t* new_root_out) {
-    if (hz_status e = state_ready(st, "hz_state_apply")) return e;
-    if (m == 0) return HZ_OK;
-    if (!idx || !fields) return set_err(HZ_ERR_ARG, "hz_state_apply: null argument");
-    if (m > HZ_STATE_MAX_M) return set_err(HZ_ERR_ARG, "hz_state_apply: %zu updates in one call (at most %u)", m, HZ_STATE_MAX_M);
-    const uint32_t k = st->k, M = (uint32_t)m;
-    if (n_sib < k || n_sib > 64) return set_err(HZ_ERR_ARG, "hz_state_apply: n_sib = %zu (%u .. 64)", n_sib, k);
-    if (hz_status e = state_keys(st, "hz_state_apply", idx, m)) return e;
-    for (size_t i = 0; i < m * 4; i++)
-        if (!canon_lt_p(fields + i * 32)) return set_err(HZ_ERR_INPUT, "hz_state_apply: field %zu of update %zu >= r", i & 3, i >> 2);
+// The body of an apply in two halves, so that a caller whose fields are already in device memory (ledger.hip) runs the same tree update
+// as hz_state_apply. prepare: the integer tables of the call (which earlier update made the version a thread reads), the per-call
+// buffers grown, the tables queued for upload. launch: state hash, leaf hash, k levels, write-back; siblings, old values and roots
+// stay in the buffers `prepare` named. Nothing here synchronises.
+hz_status hz::state_apply_prepare(hz_state* st, uint32_t M, const uint64_t* idx, uint32_t n_sib, StateCallBufs* out) {
+    const uint32_t k = st->k;
     HZ_HIP(hipSetDevice(st->device));
-
     // integer tables of the call, one pinned block: keys u64[m] | residues u32[m] | prev_same i32[m] | sib_src i32[k][m] | last u8[k + 1][m]
     const size_t o_res = (size_t)M * 8, o_prev = o_res + (size_t)M * 4, o_src = o_prev + (size_t)M * 4, o_last = o_src + (size_t)k * M * 4;
     const size_t ints_bytes = o_last + (size_t)(k + 1) * M;
@@ -336,6 +331,20 @@ extern "C" hz_status hz_state_apply(hz_state* st, size_t m, const uint64_t* idx,
     HZ_HIP(grow(st->oldval, (size_t)M * 32));
     HZ_HIP(grow(st->ver, ((size_t)(k + 1) * M + 1) * 32));   // one element ahead of version 0 of the root: the root the call found
     HZ_HIP(grow(st->sib, (size_t)M * n_sib * 32));
+    HZ_HIP(hipMemcpyAsync(st->ints.p, st->h_ints.p, ints_bytes, hipMemcpyHostToDevice, st->s));
+    if (out) {
+        out->fields = (uint8_t*)st->fields.p;
+        out->siblings = (uint8_t*)st->sib.p;
+        out->old_value = (uint8_t*)st->oldval.p;
+        out->old_root = (uint8_t*)st->ver.p;
+        out->new_root = (uint8_t*)st->ver.p + 32;
+    }
+    return HZ_OK;
+}
+
+hz_status hz::state_apply_launch(hz_state* st, uint32_t M, uint32_t n_sib, bool clear_siblings) {
+    const uint32_t k = st->k;
+    const size_t o_res = (size_t)M * 8, o_prev = o_res + (size_t)M * 4, o_src = o_prev + (size_t)M * 4, o_last = o_src + (size_t)k * M * 4;
     uint8_t* db = (uint8_t*)st->ints.p;
     const uint64_t* d_keys = (const uint64_t*)db;
     const uint32_t* d_res = (const uint32_t*)(db + o_res);
@@ -344,9 +353,7 @@ extern "C" hz_status hz_state_apply(hz_state* st, size_t m, const uint64_t* idx,
     const uint8_t* d_last = db + o_last;
     uint8_t* ver = (uint8_t*)st->ver.p + 32;   // [k + 1][m], depth 0 first
     hipStream_t s = st->s;
-    HZ_HIP(hipMemcpyAsync(st->ints.p, st->h_ints.p, ints_bytes, hipMemcpyHostToDevice, s));
-    HZ_HIP(hipMemcpyAsync(st->fields.p, fields, (size_t)M * 128, hipMemcpyHostToDevice, s));
-    if (siblings_out && n_sib > k) HZ_HIP(hipMemsetAsync(st->sib.p, 0, (size_t)M * n_sib * 32, s));
+    if (clear_siblings && n_sib > k) HZ_HIP(hipMemsetAsync(st->sib.p, 0, (size_t)M * n_sib * 32, s));
     HZ_HIP(hipEventRecord(st->e0, s));
     hipLaunchKernelGGL(k_state_value, dim3((M + 63) / 64), dim3(64), 0, s, (const uint8_t*)st->fields.p, (size_t)4, (size_t)1, (uint8_t*)st->uval.p, M);
     HZ_HIP(hipGetLastError());
@@ -355,7 +362,7 @@ extern "C" hz_status hz_state_apply(hz_state* st, size_t m, const uint64_t* idx,
     HZ_HIP(hipGetLastError());
     for (uint32_t d = k; d-- > 0;) {
         hipLaunchKernelGGL(k_state_level_apply, dim3((4 * M + 63) / 64), dim3(64), 0, s, d_res, d_src + (size_t)d * M, (const uint8_t*)(ver + (size_t)(d + 1) * M * 32),
-                           (const uint8_t*)st->level(d + 1), ver + (size_t)d * M * 32, (uint8_t*)st->sib.p, (const Fr*)st->pos3.p, d, (uint32_t)n_sib, M);
+                           (const uint8_t*)st->level(d + 1), ver + (size_t)d * M * 32, (uint8_t*)st->sib.p, (const Fr*)st->pos3.p, d, n_sib, M);
         HZ_HIP(hipGetLastError());
     }
     // the root before the first update is set aside before the write-back replaces it: old roots = (that, versions 0 .. m - 2 of the root)
@@ -365,15 +372,42 @@ extern "C" hz_status hz_state_apply(hz_state* st, size_t m, const uint64_t* idx,
                        (uint8_t*)st->levels.p, (uint8_t*)st->value.p, st->first_idx, k, M);
     HZ_HIP(hipGetLastError());
     HZ_HIP(hipEventRecord(st->e1, s));
-    if (old_root_out) HZ_HIP(hipMemcpyAsync(old_root_out, st->ver.p, (size_t)M * 32, hipMemcpyDeviceToHost, s));
-    if (new_root_out) HZ_HIP(hipMemcpyAsync(new_root_out, ver, (size_t)M * 32, hipMemcpyDeviceToHost, s));
-    if (old_value_out) HZ_HIP(hipMemcpyAsync(old_value_out, st->oldval.p, (size_t)M * 32, hipMemcpyDeviceToHost, s));
-    if (siblings_out) HZ_HIP(hipMemcpyAsync(siblings_out, st->sib.p, (size_t)M * n_sib * 32, hipMemcpyDeviceToHost, s));
-    HZ_HIP(hipStreamSynchronize(s));
+    return HZ_OK;
+}
+
+hz_status hz::state_apply_finish(hz_state* st) {
+    HZ_HIP(hipStreamSynchronize(st->s));
     float ms = 0;
     HZ_HIP(hipEventElapsedTime(&ms, st->e0, st->e1));
     st->device_ms = ms;
     return HZ_OK;
+}
+
+hipStream_t hz::state_stream(const hz_state* st) { return st->s; }
+const uint8_t* hz::state_root_dev(const hz_state* st) { return st->level(0); }
+bool hz::state_loaded(const hz_state* st) { return st->loaded; }
+
+extern "C" hz_status hz_state_apply(hz_state* st, size_t m, const uint64_t* idx, const uint8_t* fields, size_t n_sib, uint8_t* siblings_out,
+                                    uint8_t* old_value_out, uint8_t* old_root_out, uint8_t* new_root_out) {
+    if (hz_status e = state_ready(st, "hz_state_apply")) return e;
+    if (m == 0) return HZ_OK;
+    if (!idx || !fields) return set_err(HZ_ERR_ARG, "hz_state_apply: null argument");
+    if (m > HZ_STATE_MAX_M) return set_err(HZ_ERR_ARG, "hz_state_apply: %zu updates in one call (at most %u)", m, HZ_STATE_MAX_M);
+    const uint32_t k = st->k, M = (uint32_t)m;
+    if (n_sib < k || n_sib > 64) return set_err(HZ_ERR_ARG, "hz_state_apply: n_sib = %zu (%u .. 64)", n_sib, k);
+    if (hz_status e = state_keys(st, "hz_state_apply", idx, m)) return e;
+    for (size_t i = 0; i < m * 4; i++)
+        if (!canon_lt_p(fields + i * 32)) return set_err(HZ_ERR_INPUT, "hz_state_apply: field %zu of update %zu >= r", i & 3, i >> 2);
+    StateCallBufs b;
+    if (hz_status e = state_apply_prepare(st, M, idx, (uint32_t)n_sib, &b)) return e;
+    hipStream_t s = st->s;
+    HZ_HIP(hipMemcpyAsync(b.fields, fields, (size_t)M * 128, hipMemcpyHostToDevice, s));
+    if (hz_status e = state_apply_launch(st, M, (uint32_t)n_sib, siblings_out != nullptr)) return e;
+    if (old_root_out) HZ_HIP(hipMemcpyAsync(old_root_out, b.old_root, (size_t)M * 32, hipMemcpyDeviceToHost, s));
+    if (new_root_out) HZ_HIP(hipMemcpyAsync(new_root_out, b.new_root, (size_t)M * 32, hipMemcpyDeviceToHost, s));
+    if (old_value_out) HZ_HIP(hipMemcpyAsync(old_value_out, b.old_value, (size_t)M * 32, hipMemcpyDeviceToHost, s));
+    if (siblings_out) HZ_HIP(hipMemcpyAsync(siblings_out, b.siblings, (size_t)M * n_sib * 32, hipMemcpyDeviceToHost, s));
+    return state_apply_finish(st);
 }
 
 extern "C" hz_status hz_state_proofs(hz_state* st, size_t n, const uint64_t* idx, size_t n_sib, uint8_t* siblings_out, uint8_t* value_out) {

@@ -338,7 +338,7 @@ hz_status hz_poseidon_dag(int32_t device, uint8_t* vals, uint64_t n_vals, const 
  *                       skipped), value_out the N state hashes -- what hzb_db_set_base (hz_host.h) takes as a base
  *   hz_state_device_ms  device time of the last load / apply (first kernel to write-back, HIP events)
  * OUT OF SCOPE: inserts and new accounts (a deposit that creates a leaf changes the tree's shape), the exit tree, transaction semantics
- * (balances, nonces, fees: the batch builder's), more than one device per state. A state is used by one thread at a time. */
+ * (balances, nonces, fees: hz_ledger's, below), more than one device per state. A state is used by one thread at a time. */
 typedef struct hz_state hz_state;
 hz_status hz_state_create(int32_t device, int32_t k, uint64_t first_idx, hz_state** out);
 void hz_state_destroy(hz_state* st);
@@ -393,6 +393,83 @@ hz_status hz_smt_apply(hz_smt* t, size_t m, const uint64_t* key, const uint8_t* 
 hz_status hz_smt_proofs(hz_smt* t, size_t n, const uint64_t* key, size_t n_sib, uint8_t* siblings_out, uint8_t* found_out, uint8_t* value_out,
                         uint64_t* not_found_key_out, uint8_t* not_found_value_out, uint8_t* is_old0_out);
 hz_status hz_smt_plan(size_t m, const uint64_t* key, size_t n_sib, uint32_t* depth_out, uint8_t* fnc_out, uint64_t* old_key_out, uint8_t* is_old0_out);
+
+/* Device-resident ledger: an hz_state plus the four leaf-field planes (e0, balance, ay, ethAddr; [N][32] each) kept in HBM, so that a
+ * batch of L2 transfers between existing accounts -- and the fee transactions that end it -- is computed AND applied on the device: the
+ * amounts (float40), fees (src/compute-fee.circom), balances and nonces with the sequential semantics of BatchBuilder.build in
+ * circuits_amd/builder.py (its L2 branch is the checker), then the tree update of hz_state_apply on the new leaves, without a host
+ * round trip for any 256-bit value. The outputs are every state-dependent input RollupMain wants for such a batch.
+ *   hz_ledger_create / _destroy   as hz_state_create (4 <= k <= 24)
+ *   hz_ledger_load      as hz_state_load, but the planes stay resident
+ *   hz_ledger_root      the current root
+ *   hz_ledger_accounts  the resident leaf fields of n accounts: fields_out [n][4][32]
+ *   hz_ledger_tree      the tree, borrowed: hz_state_proofs / _download / _root work on it (hz_state_apply / _load on it would leave the
+ *                       planes behind: do not)
+ *   hz_ledger_apply_l2  m ordered transactions and F fee slots (F <= 64; fee_plan_tokens[F] zero-padded as feePlanTokens is,
+ *                       fee_idxs[F] with 0 = unused slot). from_idx == 0 is a NOP (padding). Transaction i, in order: amount =
+ *                       float2fix(amount_f); fee = amount * table[user_fee] >> 60 below selector 192, amount * table[user_fee] from 192
+ *                       on; the sender's balance -= amount + fee, nonce += 1; when amount != 0 the receiver -- as it stands after the
+ *                       sender's update: a self-transfer sees the new leaf -- gets balance += amount, otherwise processor 2 is a NOP
+ *                       (its fields zero except tokenID2 = token_id, siblings2 zero, no update). The fee is added to the first slot s
+ *                       with fee_plan_tokens[s] == token_id (padding zeros included, as plan.index does), to none if no slot matches.
+ *                       After the last transaction slot j with fee_idxs[j] != 0 adds accumulated fee j to that account, in slot order.
+ *                       The updates of a call (two per active transaction, minus receivers of zero amounts, plus active fee slots) must
+ *                       be at most 65536; k <= n_sib <= 64 (the circuits want nLevels + 1). `out` (may be NULL) is a struct of nullable
+ *                       host pointers; every array is canonical 32-byte little-endian elements in the row-major flattening
+ *                       hz_set_input takes.
+ *   hz_ledger_outputs_dev  the same arrays as DEVICE pointers of the last successful apply, valid until the ledger's next call: each can
+ *                       go to hz_set_input_dev unchanged
+ *   hz_ledger_plan_l2   DIAGNOSTIC, no device: the integer plan alone. Events are the updates in order (sender, then receiver, of each
+ *                       transaction; then the fee slots). Per transaction: ev_sender_out / ev_receiver_out (event number or -1),
+ *                       fee_slot_out (or -1), last_event_out (last event of transactions 0 .. i, -1 none). Per event (room for
+ *                       2 m + F): ev_account_out, ev_prev_out (the previous event on the same account or -1). Every output may be NULL
+ *   hz_ledger_device_ms / _semantic_ms  device time of the last apply: first kernel to the last write-back; first kernel to the
+ *                       failure-word read (the semantic kernels alone)
+ * REFUSALS. A batch the circuit would reject is refused as a whole with HZ_ERR_INPUT; hz_last_error names the LOWEST offending
+ * transaction index and one reason, the lowest reason code if several hold there:
+ *   1 the sender's token != token_id          2 nonce != the sender's current nonce      3 the sender's balance < amount + fee
+ *   4 the receiver's token != token_id (only when amount != 0)       5 a new balance >= 2^192
+ *   6 fee slot j: the account's token != fee_plan_tokens[j], reported with index m + j, after every transaction
+ * builder.py raises for 1, 3 and 6 and builds inputs the circuit rejects for 2 and 4; the ledger refuses those two as well. A refused
+ * call changes nothing (fields, tree, root), writes none of its outputs and leaves no work in flight; the one exception is hz_smt_apply's:
+ * a HIP failure reported after the write-back was queued. HZ_ERR_ARG: null arguments, an index outside the state, to_idx 0 or 1 (transfer
+ * to an address, exit: not supported yet), amount_f >= 2^40, too many updates, n_sib outside k .. 64, F > 64, apply before load.
+ * OUT OF SCOPE: L1 transactions, new accounts, exits, transfers to an address, atomic (rqOffset) fields, signatures, more than one
+ * device per ledger. One thread at a time. */
+typedef struct hz_ledger hz_ledger;
+typedef struct {
+    uint64_t from_idx, to_idx, amount_f /* float40 */, nonce;
+    uint32_t token_id;
+    uint8_t user_fee;
+} hz_l2tx;
+#define HZ_LEDGER_ARRAYS 27
+typedef struct {
+    uint8_t *tokenID1, *nonce1, *sign1, *balance1, *ay1, *ethAddr1; /* [m]: the sender BEFORE; zero for a NOP */
+    uint8_t* siblings1;                                             /* [m][n_sib] */
+    uint8_t *tokenID2, *nonce2, *sign2, *balance2, *ay2, *ethAddr2; /* [m]: the receiver before processor 2 */
+    uint8_t* siblings2;                                             /* [m][n_sib] */
+    uint8_t* state_root_after;                                      /* [m]: unchanged across a NOP; its first m - 1 rows are imStateRoot */
+    uint8_t* acc_fee_after;                                         /* [m][F]: imAccFeeOut */
+    uint8_t *tokenID3, *nonce3, *sign3, *balance3, *ay3, *ethAddr3; /* [F]: the fee receiver before its update; zero for an unused slot */
+    uint8_t* siblings3;                                             /* [F][n_sib] */
+    uint8_t* state_root_after_fee;                                  /* [F]: imStateRootFee is its first F - 1 rows */
+    uint8_t* final_acc_fee;                                         /* [F]: imFinalAccFee */
+    uint8_t *old_root, *new_root;                                   /* [1] each; imInitStateRootFee is state_root_after[m - 1] */
+} hz_ledger_out;
+hz_status hz_ledger_create(int32_t device, int32_t k, uint64_t first_idx, hz_ledger** out);
+void hz_ledger_destroy(hz_ledger* l);
+hz_status hz_ledger_load(hz_ledger* l, const uint8_t* e0, const uint8_t* balance, const uint8_t* ay, const uint8_t* eth_addr);
+hz_status hz_ledger_root(hz_ledger* l, uint8_t* out32);
+hz_status hz_ledger_accounts(hz_ledger* l, size_t n, const uint64_t* idx, uint8_t* fields_out);
+hz_state* hz_ledger_tree(hz_ledger* l);
+hz_status hz_ledger_apply_l2(hz_ledger* l, size_t m, const hz_l2tx* txs, size_t F, const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs,
+                             size_t n_sib, const hz_ledger_out* out);
+hz_status hz_ledger_outputs_dev(hz_ledger* l, hz_ledger_out* dev);
+hz_status hz_ledger_plan_l2(size_t m, const hz_l2tx* txs, size_t F, const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs, int32_t k,
+                            uint64_t first_idx, int32_t* ev_sender_out, int32_t* ev_receiver_out, int32_t* fee_slot_out, int32_t* last_event_out,
+                            size_t* n_events_out, uint64_t* ev_account_out, int32_t* ev_prev_out);
+double hz_ledger_device_ms(const hz_ledger* l);
+double hz_ledger_semantic_ms(const hz_ledger* l);
 
 /* Poseidon batch: n independent permutations of width t = n_inputs + 1 (2..7). ----------------
  * `in`  : [n][t-1] canonical elements; `out`: [n] digests (state[0] after the last round).
