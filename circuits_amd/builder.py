@@ -928,13 +928,16 @@ def l2_state_signals(n_tx, max_fee):
     return sig
 
 
-def l2_batch_inputs(ledger, db_like, txs, n_tx, n_levels, max_l1, max_fee, fee_tokens, fee_idxs, chain_id, host_outputs=True):
+def l2_batch_inputs(ledger, db_like, txs, n_tx, n_levels, max_l1, max_fee, fee_tokens, fee_idxs, chain_id, host_outputs=True, verify=False):
     """The complete RollupMain(n_tx, n_levels, max_l1, max_fee) input dictionary of a batch of L2 transfers between existing accounts:
     the transaction-only signals from this module's helpers, every state-dependent signal from capi.Ledger.apply_l2 (which also applies
     the batch to the ledger), the exit-side signals zero. db_like: anything with last_idx and num_batch (a RollupDB, or a namespace);
     num_batch is advanced. txs: transaction dictionaries (fromIdx, toIdx, amount or amountF, tokenID, userFee, nonce, optionally signer or
     r8x / r8y / s); fewer than n_tx are padded with NOPs. host_outputs=False: the state-dependent signals stay on the device -- they
     are left out of the dictionary, and the second value returned maps each to (device pointer, elements) for hz_set_input_dev.
+    verify=True: the transactions are signed first (as below) and go through capi.Ledger.apply_l2_signed, which verifies every signature
+    on the device against the resident keys before the batch is applied and refuses it otherwise; txCompressedData and
+    txCompressedDataV2 are then the ledger's arrays (device signals too with host_outputs=False).
     -> (inputs, device signals or None)"""
     if len(txs) > n_tx:
         raise ValueError("batch full")
@@ -945,7 +948,13 @@ def l2_batch_inputs(ledger, db_like, txs, n_tx, n_levels, max_l1, max_fee, fee_t
     plan = list(fee_tokens) + [0] * (max_fee - len(fee_tokens))
     idxs = list(fee_idxs) + [0] * (max_fee - len(fee_idxs))
     padded = txs + [{}] * (n_tx - len(txs))
-    out = ledger.apply_l2(padded, plan, idxs, n_sib=n_levels + 1, outputs=host_outputs)
+    if verify:
+        for t in padded:
+            if t.get("fromIdx", 0) and "signer" in t:
+                t.update(t["signer"].sign_msg(build_hash_sig(t, chain_id)))
+        out = ledger.apply_l2_signed(padded, plan, idxs, chain_id, db_like.num_batch + 1, n_sib=n_levels + 1, outputs=host_outputs)
+    else:
+        out = ledger.apply_l2(padded, plan, idxs, n_sib=n_levels + 1, outputs=host_outputs)
     inp = {"oldLastIdx": db_like.last_idx, "globalChainID": chain_id, "currentNumBatch": db_like.num_batch + 1, "feePlanTokens": plan, "feeIdxs": idxs}
     db_like.num_batch += 1
     names = ("txCompressedData amountF txCompressedDataV2 fromIdx auxFromIdx toIdx auxToIdx toBjjAy toEthAddr maxNumBatch onChain newAccount "
@@ -956,7 +965,7 @@ def l2_batch_inputs(ledger, db_like, txs, n_tx, n_levels, max_l1, max_fee, fee_t
     for t in padded:
         sig = {"r8x": 0, "r8y": 0, "s": 0}
         if t.get("fromIdx", 0):
-            sig = t["signer"].sign_msg(build_hash_sig(t, chain_id)) if "signer" in t else {k: t.get(k, 0) for k in ("r8x", "r8y", "s")}
+            sig = t["signer"].sign_msg(build_hash_sig(t, chain_id)) if "signer" in t and not verify else {k: t.get(k, 0) for k in ("r8x", "r8y", "s")}
         vals = {"txCompressedData": build_tx_compressed_data(t, chain_id), "amountF": t.get("amountF", 0), "txCompressedDataV2": build_tx_compressed_data_v2(t),
                 "fromIdx": t.get("fromIdx", 0), "toIdx": t.get("toIdx", 0), "toBjjAy": t.get("toBjjAy", 0), "toEthAddr": t.get("toEthAddr", 0),
                 "maxNumBatch": t.get("maxNumBatch", 0), "s": sig["s"], "r8x": sig["r8x"], "r8y": sig["r8y"], "fromBjjCompressed": [0] * 256}
@@ -966,9 +975,14 @@ def l2_batch_inputs(ledger, db_like, txs, n_tx, n_levels, max_l1, max_fee, fee_t
         inp[k] = [0] * (n_tx - 1)
     inp["imOutIdx"] = [db_like.last_idx] * (n_tx - 1)
     sigs = l2_state_signals(n_tx, max_fee)
+    sig_signals = {"txCompressedData": "tx_compressed_data", "txCompressedDataV2": "tx_compressed_data_v2"} if verify else {}
     if not host_outputs:
         dev = ledger.outputs_dev()
         devsig = {}
+        sig_dev = ledger.sig_outputs_dev() if verify else {}
+        for name, arr in sig_signals.items():
+            del inp[name]
+            devsig[name] = (sig_dev[arr], n_tx)
         for name, (arr, first, rows) in sigs.items():
             width = {"siblings": n_levels + 1, "imAccFeeOut": max_fee}.get(name.rstrip("123"), 1)
             devsig[name] = (dev[arr] + first * width * 32, rows * width)
@@ -981,6 +995,8 @@ def l2_batch_inputs(ledger, db_like, txs, n_tx, n_levels, max_l1, max_fee, fee_t
     for name, (arr, first, rows) in sigs.items():
         v = ints(out[arr][first:first + rows])
         inp[name] = v[0] if name in ("imInitStateRootFee", "oldStateRoot") else v
+    for name, arr in sig_signals.items():
+        inp[name] = ints(out[arr])
     return inp, None
 
 

@@ -71,6 +71,7 @@ EXPORTS = [
     "hz_smt_create", "hz_smt_destroy", "hz_smt_reset", "hz_smt_root", "hz_smt_size", "hz_smt_device_ms", "hz_smt_apply", "hz_smt_proofs", "hz_smt_plan",
     "hz_ledger_create", "hz_ledger_destroy", "hz_ledger_load", "hz_ledger_root", "hz_ledger_accounts", "hz_ledger_tree", "hz_ledger_apply_l2",
     "hz_ledger_outputs_dev", "hz_ledger_plan_l2", "hz_ledger_device_ms", "hz_ledger_semantic_ms",
+    "hz_ledger_apply_l2_signed", "hz_ledger_verify_l2", "hz_ledger_sig_outputs_dev", "hz_ledger_sig_ms",
 ]
 
 
@@ -86,6 +87,28 @@ LEDGER_ARRAYS = (
     [("state_root_after", "tx", None), ("acc_fee_after", "tx", "fee")] +
     [(f + "3", "fee", None) for f in ("tokenID", "nonce", "sign", "balance", "ay", "ethAddr")] + [("siblings3", "fee", "sib")] +
     [("state_root_after_fee", "fee", None), ("final_acc_fee", "fee", None), ("old_root", "one", None), ("new_root", "one", None)])
+
+
+class hz_l2sig(ctypes.Structure):
+    _fields_ = [("s", ctypes.c_uint8 * 32), ("r8x", ctypes.c_uint8 * 32), ("r8y", ctypes.c_uint8 * 32), ("to_eth_addr", ctypes.c_uint8 * 32),
+                ("to_bjj_ay", ctypes.c_uint8 * 32), ("max_num_batch", ctypes.c_uint32), ("to_bjj_sign", ctypes.c_uint8)]
+
+
+# hz_ledger_sig_out's arrays in order, [m, 32] each
+LEDGER_SIG_ARRAYS = ("tx_compressed_data", "tx_compressed_data_v2", "sig_l2_hash")
+
+
+def l2sig_array(txs):
+    """[{s, r8x, r8y, toEthAddr, toBjjAy, maxNumBatch, toBjjSign}] (builder's transaction dictionaries; missing keys are 0) -> hz_l2sig
+    array. A value that does not fit its member is passed on truncated to 256 bits / as the library's argument error."""
+    arr = (hz_l2sig * max(len(txs), 1))()
+    for i, t in enumerate(txs):
+        g = arr[i]
+        for member, key in (("s", "s"), ("r8x", "r8x"), ("r8y", "r8y"), ("to_eth_addr", "toEthAddr"), ("to_bjj_ay", "toBjjAy")):
+            getattr(g, member)[:] = list((int(t.get(key, 0)) % (1 << 256)).to_bytes(32, "little"))
+        g.max_num_batch = t.get("maxNumBatch", 0)
+        g.to_bjj_sign = min(int(t.get("toBjjSign", 0)), 255)
+    return arr
 
 
 def l2tx_array(txs):
@@ -239,7 +262,11 @@ class Lib:
         c.hz_ledger_apply_l2.argtypes = [vp, sz, vp, sz, vp, vp, sz, vp]
         c.hz_ledger_outputs_dev.argtypes = [vp, vp]
         c.hz_ledger_plan_l2.argtypes = [sz, vp, sz, vp, vp, ctypes.c_int32, u64, vp, vp, vp, vp, ctypes.POINTER(sz), vp, vp]
-        for f in ("hz_ledger_device_ms", "hz_ledger_semantic_ms"):
+        u32 = ctypes.c_uint32
+        c.hz_ledger_apply_l2_signed.argtypes = [vp, sz, vp, vp, u32, u32, sz, vp, vp, sz, vp, vp]
+        c.hz_ledger_verify_l2.argtypes = [vp, sz, vp, vp, u32, u32, vp, vp]
+        c.hz_ledger_sig_outputs_dev.argtypes = [vp, vp]
+        for f in ("hz_ledger_device_ms", "hz_ledger_semantic_ms", "hz_ledger_sig_ms"):
             getattr(c, f).argtypes = [vp]
             getattr(c, f).restype = ctypes.c_double
 
@@ -815,6 +842,65 @@ class Ledger:
         ptrs = (ctypes.c_void_p * len(LEDGER_ARRAYS))()
         self.L._check(self.L.c.hz_ledger_outputs_dev(self.h, ctypes.addressof(ptrs)))
         return {name: ptrs[i] for i, (name, _, _) in enumerate(LEDGER_ARRAYS)}
+
+    def _sig_out(self, m, outputs, into):
+        import numpy as np
+        out, ptrs = {}, (ctypes.c_void_p * len(LEDGER_SIG_ARRAYS))()
+        if outputs:
+            for i, name in enumerate(LEDGER_SIG_ARRAYS):
+                out[name] = into[name] if into is not None else np.zeros((m, 32), dtype=np.uint8)
+                assert out[name].shape == (m, 32) and out[name].dtype == np.uint8 and out[name].flags.c_contiguous
+                ptrs[i] = out[name].ctypes.data
+        return out, ptrs
+
+    def apply_l2_signed(self, txs, fee_plan_tokens, fee_idxs, chain_id, current_num_batch, n_sib=None, outputs=True, into=None):
+        """apply_l2 with every L2 signature verified on the device first, against the senders' resident keys. txs: transaction
+        dictionaries that also hold s, r8x, r8y and optionally toEthAddr, toBjjAy, toBjjSign, maxNumBatch. Returns apply_l2's
+        dictionary with tx_compressed_data, tx_compressed_data_v2 and sig_l2_hash ([m, 32]) added. A rejected signature refuses the
+        batch with reason 7, an expired maxNumBatch with reason 8."""
+        import numpy as np
+        n_sib = self.k if n_sib is None else n_sib
+        arr, sigs = l2tx_array(txs), l2sig_array(txs)
+        m = len(txs)
+        plan = np.ascontiguousarray(fee_plan_tokens, dtype=np.uint32)
+        idxs = np.ascontiguousarray(fee_idxs, dtype=np.uint64)
+        F = plan.size
+        if idxs.size != F:
+            raise ValueError("fee_plan_tokens and fee_idxs differ in length")
+        out, ptrs = {}, (ctypes.c_void_p * len(LEDGER_ARRAYS))()
+        if outputs:
+            for i, (name, shape) in enumerate(self.shapes(m, F, min(max(n_sib, 0), 64))):
+                out[name] = into[name] if into is not None else np.zeros(shape, dtype=np.uint8)
+                assert out[name].shape == shape and out[name].dtype == np.uint8 and out[name].flags.c_contiguous
+                ptrs[i] = out[name].ctypes.data
+        sig_out, sig_ptrs = self._sig_out(m, outputs, into)
+        self.L._check(self.L.c.hz_ledger_apply_l2_signed(self.h, m, ctypes.addressof(arr), ctypes.addressof(sigs), chain_id, current_num_batch, F, plan.ctypes.data,
+                                                         idxs.ctypes.data, n_sib, ctypes.addressof(ptrs) if outputs else None,
+                                                         ctypes.addressof(sig_ptrs) if outputs else None))
+        out.update(sig_out)
+        return out
+
+    def verify_l2(self, txs, chain_id, current_num_batch, outputs=False):
+        """the mempool filter: one verdict per transaction against the resident keys -- 0 accepted (or a NOP), 7 signature rejected, 8
+        maxNumBatch expired -- as a uint8 array; nothing resident changes. outputs=True: (verdicts, the three signature arrays)"""
+        import numpy as np
+        arr, sigs = l2tx_array(txs), l2sig_array(txs)
+        m = len(txs)
+        verdict = np.zeros(max(m, 1), dtype=np.uint8)
+        sig_out, sig_ptrs = self._sig_out(m, outputs, None)
+        self.L._check(self.L.c.hz_ledger_verify_l2(self.h, m, ctypes.addressof(arr), ctypes.addressof(sigs), chain_id, current_num_batch, verdict.ctypes.data,
+                                                   ctypes.addressof(sig_ptrs) if outputs else None))
+        return (verdict[:m], sig_out) if outputs else verdict[:m]
+
+    def sig_outputs_dev(self):
+        """device pointers of the three signature arrays of the last successful apply_l2_signed / verify_l2, by name"""
+        ptrs = (ctypes.c_void_p * len(LEDGER_SIG_ARRAYS))()
+        self.L._check(self.L.c.hz_ledger_sig_outputs_dev(self.h, ctypes.addressof(ptrs)))
+        return {name: ptrs[i] for i, name in enumerate(LEDGER_SIG_ARRAYS)}
+
+    def sig_ms(self):
+        """device time of the two signature kernels of the last apply_l2_signed / verify_l2"""
+        return self.L.c.hz_ledger_sig_ms(self.h)
 
     def device_ms(self):
         """device time of the last apply_l2"""

@@ -14,6 +14,8 @@
 //   the tree update    state_apply_launch (state.hip): the body of hz_state_apply on the records k_ledger_scan wrote
 //   k_ledger_gather    events back to transactions: siblings1/2/3, the root after each transaction and fee slot
 //   k_ledger_writeback the last leaf of every touched account into the resident planes
+// hz_ledger_apply_l2_signed adds the two signature kernels of ledger_sig.hip after k_ledger_scan, on the same stream and
+// before the one synchronise: they lower the same failure word with reasons 7 and 8. hz_ledger_verify_l2 runs those two alone.
 // Values are plain 256-bit integers in eight 32-bit limbs (the Fc container of fr.h, nothing is reduced modulo r); deltas are
 // two's complement: every true prefix is below 2^220 in magnitude, so a set top bit means "negative".
 #define HZ_FR_INLINE 1
@@ -287,9 +289,17 @@ static hipError_t grow_dev(DevBuf& b, size_t bytes) { return b.bytes >= bytes ? 
 
 static size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 
-static const char* const LEDGER_REASON[7] = {"", "the sender's token is not the transaction's", "the nonce is not the sender's current nonce",
+static const char* const LEDGER_REASON[9] = {"", "the sender's token is not the transaction's", "the nonce is not the sender's current nonce",
                                              "the sender's balance is below amount + fee", "the receiver's token is not the transaction's",
-                                             "a new balance reaches 2^192", "the fee account's token is not the slot's plan token"};
+                                             "a new balance reaches 2^192", "the fee account's token is not the slot's plan token",
+                                             "the signature is rejected", "max_num_batch has expired"};
+
+// ledger_sig.hip
+hipError_t launch_ledger_sig(const hz_l2tx* d_txs, const hz_l2sig* d_sigs, uint32_t chain_id, uint32_t current_num_batch, uint8_t* d_tcd, uint8_t* d_v2, uint8_t* d_hash,
+                             const uint8_t* planes, const void* b8_table, uint32_t N, uint64_t first_idx, uint32_t* d_fail_word, uint8_t* d_verdict, uint32_t m,
+                             hipStream_t s);
+void ledger_sig_b8_table_host(void* out);
+size_t ledger_sig_b8_table_bytes();
 
 }  // namespace hz
 
@@ -310,7 +320,16 @@ struct hz_ledger {
     bool have_outputs = false;
     hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
     double device_ms = 0.0, semantic_ms = 0.0;
+    // signatures: the uploaded hz_l2sig, the three per-transaction arrays and the verdict bytes, the fixed-base table (once per ledger)
+    DevBuf sig_in, sig_outs, b8_table;
+    uint8_t* sig_dev[3] = {nullptr, nullptr, nullptr};
+    uint8_t* verdict_dev = nullptr;
+    bool have_sig_outputs = false;
+    hipEvent_t es0 = nullptr, es1 = nullptr;
+    double sig_ms = 0.0;
     ~hz_ledger() {
+        if (es0) (void)hipEventDestroy(es0);
+        if (es1) (void)hipEventDestroy(es1);
         if (e0) (void)hipEventDestroy(e0);
         if (e1) (void)hipEventDestroy(e1);
         if (e2) (void)hipEventDestroy(e2);
@@ -397,6 +416,8 @@ extern "C" hz_status hz_ledger_create(int32_t device, int32_t k, uint64_t first_
     HZ_HIP(hipEventCreate(&l->e0));
     HZ_HIP(hipEventCreate(&l->e1));
     HZ_HIP(hipEventCreate(&l->e2));
+    HZ_HIP(hipEventCreate(&l->es0));
+    HZ_HIP(hipEventCreate(&l->es1));
     *out = l.release();
     return HZ_OK;
 }
@@ -410,7 +431,7 @@ extern "C" void hz_ledger_destroy(hz_ledger* l) {
 
 extern "C" hz_status hz_ledger_load(hz_ledger* l, const uint8_t* e0, const uint8_t* balance, const uint8_t* ay, const uint8_t* eth_addr) {
     if (!l || !e0 || !balance || !ay || !eth_addr) return set_err(HZ_ERR_ARG, "hz_ledger_load: null argument");
-    l->have_outputs = false;
+    l->have_outputs = l->have_sig_outputs = false;
     if (hz_status e = hz_state_load(l->tree, e0, balance, ay, eth_addr)) return e;   // checks every field < r
     const uint8_t* src[4] = {e0, balance, ay, eth_addr};
     hipStream_t s = state_stream(l->tree);
@@ -441,7 +462,7 @@ extern "C" hz_status hz_ledger_accounts(hz_ledger* l, size_t n, const uint64_t* 
         acct[i] = (uint32_t)(idx[i] - l->first_idx);
     }
     HZ_HIP(hipSetDevice(l->device));
-    l->have_outputs = false;   // the call's buffers are reused
+    l->have_outputs = l->have_sig_outputs = false;   // the call's buffers are reused
     hipStream_t s = state_stream(l->tree);
     HZ_HIP(grow_dev(l->ints, n * 4));
     HZ_HIP(grow_dev(l->work, n * 128));
@@ -462,15 +483,63 @@ extern "C" hz_status hz_ledger_outputs_dev(hz_ledger* l, hz_ledger_out* dev) {
     return HZ_OK;
 }
 
-extern "C" hz_status hz_ledger_apply_l2(hz_ledger* l, size_t m, const hz_l2tx* txs, size_t F, const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs,
-                                        size_t n_sib, const hz_ledger_out* out) {
+// the argument checks of the signed calls beyond those of the transactions; a NOP's entry is not looked at
+static hz_status ledger_check_sigs(const char* who, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, uint32_t chain_id) {
+    if (m && !sigs) return set_err(HZ_ERR_ARG, "%s: null sigs", who);
+    if (chain_id >> 16) return set_err(HZ_ERR_ARG, "%s: chain_id = %u has more than 16 bits", who, chain_id);
+    for (size_t i = 0; i < m; i++) {
+        if (txs[i].from_idx == 0) continue;
+        const hz_l2sig& g = sigs[i];
+        if (g.to_bjj_sign > 1) return set_err(HZ_ERR_ARG, "%s: tx %zu: to_bjj_sign = %u", who, i, (unsigned)g.to_bjj_sign);
+        for (int b = 20; b < 32; b++)
+            if (g.to_eth_addr[b]) return set_err(HZ_ERR_ARG, "%s: tx %zu: to_eth_addr has more than 160 bits", who, i);
+        const uint8_t* f[4] = {g.s, g.r8x, g.r8y, g.to_bjj_ay};
+        static const char* const name[4] = {"s", "r8x", "r8y", "to_bjj_ay"};
+        for (int q = 0; q < 4; q++)
+            if (!canon_lt_p(f[q])) return set_err(HZ_ERR_INPUT, "%s: tx %zu: %s is not below the field's modulus", who, i, name[q]);
+    }
+    return HZ_OK;
+}
+
+// the signatures and the fixed-base table on the device, room for the three arrays and the verdict bytes
+static hz_status ledger_sig_prepare(hz_ledger* l, size_t m, const hz_l2sig* sigs, hipStream_t s) {
+    if (!l->b8_table.p) {
+        std::vector<uint8_t> table(ledger_sig_b8_table_bytes());
+        ledger_sig_b8_table_host(table.data());
+        HZ_HIP(l->b8_table.alloc(table.size()));
+        HZ_HIP(hipMemcpy(l->b8_table.p, table.data(), table.size(), hipMemcpyHostToDevice));
+    }
+    const size_t rows = m ? m : 1;
+    HZ_HIP(grow_dev(l->sig_in, rows * sizeof(hz_l2sig)));
+    HZ_HIP(grow_dev(l->sig_outs, rows * 96 + align16(rows)));
+    uint8_t* at = (uint8_t*)l->sig_outs.p;
+    for (int a = 0; a < 3; a++) l->sig_dev[a] = at + (size_t)a * rows * 32;
+    l->verdict_dev = at + rows * 96;
+    if (m) HZ_HIP(hipMemcpyAsync(l->sig_in.p, sigs, m * sizeof(hz_l2sig), hipMemcpyHostToDevice, s));
+    return HZ_OK;
+}
+
+static hz_status ledger_sig_copy_out(hz_ledger* l, size_t m, const hz_ledger_sig_out* sig_out, hipStream_t s) {
+    if (!sig_out || !m) return HZ_OK;
+    uint8_t* const h[3] = {sig_out->tx_compressed_data, sig_out->tx_compressed_data_v2, sig_out->sig_l2_hash};
+    for (int a = 0; a < 3; a++)
+        if (h[a]) HZ_HIP(hipMemcpyAsync(h[a], l->sig_dev[a], m * 32, hipMemcpyDeviceToHost, s));
+    return HZ_OK;
+}
+
+// hz_ledger_apply_l2 (sigs == nullptr) and hz_ledger_apply_l2_signed
+static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, bool with_sigs, uint32_t chain_id,
+                              uint32_t current_num_batch, size_t F, const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs, size_t n_sib, const hz_ledger_out* out,
+                              const hz_ledger_sig_out* sig_out) {
     static_assert(sizeof(hz_ledger_out) == HZ_LEDGER_ARRAYS * sizeof(uint8_t*), "hz_ledger_out is an array of pointers");
-    if (hz_status e = ledger_ready(l, "hz_ledger_apply_l2")) return e;
+    if (hz_status e = ledger_ready(l, who)) return e;
     const uint32_t k = l->k, N = l->N;
-    if (n_sib < k || n_sib > 64) return set_err(HZ_ERR_ARG, "hz_ledger_apply_l2: n_sib = %zu (%u .. 64)", n_sib, k);
+    if (n_sib < k || n_sib > 64) return set_err(HZ_ERR_ARG, "%s: n_sib = %zu (%u .. 64)", who, n_sib, k);
     LedgerPlan& p = l->plan;
-    if (hz_status e = ledger_check_plan("hz_ledger_apply_l2", m, txs, F, fee_plan_tokens, fee_idxs, k, l->first_idx, p)) return e;
-    l->have_outputs = false;
+    if (hz_status e = ledger_check_plan(who, m, txs, F, fee_plan_tokens, fee_idxs, k, l->first_idx, p)) return e;
+    if (with_sigs)
+        if (hz_status e = ledger_check_sigs(who, m, txs, sigs, chain_id)) return e;
+    l->have_outputs = l->have_sig_outputs = false;
     const uint32_t m32 = (uint32_t)m, F32 = (uint32_t)F, S = (uint32_t)n_sib;
     const uint32_t M = (uint32_t)p.account.size(), G = (uint32_t)p.seg_start.size() - 1;
     const uint32_t n_chunks = m32 ? (m32 + HZ_LEDGER_CHUNK - 1) / HZ_LEDGER_CHUNK : 1u;
@@ -563,6 +632,8 @@ extern "C" hz_status hz_ledger_apply_l2(hz_ledger* l, size_t m, const hz_l2tx* t
         if (hz_status e = state_apply_prepare(l->tree, M, p.account.data(), S, &tb)) return e;
     HZ_HIP(hipMemcpyAsync(l->ints.p, l->h_ints, ints_bytes, hipMemcpyHostToDevice, s));
     HZ_HIP(hipMemsetAsync(d_fail, 0xFF, 4, s));
+    if (with_sigs)
+        if (hz_status e = ledger_sig_prepare(l, m, sigs, s)) return e;
 
     // ---- the semantic kernels
     HZ_HIP(hipEventRecord(l->e0, s));
@@ -583,6 +654,12 @@ extern "C" hz_status hz_ledger_apply_l2(hz_ledger* l, size_t m, const hz_l2tx* t
                            (const uint8_t*)l->planes.p, wb + w_before, tb.fields, d_fail, N, G, m32);
         HZ_HIP(hipGetLastError());
     }
+    if (with_sigs) {   // they read the planes and the uploads only: any place before the failure-word read would do
+        HZ_HIP(hipEventRecord(l->es0, s));
+        HZ_HIP(launch_ledger_sig(d_txs, (const hz_l2sig*)l->sig_in.p, chain_id, current_num_batch, l->sig_dev[0], l->sig_dev[1], l->sig_dev[2],
+                                 (const uint8_t*)l->planes.p, l->b8_table.p, N, l->first_idx, d_fail, nullptr, m32, s));
+        HZ_HIP(hipEventRecord(l->es1, s));
+    }
     HZ_HIP(hipEventRecord(l->e1, s));
     HZ_HIP(hipMemcpyAsync(l->h_fail, d_fail, 4, hipMemcpyDeviceToHost, s));
     HZ_HIP(hipStreamSynchronize(s));   // the one round trip: nothing resident has been written yet
@@ -590,10 +667,8 @@ extern "C" hz_status hz_ledger_apply_l2(hz_ledger* l, size_t m, const hz_l2tx* t
     if (word != 0xFFFFFFFFu) {
         const uint32_t unit = word >> 8, reason = word & 0xFFu;
         if (unit >= m32)
-            return set_err(HZ_ERR_INPUT, "hz_ledger_apply_l2: refused at index %u (fee slot %u), reason %u: %s", unit, unit - m32, reason,
-                           LEDGER_REASON[reason < 7 ? reason : 0]);
-        return set_err(HZ_ERR_INPUT, "hz_ledger_apply_l2: refused at index %u (transaction %u), reason %u: %s", unit, unit, reason,
-                       LEDGER_REASON[reason < 7 ? reason : 0]);
+            return set_err(HZ_ERR_INPUT, "%s: refused at index %u (fee slot %u), reason %u: %s", who, unit, unit - m32, reason, LEDGER_REASON[reason < 9 ? reason : 0]);
+        return set_err(HZ_ERR_INPUT, "%s: refused at index %u (transaction %u), reason %u: %s", who, unit, unit, reason, LEDGER_REASON[reason < 9 ? reason : 0]);
     }
 
     // ---- outputs, tree, resident planes
@@ -626,6 +701,8 @@ extern "C" hz_status hz_ledger_apply_l2(hz_ledger* l, size_t m, const hz_l2tx* t
         for (int a = 0; a < HZ_LEDGER_ARRAYS; a++)
             if (h[a] && elems[a]) HZ_HIP(hipMemcpyAsync(h[a], od.a[a], elems[a] * 32, hipMemcpyDeviceToHost, s));
     }
+    if (with_sigs)
+        if (hz_status e = ledger_sig_copy_out(l, m, sig_out, s)) return e;
     if (M) {
         if (hz_status e = state_apply_finish(l->tree)) return e;
     } else {
@@ -638,5 +715,72 @@ extern "C" hz_status hz_ledger_apply_l2(hz_ledger* l, size_t m, const hz_l2tx* t
     l->device_ms = ms;
     l->out_dev = od;
     l->have_outputs = true;
+    if (with_sigs) {
+        HZ_HIP(hipEventElapsedTime(&ms, l->es0, l->es1));
+        l->sig_ms = ms;
+        l->have_sig_outputs = true;
+    }
     return HZ_OK;
 }
+
+extern "C" hz_status hz_ledger_apply_l2(hz_ledger* l, size_t m, const hz_l2tx* txs, size_t F, const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs,
+                                        size_t n_sib, const hz_ledger_out* out) {
+    return ledger_apply(l, "hz_ledger_apply_l2", m, txs, nullptr, false, 0, 0, F, fee_plan_tokens, fee_idxs, n_sib, out, nullptr);
+}
+
+extern "C" hz_status hz_ledger_apply_l2_signed(hz_ledger* l, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, uint32_t chain_id, uint32_t current_num_batch,
+                                               size_t F, const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs, size_t n_sib, const hz_ledger_out* out,
+                                               const hz_ledger_sig_out* sig_out) {
+    return ledger_apply(l, "hz_ledger_apply_l2_signed", m, txs, sigs, true, chain_id, current_num_batch, F, fee_plan_tokens, fee_idxs, n_sib, out, sig_out);
+}
+
+extern "C" hz_status hz_ledger_verify_l2(hz_ledger* l, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, uint32_t chain_id, uint32_t current_num_batch,
+                                         uint8_t* verdict_out, const hz_ledger_sig_out* sig_out) {
+    const char* who = "hz_ledger_verify_l2";
+    if (hz_status e = ledger_ready(l, who)) return e;
+    if (m && (!txs || !verdict_out)) return set_err(HZ_ERR_ARG, "%s: null argument", who);
+    if (m > HZ_LEDGER_MAX_TX) return set_err(HZ_ERR_ARG, "%s: %zu transactions in one call (at most %u)", who, m, HZ_LEDGER_MAX_TX);
+    for (size_t i = 0; i < m; i++) {
+        const hz_l2tx& t = txs[i];
+        if (t.from_idx == 0) continue;
+        if (!ledger_has(l->first_idx, l->N, t.from_idx))
+            return set_err(HZ_ERR_ARG, "%s: tx %zu: from_idx = %llu is outside the state", who, i, (unsigned long long)t.from_idx);
+        if (t.to_idx <= 1)
+            return set_err(HZ_ERR_ARG, "%s: tx %zu: to_idx = %llu (%s) is not supported yet", who, i, (unsigned long long)t.to_idx,
+                           t.to_idx ? "an exit" : "a transfer to an address");
+        if (!ledger_has(l->first_idx, l->N, t.to_idx))
+            return set_err(HZ_ERR_ARG, "%s: tx %zu: to_idx = %llu is outside the state", who, i, (unsigned long long)t.to_idx);
+        if (t.amount_f >> 40) return set_err(HZ_ERR_ARG, "%s: tx %zu: amount_f has more than 40 bits", who, i);
+    }
+    if (hz_status e = ledger_check_sigs(who, m, txs, sigs, chain_id)) return e;
+    l->have_outputs = l->have_sig_outputs = false;
+    HZ_HIP(hipSetDevice(l->device));
+    hipStream_t s = state_stream(l->tree);
+    HZ_HIP(grow_dev(l->ints, (m ? m : 1) * sizeof(hz_l2tx)));
+    if (m) HZ_HIP(hipMemcpyAsync(l->ints.p, txs, m * sizeof(hz_l2tx), hipMemcpyHostToDevice, s));
+    if (hz_status e = ledger_sig_prepare(l, m, sigs, s)) return e;
+    HZ_HIP(hipEventRecord(l->es0, s));
+    HZ_HIP(launch_ledger_sig((const hz_l2tx*)l->ints.p, (const hz_l2sig*)l->sig_in.p, chain_id, current_num_batch, l->sig_dev[0], l->sig_dev[1], l->sig_dev[2],
+                             (const uint8_t*)l->planes.p, l->b8_table.p, l->N, l->first_idx, nullptr, l->verdict_dev, (uint32_t)m, s));
+    HZ_HIP(hipEventRecord(l->es1, s));
+    if (m) HZ_HIP(hipMemcpyAsync(verdict_out, l->verdict_dev, m, hipMemcpyDeviceToHost, s));
+    if (hz_status e = ledger_sig_copy_out(l, m, sig_out, s)) return e;
+    HZ_HIP(hipStreamSynchronize(s));
+    float ms = 0;
+    HZ_HIP(hipEventElapsedTime(&ms, l->es0, l->es1));
+    l->sig_ms = ms;
+    l->have_sig_outputs = true;
+    return HZ_OK;
+}
+
+extern "C" hz_status hz_ledger_sig_outputs_dev(hz_ledger* l, hz_ledger_sig_out* dev) {
+    if (!l || !dev) return set_err(HZ_ERR_ARG, "hz_ledger_sig_outputs_dev: null argument");
+    if (!l->have_sig_outputs)
+        return set_err(HZ_ERR_ARG, "hz_ledger_sig_outputs_dev: no successful hz_ledger_apply_l2_signed / hz_ledger_verify_l2 since the ledger's last other call");
+    dev->tx_compressed_data = l->sig_dev[0];
+    dev->tx_compressed_data_v2 = l->sig_dev[1];
+    dev->sig_l2_hash = l->sig_dev[2];
+    return HZ_OK;
+}
+
+extern "C" double hz_ledger_sig_ms(const hz_ledger* l) { return l ? l->sig_ms : 0.0; }

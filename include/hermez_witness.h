@@ -434,8 +434,27 @@ hz_status hz_smt_plan(size_t m, const uint64_t* key, size_t n_sib, uint32_t* dep
  * call changes nothing (fields, tree, root), writes none of its outputs and leaves no work in flight; the one exception is hz_smt_apply's:
  * a HIP failure reported after the write-back was queued. HZ_ERR_ARG: null arguments, an index outside the state, to_idx 0 or 1 (transfer
  * to an address, exit: not supported yet), amount_f >= 2^40, too many updates, n_sib outside k .. 64, F > 64, apply before load.
- * OUT OF SCOPE: L1 transactions, new accounts, exits, transfers to an address, atomic (rqOffset) fields, signatures, more than one
- * device per ledger. One thread at a time. */
+ * SIGNATURES. hz_ledger_apply_l2 looks at no signature; the calls below verify every L2 signature on the device, against
+ * the sender's RESIDENT key (ay, sign), before anything is applied:
+ *   hz_ledger_apply_l2_signed  hz_ledger_apply_l2 with sigs[m] (entry i belongs to txs[i]; a NOP's entry is ignored) and the checks of
+ *                       EdDSAPoseidonVerifier and of maxNumBatch added. The message is M = Poseidon(6)(txCompressedData, toEthAddr |
+ *                       amountF << 160 | maxNumBatch << 200, toBjjAy, 0, 0, 0) (src/decode-tx.circom:249-283, rq* fields zero). Accepted
+ *                       iff S < l, AySign2Ax finds Ax for the resident (ay, sign), 8 A has x != 0, and BabyAdd(R8, hm * 8A) == S * B8
+ *                       with hm = Poseidon(5)(R8x, R8y, Ax, Ay, M) as the full integer, the affine formula on R8 as given (R8 is not
+ *                       checked to be on the curve) and both of its denominators nonzero. sig_out (may be NULL; nullable host
+ *                       pointers): txCompressedData, txCompressedDataV2 and M of every transaction, [m] each; a NOP's rows are those of
+ *                       the empty transaction
+ *   hz_ledger_verify_l2 the mempool filter: the same kernels, one verdict per transaction (0 accepted or NOP, 7, 8; 7 beside 8 is 7) in
+ *                       verdict_out[m]. Changes nothing resident and refuses nothing; the transactions need not be applicable in order
+ *   hz_ledger_sig_outputs_dev  sig_out's arrays as DEVICE pointers of the last successful hz_ledger_apply_l2_signed / _verify_l2, valid
+ *                       until the ledger's next call; fit for hz_set_input_dev
+ *   hz_ledger_sig_ms    device time of the two signature kernels of the last such call
+ * Further refusal reasons of hz_ledger_apply_l2_signed, in the same order with reasons 1 - 6 (lowest index, then lowest reason):
+ *   7 the signature is rejected (any cause above)       8 max_num_batch != 0 and max_num_batch < current_num_batch
+ * HZ_ERR_INPUT: s, r8x, r8y or to_bjj_ay >= r. HZ_ERR_ARG: null sigs, to_eth_addr >= 2^160, chain_id >= 2^16, to_bjj_sign > 1, and
+ * everything hz_ledger_apply_l2 refuses as an argument.
+ * OUT OF SCOPE: L1 transactions, new accounts, exits, transfers to an address, atomic (rqOffset) fields, batch (random linear
+ * combination) verification of signatures, more than one device per ledger. One thread at a time. */
 typedef struct hz_ledger hz_ledger;
 typedef struct {
     uint64_t from_idx, to_idx, amount_f /* float40 */, nonce;
@@ -470,6 +489,22 @@ hz_status hz_ledger_plan_l2(size_t m, const hz_l2tx* txs, size_t F, const uint32
                             size_t* n_events_out, uint64_t* ev_account_out, int32_t* ev_prev_out);
 double hz_ledger_device_ms(const hz_ledger* l);
 double hz_ledger_semantic_ms(const hz_ledger* l);
+typedef struct {
+    uint8_t s[32], r8x[32], r8y[32]; /* canonical little-endian */
+    uint8_t to_eth_addr[32], to_bjj_ay[32];
+    uint32_t max_num_batch;
+    uint8_t to_bjj_sign;
+} hz_l2sig;
+typedef struct {
+    uint8_t *tx_compressed_data, *tx_compressed_data_v2, *sig_l2_hash; /* [m] each, nullable */
+} hz_ledger_sig_out;
+hz_status hz_ledger_apply_l2_signed(hz_ledger* l, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, uint32_t chain_id, uint32_t current_num_batch,
+                                    size_t F, const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs, size_t n_sib, const hz_ledger_out* out,
+                                    const hz_ledger_sig_out* sig_out);
+hz_status hz_ledger_verify_l2(hz_ledger* l, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, uint32_t chain_id, uint32_t current_num_batch,
+                              uint8_t* verdict_out /* [m]: 0, 7 or 8 */, const hz_ledger_sig_out* sig_out);
+hz_status hz_ledger_sig_outputs_dev(hz_ledger* l, hz_ledger_sig_out* dev);
+double hz_ledger_sig_ms(const hz_ledger* l);
 
 /* Poseidon batch: n independent permutations of width t = n_inputs + 1 (2..7). ----------------
  * `in`  : [n][t-1] canonical elements; `out`: [n] digests (state[0] after the last round).
