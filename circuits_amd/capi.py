@@ -678,19 +678,19 @@ class Ctx:
         return s.name.decode(), s.index
 
 
-class State:
-    """hz_state: the account tree of N = 2^k consecutive accounts resident on the device (builder.DenseState's geometry). Field elements
-    cross as numpy uint8 arrays of 32-byte little-endian canonical integers."""
+class _Resident:
+    """a device-resident structure of the library behind its handle: created by `_create` (arguments, then the handle's address), destroyed
+    by `_destroy`, its 32-byte root read by `_root` -- the names of three C functions"""
+    _create = _destroy = _root = None
 
-    def __init__(self, L, k, first_idx=256, device=0):
+    def _open(self, L, *args):
         self.L = L
         self.h = ctypes.c_void_p()
-        L._check(L.c.hz_state_create(device, k, first_idx, ctypes.byref(self.h)))
-        self.k, self.N, self.first_idx = k, 1 << k, first_idx
+        L._check(getattr(L.c, self._create)(*args, ctypes.byref(self.h)))
 
     def close(self):
         if self.h:
-            self.L.c.hz_state_destroy(self.h)
+            getattr(self.L.c, self._destroy)(self.h)
             self.h = ctypes.c_void_p()
 
     def __del__(self):
@@ -698,6 +698,21 @@ class State:
             self.close()
         except Exception:
             pass
+
+    def root(self):
+        out = (ctypes.c_uint8 * 32)()
+        self.L._check(getattr(self.L.c, self._root)(self.h, out))
+        return int.from_bytes(bytes(out), "little")
+
+
+class State(_Resident):
+    """hz_state: the account tree of N = 2^k consecutive accounts resident on the device (builder.DenseState's geometry). Field elements
+    cross as numpy uint8 arrays of 32-byte little-endian canonical integers."""
+    _create, _destroy, _root = "hz_state_create", "hz_state_destroy", "hz_state_root"
+
+    def __init__(self, L, k, first_idx=256, device=0):
+        self._open(L, device, k, first_idx)
+        self.k, self.N, self.first_idx = k, 1 << k, first_idx
 
     @staticmethod
     def _fr(a, shape):
@@ -711,11 +726,6 @@ class State:
         """the four leaf fields as [N, 32] arrays indexed by account idx - first_idx; builds the whole tree on the device"""
         cols = [self._fr(a, (self.N, 32)) for a in (e0, balance, ay, eth_addr)]
         self.L._check(self.L.c.hz_state_load(self.h, *[a.ctypes.data for a in cols]))
-
-    def root(self):
-        out = (ctypes.c_uint8 * 32)()
-        self.L._check(self.L.c.hz_state_root(self.h, out))
-        return int.from_bytes(bytes(out), "little")
 
     def apply(self, idx, fields, n_sib=None):
         """m ordered updates of existing accounts: idx [m] integers, fields [m, 4, 32] (e0, balance, ay, ethAddr). Returns a dictionary of
@@ -766,35 +776,18 @@ class _BorrowedState(State):
         self.h = ctypes.c_void_p()
 
 
-class Ledger:
+class Ledger(_Resident):
     """hz_ledger: an hz_state plus the resident leaf fields; L2 transfers and the batch's fee transactions computed and applied on the
     device. Field elements cross as numpy uint8 arrays of 32-byte little-endian canonical integers."""
+    _create, _destroy, _root = "hz_ledger_create", "hz_ledger_destroy", "hz_ledger_root"
 
     def __init__(self, L, k, first_idx=256, device=0):
-        self.L = L
-        self.h = ctypes.c_void_p()
-        L._check(L.c.hz_ledger_create(device, k, first_idx, ctypes.byref(self.h)))
+        self._open(L, device, k, first_idx)
         self.k, self.N, self.first_idx = k, 1 << k, first_idx
-
-    def close(self):
-        if self.h:
-            self.L.c.hz_ledger_destroy(self.h)
-            self.h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def load(self, e0, balance, ay, eth_addr):
         cols = [State._fr(a, (self.N, 32)) for a in (e0, balance, ay, eth_addr)]
         self.L._check(self.L.c.hz_ledger_load(self.h, *[a.ctypes.data for a in cols]))
-
-    def root(self):
-        out = (ctypes.c_uint8 * 32)()
-        self.L._check(self.L.c.hz_ledger_root(self.h, out))
-        return int.from_bytes(bytes(out), "little")
 
     def accounts(self, idx):
         """the resident leaf fields (e0, balance, ay, ethAddr) of the accounts idx -> [n, 4, 32]"""
@@ -814,12 +807,9 @@ class Ledger:
         cols = {"sib": n_sib, "fee": F}
         return [(name, (rows[r], 32) if c is None else (rows[r], cols[c], 32)) for name, r, c in LEDGER_ARRAYS]
 
-    def apply_l2(self, txs, fee_plan_tokens, fee_idxs, n_sib=None, outputs=True, into=None):
-        """txs: transaction dictionaries (fromIdx, toIdx, amountF, nonce, tokenID, userFee) or an hz_l2tx array; fee_plan_tokens /
-        fee_idxs: [F]. Returns a dictionary of numpy arrays named as hz_ledger_out's members (outputs=False: nothing is copied to the
-        host, outputs_dev has them; into: a dictionary of arrays to fill instead of fresh ones)."""
+    def _l2_args(self, txs, fee_plan_tokens, fee_idxs, n_sib, outputs, into):
+        """what apply_l2 and apply_l2_signed pass on: the hz_l2tx array, the fee arrays, the output arrays by name and their pointers"""
         import numpy as np
-        n_sib = self.k if n_sib is None else n_sib
         arr = txs if isinstance(txs, ctypes.Array) else l2tx_array(txs)
         m = len(txs)
         plan = np.ascontiguousarray(fee_plan_tokens, dtype=np.uint32)
@@ -833,6 +823,14 @@ class Ledger:
                 out[name] = into[name] if into is not None else np.zeros(shape, dtype=np.uint8)
                 assert out[name].shape == shape and out[name].dtype == np.uint8 and out[name].flags.c_contiguous
                 ptrs[i] = out[name].ctypes.data
+        return arr, m, plan, idxs, F, out, ptrs
+
+    def apply_l2(self, txs, fee_plan_tokens, fee_idxs, n_sib=None, outputs=True, into=None):
+        """txs: transaction dictionaries (fromIdx, toIdx, amountF, nonce, tokenID, userFee) or an hz_l2tx array; fee_plan_tokens /
+        fee_idxs: [F]. Returns a dictionary of numpy arrays named as hz_ledger_out's members (outputs=False: nothing is copied to the
+        host, outputs_dev has them; into: a dictionary of arrays to fill instead of fresh ones)."""
+        n_sib = self.k if n_sib is None else n_sib
+        arr, m, plan, idxs, F, out, ptrs = self._l2_args(txs, fee_plan_tokens, fee_idxs, n_sib, outputs, into)
         self.L._check(self.L.c.hz_ledger_apply_l2(self.h, m, ctypes.addressof(arr), F, plan.ctypes.data, idxs.ctypes.data, n_sib,
                                                   ctypes.addressof(ptrs) if outputs else None))
         return out
@@ -858,21 +856,9 @@ class Ledger:
         dictionaries that also hold s, r8x, r8y and optionally toEthAddr, toBjjAy, toBjjSign, maxNumBatch. Returns apply_l2's
         dictionary with tx_compressed_data, tx_compressed_data_v2 and sig_l2_hash ([m, 32]) added. A rejected signature refuses the
         batch with reason 7, an expired maxNumBatch with reason 8."""
-        import numpy as np
         n_sib = self.k if n_sib is None else n_sib
-        arr, sigs = l2tx_array(txs), l2sig_array(txs)
-        m = len(txs)
-        plan = np.ascontiguousarray(fee_plan_tokens, dtype=np.uint32)
-        idxs = np.ascontiguousarray(fee_idxs, dtype=np.uint64)
-        F = plan.size
-        if idxs.size != F:
-            raise ValueError("fee_plan_tokens and fee_idxs differ in length")
-        out, ptrs = {}, (ctypes.c_void_p * len(LEDGER_ARRAYS))()
-        if outputs:
-            for i, (name, shape) in enumerate(self.shapes(m, F, min(max(n_sib, 0), 64))):
-                out[name] = into[name] if into is not None else np.zeros(shape, dtype=np.uint8)
-                assert out[name].shape == shape and out[name].dtype == np.uint8 and out[name].flags.c_contiguous
-                ptrs[i] = out[name].ctypes.data
+        arr, m, plan, idxs, F, out, ptrs = self._l2_args(txs, fee_plan_tokens, fee_idxs, n_sib, outputs, into)
+        sigs = l2sig_array(txs)
         sig_out, sig_ptrs = self._sig_out(m, outputs, into)
         self.L._check(self.L.c.hz_ledger_apply_l2_signed(self.h, m, ctypes.addressof(arr), ctypes.addressof(sigs), chain_id, current_num_batch, F, plan.ctypes.data,
                                                          idxs.ctypes.data, n_sib, ctypes.addressof(ptrs) if outputs else None,
@@ -911,35 +897,18 @@ class Ledger:
         return self.L.c.hz_ledger_semantic_ms(self.h)
 
 
-class SparseTree:
+class SparseTree(_Resident):
     """hz_smt: a circomlib sparse Merkle tree resident on the device that accepts inserts and updates (the exit tree; the state tree under
     create-account deposits). Field elements cross as numpy uint8 arrays of 32-byte little-endian canonical integers."""
+    _create, _destroy, _root = "hz_smt_create", "hz_smt_destroy", "hz_smt_root"
 
     def __init__(self, L, n_sib_max, device=0):
-        self.L = L
-        self.h = ctypes.c_void_p()
-        L._check(L.c.hz_smt_create(device, n_sib_max, ctypes.byref(self.h)))
+        self._open(L, device, n_sib_max)
         self.n_sib_max = n_sib_max
-
-    def close(self):
-        if self.h:
-            self.L.c.hz_smt_destroy(self.h)
-            self.h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def reset(self):
         """the empty tree again; the device pools are kept"""
         self.L._check(self.L.c.hz_smt_reset(self.h))
-
-    def root(self):
-        out = (ctypes.c_uint8 * 32)()
-        self.L._check(self.L.c.hz_smt_root(self.h, out))
-        return int.from_bytes(bytes(out), "little")
 
     def size(self):
         """keys held"""

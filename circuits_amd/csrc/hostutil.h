@@ -1,5 +1,5 @@
-// Host-side plumbing shared by the C-ABI translation units: error text, HIP error mapping,
-// RAII device buffers.
+// Host-side plumbing shared by the C-ABI translation units: error text, HIP error mapping, RAII device and pinned buffers, the
+// offsets of the arrays of one block.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -25,16 +25,58 @@ struct DevBuf {
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;
     ~DevBuf() { release(); }
+    // p == nullptr and bytes == 0 after a failure and for n == 0: `bytes` never claims room that is not there
     hipError_t alloc(size_t n) {
         release();
-        bytes = n;
         if (n == 0) return hipSuccess;
-        return hipMalloc(&p, n);
+        const hipError_t e = hipMalloc(&p, n);
+        if (e == hipSuccess)
+            bytes = n;
+        else
+            p = nullptr;
+        return e;
     }
+    // room for n bytes, half as much again when it has to allocate; the contents are not kept
+    hipError_t grow(size_t n) { return n <= bytes ? hipSuccess : alloc(n + n / 2); }
     void release() {
         if (p) (void)hipFree(p);
         p = nullptr;
         bytes = 0;
+    }
+};
+
+// DevBuf's pinned counterpart
+struct PinnedBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf&) = delete;
+    PinnedBuf& operator=(const PinnedBuf&) = delete;
+    ~PinnedBuf() { release(); }
+    hipError_t grow(size_t n) {
+        if (n <= bytes) return hipSuccess;
+        release();
+        const hipError_t e = hipHostMalloc(&p, n + n / 2, hipHostMallocDefault);
+        if (e == hipSuccess)
+            bytes = n + n / 2;
+        else
+            p = nullptr;
+        return e;
+    }
+    void release() {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+};
+
+// the arrays of one block behind each other, each at a multiple of 16 bytes: take() returns an array's offset, `end` is the block's size
+struct Carve {
+    size_t end = 0;
+    size_t take(size_t bytes) {
+        const size_t at = end;
+        end = (end + bytes + 15) & ~(size_t)15;
+        return at;
     }
 };
 

@@ -17,7 +17,8 @@
 // hz_ledger_apply_l2_signed adds the two signature kernels of ledger_sig.hip after k_ledger_scan, on the same stream and
 // before the one synchronise: they lower the same failure word with reasons 7 and 8. hz_ledger_verify_l2 runs those two alone.
 // Values are plain 256-bit integers in eight 32-bit limbs (the Fc container of fr.h, nothing is reduced modulo r); deltas are
-// two's complement: every true prefix is below 2^220 in magnitude, so a set top bit means "negative".
+// two's complement: every true prefix is below 2^220 in magnitude, so a set top bit means "negative"; the arithmetic is u256.h's, shared
+// with ledger_sig.h. Buffers and block offsets are hostutil.h's, the event holder resident.h's; the stream is the tree's (state_stream).
 #define HZ_FR_INLINE 1
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -25,9 +26,10 @@
 #include <vector>
 #include "../../include/hermez_witness.h"
 #include "devcommon.h"
-#include "hostutil.h"
 #include "ledger_plan.h"
+#include "resident.h"
 #include "state_internal.h"
+#include "u256.h"
 
 #define HZ_LEDGER_MAX_EVENTS 65536u
 #define HZ_LEDGER_MAX_TX (1u << 20)
@@ -35,70 +37,6 @@
 #define HZ_LEDGER_CHUNK 64u   // transactions per lane of the fee scan
 
 namespace hz {
-
-// ---- 256-bit integers -----------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ Fc u256_zero() {
-    Fc r;
-#pragma unroll
-    for (int i = 0; i < 8; i++) r.v[i] = 0u;
-    return r;
-}
-__device__ __forceinline__ Fc u256_add(const Fc& a, const Fc& b) {
-    Fc r;
-    uint64_t c = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        c += (uint64_t)a.v[i] + b.v[i];
-        r.v[i] = (uint32_t)c;
-        c >>= 32;
-    }
-    return r;
-}
-__device__ __forceinline__ Fc u256_neg(const Fc& a) {
-    Fc r;
-    uint64_t c = 1;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        c += (uint64_t)(~a.v[i]);
-        r.v[i] = (uint32_t)c;
-        c >>= 32;
-    }
-    return r;
-}
-__device__ __forceinline__ Fc u256_mul_u32(const Fc& a, uint32_t w) {
-    Fc r;
-    uint64_t c = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        c += (uint64_t)a.v[i] * w;
-        r.v[i] = (uint32_t)c;
-        c >>= 32;
-    }
-    return r;
-}
-__device__ __forceinline__ Fc u256_mul_u64(const Fc& a, uint64_t t) {
-    const Fc lo = u256_mul_u32(a, (uint32_t)t), hi = u256_mul_u32(a, (uint32_t)(t >> 32));
-    Fc sh;
-    sh.v[0] = 0u;
-#pragma unroll
-    for (int i = 1; i < 8; i++) sh.v[i] = hi.v[i - 1];
-    return u256_add(lo, sh);
-}
-__device__ __forceinline__ Fc u256_shr60(const Fc& a) {
-    Fc r;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        const uint32_t lo = i + 1 < 8 ? a.v[i + 1] : 0u, hi = i + 2 < 8 ? a.v[i + 2] : 0u;
-        r.v[i] = (lo >> 28) | (hi << 4);
-    }
-    return r;
-}
-__device__ __forceinline__ Fc u256_u64(uint64_t x) {
-    Fc r = u256_zero();
-    r.v[0] = (uint32_t)x;
-    r.v[1] = (uint32_t)(x >> 32);
-    return r;
-}
 
 // the 27 output arrays in hz_ledger_out's order, as device pointers
 struct LedgerOutDev {
@@ -118,7 +56,7 @@ __global__ __launch_bounds__(64) void k_ledger_tx(const hz_l2tx* __restrict__ tx
                                                   uint8_t* __restrict__ fee_out, uint8_t* __restrict__ delta, uint32_t m) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= m) return;
-    Fc fee = u256_zero();
+    Fc fee = fc_zero();
     if (txs[i].from_idx != 0) {
         const uint64_t af = txs[i].amount_f;
         Fc amount = u256_u64(af & ((1ull << 35) - 1));
@@ -138,7 +76,7 @@ __global__ __launch_bounds__(64) void k_ledger_fee_sum(const uint8_t* __restrict
                                                        uint32_t m, uint32_t F) {
     const uint32_t c = blockIdx.x, j = threadIdx.x;
     if (j >= F) return;
-    Fc acc = u256_zero();
+    Fc acc = fc_zero();
     const uint32_t end = min(m, (c + 1) * HZ_LEDGER_CHUNK);
     for (uint32_t i = c * HZ_LEDGER_CHUNK; i < end; i++)
         if (slot[i] == (int32_t)j) acc = u256_add(acc, load_fr(fee + (size_t)i * 32));
@@ -151,7 +89,7 @@ __global__ __launch_bounds__(64) void k_ledger_fee_scan(const uint8_t* __restric
                                                         uint8_t* __restrict__ delta, uint32_t m, uint32_t F, uint32_t n_chunks) {
     const uint32_t c = blockIdx.x, j = threadIdx.x;
     if (j >= F) return;
-    Fc acc = u256_zero();
+    Fc acc = fc_zero();
     for (uint32_t b = 0; b < c; b++) acc = u256_add(acc, load_fr(chunk_sum + ((size_t)b * F + j) * 32));
     const uint32_t end = min(m, (c + 1) * HZ_LEDGER_CHUNK);
     for (uint32_t i = c * HZ_LEDGER_CHUNK; i < end; i++) {
@@ -211,7 +149,7 @@ __device__ __forceinline__ void ledger_put_leaf(const LedgerOutDev& o, int base,
                                                 const uint8_t* __restrict__ before, const uint8_t* __restrict__ planes, uint32_t N) {
     Fc f[6];
 #pragma unroll
-    for (int q = 0; q < 6; q++) f[q] = u256_zero();
+    for (int q = 0; q < 6; q++) f[q] = fc_zero();
     f[0].v[0] = tok;
     if (ev >= 0) {
         const Fc e0 = load_fr(before + (size_t)ev * 64);
@@ -259,11 +197,11 @@ __global__ __launch_bounds__(256) void k_ledger_gather(const LedgerOutDev o, con
     }
     if (u < m) {
         const int32_t a = ev_s[u], b = ev_r[u];
-        store_fr(o.a[LO_SIB1] + ((size_t)u * n_sib + d) * 32, a >= 0 && d < k ? load_fr(sib + ((size_t)a * n_sib + d) * 32) : u256_zero());
-        store_fr(o.a[LO_SIB2] + ((size_t)u * n_sib + d) * 32, b >= 0 && d < k ? load_fr(sib + ((size_t)b * n_sib + d) * 32) : u256_zero());
+        store_fr(o.a[LO_SIB1] + ((size_t)u * n_sib + d) * 32, a >= 0 && d < k ? load_fr(sib + ((size_t)a * n_sib + d) * 32) : fc_zero());
+        store_fr(o.a[LO_SIB2] + ((size_t)u * n_sib + d) * 32, b >= 0 && d < k ? load_fr(sib + ((size_t)b * n_sib + d) * 32) : fc_zero());
     } else {
         const int32_t a = ev_fee[u - m];
-        store_fr(o.a[LO_SIB3] + ((size_t)(u - m) * n_sib + d) * 32, a >= 0 && d < k ? load_fr(sib + ((size_t)a * n_sib + d) * 32) : u256_zero());
+        store_fr(o.a[LO_SIB3] + ((size_t)(u - m) * n_sib + d) * 32, a >= 0 && d < k ? load_fr(sib + ((size_t)a * n_sib + d) * 32) : fc_zero());
     }
 }
 
@@ -284,10 +222,6 @@ __global__ __launch_bounds__(256) void k_ledger_accounts(const uint32_t* __restr
     if (t >= 4 * n) return;
     store_fr(out + (size_t)t * 32, load_fr(planes + ((size_t)(t & 3u) * N + acct[t >> 2]) * 32));
 }
-
-static hipError_t grow_dev(DevBuf& b, size_t bytes) { return b.bytes >= bytes ? hipSuccess : b.alloc(bytes + bytes / 2); }
-
-static size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 static const char* const LEDGER_REASON[9] = {"", "the sender's token is not the transaction's", "the nonce is not the sender's current nonce",
                                              "the sender's balance is below amount + fee", "the receiver's token is not the transaction's",
@@ -312,29 +246,20 @@ struct hz_ledger {
     hz_state* tree = nullptr;
     DevBuf planes;             // resident: e0 | balance | ay | ethAddr, [N][32] each
     DevBuf ints, work, outs;   // per call, grown on demand
-    void* h_ints = nullptr;    // pinned
-    size_t h_ints_bytes = 0;
-    uint32_t* h_fail = nullptr;   // pinned
+    PinnedBuf h_ints, h_fail;   // the call's integer tables; the failure word as the device left it
     LedgerPlan plan;
     LedgerOutDev out_dev{};
     bool have_outputs = false;
-    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
+    DevEvent e0, e1, e2;       // on the tree's stream (state_stream): before the semantic kernels, after them, after the write-back
     double device_ms = 0.0, semantic_ms = 0.0;
     // signatures: the uploaded hz_l2sig, the three per-transaction arrays and the verdict bytes, the fixed-base table (once per ledger)
     DevBuf sig_in, sig_outs, b8_table;
     uint8_t* sig_dev[3] = {nullptr, nullptr, nullptr};
     uint8_t* verdict_dev = nullptr;
     bool have_sig_outputs = false;
-    hipEvent_t es0 = nullptr, es1 = nullptr;
+    DevEvent es0, es1;
     double sig_ms = 0.0;
     ~hz_ledger() {
-        if (es0) (void)hipEventDestroy(es0);
-        if (es1) (void)hipEventDestroy(es1);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        if (e2) (void)hipEventDestroy(e2);
-        if (h_ints) (void)hipHostFree(h_ints);
-        if (h_fail) (void)hipHostFree(h_fail);
         if (tree) hz_state_destroy(tree);
     }
 };
@@ -347,13 +272,9 @@ static hz_status ledger_ready(const hz_ledger* l, const char* who) {
 
 static bool ledger_has(uint64_t first_idx, uint64_t N, uint64_t idx) { return idx >= first_idx && idx - first_idx < N; }
 
-// the argument checks hz_ledger_apply_l2 and hz_ledger_plan_l2 share; on success the plan is made
-static hz_status ledger_check_plan(const char* who, size_t m, const hz_l2tx* txs, size_t F, const uint32_t* plan_tokens, const uint64_t* fee_idxs, uint32_t k,
-                                   uint64_t first_idx, LedgerPlan& plan) {
-    if ((m && !txs) || (F && (!plan_tokens || !fee_idxs))) return set_err(HZ_ERR_ARG, "%s: null argument", who);
-    if (F > HZ_LEDGER_MAX_F) return set_err(HZ_ERR_ARG, "%s: F = %zu fee slots (at most %u)", who, F, HZ_LEDGER_MAX_F);
-    if (m > HZ_LEDGER_MAX_TX) return set_err(HZ_ERR_ARG, "%s: %zu transactions in one call (at most %u)", who, m, HZ_LEDGER_MAX_TX);
-    const uint64_t N = 1ull << k, last = first_idx + N - 1;
+// the per-transaction argument checks of every call that takes transactions; a NOP (from_idx == 0) is not looked at
+static hz_status ledger_check_txs(const char* who, size_t m, const hz_l2tx* txs, uint64_t first_idx, uint64_t N) {
+    const uint64_t last = first_idx + N - 1;
     for (size_t i = 0; i < m; i++) {
         const hz_l2tx& t = txs[i];
         if (t.from_idx == 0) continue;
@@ -368,6 +289,17 @@ static hz_status ledger_check_plan(const char* who, size_t m, const hz_l2tx* txs
                            (unsigned long long)first_idx, (unsigned long long)last);
         if (t.amount_f >> 40) return set_err(HZ_ERR_ARG, "%s: tx %zu: amount_f has more than 40 bits", who, i);
     }
+    return HZ_OK;
+}
+
+// the argument checks hz_ledger_apply_l2 and hz_ledger_plan_l2 share; on success the plan is made
+static hz_status ledger_check_plan(const char* who, size_t m, const hz_l2tx* txs, size_t F, const uint32_t* plan_tokens, const uint64_t* fee_idxs, uint32_t k,
+                                   uint64_t first_idx, LedgerPlan& plan) {
+    if ((m && !txs) || (F && (!plan_tokens || !fee_idxs))) return set_err(HZ_ERR_ARG, "%s: null argument", who);
+    if (F > HZ_LEDGER_MAX_F) return set_err(HZ_ERR_ARG, "%s: F = %zu fee slots (at most %u)", who, F, HZ_LEDGER_MAX_F);
+    if (m > HZ_LEDGER_MAX_TX) return set_err(HZ_ERR_ARG, "%s: %zu transactions in one call (at most %u)", who, m, HZ_LEDGER_MAX_TX);
+    const uint64_t N = 1ull << k, last = first_idx + N - 1;
+    if (hz_status e = ledger_check_txs(who, m, txs, first_idx, N)) return e;
     for (size_t j = 0; j < F; j++)
         if (fee_idxs[j] != 0 && !ledger_has(first_idx, N, fee_idxs[j]))
             return set_err(HZ_ERR_ARG, "%s: fee_idxs[%zu] = %llu is outside the state (%llu .. %llu)", who, j, (unsigned long long)fee_idxs[j],
@@ -412,12 +344,8 @@ extern "C" hz_status hz_ledger_create(int32_t device, int32_t k, uint64_t first_
     l->first_idx = first_idx;
     HZ_HIP(hipSetDevice(device));
     HZ_HIP(l->planes.alloc((size_t)4 * l->N * 32));
-    HZ_HIP(hipHostMalloc((void**)&l->h_fail, 64, hipHostMallocDefault));
-    HZ_HIP(hipEventCreate(&l->e0));
-    HZ_HIP(hipEventCreate(&l->e1));
-    HZ_HIP(hipEventCreate(&l->e2));
-    HZ_HIP(hipEventCreate(&l->es0));
-    HZ_HIP(hipEventCreate(&l->es1));
+    HZ_HIP(l->h_fail.grow(64));
+    for (DevEvent* e : {&l->e0, &l->e1, &l->e2, &l->es0, &l->es1}) HZ_HIP(e->create());
     *out = l.release();
     return HZ_OK;
 }
@@ -464,8 +392,8 @@ extern "C" hz_status hz_ledger_accounts(hz_ledger* l, size_t n, const uint64_t* 
     HZ_HIP(hipSetDevice(l->device));
     l->have_outputs = l->have_sig_outputs = false;   // the call's buffers are reused
     hipStream_t s = state_stream(l->tree);
-    HZ_HIP(grow_dev(l->ints, n * 4));
-    HZ_HIP(grow_dev(l->work, n * 128));
+    HZ_HIP(l->ints.grow(n * 4));
+    HZ_HIP(l->work.grow(n * 128));
     HZ_HIP(hipMemcpyAsync(l->ints.p, acct.data(), n * 4, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_ledger_accounts, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, s, (const uint32_t*)l->ints.p, (const uint8_t*)l->planes.p,
                        (uint8_t*)l->work.p, l->N, (uint32_t)n);
@@ -510,8 +438,8 @@ static hz_status ledger_sig_prepare(hz_ledger* l, size_t m, const hz_l2sig* sigs
         HZ_HIP(hipMemcpy(l->b8_table.p, table.data(), table.size(), hipMemcpyHostToDevice));
     }
     const size_t rows = m ? m : 1;
-    HZ_HIP(grow_dev(l->sig_in, rows * sizeof(hz_l2sig)));
-    HZ_HIP(grow_dev(l->sig_outs, rows * 96 + align16(rows)));
+    HZ_HIP(l->sig_in.grow(rows * sizeof(hz_l2sig)));
+    HZ_HIP(l->sig_outs.grow(rows * 96 + rows));
     uint8_t* at = (uint8_t*)l->sig_outs.p;
     for (int a = 0; a < 3; a++) l->sig_dev[a] = at + (size_t)a * rows * 32;
     l->verdict_dev = at + rows * 96;
@@ -547,24 +475,13 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
     hipStream_t s = state_stream(l->tree);
 
     // ---- integer tables, one pinned block
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o = align16(o + bytes);
-        return at;
-    };
-    const size_t o_tx = take(m * sizeof(hz_l2tx)), o_pos_s = take(m * 4), o_pos_r = take(m * 4), o_ev_s = take(m * 4), o_ev_r = take(m * 4),
-                 o_slot = take(m * 4), o_last = take((m + F) * 4), o_ev_fee = take(F * 4), o_pos_fee = take(F * 4), o_plan = take(F * 4),
-                 o_acct = take((size_t)M * 4), o_pos = take((size_t)M * sizeof(LedgerPos)), o_seg = take(((size_t)G + 1) * 4);
-    const size_t ints_bytes = o ? o : 16;
-    if (l->h_ints_bytes < ints_bytes) {
-        if (l->h_ints) (void)hipHostFree(l->h_ints);
-        l->h_ints = nullptr;
-        l->h_ints_bytes = 0;
-        HZ_HIP(hipHostMalloc(&l->h_ints, ints_bytes + ints_bytes / 2, hipHostMallocDefault));
-        l->h_ints_bytes = ints_bytes + ints_bytes / 2;
-    }
-    uint8_t* hb = (uint8_t*)l->h_ints;
+    Carve c;
+    const size_t o_tx = c.take(m * sizeof(hz_l2tx)), o_pos_s = c.take(m * 4), o_pos_r = c.take(m * 4), o_ev_s = c.take(m * 4), o_ev_r = c.take(m * 4),
+                 o_slot = c.take(m * 4), o_last = c.take((m + F) * 4), o_ev_fee = c.take(F * 4), o_pos_fee = c.take(F * 4), o_plan = c.take(F * 4),
+                 o_acct = c.take((size_t)M * 4), o_pos = c.take((size_t)M * sizeof(LedgerPos)), o_seg = c.take(((size_t)G + 1) * 4);
+    const size_t ints_bytes = c.end;   // (G + 1 >= 1: never empty)
+    HZ_HIP(l->h_ints.grow(ints_bytes));
+    uint8_t* hb = (uint8_t*)l->h_ints.p;
     std::vector<uint32_t> pos_of(M);
     for (uint32_t q = 0; q < M; q++) pos_of[p.perm[q]] = q;
     if (m) memcpy(hb + o_tx, txs, m * sizeof(hz_l2tx));
@@ -609,9 +526,9 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
     elems[LO_OLD_ROOT] = elems[LO_NEW_ROOT] = 1;
     size_t out_bytes = 0;
     for (int a = 0; a < HZ_LEDGER_ARRAYS; a++) out_bytes += elems[a] * 32;
-    HZ_HIP(grow_dev(l->ints, ints_bytes));
-    HZ_HIP(grow_dev(l->work, w));
-    HZ_HIP(grow_dev(l->outs, out_bytes));
+    HZ_HIP(l->ints.grow(ints_bytes));
+    HZ_HIP(l->work.grow(w));
+    HZ_HIP(l->outs.grow(out_bytes));
     LedgerOutDev od;
     {
         uint8_t* at = (uint8_t*)l->outs.p;
@@ -630,7 +547,7 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
     StateCallBufs tb{};
     if (M)
         if (hz_status e = state_apply_prepare(l->tree, M, p.account.data(), S, &tb)) return e;
-    HZ_HIP(hipMemcpyAsync(l->ints.p, l->h_ints, ints_bytes, hipMemcpyHostToDevice, s));
+    HZ_HIP(hipMemcpyAsync(l->ints.p, l->h_ints.p, ints_bytes, hipMemcpyHostToDevice, s));
     HZ_HIP(hipMemsetAsync(d_fail, 0xFF, 4, s));
     if (with_sigs)
         if (hz_status e = ledger_sig_prepare(l, m, sigs, s)) return e;
@@ -661,9 +578,9 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
         HZ_HIP(hipEventRecord(l->es1, s));
     }
     HZ_HIP(hipEventRecord(l->e1, s));
-    HZ_HIP(hipMemcpyAsync(l->h_fail, d_fail, 4, hipMemcpyDeviceToHost, s));
+    HZ_HIP(hipMemcpyAsync(l->h_fail.p, d_fail, 4, hipMemcpyDeviceToHost, s));
     HZ_HIP(hipStreamSynchronize(s));   // the one round trip: nothing resident has been written yet
-    const uint32_t word = *l->h_fail;
+    const uint32_t word = *(const uint32_t*)l->h_fail.p;
     if (word != 0xFFFFFFFFu) {
         const uint32_t unit = word >> 8, reason = word & 0xFFu;
         if (unit >= m32)
@@ -740,23 +657,12 @@ extern "C" hz_status hz_ledger_verify_l2(hz_ledger* l, size_t m, const hz_l2tx* 
     if (hz_status e = ledger_ready(l, who)) return e;
     if (m && (!txs || !verdict_out)) return set_err(HZ_ERR_ARG, "%s: null argument", who);
     if (m > HZ_LEDGER_MAX_TX) return set_err(HZ_ERR_ARG, "%s: %zu transactions in one call (at most %u)", who, m, HZ_LEDGER_MAX_TX);
-    for (size_t i = 0; i < m; i++) {
-        const hz_l2tx& t = txs[i];
-        if (t.from_idx == 0) continue;
-        if (!ledger_has(l->first_idx, l->N, t.from_idx))
-            return set_err(HZ_ERR_ARG, "%s: tx %zu: from_idx = %llu is outside the state", who, i, (unsigned long long)t.from_idx);
-        if (t.to_idx <= 1)
-            return set_err(HZ_ERR_ARG, "%s: tx %zu: to_idx = %llu (%s) is not supported yet", who, i, (unsigned long long)t.to_idx,
-                           t.to_idx ? "an exit" : "a transfer to an address");
-        if (!ledger_has(l->first_idx, l->N, t.to_idx))
-            return set_err(HZ_ERR_ARG, "%s: tx %zu: to_idx = %llu is outside the state", who, i, (unsigned long long)t.to_idx);
-        if (t.amount_f >> 40) return set_err(HZ_ERR_ARG, "%s: tx %zu: amount_f has more than 40 bits", who, i);
-    }
+    if (hz_status e = ledger_check_txs(who, m, txs, l->first_idx, l->N)) return e;
     if (hz_status e = ledger_check_sigs(who, m, txs, sigs, chain_id)) return e;
     l->have_outputs = l->have_sig_outputs = false;
     HZ_HIP(hipSetDevice(l->device));
     hipStream_t s = state_stream(l->tree);
-    HZ_HIP(grow_dev(l->ints, (m ? m : 1) * sizeof(hz_l2tx)));
+    HZ_HIP(l->ints.grow((m ? m : 1) * sizeof(hz_l2tx)));
     if (m) HZ_HIP(hipMemcpyAsync(l->ints.p, txs, m * sizeof(hz_l2tx), hipMemcpyHostToDevice, s));
     if (hz_status e = ledger_sig_prepare(l, m, sigs, s)) return e;
     HZ_HIP(hipEventRecord(l->es0, s));

@@ -11,6 +11,7 @@
 #pragma once
 #include "babyjub.h"
 #include "poseidon.h"
+#include "u256.h"
 
 namespace hz {
 
@@ -45,24 +46,7 @@ HZ_HD constexpr uint32_t sig_sqrt_zexp(int i) {   // (q - 1) / 2 with r - 1 = 2^
     return k[i];
 }
 
-// ---- plain 256-bit integers -------------------------------------------------------------------------------------------------------------
-// r |= v << sh (sh a constant once inlined)
-HZ_HD void sig_or_shl(Fc& r, uint64_t v, int sh) {
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        const int lo = 32 * i - sh;   // the bit of v that lands on bit 0 of limb i
-        uint32_t w = 0;
-        if (lo >= 0 && lo < 64) w = (uint32_t)(v >> lo);
-        if (lo < 0 && lo > -32) w = (uint32_t)(v << (-lo));
-        r.v[i] |= w;
-    }
-}
-HZ_HD bool sig_less(const Fc& a, const Fc& b) {
-    uint64_t br = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) br = (((uint64_t)a.v[i] - b.v[i] - br) >> 63) & 1;
-    return br != 0;
-}
+// ---- the two bounds as plain 256-bit integers (the arithmetic is u256.h's) ------------------------------------------------------------------
 HZ_HD Fc sig_l_c() {
     Fc r;
 #pragma unroll
@@ -84,31 +68,31 @@ struct SigTx {
 };
 HZ_HD Fc sig_tx_compressed_data(const SigTx& t, uint32_t chain_id) {
     Fc r = fc_zero();
-    sig_or_shl(r, HZ_SIG_CONST, 0);
-    sig_or_shl(r, chain_id & 0xFFFFu, 32);
-    sig_or_shl(r, t.from_idx & 0xFFFFFFFFFFFFull, 48);
-    sig_or_shl(r, t.to_idx & 0xFFFFFFFFFFFFull, 96);
-    sig_or_shl(r, t.token_id, 144);
-    sig_or_shl(r, t.nonce & 0xFFFFFFFFFFull, 176);
-    sig_or_shl(r, t.user_fee & 0xFFu, 216);
-    sig_or_shl(r, t.to_bjj_sign & 1u, 224);
+    u256_or_shl(r, HZ_SIG_CONST, 0);
+    u256_or_shl(r, chain_id & 0xFFFFu, 32);
+    u256_or_shl(r, t.from_idx & 0xFFFFFFFFFFFFull, 48);
+    u256_or_shl(r, t.to_idx & 0xFFFFFFFFFFFFull, 96);
+    u256_or_shl(r, t.token_id, 144);
+    u256_or_shl(r, t.nonce & 0xFFFFFFFFFFull, 176);
+    u256_or_shl(r, t.user_fee & 0xFFu, 216);
+    u256_or_shl(r, t.to_bjj_sign & 1u, 224);
     return r;
 }
 HZ_HD Fc sig_tx_compressed_data_v2(const SigTx& t) {
     Fc r = fc_zero();
-    sig_or_shl(r, t.from_idx & 0xFFFFFFFFFFFFull, 0);
-    sig_or_shl(r, t.to_idx & 0xFFFFFFFFFFFFull, 48);
-    sig_or_shl(r, t.amount_f & 0xFFFFFFFFFFull, 96);
-    sig_or_shl(r, t.token_id, 136);
-    sig_or_shl(r, t.nonce & 0xFFFFFFFFFFull, 168);
-    sig_or_shl(r, t.user_fee & 0xFFu, 208);
-    sig_or_shl(r, t.to_bjj_sign & 1u, 216);
+    u256_or_shl(r, t.from_idx & 0xFFFFFFFFFFFFull, 0);
+    u256_or_shl(r, t.to_idx & 0xFFFFFFFFFFFFull, 48);
+    u256_or_shl(r, t.amount_f & 0xFFFFFFFFFFull, 96);
+    u256_or_shl(r, t.token_id, 136);
+    u256_or_shl(r, t.nonce & 0xFFFFFFFFFFull, 168);
+    u256_or_shl(r, t.user_fee & 0xFFu, 208);
+    u256_or_shl(r, t.to_bjj_sign & 1u, 216);
     return r;
 }
 HZ_HD Fc sig_e1(const SigTx& t) {   // toEthAddr | amountF << 160 | maxNumBatch << 200
     Fc r = t.to_eth_addr;
-    sig_or_shl(r, t.amount_f & 0xFFFFFFFFFFull, 160);
-    sig_or_shl(r, t.max_num_batch, 200);
+    u256_or_shl(r, t.amount_f & 0xFFFFFFFFFFull, 160);
+    u256_or_shl(r, t.max_num_batch, 200);
     return r;
 }
 // M = Poseidon(6)(txCompressedData, e1, toBjjAy, 0, 0, 0): the rq* fields are zero. K7: the digest-only constant block of t = 7
@@ -262,7 +246,7 @@ HZ_HD bool sig_recover_ax(const Fr& ay, uint32_t sign, const Fr& a, const Fr& d,
     const bool has = sig_sqrt(n, x);
     const Fc xc = fr_to_canon(x);
     const bool zero = fc_is_zero(xc);
-    const bool above = sig_less(sig_half_c(), xc);
+    const bool above = u256_less(sig_half_c(), xc);
     ax = (above != (sign != 0)) ? fr_neg(x) : x;
     return has && !(zero && sign != 0);
 }
@@ -271,7 +255,7 @@ HZ_HD bool sig_recover_ax(const Fr& ay, uint32_t sign, const Fr& a, const Fr& d,
 // constant block of t = 6, table: sig_b8_table's. No early exit: the lanes of a wavefront walk the same code.
 HZ_HD bool sig_verify(const Fc& s, const Fc& r8x, const Fc& r8y, const Fc& ay_c, uint32_t sign, const Fc& msg, const Fr* K6, const Fr* table) {
     const Fr a = bj_a(), d = bj_d();
-    bool ok = sig_less(s, sig_l_c());   // the malleability guard
+    bool ok = u256_less(s, sig_l_c());   // the malleability guard
     const Fr ay = fr_from_canon(ay_c), x1 = fr_from_canon(r8x), y1 = fr_from_canon(r8y);
     Fr ax;
     ok = sig_recover_ax(ay, sign, a, d, ax) && ok;

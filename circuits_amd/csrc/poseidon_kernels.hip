@@ -182,10 +182,9 @@ extern "C" hz_status hz_poseidon_dag(int32_t device, uint8_t* vals, uint64_t n_v
         HZ_HIP(hipEventCreate(&R.e0));
         HZ_HIP(hipEventCreate(&R.e1));
     }
-    auto grow = [](DevBuf& b, size_t bytes) -> hipError_t { return b.bytes >= bytes ? hipSuccess : b.alloc(bytes + bytes / 2); };
-    HZ_HIP(grow(R.vals, n_vals * 32));
-    HZ_HIP(grow(R.in, n_jobs * HZ_DAG_MAX_IN * sizeof(uint32_t)));
-    HZ_HIP(grow(R.out, n_jobs * sizeof(uint32_t)));
+    HZ_HIP(R.vals.grow(n_vals * 32));
+    HZ_HIP(R.in.grow(n_jobs * HZ_DAG_MAX_IN * sizeof(uint32_t)));
+    HZ_HIP(R.out.grow(n_jobs * sizeof(uint32_t)));
     HZ_HIP(hipMemcpyAsync(R.vals.p, vals, n_vals * 32, hipMemcpyHostToDevice, R.s));
     HZ_HIP(hipMemcpyAsync(R.in.p, job_in, n_jobs * HZ_DAG_MAX_IN * sizeof(uint32_t), hipMemcpyHostToDevice, R.s));
     HZ_HIP(hipMemcpyAsync(R.out.p, job_out, n_jobs * sizeof(uint32_t), hipMemcpyHostToDevice, R.s));

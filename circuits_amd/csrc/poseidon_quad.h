@@ -16,7 +16,11 @@ namespace hz {
 //   M1[9]    MDS matrix, Montgomery form: multiplies a Montgomery operand (a lane that passed no S-box in a partial round)
 //   M2[9]    MDS matrix times R^2: multiplies a CANONICAL operand (the S-box output as the witness stores it, poseidon.h "kCanon")
 struct Pos3Dense { const Fr* C; const Fr* M1; const Fr* M2; };
-#define HZ_POS3_DENSE_FRS (195 + 9 + 9)
+#define HZ_POS3_C_FRS 195
+#define HZ_POS3_M_FRS 9
+#define HZ_POS3_DENSE_FRS (HZ_POS3_C_FRS + HZ_POS3_M_FRS + HZ_POS3_M_FRS)
+// the three tables inside a buffer upload_pos3_dense (kernels.h) filled
+__device__ __forceinline__ Pos3Dense pos3_dense_view(const Fr* pos3) { return Pos3Dense{pos3, pos3 + HZ_POS3_C_FRS, pos3 + HZ_POS3_C_FRS + HZ_POS3_M_FRS}; }
 
 template <int CTRL>
 __device__ __forceinline__ Fr quad_bcast(const Fr& a) {

@@ -8,15 +8,14 @@
 // every hash where its two inputs lie as (kind, index) -- this call's leaf hashes or versions, the resident pools, or zero. The
 // dependent device work is max D + 2 launches whatever m is: leaf (state hash + leaf hash), one level launch per depth from max D - 1
 // down to 0, write-back; one gather launch (roots and old values, read before the write-back replaces them) rides between.
+// Buffers and block offsets are hostutil.h's, stream, timing and the constants' upload resident.h's, the hashes state_dev.h's: state.hip's.
 #define HZ_FR_INLINE 1
 #include <hip/hip_runtime.h>
 #include <memory>
 #include <vector>
 #include "../../include/hermez_witness.h"
 #include "devcommon.h"
-#include "hostutil.h"
-#include "kernels.h"
-#include "poseidon_quad.h"
+#include "resident.h"
 #include "smt_plan.h"
 #include "state_dev.h"
 
@@ -52,13 +51,9 @@ __global__ __launch_bounds__(64) void k_smt_level(const SmtLevelOp* __restrict__
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t e = t >> 2;
     if (e >= n) return;   // (whole quads leave together)
-    const Pos3Dense K{pos3, pos3 + 195, pos3 + 204};
     const SmtLevelOp op = ops[e];
     const Fc sib = smt_load(bases, op.other);
-    const Fr own = fr_from_canon(smt_load(bases, op.own));
-    const Fr other = fr_from_canon(sib);
-    const bool right = op.meta >> 31;   // the path goes right: the other child is the left input
-    const Fr h = poseidon3_quad_digest(fr_select(right, other, own), fr_select(right, own, other), K, t & 3u);
+    const Fr h = state_level_hash(smt_load(bases, op.own), sib, op.meta >> 31, pos3, t & 3u);
     if ((t & 3u) == 0) {
         if (sib_out && (op.meta >> 30 & 1u)) store_fr(sib_out + ((size_t)(op.meta & 0xFFFFu) * n_sib + (op.meta >> 16 & 63u)) * 32, sib);
         store_fr(ver_out + (size_t)e * 32, fr_to_canon(h));
@@ -83,50 +78,20 @@ __global__ __launch_bounds__(256) void k_smt_writeback(const SmtCopy* __restrict
     store_fr(const_cast<uint8_t*>(bases[c.dst >> 29]) + (size_t)(c.dst & 0x1FFFFFFFu) * 32, smt_load(bases, c.src));
 }
 
-struct SmtPinned {
-    void* p = nullptr;
-    size_t bytes = 0;
-    ~SmtPinned() { if (p) (void)hipHostFree(p); }
-    hipError_t grow(size_t n) {
-        if (n <= bytes) return hipSuccess;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        bytes = 0;
-        const hipError_t e = hipHostMalloc(&p, n + n / 2, hipHostMallocDefault);
-        if (e == hipSuccess) bytes = n + n / 2;
-        return e;
-    }
-};
-
-static hipError_t smt_grow(DevBuf& b, size_t bytes) {
-    if (b.bytes >= bytes) return hipSuccess;
-    const hipError_t e = b.alloc(bytes + bytes / 2);
-    if (e != hipSuccess) b.release();   // (alloc leaves the size it was asked for behind)
-    return e;
-}
-
 }  // namespace hz
 
 using namespace hz;
 
 struct hz_smt {
-    int32_t device = 0;
     uint32_t n_sib_max = 0;
     SmtShape shape;
     DevBuf node, leaf, value, pos3;                      // resident pools, the quad form's constants
     DevBuf fields, lv, lh, ver, out, sib, ints;          // per call, grown on demand
-    SmtPinned h_ints;
+    PinnedBuf h_ints;
     std::vector<SmtCopy> copies;
-    hipStream_t s = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    double device_ms = 0.0;
+    Resident r;               // device, stream, device time of the last apply
     bool wb_queued = false;   // the call in progress has queued its write-back: the pools may have changed
     bool poisoned = false;    // a call failed after that point: shape and pools may disagree until hz_smt_reset
-    ~hz_smt() {
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        if (s) (void)hipStreamDestroy(s);
-    }
 };
 
 // a pool that holds `used` entries gets room for `want`: a larger buffer and a device-to-device copy
@@ -136,8 +101,8 @@ static hz_status smt_pool(hz_smt* t, DevBuf& pool, size_t used, size_t want) {
     while (cap < want * 32) cap *= 2;
     DevBuf grown;
     HZ_HIP(grown.alloc(cap));
-    if (used) HZ_HIP(hipMemcpyAsync(grown.p, pool.p, used * 32, hipMemcpyDeviceToDevice, t->s));
-    HZ_HIP(hipStreamSynchronize(t->s));
+    if (used) HZ_HIP(hipMemcpyAsync(grown.p, pool.p, used * 32, hipMemcpyDeviceToDevice, t->r.s));
+    HZ_HIP(hipStreamSynchronize(t->r.s));
     pool.release();
     pool.p = grown.p;
     pool.bytes = grown.bytes;
@@ -145,8 +110,6 @@ static hz_status smt_pool(hz_smt* t, DevBuf& pool, size_t used, size_t want) {
     grown.bytes = 0;
     return HZ_OK;
 }
-
-static size_t align8(size_t n) { return (n + 7) & ~(size_t)7; }
 
 // the kinds' buffers as the kernels index them
 static void smt_bases(const hz_smt* t, const void** b) {
@@ -184,34 +147,26 @@ extern "C" hz_status hz_smt_create(int32_t device, int32_t n_sib_max, hz_smt** o
     if (!out) return set_err(HZ_ERR_ARG, "hz_smt_create: null argument");
     *out = nullptr;
     if (n_sib_max < 1 || n_sib_max > HZ_SMT_MAX_DEPTH) return set_err(HZ_ERR_ARG, "hz_smt_create: n_sib_max = %d (1 .. %d)", n_sib_max, HZ_SMT_MAX_DEPTH);
-    const int32_t n_dev = hz_device_count();
-    if (n_dev <= 0) return set_err(HZ_ERR_NODEVICE, "no usable gfx950 device");
-    if (device < 0 || device >= n_dev) return set_err(HZ_ERR_ARG, "hz_smt_create: device %d of %d", device, n_dev);
-    HZ_HIP(hipSetDevice(device));
     std::unique_ptr<hz_smt> t(new hz_smt);
-    t->device = device;
+    if (hz_status e = t->r.open("hz_smt_create", device)) return e;
     t->n_sib_max = (uint32_t)n_sib_max;
     t->shape.begin();
-    HZ_HIP(t->pos3.alloc(pos3_dense_bytes()));
-    HZ_HIP(upload_pos3_dense((Fr*)t->pos3.p));
-    HZ_HIP(hipStreamCreateWithFlags(&t->s, hipStreamNonBlocking));
-    HZ_HIP(hipEventCreate(&t->e0));
-    HZ_HIP(hipEventCreate(&t->e1));
+    if (hz_status e = pos3_dense_create(t->pos3)) return e;
     *out = t.release();
     return HZ_OK;
 }
 
 extern "C" void hz_smt_destroy(hz_smt* t) {
     if (!t) return;
-    (void)hipSetDevice(t->device);
-    if (t->s) (void)hipStreamSynchronize(t->s);
+    (void)hipSetDevice(t->r.device);
+    if (t->r.s) (void)hipStreamSynchronize(t->r.s);
     delete t;
 }
 
 extern "C" hz_status hz_smt_reset(hz_smt* t) {
     if (!t) return set_err(HZ_ERR_ARG, "hz_smt_reset: null tree");
-    (void)hipSetDevice(t->device);
-    if (t->s) (void)hipStreamSynchronize(t->s);
+    (void)hipSetDevice(t->r.device);
+    if (t->r.s) (void)hipStreamSynchronize(t->r.s);
     t->shape.clear();
     t->poisoned = false;
     return HZ_OK;
@@ -219,7 +174,7 @@ extern "C" hz_status hz_smt_reset(hz_smt* t) {
 
 extern "C" uint64_t hz_smt_size(const hz_smt* t) { return t ? t->shape.leaves() : 0; }
 
-extern "C" double hz_smt_device_ms(const hz_smt* t) { return t ? t->device_ms : 0.0; }
+extern "C" double hz_smt_device_ms(const hz_smt* t) { return t ? t->r.device_ms : 0.0; }
 
 extern "C" hz_status hz_smt_root(hz_smt* t, uint8_t* out32) {
     if (hz_status e = smt_usable(t, "hz_smt_root")) return e;
@@ -229,10 +184,10 @@ extern "C" hz_status hz_smt_root(hz_smt* t, uint8_t* out32) {
         for (int i = 0; i < 32; i++) out32[i] = 0;
         return HZ_OK;
     }
-    HZ_HIP(hipSetDevice(t->device));
+    HZ_HIP(hipSetDevice(t->r.device));
     const uint8_t* pool = (const uint8_t*)(src >> 29 == SMT_LEAF ? t->leaf.p : t->node.p);
-    HZ_HIP(hipMemcpyAsync(out32, pool + (size_t)(src & 0x1FFFFFFFu) * 32, 32, hipMemcpyDeviceToHost, t->s));
-    HZ_HIP(hipStreamSynchronize(t->s));
+    HZ_HIP(hipMemcpyAsync(out32, pool + (size_t)(src & 0x1FFFFFFFu) * 32, 32, hipMemcpyDeviceToHost, t->r.s));
+    HZ_HIP(hipStreamSynchronize(t->r.s));
     return HZ_OK;
 }
 
@@ -240,7 +195,7 @@ extern "C" hz_status hz_smt_root(hz_smt* t, uint8_t* out32) {
 static hz_status smt_apply_device(hz_smt* t, uint32_t M, const uint64_t* key, const uint8_t* fields, uint32_t n_sib, uint8_t* siblings_out, uint8_t* old_value_out,
                                   uint8_t* old_root_out, uint8_t* new_root_out) {
     SmtShape& sh = t->shape;
-    HZ_HIP(hipSetDevice(t->device));
+    HZ_HIP(hipSetDevice(t->r.device));
     if (hz_status e = smt_pool(t, t->node, sh.nodes0, sh.nodes())) return e;
     if (hz_status e = smt_pool(t, t->leaf, sh.leaves0, sh.leaves())) return e;
     if (hz_status e = smt_pool(t, t->value, sh.leaves0, sh.leaves())) return e;
@@ -249,17 +204,19 @@ static hz_status smt_apply_device(hz_smt* t, uint32_t M, const uint64_t* key, co
     const size_t V = sh.versions();
     // what the gather reads: roots [m + 1] | old values [m]; what the write-back scatters
     const size_t G = (size_t)2 * M + 1, W = sh.touched_nodes.size() + 2 * sh.touched_leaves.size();
-    // the integer tables of the call, one pinned block: bases [8] | keys u64[m] | level ops [V] | gather list [G] | write-back list [W]
-    const size_t o_keys = 64, o_ops = o_keys + (size_t)M * 8, o_gather = align8(o_ops + V * sizeof(SmtLevelOp)), o_wb = o_gather + G * sizeof(SmtCopy);
-    const size_t ints_bytes = o_wb + W * sizeof(SmtCopy);
+    // the integer tables of the call, one pinned block: bases [8] (at offset 0) | keys u64[m] | level ops [V] | gather list [G] | write-back list [W]
+    Carve c;
+    c.take(64);
+    const size_t o_keys = c.take((size_t)M * 8), o_ops = c.take(V * sizeof(SmtLevelOp)), o_gather = c.take(G * sizeof(SmtCopy)), o_wb = c.take(W * sizeof(SmtCopy));
+    const size_t ints_bytes = c.end;
     HZ_HIP(t->h_ints.grow(ints_bytes));
-    HZ_HIP(smt_grow(t->ints, ints_bytes));
-    HZ_HIP(smt_grow(t->fields, (size_t)M * 128));
-    HZ_HIP(smt_grow(t->lv, (size_t)M * 32));
-    HZ_HIP(smt_grow(t->lh, (size_t)M * 32));
-    HZ_HIP(smt_grow(t->ver, (V + 1) * 32));
-    HZ_HIP(smt_grow(t->out, G * 32));
-    if (siblings_out) HZ_HIP(smt_grow(t->sib, (size_t)M * n_sib * 32));
+    HZ_HIP(t->ints.grow(ints_bytes));
+    HZ_HIP(t->fields.grow((size_t)M * 128));
+    HZ_HIP(t->lv.grow((size_t)M * 32));
+    HZ_HIP(t->lh.grow((size_t)M * 32));
+    HZ_HIP(t->ver.grow((V + 1) * 32));
+    HZ_HIP(t->out.grow(G * 32));
+    if (siblings_out) HZ_HIP(t->sib.grow((size_t)M * n_sib * 32));
     uint8_t* hb = (uint8_t*)t->h_ints.p;
     smt_bases(t, (const void**)hb);
     uint64_t* h_keys = (uint64_t*)(hb + o_keys);
@@ -283,11 +240,11 @@ static hz_status smt_apply_device(hz_smt* t, uint32_t M, const uint64_t* key, co
 
     const uint8_t* db = (const uint8_t*)t->ints.p;
     const uint8_t* const* d_bases = (const uint8_t* const*)db;
-    hipStream_t s = t->s;
+    hipStream_t s = t->r.s;
     HZ_HIP(hipMemcpyAsync(t->ints.p, t->h_ints.p, ints_bytes, hipMemcpyHostToDevice, s));
     HZ_HIP(hipMemcpyAsync(t->fields.p, fields, (size_t)M * 128, hipMemcpyHostToDevice, s));
     if (siblings_out) HZ_HIP(hipMemsetAsync(t->sib.p, 0, (size_t)M * n_sib * 32, s));
-    HZ_HIP(hipEventRecord(t->e0, s));
+    HZ_HIP(t->r.begin());
     hipLaunchKernelGGL(k_smt_leaf, dim3((M + 63) / 64), dim3(64), 0, s, (const uint64_t*)(db + o_keys), (const uint8_t*)t->fields.p, (uint8_t*)t->lv.p, (uint8_t*)t->lh.p, M);
     HZ_HIP(hipGetLastError());
     for (uint32_t d = sh.max_depth; d-- > 0;) {
@@ -301,17 +258,13 @@ static hz_status smt_apply_device(hz_smt* t, uint32_t M, const uint64_t* key, co
     t->wb_queued = true;
     hipLaunchKernelGGL(k_smt_writeback, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, s, (const SmtCopy*)(db + o_wb), d_bases, (uint32_t)W);
     HZ_HIP(hipGetLastError());
-    HZ_HIP(hipEventRecord(t->e1, s));
+    HZ_HIP(t->r.end());
     const uint8_t* out = (const uint8_t*)t->out.p;
     if (old_root_out) HZ_HIP(hipMemcpyAsync(old_root_out, out, (size_t)M * 32, hipMemcpyDeviceToHost, s));
     if (new_root_out) HZ_HIP(hipMemcpyAsync(new_root_out, out + 32, (size_t)M * 32, hipMemcpyDeviceToHost, s));
     if (old_value_out) HZ_HIP(hipMemcpyAsync(old_value_out, out + ((size_t)M + 1) * 32, (size_t)M * 32, hipMemcpyDeviceToHost, s));
     if (siblings_out) HZ_HIP(hipMemcpyAsync(siblings_out, t->sib.p, (size_t)M * n_sib * 32, hipMemcpyDeviceToHost, s));
-    HZ_HIP(hipStreamSynchronize(s));
-    float ms = 0;
-    HZ_HIP(hipEventElapsedTime(&ms, t->e0, t->e1));
-    t->device_ms = ms;
-    return HZ_OK;
+    return t->r.finish();
 }
 
 extern "C" hz_status hz_smt_apply(hz_smt* t, size_t m, const uint64_t* key, const uint8_t* fields, size_t n_sib, uint8_t* siblings_out, uint64_t* old_key_out,
@@ -334,7 +287,7 @@ extern "C" hz_status hz_smt_apply(hz_smt* t, size_t m, const uint64_t* key, cons
     if (hz_status e = smt_apply_device(t, (uint32_t)m, key, fields, (uint32_t)n_sib, siblings_out, old_value_out, old_root_out, new_root_out)) {
         // nothing of the call stays in flight (its copies read the pinned block and the caller's buffers). Before the write-back was
         // queued the pools are as they were and the roll-back is exact; after it they may not be, and the tree says so from now on
-        (void)hipStreamSynchronize(t->s);
+        (void)hipStreamSynchronize(t->r.s);
         sh.rollback();
         t->poisoned = t->wb_queued;
         return e;
@@ -352,15 +305,15 @@ extern "C" hz_status hz_smt_apply(hz_smt* t, size_t m, const uint64_t* key, cons
 static hz_status smt_proofs_device(hz_smt* t, size_t n, size_t n_sib, uint8_t* siblings_out, uint8_t* value_out, uint8_t* not_found_value_out) {
     const std::vector<SmtCopy>& list = t->copies;
     const size_t o_value = n * n_sib, o_nf = o_value + n, total = o_nf + n;
-    HZ_HIP(hipSetDevice(t->device));
+    HZ_HIP(hipSetDevice(t->r.device));
     const size_t ints_bytes = 64 + list.size() * sizeof(SmtCopy);
     HZ_HIP(t->h_ints.grow(ints_bytes));
-    HZ_HIP(smt_grow(t->ints, ints_bytes));
-    HZ_HIP(smt_grow(t->out, total * 32));
+    HZ_HIP(t->ints.grow(ints_bytes));
+    HZ_HIP(t->out.grow(total * 32));
     uint8_t* hb = (uint8_t*)t->h_ints.p;
     smt_bases(t, (const void**)hb);
     for (size_t i = 0; i < list.size(); i++) ((SmtCopy*)(hb + 64))[i] = list[i];
-    hipStream_t s = t->s;
+    hipStream_t s = t->r.s;
     HZ_HIP(hipMemcpyAsync(t->ints.p, t->h_ints.p, ints_bytes, hipMemcpyHostToDevice, s));
     HZ_HIP(hipMemsetAsync(t->out.p, 0, total * 32, s));
     if (!list.empty()) {
@@ -407,7 +360,7 @@ extern "C" hz_status hz_smt_proofs(hz_smt* t, size_t n, const uint64_t* key, siz
     }
     if (siblings_out || value_out || not_found_value_out)
         if (hz_status e = smt_proofs_device(t, n, n_sib, siblings_out, value_out, not_found_value_out)) {
-            (void)hipStreamSynchronize(t->s);   // nothing stays in flight over the pinned block or the caller's buffers
+            (void)hipStreamSynchronize(t->r.s);   // nothing stays in flight over the pinned block or the caller's buffers
             return e;
         }
     for (size_t i = 0; i < n; i++) {

@@ -15,15 +15,16 @@
 //
 // The level hash is the quad-lane Poseidon(3) of poseidon_quad.h: a call is a few dozen wavefronts and k dependent hashes long, so it
 // costs the length of one hash, not the number of hashes.
+//
+// Shared with smt_tree.hip and ledger.hip: the growing device and pinned buffers and the block offsets (hostutil.h), the stream, the
+// timing events and the upload of the level hash's constants (resident.h), the leaf hashes and the level hash (state_dev.h).
 #define HZ_FR_INLINE 1
 #include <hip/hip_runtime.h>
 #include <memory>
 #include <vector>
 #include "../../include/hermez_witness.h"
 #include "devcommon.h"
-#include "hostutil.h"
-#include "kernels.h"
-#include "poseidon_quad.h"
+#include "resident.h"
 #include "state_dev.h"
 #include "state_internal.h"
 
@@ -68,10 +69,7 @@ __global__ __launch_bounds__(256) void k_state_level_load(const uint8_t* __restr
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t q = t >> 2;
     if (q >= n) return;   // (whole quads leave together)
-    const Pos3Dense K{pos3, pos3 + 195, pos3 + 204};
-    const Fr l = fr_from_canon(load_fr(below + (size_t)q * 32));
-    const Fr r = fr_from_canon(load_fr(below + ((size_t)q + n) * 32));
-    const Fr h = poseidon3_quad_digest(l, r, K, t & 3u);
+    const Fr h = state_level_hash(load_fr(below + (size_t)q * 32), load_fr(below + ((size_t)q + n) * 32), false, pos3, t & 3u);
     if ((t & 3u) == 0) store_fr(out + (size_t)q * 32, fr_to_canon(h));
 }
 
@@ -83,15 +81,11 @@ __global__ __launch_bounds__(64) void k_state_level_apply(const uint32_t* __rest
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t j = t >> 2;
     if (j >= m) return;
-    const Pos3Dense K{pos3, pos3 + 195, pos3 + 204};
     const uint32_t p = res[j];
     const uint32_t q = (p & ((2u << d) - 1u)) ^ (1u << d);
     const int32_t src = sib_src[j];
     const Fc sib = src >= 0 ? load_fr(ver_below + (size_t)src * 32) : load_fr(level_below + (size_t)q * 32);
-    const Fr own = fr_from_canon(load_fr(ver_below + (size_t)j * 32));
-    const Fr other = fr_from_canon(sib);
-    const bool right = (p >> d) & 1u;   // the path goes right: the sibling is the left input
-    const Fr h = poseidon3_quad_digest(fr_select(right, other, own), fr_select(right, own, other), K, t & 3u);
+    const Fr h = state_level_hash(load_fr(ver_below + (size_t)j * 32), sib, (p >> d) & 1u, pos3, t & 3u);
     if ((t & 3u) == 0) {
         store_fr(sib_out + ((size_t)j * n_sib + d) * 32, sib);
         store_fr(ver_out + (size_t)j * 32, fr_to_canon(h));
@@ -159,29 +153,26 @@ struct NodeTable {
     }
 };
 
-struct PinnedBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
-    hipError_t grow(size_t n) {
-        if (n <= bytes) return hipSuccess;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        bytes = 0;
-        const hipError_t e = hipHostMalloc(&p, n + n / 2, hipHostMallocDefault);
-        if (e == hipSuccess) bytes = n + n / 2;
-        return e;
+// the integer tables of an apply, one block (pinned, then uploaded): keys u64[m] | residues u32[m] | prev_same i32[m] | sib_src i32[k][m] |
+// last u8[k + 1][m]. The keys lie at offset 0.
+struct StateInts {
+    size_t res, prev, src, last, bytes;
+    StateInts(uint32_t k, uint32_t M) {
+        Carve c;
+        c.take((size_t)M * 8);
+        res = c.take((size_t)M * 4);
+        prev = c.take((size_t)M * 4);
+        src = c.take((size_t)k * M * 4);
+        last = c.take((size_t)(k + 1) * M);
+        bytes = c.end;
     }
 };
-
-static hipError_t grow(DevBuf& b, size_t bytes) { return b.bytes >= bytes ? hipSuccess : b.alloc(bytes + bytes / 2); }
 
 }  // namespace hz
 
 using namespace hz;
 
 struct hz_state {
-    int32_t device = 0;
     uint32_t k = 0, N = 0;
     uint64_t first_idx = 0;
     bool loaded = false;
@@ -189,15 +180,8 @@ struct hz_state {
     DevBuf fields, uval, oldval, ver, sib, ints;  // per call, grown on demand
     PinnedBuf h_ints;
     NodeTable table;
-    hipStream_t s = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    double device_ms = 0.0;
+    Resident r;   // device, stream, device time of the last load / apply
     uint8_t* level(uint32_t d) const { return (uint8_t*)levels.p + (((size_t)1 << d) - 1) * 32; }
-    ~hz_state() {
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        if (s) (void)hipStreamDestroy(s);
-    }
 };
 
 static hz_status state_ready(const hz_state* st, const char* who) {
@@ -219,30 +203,22 @@ extern "C" hz_status hz_state_create(int32_t device, int32_t k, uint64_t first_i
     *out = nullptr;
     if (k < HZ_STATE_MIN_K || k > HZ_STATE_MAX_K) return set_err(HZ_ERR_ARG, "hz_state_create: k = %d (%d .. %d)", k, HZ_STATE_MIN_K, HZ_STATE_MAX_K);
     if (first_idx > (1ull << 48)) return set_err(HZ_ERR_ARG, "hz_state_create: first_idx beyond 2^48 (the circuits' idx has 48 bits)");
-    const int32_t n_dev = hz_device_count();
-    if (n_dev <= 0) return set_err(HZ_ERR_NODEVICE, "no usable gfx950 device");
-    if (device < 0 || device >= n_dev) return set_err(HZ_ERR_ARG, "hz_state_create: device %d of %d", device, n_dev);
-    HZ_HIP(hipSetDevice(device));
     std::unique_ptr<hz_state> st(new hz_state);
-    st->device = device;
+    if (hz_status e = st->r.open("hz_state_create", device)) return e;
     st->k = (uint32_t)k;
     st->N = 1u << k;
     st->first_idx = first_idx;
     HZ_HIP(st->levels.alloc(((size_t)2 * st->N - 1) * 32));
     HZ_HIP(st->value.alloc((size_t)st->N * 32));
-    HZ_HIP(st->pos3.alloc(pos3_dense_bytes()));
-    HZ_HIP(upload_pos3_dense((Fr*)st->pos3.p));
-    HZ_HIP(hipStreamCreateWithFlags(&st->s, hipStreamNonBlocking));
-    HZ_HIP(hipEventCreate(&st->e0));
-    HZ_HIP(hipEventCreate(&st->e1));
+    if (hz_status e = pos3_dense_create(st->pos3)) return e;
     *out = st.release();
     return HZ_OK;
 }
 
 extern "C" void hz_state_destroy(hz_state* st) {
     if (!st) return;
-    (void)hipSetDevice(st->device);
-    if (st->s) (void)hipStreamSynchronize(st->s);
+    (void)hipSetDevice(st->r.device);
+    if (st->r.s) (void)hipStreamSynchronize(st->r.s);
     delete st;
 }
 
@@ -253,27 +229,24 @@ extern "C" hz_status hz_state_load(hz_state* st, const uint8_t* e0, const uint8_
     for (int f = 0; f < 4; f++)
         for (size_t i = 0; i < N; i++)
             if (!canon_lt_p(src[f] + i * 32)) return set_err(HZ_ERR_INPUT, "hz_state_load: field %d of account %zu >= r", f, i);
-    HZ_HIP(hipSetDevice(st->device));
+    HZ_HIP(hipSetDevice(st->r.device));
     st->loaded = false;
     // the upload: the four field planes behind each other in one buffer, dropped again when the tree stands
     DevBuf planes;
     HZ_HIP(planes.alloc((size_t)4 * N * 32));
-    for (int f = 0; f < 4; f++) HZ_HIP(hipMemcpyAsync((uint8_t*)planes.p + (size_t)f * N * 32, src[f], (size_t)N * 32, hipMemcpyHostToDevice, st->s));
-    HZ_HIP(hipEventRecord(st->e0, st->s));
-    hipLaunchKernelGGL(k_state_value, dim3((N + 255) / 256), dim3(256), 0, st->s, (const uint8_t*)planes.p, (size_t)1, (size_t)N, (uint8_t*)st->value.p, N);
+    for (int f = 0; f < 4; f++) HZ_HIP(hipMemcpyAsync((uint8_t*)planes.p + (size_t)f * N * 32, src[f], (size_t)N * 32, hipMemcpyHostToDevice, st->r.s));
+    HZ_HIP(st->r.begin());
+    hipLaunchKernelGGL(k_state_value, dim3((N + 255) / 256), dim3(256), 0, st->r.s, (const uint8_t*)planes.p, (size_t)1, (size_t)N, (uint8_t*)st->value.p, N);
     HZ_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_state_leaf_load, dim3((N + 255) / 256), dim3(256), 0, st->s, (const uint8_t*)st->value.p, st->level(k), st->first_idx, N);
+    hipLaunchKernelGGL(k_state_leaf_load, dim3((N + 255) / 256), dim3(256), 0, st->r.s, (const uint8_t*)st->value.p, st->level(k), st->first_idx, N);
     HZ_HIP(hipGetLastError());
     for (uint32_t d = k; d-- > 0;) {
         const uint32_t n = 1u << d;
-        hipLaunchKernelGGL(k_state_level_load, dim3((4 * n + 255) / 256), dim3(256), 0, st->s, (const uint8_t*)st->level(d + 1), st->level(d), (const Fr*)st->pos3.p, n);
+        hipLaunchKernelGGL(k_state_level_load, dim3((4 * n + 255) / 256), dim3(256), 0, st->r.s, (const uint8_t*)st->level(d + 1), st->level(d), (const Fr*)st->pos3.p, n);
         HZ_HIP(hipGetLastError());
     }
-    HZ_HIP(hipEventRecord(st->e1, st->s));
-    HZ_HIP(hipStreamSynchronize(st->s));
-    float ms = 0;
-    HZ_HIP(hipEventElapsedTime(&ms, st->e0, st->e1));
-    st->device_ms = ms;
+    HZ_HIP(st->r.end());
+    if (hz_status e = st->r.finish()) return e;
     st->loaded = true;
     return HZ_OK;
 }
@@ -281,13 +254,13 @@ extern "C" hz_status hz_state_load(hz_state* st, const uint8_t* e0, const uint8_
 extern "C" hz_status hz_state_root(hz_state* st, uint8_t* out32) {
     if (hz_status e = state_ready(st, "hz_state_root")) return e;
     if (!out32) return set_err(HZ_ERR_ARG, "hz_state_root: null argument");
-    HZ_HIP(hipSetDevice(st->device));
-    HZ_HIP(hipMemcpyAsync(out32, st->level(0), 32, hipMemcpyDeviceToHost, st->s));
-    HZ_HIP(hipStreamSynchronize(st->s));
+    HZ_HIP(hipSetDevice(st->r.device));
+    HZ_HIP(hipMemcpyAsync(out32, st->level(0), 32, hipMemcpyDeviceToHost, st->r.s));
+    HZ_HIP(hipStreamSynchronize(st->r.s));
     return HZ_OK;
 }
 
-extern "C" double hz_state_device_ms(const hz_state* st) { return st ? st->device_ms : 0.0; }
+extern "C" double hz_state_device_ms(const hz_state* st) { return st ? st->r.device_ms : 0.0; }
 
 // The body of an apply in two halves, so that a caller whose fields are already in device memory (ledger.hip) runs the same tree update
 // as hz_state_apply. prepare: the integer tables of the call (which earlier update made the version a thread reads), the per-call
@@ -295,17 +268,15 @@ extern "C" double hz_state_device_ms(const hz_state* st) { return st ? st->devic
 // stay in the buffers `prepare` named. Nothing here synchronises.
 hz_status hz::state_apply_prepare(hz_state* st, uint32_t M, const uint64_t* idx, uint32_t n_sib, StateCallBufs* out) {
     const uint32_t k = st->k;
-    HZ_HIP(hipSetDevice(st->device));
-    // integer tables of the call, one pinned block: keys u64[m] | residues u32[m] | prev_same i32[m] | sib_src i32[k][m] | last u8[k + 1][m]
-    const size_t o_res = (size_t)M * 8, o_prev = o_res + (size_t)M * 4, o_src = o_prev + (size_t)M * 4, o_last = o_src + (size_t)k * M * 4;
-    const size_t ints_bytes = o_last + (size_t)(k + 1) * M;
-    HZ_HIP(st->h_ints.grow(ints_bytes));
+    HZ_HIP(hipSetDevice(st->r.device));
+    const StateInts o(k, M);
+    HZ_HIP(st->h_ints.grow(o.bytes));
     uint8_t* hb = (uint8_t*)st->h_ints.p;
     uint64_t* h_keys = (uint64_t*)hb;
-    uint32_t* h_res = (uint32_t*)(hb + o_res);
-    int32_t* h_prev = (int32_t*)(hb + o_prev);
-    int32_t* h_src = (int32_t*)(hb + o_src);
-    uint8_t* h_last = hb + o_last;
+    uint32_t* h_res = (uint32_t*)(hb + o.res);
+    int32_t* h_prev = (int32_t*)(hb + o.prev);
+    int32_t* h_src = (int32_t*)(hb + o.src);
+    uint8_t* h_last = hb + o.last;
     for (uint32_t j = 0; j < M; j++) {
         h_keys[j] = idx[j];
         h_res[j] = (uint32_t)idx[j] & (st->N - 1);
@@ -325,13 +296,13 @@ hz_status hz::state_apply_prepare(hz_state* st, uint32_t M, const uint64_t* idx,
         }
     }
 
-    HZ_HIP(grow(st->ints, ints_bytes));
-    HZ_HIP(grow(st->fields, (size_t)M * 128));
-    HZ_HIP(grow(st->uval, (size_t)M * 32));
-    HZ_HIP(grow(st->oldval, (size_t)M * 32));
-    HZ_HIP(grow(st->ver, ((size_t)(k + 1) * M + 1) * 32));   // one element ahead of version 0 of the root: the root the call found
-    HZ_HIP(grow(st->sib, (size_t)M * n_sib * 32));
-    HZ_HIP(hipMemcpyAsync(st->ints.p, st->h_ints.p, ints_bytes, hipMemcpyHostToDevice, st->s));
+    HZ_HIP(st->ints.grow(o.bytes));
+    HZ_HIP(st->fields.grow((size_t)M * 128));
+    HZ_HIP(st->uval.grow((size_t)M * 32));
+    HZ_HIP(st->oldval.grow((size_t)M * 32));
+    HZ_HIP(st->ver.grow(((size_t)(k + 1) * M + 1) * 32));   // one element ahead of version 0 of the root: the root the call found
+    HZ_HIP(st->sib.grow((size_t)M * n_sib * 32));
+    HZ_HIP(hipMemcpyAsync(st->ints.p, st->h_ints.p, o.bytes, hipMemcpyHostToDevice, st->r.s));
     if (out) {
         out->fields = (uint8_t*)st->fields.p;
         out->siblings = (uint8_t*)st->sib.p;
@@ -344,17 +315,17 @@ hz_status hz::state_apply_prepare(hz_state* st, uint32_t M, const uint64_t* idx,
 
 hz_status hz::state_apply_launch(hz_state* st, uint32_t M, uint32_t n_sib, bool clear_siblings) {
     const uint32_t k = st->k;
-    const size_t o_res = (size_t)M * 8, o_prev = o_res + (size_t)M * 4, o_src = o_prev + (size_t)M * 4, o_last = o_src + (size_t)k * M * 4;
+    const StateInts o(k, M);
     uint8_t* db = (uint8_t*)st->ints.p;
     const uint64_t* d_keys = (const uint64_t*)db;
-    const uint32_t* d_res = (const uint32_t*)(db + o_res);
-    const int32_t* d_prev = (const int32_t*)(db + o_prev);
-    const int32_t* d_src = (const int32_t*)(db + o_src);
-    const uint8_t* d_last = db + o_last;
+    const uint32_t* d_res = (const uint32_t*)(db + o.res);
+    const int32_t* d_prev = (const int32_t*)(db + o.prev);
+    const int32_t* d_src = (const int32_t*)(db + o.src);
+    const uint8_t* d_last = db + o.last;
     uint8_t* ver = (uint8_t*)st->ver.p + 32;   // [k + 1][m], depth 0 first
-    hipStream_t s = st->s;
+    hipStream_t s = st->r.s;
     if (clear_siblings && n_sib > k) HZ_HIP(hipMemsetAsync(st->sib.p, 0, (size_t)M * n_sib * 32, s));
-    HZ_HIP(hipEventRecord(st->e0, s));
+    HZ_HIP(st->r.begin());
     hipLaunchKernelGGL(k_state_value, dim3((M + 63) / 64), dim3(64), 0, s, (const uint8_t*)st->fields.p, (size_t)4, (size_t)1, (uint8_t*)st->uval.p, M);
     HZ_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_state_leaf_apply, dim3((M + 63) / 64), dim3(64), 0, s, d_keys, d_prev, (const uint8_t*)st->uval.p, (const uint8_t*)st->value.p,
@@ -371,19 +342,13 @@ hz_status hz::state_apply_launch(hz_state* st, uint32_t M, uint32_t n_sib, bool 
     hipLaunchKernelGGL(k_state_writeback, dim3((wb + 255) / 256), dim3(256), 0, s, d_res, d_keys, d_last, (const uint8_t*)ver, (const uint8_t*)st->uval.p,
                        (uint8_t*)st->levels.p, (uint8_t*)st->value.p, st->first_idx, k, M);
     HZ_HIP(hipGetLastError());
-    HZ_HIP(hipEventRecord(st->e1, s));
+    HZ_HIP(st->r.end());
     return HZ_OK;
 }
 
-hz_status hz::state_apply_finish(hz_state* st) {
-    HZ_HIP(hipStreamSynchronize(st->s));
-    float ms = 0;
-    HZ_HIP(hipEventElapsedTime(&ms, st->e0, st->e1));
-    st->device_ms = ms;
-    return HZ_OK;
-}
+hz_status hz::state_apply_finish(hz_state* st) { return st->r.finish(); }
 
-hipStream_t hz::state_stream(const hz_state* st) { return st->s; }
+hipStream_t hz::state_stream(const hz_state* st) { return st->r.s; }
 const uint8_t* hz::state_root_dev(const hz_state* st) { return st->level(0); }
 bool hz::state_loaded(const hz_state* st) { return st->loaded; }
 
@@ -400,7 +365,7 @@ extern "C" hz_status hz_state_apply(hz_state* st, size_t m, const uint64_t* idx,
         if (!canon_lt_p(fields + i * 32)) return set_err(HZ_ERR_INPUT, "hz_state_apply: field %zu of update %zu >= r", i & 3, i >> 2);
     StateCallBufs b;
     if (hz_status e = state_apply_prepare(st, M, idx, (uint32_t)n_sib, &b)) return e;
-    hipStream_t s = st->s;
+    hipStream_t s = st->r.s;
     HZ_HIP(hipMemcpyAsync(b.fields, fields, (size_t)M * 128, hipMemcpyHostToDevice, s));
     if (hz_status e = state_apply_launch(st, M, (uint32_t)n_sib, siblings_out != nullptr)) return e;
     if (old_root_out) HZ_HIP(hipMemcpyAsync(old_root_out, b.old_root, (size_t)M * 32, hipMemcpyDeviceToHost, s));
@@ -418,12 +383,12 @@ extern "C" hz_status hz_state_proofs(hz_state* st, size_t n, const uint64_t* idx
     if (n > ((size_t)1 << 24)) return set_err(HZ_ERR_ARG, "hz_state_proofs: %zu proofs in one call (at most 2^24)", n);
     if (n_sib < k || n_sib > 64) return set_err(HZ_ERR_ARG, "hz_state_proofs: n_sib = %zu (%u .. 64)", n_sib, k);
     if (hz_status e = state_keys(st, "hz_state_proofs", idx, n)) return e;
-    HZ_HIP(hipSetDevice(st->device));
+    HZ_HIP(hipSetDevice(st->r.device));
     const uint32_t n32 = (uint32_t)n;
-    HZ_HIP(grow(st->ints, n * 8));
-    HZ_HIP(grow(st->sib, n * n_sib * 32));
-    HZ_HIP(grow(st->oldval, n * 32));
-    hipStream_t s = st->s;
+    HZ_HIP(st->ints.grow(n * 8));
+    HZ_HIP(st->sib.grow(n * n_sib * 32));
+    HZ_HIP(st->oldval.grow(n * 32));
+    hipStream_t s = st->r.s;
     HZ_HIP(hipMemcpyAsync(st->ints.p, idx, n * 8, hipMemcpyHostToDevice, s));
     if (n_sib > k) HZ_HIP(hipMemsetAsync(st->sib.p, 0, n * n_sib * 32, s));
     const size_t threads = (size_t)(k + 1) * n32;
@@ -438,11 +403,11 @@ extern "C" hz_status hz_state_proofs(hz_state* st, size_t n, const uint64_t* idx
 
 extern "C" hz_status hz_state_download(hz_state* st, uint8_t* const* levels_out, uint8_t* value_out) {
     if (hz_status e = state_ready(st, "hz_state_download")) return e;
-    HZ_HIP(hipSetDevice(st->device));
+    HZ_HIP(hipSetDevice(st->r.device));
     if (levels_out)
         for (uint32_t d = 0; d <= st->k; d++)
-            if (levels_out[d]) HZ_HIP(hipMemcpyAsync(levels_out[d], st->level(d), ((size_t)32) << d, hipMemcpyDeviceToHost, st->s));
-    if (value_out) HZ_HIP(hipMemcpyAsync(value_out, st->value.p, (size_t)st->N * 32, hipMemcpyDeviceToHost, st->s));
-    HZ_HIP(hipStreamSynchronize(st->s));
+            if (levels_out[d]) HZ_HIP(hipMemcpyAsync(levels_out[d], st->level(d), ((size_t)32) << d, hipMemcpyDeviceToHost, st->r.s));
+    if (value_out) HZ_HIP(hipMemcpyAsync(value_out, st->value.p, (size_t)st->N * 32, hipMemcpyDeviceToHost, st->r.s));
+    HZ_HIP(hipStreamSynchronize(st->r.s));
     return HZ_OK;
 }

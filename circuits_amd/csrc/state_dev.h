@@ -1,6 +1,8 @@
-// The two leaf-side hashes of an account tree, shared by the dense tree (state.hip) and the sparse one (smt_tree.hip).
+// The hashes of an account tree, shared by the dense tree (state.hip) and the sparse one (smt_tree.hip): the two leaf-side ones and the
+// level hash.
 #pragma once
 #include "devcommon.h"
+#include "poseidon_quad.h"
 
 namespace hz {
 
@@ -19,6 +21,14 @@ __device__ __forceinline__ Fc state_leaf_hash(uint64_t key, const Fc& value) {
     const Fr x[3] = {fr_from_u64(key), fr_from_canon(value), fr_one()};
     NoSink sink;
     return fr_to_canon(poseidon_hash<4>(x, poseidon_consts<4>(), sink));
+}
+
+// level hash: the node above two canonical children, by a quad of lanes (poseidon_quad.h; pos3: the dense constants). `right`: the
+// path goes right, so `other` is the left input. Every lane of the quad passes the same values and gets the digest in MONTGOMERY form:
+// only the lane that stores it pays for fr_to_canon (a reduction on the dependent chain of every level otherwise).
+__device__ __forceinline__ Fr state_level_hash(const Fc& own, const Fc& other, bool right, const Fr* __restrict__ pos3, uint32_t lane_in_quad) {
+    const Fr o = fr_from_canon(own), s = fr_from_canon(other);
+    return poseidon3_quad_digest(fr_select(right, s, o), fr_select(right, o, s), pos3_dense_view(pos3), lane_in_quad);
 }
 
 }  // namespace hz

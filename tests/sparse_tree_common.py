@@ -62,6 +62,17 @@ def draw_mix(m, seed):
     return [pool[int(i)] for i in rng.integers(0, len(pool), size=m)]
 
 
+def regrow_calls():
+    """three calls on one tree of n_sib_max = 10 -> [(keys, n_sib)] of 3, 200 and 3 ops with n_sib = 7, 10, 7. The large call draws from 120
+    keys that share their low 6 bits eight at a time (distinct low 9 bits: leaves at depth 7 .. 9, inserts and updates); the small calls
+    touch keys that are alone below bit 6, so their leaves stay above depth 7"""
+    crowd = [(r & 63) << 20 | 1 << 16 | r for r in range(512) if (r & 63) < 15]
+    lone = [7 << 16 | 60, 8 << 16 | 61, 9 << 16 | 62, 10 << 16 | 63]
+    rng = np.random.default_rng(10)
+    large = [crowd[int(i)] for i in rng.integers(0, len(crowd), size=198)] + lone[1:3]
+    return [([lone[0], crowd[0], lone[0]], 7), (large, 10), ([lone[3], lone[1], lone[3]], 7)]
+
+
 def smt_replay(keys, fields, smt=None):
     """the checker: builder.SMT, one op at a time -> (smt, per-op results). A result holds SMTProcessor's inputs as the SMT states them
     plus fnc (1 insert, 0 update), the new value, the depth of the op's leaf and of the walk that preceded it"""

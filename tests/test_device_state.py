@@ -171,3 +171,22 @@ def test_download_feeds_the_native_builder(hz):
     assert db.state_root == st.root()
     db.close()
     st.close()
+
+
+def test_one_handle_regrows_its_call_buffers(hz):
+    """3, 200 and 3 updates on one state of k = 6, with n_sib = k, k + 3, k: the per-call buffers are grown by the second call and reused
+    by the third; every output of every call, the zero padding beyond depth k included, and the final tree are the checker's"""
+    k = 6
+    base = C.base_state(k)
+    st = _device_state(hz, base)
+    t, all_idx, all_fields = None, [], []
+    for call, (m, n_sib) in enumerate([(3, k), (200, k + 3), (3, k)]):
+        idx, fields = C.draw_updates(base, m, seed=300 + call)
+        t, _, _, got = _check_apply(st, base, idx, fields, n_sib=n_sib, smt=t)
+        assert got["siblings"].shape == (m, n_sib, 32)
+        all_idx += idx
+        all_fields += fields
+    assert st.root() == t.root
+    levels, value = C.rebuild_levels(k, base.first_idx, C.final_cols(base, all_idx, all_fields))
+    _same_arrays(st, levels, value)
+    st.close()

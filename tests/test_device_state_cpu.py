@@ -147,3 +147,16 @@ def test_state_kernels_use_no_scratch():
                  "hz::k_state_writeback", "hz::k_state_proofs"):
         assert name in rows, sorted(rows)
         assert rows[name]["scratch"] == 0, "%s uses %d bytes of scratch per lane" % (name, rows[name]["scratch"])
+
+
+def test_growing_buffers_stay_empty_after_a_failed_allocation(tmp_path):
+    """csrc/hostutil.h as a stand-alone host program (tests/native/devbuf_check.cpp): after a grow that fails, DevBuf and PinnedBuf hold
+    p == nullptr and bytes == 0, a second grow of the same size fails again, grow(0) on an empty buffer succeeds. No device is needed:
+    2^60 bytes are refused with a plain error return everywhere."""
+    import os
+    import subprocess
+    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "native", "devbuf_check.cpp")
+    exe = str(tmp_path / "devbuf_check")
+    subprocess.check_call([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-O1", "-std=c++17", src, "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0 and "failures=0" in r.stdout, r.stdout + r.stderr

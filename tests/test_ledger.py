@@ -234,3 +234,24 @@ def test_the_circuit_accepts_the_ledgers_inputs(hz):
     assert g.read_raw_bytes() == witness
     lg.close()
     lg2.close()
+
+
+def test_one_handle_regrows_its_call_buffers(hz):
+    """3, 120 and 3 transfers with F = 2 on one ledger of k = 6, with n_sib = k, k + 3, k: the per-call buffers (the ledger's and its tree's)
+    are grown by the second call and reused by the third; every output of every call, the zero padding beyond depth k included, the
+    resident fields and the final tree are the builder's"""
+    k = 6
+    base = C.base_state(k)
+    lg = base.to_ledger(hz)
+    plan, idxs = [1, 0], [base.first_idx + 9, 0]
+    rng, nonce, db = np.random.default_rng(77), {}, None
+    for m, n_sib in [(3, k), (120, k + 3), (3, k)]:
+        txs = []
+        for i in range(m):
+            f, t = (base.first_idx + int(x) for x in rng.integers(0, base.N, size=2))
+            txs.append(C.tx(f, t, 1000 + i, C.SELECTORS[i % len(C.SELECTORS)], nonce=nonce.get(f, 0)))
+            nonce[f] = nonce.get(f, 0) + 1
+        db, _, got = _check(lg, base, txs, plan, idxs, db=db, n_levels=n_sib - 1)
+        assert got["siblings1"].shape == (m, n_sib, 32) and got["siblings3"].shape == (2, n_sib, 32)
+    _final_tree_matches(lg, base, db)
+    lg.close()

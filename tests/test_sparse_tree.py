@@ -228,3 +228,21 @@ def test_refused_calls_leave_the_tree_untouched(hz):
             hz.smt(bad)
         assert e.value.status == 1
     tree.close()
+
+
+def test_one_handle_regrows_its_call_buffers(hz):
+    """3, 200 and 3 ops on one tree of n_sib_max = 10, with n_sib = 7, 10, 7: the per-call buffers are grown by the second call and reused
+    by the third; every output of every call, the zero padding included, and the final root are the checker's"""
+    calls = C.regrow_calls()
+    assert [len(keys) for keys, _ in calls] == [3, 200, 3] and [n_sib for _, n_sib in calls] == [7, 10, 7]
+    tree = hz.smt(10)
+    t, n = None, 0
+    for keys, n_sib in calls:
+        fields = C.make_fields(keys, seed=50 + n)
+        t, res = C.smt_replay(keys, fields, smt=t)
+        assert all(r["depth"] < n_sib for r in res) and {r["fnc"] for r in res} == {0, 1}
+        got = _apply_and_check(tree, keys, fields, res, n_sib=n_sib)
+        assert got["siblings"].shape == (len(keys), n_sib, 32)
+        n += len(keys)
+    assert tree.root() == t.root and tree.size() == len({k for keys, _ in calls for k in keys})
+    tree.close()
