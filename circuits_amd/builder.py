@@ -938,6 +938,9 @@ def l2_batch_inputs(ledger, db_like, txs, n_tx, n_levels, max_l1, max_fee, fee_t
     verify=True: the transactions are signed first (as below) and go through capi.Ledger.apply_l2_signed, which verifies every signature
     on the device against the resident keys before the batch is applied and refuses it otherwise; txCompressedData and
     txCompressedDataV2 are then the ledger's arrays (device signals too with host_outputs=False).
+    A transaction with toIdx == 0 (transferToEthAddr / transferToBjj: toEthAddr, or the "any" address plus toBjjAy / toBjjSign) sends the
+    batch through capi.Ledger.apply_l2_addr instead: the ledger finds the receivers and auxToIdx is its array (a device signal too with
+    host_outputs=False). A batch without one takes the calls above and gives the same dictionary as before.
     -> (inputs, device signals or None)"""
     if len(txs) > n_tx:
         raise ValueError("batch full")
@@ -948,10 +951,14 @@ def l2_batch_inputs(ledger, db_like, txs, n_tx, n_levels, max_l1, max_fee, fee_t
     plan = list(fee_tokens) + [0] * (max_fee - len(fee_tokens))
     idxs = list(fee_idxs) + [0] * (max_fee - len(fee_idxs))
     padded = txs + [{}] * (n_tx - len(txs))
+    by_addr = any(t.get("fromIdx", 0) and t.get("toIdx", 0) == 0 for t in padded)
     if verify:
         for t in padded:
             if t.get("fromIdx", 0) and "signer" in t:
                 t.update(t["signer"].sign_msg(build_hash_sig(t, chain_id)))
+    if by_addr:
+        out = ledger.apply_l2_addr(padded, plan, idxs, chain_id, db_like.num_batch + 1, n_sib=n_levels + 1, verify=verify, outputs=host_outputs)
+    elif verify:
         out = ledger.apply_l2_signed(padded, plan, idxs, chain_id, db_like.num_batch + 1, n_sib=n_levels + 1, outputs=host_outputs)
     else:
         out = ledger.apply_l2(padded, plan, idxs, n_sib=n_levels + 1, outputs=host_outputs)
@@ -986,6 +993,9 @@ def l2_batch_inputs(ledger, db_like, txs, n_tx, n_levels, max_l1, max_fee, fee_t
         for name, (arr, first, rows) in sigs.items():
             width = {"siblings": n_levels + 1, "imAccFeeOut": max_fee}.get(name.rstrip("123"), 1)
             devsig[name] = (dev[arr] + first * width * 32, rows * width)
+        if by_addr:
+            del inp["auxToIdx"]
+            devsig["auxToIdx"] = (ledger.aux_to_idx_dev(), n_tx)
         return inp, devsig
 
     def ints(a):
@@ -997,6 +1007,8 @@ def l2_batch_inputs(ledger, db_like, txs, n_tx, n_levels, max_l1, max_fee, fee_t
         inp[name] = v[0] if name in ("imInitStateRootFee", "oldStateRoot") else v
     for name, arr in sig_signals.items():
         inp[name] = ints(out[arr])
+    if by_addr:
+        inp["auxToIdx"] = ints(out["auxToIdx"])
     return inp, None
 
 

@@ -72,6 +72,7 @@ EXPORTS = [
     "hz_ledger_create", "hz_ledger_destroy", "hz_ledger_load", "hz_ledger_root", "hz_ledger_accounts", "hz_ledger_tree", "hz_ledger_apply_l2",
     "hz_ledger_outputs_dev", "hz_ledger_plan_l2", "hz_ledger_device_ms", "hz_ledger_semantic_ms",
     "hz_ledger_apply_l2_signed", "hz_ledger_verify_l2", "hz_ledger_sig_outputs_dev", "hz_ledger_sig_ms",
+    "hz_ledger_apply_l2_addr", "hz_ledger_resolve_l2", "hz_ledger_aux_to_idx_dev", "hz_ledger_resolve_ms",
 ]
 
 
@@ -96,6 +97,7 @@ class hz_l2sig(ctypes.Structure):
 
 # hz_ledger_sig_out's arrays in order, [m, 32] each
 LEDGER_SIG_ARRAYS = ("tx_compressed_data", "tx_compressed_data_v2", "sig_l2_hash")
+LEDGER_VERIFY_SIGS = 1   # hz_ledger_apply_l2_addr's flag
 
 
 def l2sig_array(txs):
@@ -266,7 +268,10 @@ class Lib:
         c.hz_ledger_apply_l2_signed.argtypes = [vp, sz, vp, vp, u32, u32, sz, vp, vp, sz, vp, vp]
         c.hz_ledger_verify_l2.argtypes = [vp, sz, vp, vp, u32, u32, vp, vp]
         c.hz_ledger_sig_outputs_dev.argtypes = [vp, vp]
-        for f in ("hz_ledger_device_ms", "hz_ledger_semantic_ms", "hz_ledger_sig_ms"):
+        c.hz_ledger_apply_l2_addr.argtypes = [vp, sz, vp, vp, u32, vp, u32, u32, sz, vp, vp, sz, vp, vp, vp]
+        c.hz_ledger_resolve_l2.argtypes = [vp, sz, vp, vp, vp]
+        c.hz_ledger_aux_to_idx_dev.argtypes = [vp, ctypes.POINTER(vp)]
+        for f in ("hz_ledger_device_ms", "hz_ledger_semantic_ms", "hz_ledger_sig_ms", "hz_ledger_resolve_ms"):
             getattr(c, f).argtypes = [vp]
             getattr(c, f).restype = ctypes.c_double
 
@@ -883,6 +888,56 @@ class Ledger(_Resident):
         ptrs = (ctypes.c_void_p * len(LEDGER_SIG_ARRAYS))()
         self.L._check(self.L.c.hz_ledger_sig_outputs_dev(self.h, ctypes.addressof(ptrs)))
         return {name: ptrs[i] for i, name in enumerate(LEDGER_SIG_ARRAYS)}
+
+    def apply_l2_addr(self, txs, fee_plan_tokens, fee_idxs, chain_id, current_num_batch, n_sib=None, verify=False, aux_to_idx=None, outputs=True, into=None, sigs=None):
+        """apply_l2 over transactions whose toIdx may be 0: a receiver named by toEthAddr, or by the "any" address 2^160 - 1 plus toBjjAy /
+        toBjjSign, is found on the device (the lowest index that holds it and the token) unless aux_to_idx ([m] indices) supplies it.
+        verify=True: every signature is checked first as in apply_l2_signed, and its three arrays are returned as well. Returns
+        apply_l2's dictionary plus auxToIdx ([m, 32]). Reasons 9 (no such account), 10 and 11 (a supplied receiver does not hold the
+        signed address / key) refuse the batch. sigs: a prebuilt hz_l2sig array to go with a prebuilt hz_l2tx array."""
+        import numpy as np
+        n_sib = self.k if n_sib is None else n_sib
+        arr, m, plan, idxs, F, out, ptrs = self._l2_args(txs, fee_plan_tokens, fee_idxs, n_sib, outputs, into)
+        sigs = l2sig_array(txs) if sigs is None else sigs
+        sig_out, sig_ptrs = self._sig_out(m, outputs and verify, into)
+        aux = None
+        if aux_to_idx is not None:
+            aux = np.ascontiguousarray(aux_to_idx, dtype=np.uint64)
+            if aux.size != m:
+                raise ValueError("aux_to_idx: one entry per transaction")
+        aux_out = None
+        if outputs:
+            aux_out = into["auxToIdx"] if into is not None and "auxToIdx" in into else np.zeros((m, 32), dtype=np.uint8)
+            assert aux_out.shape == (m, 32) and aux_out.dtype == np.uint8 and aux_out.flags.c_contiguous
+        self.L._check(self.L.c.hz_ledger_apply_l2_addr(self.h, m, ctypes.addressof(arr), ctypes.addressof(sigs), LEDGER_VERIFY_SIGS if verify else 0,
+                                                       aux.ctypes.data if aux is not None else None, chain_id, current_num_batch, F, plan.ctypes.data,
+                                                       idxs.ctypes.data, n_sib, ctypes.addressof(ptrs) if outputs else None,
+                                                       ctypes.addressof(sig_ptrs) if outputs and verify else None,
+                                                       aux_out.ctypes.data if outputs and m else None))
+        out.update(sig_out)
+        if outputs:
+            out["auxToIdx"] = aux_out
+        return out
+
+    def resolve_l2(self, txs):
+        """the lookup alone: the index apply_l2_addr would find for every transaction as a uint64 array -- 0 for a NOP, for toIdx != 0 or
+        when no account matches; nothing resident changes"""
+        import numpy as np
+        arr, sigs = l2tx_array(txs), l2sig_array(txs)
+        m = len(txs)
+        out = np.zeros(max(m, 1), dtype=np.uint64)
+        self.L._check(self.L.c.hz_ledger_resolve_l2(self.h, m, ctypes.addressof(arr), ctypes.addressof(sigs), out.ctypes.data))
+        return out[:m]
+
+    def aux_to_idx_dev(self):
+        """device pointer of the [m, 32] auxToIdx rows of the last successful apply_l2_addr; valid until the ledger's next call"""
+        p = ctypes.c_void_p()
+        self.L._check(self.L.c.hz_ledger_aux_to_idx_dev(self.h, ctypes.byref(p)))
+        return p.value
+
+    def resolve_ms(self):
+        """device time of the two lookup kernels of the last apply_l2_addr / resolve_l2 (0.0 when none ran)"""
+        return self.L.c.hz_ledger_resolve_ms(self.h)
 
     def sig_ms(self):
         """device time of the two signature kernels of the last apply_l2_signed / verify_l2"""

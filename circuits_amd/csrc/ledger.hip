@@ -16,6 +16,14 @@
 //   k_ledger_writeback the last leaf of every touched account into the resident planes
 // hz_ledger_apply_l2_signed adds the two signature kernels of ledger_sig.hip after k_ledger_scan, on the same stream and
 // before the one synchronise: they lower the same failure word with reasons 7 and 8. hz_ledger_verify_l2 runs those two alone.
+// hz_ledger_apply_l2_addr accepts to_idx == 0, a receiver named by address or key. Before the plan can be made
+//   k_ledger_resolve       a lane per account: the account's key (ledger_resolve.h) probed in the table of the batch's distinct queries,
+//                          the slot's result lowered to the lowest matching account with atomicMin
+//   k_ledger_resolve_pick  a lane per transaction: its slot's result as an index, or 0
+//   -- a second synchronise, before the first: the planner needs the receivers --
+// and the pipeline above then runs on the effective receivers, while the uploaded transactions keep the signed to_idx = 0;
+// k_ledger_scan checks the receiver against the signed destination (reasons 10 and 11), k_ledger_pack writes the auxToIdx rows and the
+// leaf-2 rows of a zero-amount transfer to an address.
 // Values are plain 256-bit integers in eight 32-bit limbs (the Fc container of fr.h, nothing is reduced modulo r); deltas are
 // two's complement: every true prefix is below 2^220 in magnitude, so a set top bit means "negative"; the arithmetic is u256.h's, shared
 // with ledger_sig.h. Buffers and block offsets are hostutil.h's, the event holder resident.h's; the stream is the tree's (state_stream).
@@ -27,6 +35,7 @@
 #include "../../include/hermez_witness.h"
 #include "devcommon.h"
 #include "ledger_plan.h"
+#include "ledger_resolve.h"
 #include "resident.h"
 #include "state_internal.h"
 #include "u256.h"
@@ -106,7 +115,7 @@ __device__ __forceinline__ void ledger_fail(uint32_t* word, uint32_t unit, uint3
 
 // a lane per account group: the leaf before and after every event of the account, in order
 __global__ __launch_bounds__(64) void k_ledger_scan(const LedgerPos* __restrict__ pos, const uint32_t* __restrict__ seg_start, const hz_l2tx* __restrict__ txs,
-                                                    const uint32_t* __restrict__ plan_tok, const uint8_t* __restrict__ delta, const uint8_t* __restrict__ planes,
+                                                    const hz_l2sig* __restrict__ sigs, const uint32_t* __restrict__ plan_tok, const uint8_t* __restrict__ delta, const uint8_t* __restrict__ planes,
                                                     uint8_t* __restrict__ before, uint8_t* __restrict__ records, uint32_t* __restrict__ fail_word, uint32_t N,
                                                     uint32_t G, uint32_t m) {
     const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
@@ -124,6 +133,13 @@ __global__ __launch_bounds__(64) void k_ledger_scan(const LedgerPos* __restrict_
         const bool sender = ev.kind == LEDGER_EV_SENDER, fee = ev.kind == LEDGER_EV_FEE;
         const uint32_t tok = fee ? plan_tok[ev.unit - m] : txs[ev.unit].token_id;
         if (e0.v[0] != tok) ledger_fail(fail_word, ev.unit, sender ? 1u : fee ? 6u : 4u);
+        if (sigs && ev.kind == LEDGER_EV_RECEIVER && txs[ev.unit].to_idx == 0) {   // the signed destination against the receiver's leaf
+            const Fc to_eth = resolve_load32(sigs[ev.unit].to_eth_addr);
+            if (!resolve_fc_same(to_eth, eth)) ledger_fail(fail_word, ev.unit, 10u);
+            if (resolve_is_any(to_eth) &&
+                (!resolve_fc_same(resolve_load32(sigs[ev.unit].to_bjj_ay), ay) || (uint32_t)sigs[ev.unit].to_bjj_sign != ((e0.v[2] >> 8) & 1u)))
+                ledger_fail(fail_word, ev.unit, 11u);
+        }
         if (sender) {
             const uint64_t nonce = (uint64_t)e0.v[1] | ((uint64_t)(e0.v[2] & 0xFFu) << 32);
             if (nonce != txs[ev.unit].nonce) ledger_fail(fail_word, ev.unit, 2u);
@@ -166,8 +182,10 @@ __device__ __forceinline__ void ledger_put_leaf(const LedgerOutDev& o, int base,
     for (int q = 0; q < 6; q++) store_fr(o.a[base + q] + (size_t)row * 32, f[q]);
 }
 
-// a lane per transaction, then a lane per fee slot
-__global__ __launch_bounds__(64) void k_ledger_pack(const LedgerOutDev o, const hz_l2tx* __restrict__ txs, const int32_t* __restrict__ ev_s,
+// a lane per transaction, then a lane per fee slot. With sigs (hz_ledger_apply_l2_addr): the auxToIdx rows, and for a zero-amount
+// transfer to an address the leaf-2 rows the circuit compares with the signed destination (processor 2 is a NOP)
+__global__ __launch_bounds__(64) void k_ledger_pack(const LedgerOutDev o, const hz_l2tx* __restrict__ txs, const hz_l2sig* __restrict__ sigs,
+                                                    uint8_t* __restrict__ aux_rows, uint64_t first_idx, const int32_t* __restrict__ ev_s,
                                                     const int32_t* __restrict__ ev_r, const int32_t* __restrict__ ev_fee, const uint32_t* __restrict__ ev_acct,
                                                     const uint8_t* __restrict__ before, const uint8_t* __restrict__ planes, uint32_t N, uint32_t m, uint32_t F) {
     const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
@@ -176,6 +194,18 @@ __global__ __launch_bounds__(64) void k_ledger_pack(const LedgerOutDev o, const 
         const bool active = txs[u].from_idx != 0;
         ledger_put_leaf(o, LO_TX1, u, ev_s[u], 0u, ev_acct, before, planes, N);
         ledger_put_leaf(o, LO_TX2, u, ev_r[u], active ? txs[u].token_id : 0u, ev_acct, before, planes, N);
+        if (sigs) {
+            const bool to_addr = active && txs[u].to_idx == 0;
+            store_fr(aux_rows + (size_t)u * 32, u256_u64(to_addr && ev_r[u] >= 0 ? first_idx + ev_acct[ev_r[u]] : 0ull));
+            if (to_addr && ev_r[u] < 0) {
+                const Fc to_eth = resolve_load32(sigs[u].to_eth_addr);
+                store_fr(o.a[LO_TX2 + 5] + (size_t)u * 32, to_eth);
+                if (resolve_is_any(to_eth)) {
+                    store_fr(o.a[LO_TX2 + 4] + (size_t)u * 32, resolve_load32(sigs[u].to_bjj_ay));
+                    store_fr(o.a[LO_TX2 + 2] + (size_t)u * 32, u256_u64(sigs[u].to_bjj_sign));
+                }
+            }
+        }
     } else {
         ledger_put_leaf(o, LO_TX3, u - m, ev_fee[u - m], 0u, ev_acct, before, planes, N);
     }
@@ -223,10 +253,37 @@ __global__ __launch_bounds__(256) void k_ledger_accounts(const uint32_t* __restr
     store_fr(out + (size_t)t * 32, load_fr(planes + ((size_t)(t & 3u) * N + acct[t >> 2]) * 32));
 }
 
-static const char* const LEDGER_REASON[9] = {"", "the sender's token is not the transaction's", "the nonce is not the sender's current nonce",
+// a lane per account: its key probed in the table of the batch's queries; a hit lowers the slot's result to the lowest account
+__global__ __launch_bounds__(256) void k_ledger_resolve(const uint8_t* __restrict__ planes, const ResolveKey* __restrict__ table, uint32_t* __restrict__ result,
+                                                        uint32_t slots, uint32_t N) {
+    const uint32_t a = blockIdx.x * blockDim.x + threadIdx.x;
+    if (a >= N) return;
+    const Fc e0 = load_fr(planes + (size_t)a * 32);
+    const Fc eth = load_fr(planes + ((size_t)3 * N + a) * 32);
+    Fc ay = fc_zero();
+    if (resolve_is_any(eth)) ay = load_fr(planes + ((size_t)2 * N + a) * 32);
+    const int32_t s = resolve_probe(table, slots, resolve_key(e0.v[0], eth, ay, (e0.v[2] >> 8) & 1u));
+    // the result only falls: a lane that sees a lower account there already has nothing to add, and the holders of one address (all of
+    // them, in a state of few addresses) do not queue on one word
+    if (s >= 0 && a < __atomic_load_n(result + s, __ATOMIC_RELAXED)) atomicMin(result + s, a);
+}
+
+// a lane per transaction: the receiver its slot found as an index, or 0 (no query, or no account matches)
+__global__ __launch_bounds__(64) void k_ledger_resolve_pick(const int32_t* __restrict__ tx_slot, const uint32_t* __restrict__ result, uint64_t* __restrict__ out,
+                                                            uint64_t first_idx, uint32_t m) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const int32_t s = tx_slot[i];
+    const uint32_t a = s >= 0 ? result[s] : HZ_RESOLVE_NONE;
+    out[i] = a != HZ_RESOLVE_NONE ? first_idx + a : 0ull;
+}
+
+static const char* const LEDGER_REASON[12] = {"", "the sender's token is not the transaction's", "the nonce is not the sender's current nonce",
                                              "the sender's balance is below amount + fee", "the receiver's token is not the transaction's",
                                              "a new balance reaches 2^192", "the fee account's token is not the slot's plan token",
-                                             "the signature is rejected", "max_num_batch has expired"};
+                                             "the signature is rejected", "max_num_batch has expired",
+                                              "no account holds the signed destination with the transaction's token",
+                                              "the receiver's ethAddr is not the signed to_eth_addr", "the receiver's key is not the signed to_bjj_ay / to_bjj_sign"};
 
 // ledger_sig.hip
 hipError_t launch_ledger_sig(const hz_l2tx* d_txs, const hz_l2sig* d_sigs, uint32_t chain_id, uint32_t current_num_batch, uint8_t* d_tcd, uint8_t* d_v2, uint8_t* d_hash,
@@ -259,6 +316,12 @@ struct hz_ledger {
     bool have_sig_outputs = false;
     DevEvent es0, es1;
     double sig_ms = 0.0;
+    // receivers by address (hz_ledger_apply_l2_addr / _resolve_l2): the query table and the per-transaction results, the auxToIdx rows
+    DevBuf res, aux_rows;
+    PinnedBuf h_res;
+    bool have_aux = false;
+    DevEvent er0, er1;
+    double resolve_ms = 0.0;
     ~hz_ledger() {
         if (tree) hz_state_destroy(tree);
     }
@@ -272,8 +335,9 @@ static hz_status ledger_ready(const hz_ledger* l, const char* who) {
 
 static bool ledger_has(uint64_t first_idx, uint64_t N, uint64_t idx) { return idx >= first_idx && idx - first_idx < N; }
 
-// the per-transaction argument checks of every call that takes transactions; a NOP (from_idx == 0) is not looked at
-static hz_status ledger_check_txs(const char* who, size_t m, const hz_l2tx* txs, uint64_t first_idx, uint64_t N) {
+// the per-transaction argument checks of every call that takes transactions; a NOP (from_idx == 0) is not looked at. by_addr: to_idx == 0
+// (a receiver named by address or key) passes
+static hz_status ledger_check_txs(const char* who, size_t m, const hz_l2tx* txs, uint64_t first_idx, uint64_t N, bool by_addr = false) {
     const uint64_t last = first_idx + N - 1;
     for (size_t i = 0; i < m; i++) {
         const hz_l2tx& t = txs[i];
@@ -281,6 +345,10 @@ static hz_status ledger_check_txs(const char* who, size_t m, const hz_l2tx* txs,
         if (!ledger_has(first_idx, N, t.from_idx))
             return set_err(HZ_ERR_ARG, "%s: tx %zu: from_idx = %llu is outside the state (%llu .. %llu)", who, i, (unsigned long long)t.from_idx,
                            (unsigned long long)first_idx, (unsigned long long)last);
+        if (t.to_idx == 0 && by_addr) {
+            if (t.amount_f >> 40) return set_err(HZ_ERR_ARG, "%s: tx %zu: amount_f has more than 40 bits", who, i);
+            continue;
+        }
         if (t.to_idx <= 1)
             return set_err(HZ_ERR_ARG, "%s: tx %zu: to_idx = %llu (%s) is not supported yet", who, i, (unsigned long long)t.to_idx,
                            t.to_idx ? "an exit" : "a transfer to an address");
@@ -292,14 +360,15 @@ static hz_status ledger_check_txs(const char* who, size_t m, const hz_l2tx* txs,
     return HZ_OK;
 }
 
-// the argument checks hz_ledger_apply_l2 and hz_ledger_plan_l2 share; on success the plan is made
+// the argument checks hz_ledger_apply_l2 and hz_ledger_plan_l2 share; on success the plan is made. by_addr (hz_ledger_apply_l2_addr): the
+// checks alone -- the plan is made later, on the effective receivers
 static hz_status ledger_check_plan(const char* who, size_t m, const hz_l2tx* txs, size_t F, const uint32_t* plan_tokens, const uint64_t* fee_idxs, uint32_t k,
-                                   uint64_t first_idx, LedgerPlan& plan) {
+                                   uint64_t first_idx, LedgerPlan& plan, bool by_addr = false) {
     if ((m && !txs) || (F && (!plan_tokens || !fee_idxs))) return set_err(HZ_ERR_ARG, "%s: null argument", who);
     if (F > HZ_LEDGER_MAX_F) return set_err(HZ_ERR_ARG, "%s: F = %zu fee slots (at most %u)", who, F, HZ_LEDGER_MAX_F);
     if (m > HZ_LEDGER_MAX_TX) return set_err(HZ_ERR_ARG, "%s: %zu transactions in one call (at most %u)", who, m, HZ_LEDGER_MAX_TX);
     const uint64_t N = 1ull << k, last = first_idx + N - 1;
-    if (hz_status e = ledger_check_txs(who, m, txs, first_idx, N)) return e;
+    if (hz_status e = ledger_check_txs(who, m, txs, first_idx, N, by_addr)) return e;
     for (size_t j = 0; j < F; j++)
         if (fee_idxs[j] != 0 && !ledger_has(first_idx, N, fee_idxs[j]))
             return set_err(HZ_ERR_ARG, "%s: fee_idxs[%zu] = %llu is outside the state (%llu .. %llu)", who, j, (unsigned long long)fee_idxs[j],
@@ -309,7 +378,7 @@ static hz_status ledger_check_plan(const char* who, size_t m, const hz_l2tx* txs
         if (txs[i].from_idx != 0) events += 1 + (ledger_mantissa(txs[i].amount_f) != 0);
     for (size_t j = 0; j < F; j++) events += fee_idxs[j] != 0;
     if (events > HZ_LEDGER_MAX_EVENTS) return set_err(HZ_ERR_ARG, "%s: %zu updates in one call (at most %u)", who, events, HZ_LEDGER_MAX_EVENTS);
-    ledger_plan_l2(m, txs, F, plan_tokens, fee_idxs, plan);
+    if (!by_addr) ledger_plan_l2(m, txs, F, plan_tokens, fee_idxs, plan);
     return HZ_OK;
 }
 
@@ -345,7 +414,7 @@ extern "C" hz_status hz_ledger_create(int32_t device, int32_t k, uint64_t first_
     HZ_HIP(hipSetDevice(device));
     HZ_HIP(l->planes.alloc((size_t)4 * l->N * 32));
     HZ_HIP(l->h_fail.grow(64));
-    for (DevEvent* e : {&l->e0, &l->e1, &l->e2, &l->es0, &l->es1}) HZ_HIP(e->create());
+    for (DevEvent* e : {&l->e0, &l->e1, &l->e2, &l->es0, &l->es1, &l->er0, &l->er1}) HZ_HIP(e->create());
     *out = l.release();
     return HZ_OK;
 }
@@ -359,7 +428,7 @@ extern "C" void hz_ledger_destroy(hz_ledger* l) {
 
 extern "C" hz_status hz_ledger_load(hz_ledger* l, const uint8_t* e0, const uint8_t* balance, const uint8_t* ay, const uint8_t* eth_addr) {
     if (!l || !e0 || !balance || !ay || !eth_addr) return set_err(HZ_ERR_ARG, "hz_ledger_load: null argument");
-    l->have_outputs = l->have_sig_outputs = false;
+    l->have_outputs = l->have_sig_outputs = l->have_aux = false;
     if (hz_status e = hz_state_load(l->tree, e0, balance, ay, eth_addr)) return e;   // checks every field < r
     const uint8_t* src[4] = {e0, balance, ay, eth_addr};
     hipStream_t s = state_stream(l->tree);
@@ -390,7 +459,7 @@ extern "C" hz_status hz_ledger_accounts(hz_ledger* l, size_t n, const uint64_t* 
         acct[i] = (uint32_t)(idx[i] - l->first_idx);
     }
     HZ_HIP(hipSetDevice(l->device));
-    l->have_outputs = l->have_sig_outputs = false;   // the call's buffers are reused
+    l->have_outputs = l->have_sig_outputs = l->have_aux = false;   // the call's buffers are reused
     hipStream_t s = state_stream(l->tree);
     HZ_HIP(l->ints.grow(n * 4));
     HZ_HIP(l->work.grow(n * 128));
@@ -411,10 +480,11 @@ extern "C" hz_status hz_ledger_outputs_dev(hz_ledger* l, hz_ledger_out* dev) {
     return HZ_OK;
 }
 
-// the argument checks of the signed calls beyond those of the transactions; a NOP's entry is not looked at
-static hz_status ledger_check_sigs(const char* who, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, uint32_t chain_id) {
+// the argument checks of the signed calls beyond those of the transactions; a NOP's entry is not looked at. verify == false
+// (hz_ledger_apply_l2_addr without HZ_LEDGER_VERIFY_SIGS): the destination fields alone, s, r8x, r8y and chain_id are not read
+static hz_status ledger_check_sigs(const char* who, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, uint32_t chain_id, bool verify = true) {
     if (m && !sigs) return set_err(HZ_ERR_ARG, "%s: null sigs", who);
-    if (chain_id >> 16) return set_err(HZ_ERR_ARG, "%s: chain_id = %u has more than 16 bits", who, chain_id);
+    if (verify && chain_id >> 16) return set_err(HZ_ERR_ARG, "%s: chain_id = %u has more than 16 bits", who, chain_id);
     for (size_t i = 0; i < m; i++) {
         if (txs[i].from_idx == 0) continue;
         const hz_l2sig& g = sigs[i];
@@ -423,15 +493,16 @@ static hz_status ledger_check_sigs(const char* who, size_t m, const hz_l2tx* txs
             if (g.to_eth_addr[b]) return set_err(HZ_ERR_ARG, "%s: tx %zu: to_eth_addr has more than 160 bits", who, i);
         const uint8_t* f[4] = {g.s, g.r8x, g.r8y, g.to_bjj_ay};
         static const char* const name[4] = {"s", "r8x", "r8y", "to_bjj_ay"};
-        for (int q = 0; q < 4; q++)
+        for (int q = verify ? 0 : 3; q < 4; q++)
             if (!canon_lt_p(f[q])) return set_err(HZ_ERR_INPUT, "%s: tx %zu: %s is not below the field's modulus", who, i, name[q]);
     }
     return HZ_OK;
 }
 
-// the signatures and the fixed-base table on the device, room for the three arrays and the verdict bytes
-static hz_status ledger_sig_prepare(hz_ledger* l, size_t m, const hz_l2sig* sigs, hipStream_t s) {
-    if (!l->b8_table.p) {
+// the signatures and the fixed-base table on the device, room for the three arrays and the verdict bytes; verify == false: the upload
+// alone, for the destination fields
+static hz_status ledger_sig_prepare(hz_ledger* l, size_t m, const hz_l2sig* sigs, hipStream_t s, bool verify = true) {
+    if (verify && !l->b8_table.p) {
         std::vector<uint8_t> table(ledger_sig_b8_table_bytes());
         ledger_sig_b8_table_host(table.data());
         HZ_HIP(l->b8_table.alloc(table.size()));
@@ -455,19 +526,27 @@ static hz_status ledger_sig_copy_out(hz_ledger* l, size_t m, const hz_ledger_sig
     return HZ_OK;
 }
 
-// hz_ledger_apply_l2 (sigs == nullptr) and hz_ledger_apply_l2_signed
+// hz_ledger_apply_l2 (sigs == nullptr), hz_ledger_apply_l2_signed and, with eff_txs, hz_ledger_apply_l2_addr: the caller has checked the
+// arguments; eff_txs are the transactions with the effective receivers, which the plan is made of, while txs -- the signed ones, to_idx
+// == 0 where the receiver is named by address -- are what the kernels see; sigs are uploaded for their destination fields whether or
+// not they are verified
 static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, bool with_sigs, uint32_t chain_id,
                               uint32_t current_num_batch, size_t F, const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs, size_t n_sib, const hz_ledger_out* out,
-                              const hz_ledger_sig_out* sig_out) {
+                              const hz_ledger_sig_out* sig_out, const hz_l2tx* eff_txs = nullptr, uint8_t* aux_to_idx_out = nullptr) {
     static_assert(sizeof(hz_ledger_out) == HZ_LEDGER_ARRAYS * sizeof(uint8_t*), "hz_ledger_out is an array of pointers");
     if (hz_status e = ledger_ready(l, who)) return e;
     const uint32_t k = l->k, N = l->N;
     if (n_sib < k || n_sib > 64) return set_err(HZ_ERR_ARG, "%s: n_sib = %zu (%u .. 64)", who, n_sib, k);
     LedgerPlan& p = l->plan;
-    if (hz_status e = ledger_check_plan(who, m, txs, F, fee_plan_tokens, fee_idxs, k, l->first_idx, p)) return e;
-    if (with_sigs)
-        if (hz_status e = ledger_check_sigs(who, m, txs, sigs, chain_id)) return e;
-    l->have_outputs = l->have_sig_outputs = false;
+    const bool by_addr = eff_txs != nullptr;
+    if (by_addr) {
+        ledger_plan_l2(m, eff_txs, F, fee_plan_tokens, fee_idxs, p);
+    } else {
+        if (hz_status e = ledger_check_plan(who, m, txs, F, fee_plan_tokens, fee_idxs, k, l->first_idx, p)) return e;
+        if (with_sigs)
+            if (hz_status e = ledger_check_sigs(who, m, txs, sigs, chain_id)) return e;
+    }
+    l->have_outputs = l->have_sig_outputs = l->have_aux = false;
     const uint32_t m32 = (uint32_t)m, F32 = (uint32_t)F, S = (uint32_t)n_sib;
     const uint32_t M = (uint32_t)p.account.size(), G = (uint32_t)p.seg_start.size() - 1;
     const uint32_t n_chunks = m32 ? (m32 + HZ_LEDGER_CHUNK - 1) / HZ_LEDGER_CHUNK : 1u;
@@ -549,8 +628,10 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
         if (hz_status e = state_apply_prepare(l->tree, M, p.account.data(), S, &tb)) return e;
     HZ_HIP(hipMemcpyAsync(l->ints.p, l->h_ints.p, ints_bytes, hipMemcpyHostToDevice, s));
     HZ_HIP(hipMemsetAsync(d_fail, 0xFF, 4, s));
-    if (with_sigs)
-        if (hz_status e = ledger_sig_prepare(l, m, sigs, s)) return e;
+    if (with_sigs || by_addr)
+        if (hz_status e = ledger_sig_prepare(l, m, sigs, s, with_sigs)) return e;
+    const hz_l2sig* d_dest = by_addr ? (const hz_l2sig*)l->sig_in.p : nullptr;   // the signed destinations, for reasons 10 and 11 and the zero-amount rows
+    if (by_addr) HZ_HIP(l->aux_rows.grow((m ? m : 1) * 32));
 
     // ---- the semantic kernels
     HZ_HIP(hipEventRecord(l->e0, s));
@@ -567,7 +648,7 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
         HZ_HIP(hipGetLastError());
     }
     if (G) {
-        hipLaunchKernelGGL(k_ledger_scan, dim3((G + 63) / 64), dim3(64), 0, s, d_pos, d_seg, d_txs, (const uint32_t*)(db + o_plan), (const uint8_t*)(wb + w_delta),
+        hipLaunchKernelGGL(k_ledger_scan, dim3((G + 63) / 64), dim3(64), 0, s, d_pos, d_seg, d_txs, d_dest, (const uint32_t*)(db + o_plan), (const uint8_t*)(wb + w_delta),
                            (const uint8_t*)l->planes.p, wb + w_before, tb.fields, d_fail, N, G, m32);
         HZ_HIP(hipGetLastError());
     }
@@ -584,14 +665,14 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
     if (word != 0xFFFFFFFFu) {
         const uint32_t unit = word >> 8, reason = word & 0xFFu;
         if (unit >= m32)
-            return set_err(HZ_ERR_INPUT, "%s: refused at index %u (fee slot %u), reason %u: %s", who, unit, unit - m32, reason, LEDGER_REASON[reason < 9 ? reason : 0]);
-        return set_err(HZ_ERR_INPUT, "%s: refused at index %u (transaction %u), reason %u: %s", who, unit, unit, reason, LEDGER_REASON[reason < 9 ? reason : 0]);
+            return set_err(HZ_ERR_INPUT, "%s: refused at index %u (fee slot %u), reason %u: %s", who, unit, unit - m32, reason, LEDGER_REASON[reason < 12 ? reason : 0]);
+        return set_err(HZ_ERR_INPUT, "%s: refused at index %u (transaction %u), reason %u: %s", who, unit, unit, reason, LEDGER_REASON[reason < 12 ? reason : 0]);
     }
 
     // ---- outputs, tree, resident planes
     if (m32 + F32) {
-        hipLaunchKernelGGL(k_ledger_pack, dim3((m32 + F32 + 63) / 64), dim3(64), 0, s, od, d_txs, (const int32_t*)(db + o_ev_s), (const int32_t*)(db + o_ev_r),
-                           (const int32_t*)(db + o_ev_fee), (const uint32_t*)(db + o_acct), (const uint8_t*)(wb + w_before), (const uint8_t*)l->planes.p, N, m32, F32);
+        hipLaunchKernelGGL(k_ledger_pack, dim3((m32 + F32 + 63) / 64), dim3(64), 0, s, od, d_txs, d_dest, (uint8_t*)l->aux_rows.p, l->first_idx, (const int32_t*)(db + o_ev_s),
+                           (const int32_t*)(db + o_ev_r), (const int32_t*)(db + o_ev_fee), (const uint32_t*)(db + o_acct), (const uint8_t*)(wb + w_before), (const uint8_t*)l->planes.p, N, m32, F32);
         HZ_HIP(hipGetLastError());
     }
     const uint8_t* root0 = state_root_dev(l->tree);
@@ -620,6 +701,7 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
     }
     if (with_sigs)
         if (hz_status e = ledger_sig_copy_out(l, m, sig_out, s)) return e;
+    if (by_addr && aux_to_idx_out && m) HZ_HIP(hipMemcpyAsync(aux_to_idx_out, l->aux_rows.p, m * 32, hipMemcpyDeviceToHost, s));
     if (M) {
         if (hz_status e = state_apply_finish(l->tree)) return e;
     } else {
@@ -632,6 +714,7 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
     l->device_ms = ms;
     l->out_dev = od;
     l->have_outputs = true;
+    l->have_aux = by_addr;
     if (with_sigs) {
         HZ_HIP(hipEventElapsedTime(&ms, l->es0, l->es1));
         l->sig_ms = ms;
@@ -659,7 +742,7 @@ extern "C" hz_status hz_ledger_verify_l2(hz_ledger* l, size_t m, const hz_l2tx* 
     if (m > HZ_LEDGER_MAX_TX) return set_err(HZ_ERR_ARG, "%s: %zu transactions in one call (at most %u)", who, m, HZ_LEDGER_MAX_TX);
     if (hz_status e = ledger_check_txs(who, m, txs, l->first_idx, l->N)) return e;
     if (hz_status e = ledger_check_sigs(who, m, txs, sigs, chain_id)) return e;
-    l->have_outputs = l->have_sig_outputs = false;
+    l->have_outputs = l->have_sig_outputs = l->have_aux = false;
     HZ_HIP(hipSetDevice(l->device));
     hipStream_t s = state_stream(l->tree);
     HZ_HIP(l->ints.grow((m ? m : 1) * sizeof(hz_l2tx)));
@@ -690,3 +773,106 @@ extern "C" hz_status hz_ledger_sig_outputs_dev(hz_ledger* l, hz_ledger_sig_out* 
 }
 
 extern "C" double hz_ledger_sig_ms(const hz_ledger* l) { return l ? l->sig_ms : 0.0; }
+
+// ---- receivers named by address or key ----------------------------------------------------------------------------------
+// The lookup: out[i] is the lowest account that holds transaction i's signed destination and its token, 0 for a NOP, for to_idx != 0, for
+// a zero amount when skip_zero (processor 2 is a NOP then: no receiver is needed), or when no account matches. Host: the distinct
+// queries into the table; device: one pass over the planes, then a lane per transaction; one copy back and a synchronise.
+static hz_status ledger_resolve(hz_ledger* l, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, bool skip_zero, uint64_t* out) {
+    l->resolve_ms = 0.0;
+    size_t queries = 0;
+    for (size_t i = 0; i < m; i++) {
+        out[i] = 0;
+        queries += txs[i].from_idx != 0 && txs[i].to_idx == 0 && !(skip_zero && ledger_mantissa(txs[i].amount_f) == 0);
+    }
+    if (!queries) return HZ_OK;
+    const uint32_t slots = resolve_slots(queries), m32 = (uint32_t)m;
+    Carve c;
+    const size_t o_table = c.take((size_t)slots * sizeof(ResolveKey)), o_result = c.take((size_t)slots * 4), o_slot = c.take(m * 4), up_bytes = c.end,
+                 o_out = c.take(m * 8);
+    HZ_HIP(hipSetDevice(l->device));
+    HZ_HIP(l->h_res.grow(c.end));
+    HZ_HIP(l->res.grow(c.end));
+    uint8_t* hb = (uint8_t*)l->h_res.p;
+    uint8_t* db = (uint8_t*)l->res.p;
+    memset(hb + o_table, 0, (size_t)slots * sizeof(ResolveKey));
+    memset(hb + o_result, 0xFF, (size_t)slots * 4);
+    for (size_t i = 0; i < m; i++) {
+        int32_t slot = -1;
+        if (txs[i].from_idx != 0 && txs[i].to_idx == 0 && !(skip_zero && ledger_mantissa(txs[i].amount_f) == 0))
+            slot = resolve_insert((ResolveKey*)(hb + o_table), slots,
+                                  resolve_key(txs[i].token_id, resolve_load32(sigs[i].to_eth_addr), resolve_load32(sigs[i].to_bjj_ay), sigs[i].to_bjj_sign));
+        ((int32_t*)(hb + o_slot))[i] = slot;
+    }
+    hipStream_t s = state_stream(l->tree);
+    HZ_HIP(hipMemcpyAsync(db, hb, up_bytes, hipMemcpyHostToDevice, s));
+    HZ_HIP(hipEventRecord(l->er0, s));
+    hipLaunchKernelGGL(k_ledger_resolve, dim3((l->N + 255) / 256), dim3(256), 0, s, (const uint8_t*)l->planes.p, (const ResolveKey*)(db + o_table),
+                       (uint32_t*)(db + o_result), slots, l->N);
+    HZ_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_ledger_resolve_pick, dim3((m32 + 63) / 64), dim3(64), 0, s, (const int32_t*)(db + o_slot), (const uint32_t*)(db + o_result),
+                       (uint64_t*)(db + o_out), l->first_idx, m32);
+    HZ_HIP(hipGetLastError());
+    HZ_HIP(hipEventRecord(l->er1, s));
+    HZ_HIP(hipMemcpyAsync(hb + o_out, db + o_out, m * 8, hipMemcpyDeviceToHost, s));
+    HZ_HIP(hipStreamSynchronize(s));   // the round trip of the lookup: the planner needs the receivers
+    memcpy(out, hb + o_out, m * 8);
+    float ms = 0;
+    HZ_HIP(hipEventElapsedTime(&ms, l->er0, l->er1));
+    l->resolve_ms = ms;
+    return HZ_OK;
+}
+
+extern "C" hz_status hz_ledger_resolve_l2(hz_ledger* l, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, uint64_t* aux_to_idx_out) {
+    const char* who = "hz_ledger_resolve_l2";
+    if (hz_status e = ledger_ready(l, who)) return e;
+    if (m && (!txs || !sigs || !aux_to_idx_out)) return set_err(HZ_ERR_ARG, "%s: null argument", who);
+    if (m > HZ_LEDGER_MAX_TX) return set_err(HZ_ERR_ARG, "%s: %zu transactions in one call (at most %u)", who, m, HZ_LEDGER_MAX_TX);
+    return ledger_resolve(l, m, txs, sigs, false, aux_to_idx_out);
+}
+
+extern "C" hz_status hz_ledger_apply_l2_addr(hz_ledger* l, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, uint32_t flags, const uint64_t* aux_to_idx,
+                                             uint32_t chain_id, uint32_t current_num_batch, size_t F, const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs,
+                                             size_t n_sib, const hz_ledger_out* out, const hz_ledger_sig_out* sig_out, uint8_t* aux_to_idx_out) {
+    const char* who = "hz_ledger_apply_l2_addr";
+    if (hz_status e = ledger_ready(l, who)) return e;
+    const bool verify = (flags & HZ_LEDGER_VERIFY_SIGS) != 0;
+    if (flags & ~HZ_LEDGER_VERIFY_SIGS) return set_err(HZ_ERR_ARG, "%s: flags = %#x", who, flags);
+    if (!verify && sig_out) return set_err(HZ_ERR_ARG, "%s: sig_out without HZ_LEDGER_VERIFY_SIGS", who);
+    if (n_sib < l->k || n_sib > 64) return set_err(HZ_ERR_ARG, "%s: n_sib = %zu (%u .. 64)", who, n_sib, l->k);
+    if (hz_status e = ledger_check_plan(who, m, txs, F, fee_plan_tokens, fee_idxs, l->k, l->first_idx, l->plan, true)) return e;
+    if (hz_status e = ledger_check_sigs(who, m, txs, sigs, chain_id, verify)) return e;
+    std::vector<hz_l2tx> eff(m ? m : 1);   // (never empty: its address tells ledger_apply which call this is)
+    if (m) memcpy(eff.data(), txs, m * sizeof(hz_l2tx));
+    auto wants_receiver = [&](size_t i) { return txs[i].from_idx != 0 && txs[i].to_idx == 0 && ledger_mantissa(txs[i].amount_f) != 0; };
+    if (aux_to_idx) {
+        for (size_t i = 0; i < m; i++) {
+            if (!wants_receiver(i)) continue;
+            if (!ledger_has(l->first_idx, l->N, aux_to_idx[i]))
+                return set_err(HZ_ERR_ARG, "%s: tx %zu: aux_to_idx = %llu is outside the state (%llu .. %llu)", who, i, (unsigned long long)aux_to_idx[i],
+                               (unsigned long long)l->first_idx, (unsigned long long)(l->first_idx + l->N - 1));
+            eff[i].to_idx = aux_to_idx[i];
+        }
+        l->resolve_ms = 0.0;
+    } else {
+        std::vector<uint64_t> found(m ? m : 1);
+        l->have_outputs = l->have_sig_outputs = l->have_aux = false;
+        if (hz_status e = ledger_resolve(l, m, txs, sigs, true, found.data())) return e;
+        for (size_t i = 0; i < m; i++) {
+            if (!wants_receiver(i)) continue;
+            if (found[i] == 0)   // before the plan can exist: reported whatever else is wrong with the batch
+                return set_err(HZ_ERR_INPUT, "%s: refused at index %zu (transaction %zu), reason 9: %s", who, i, i, LEDGER_REASON[9]);
+            eff[i].to_idx = found[i];
+        }
+    }
+    return ledger_apply(l, who, m, txs, sigs, verify, chain_id, current_num_batch, F, fee_plan_tokens, fee_idxs, n_sib, out, sig_out, eff.data(), aux_to_idx_out);
+}
+
+extern "C" hz_status hz_ledger_aux_to_idx_dev(hz_ledger* l, uint8_t** dev) {
+    if (!l || !dev) return set_err(HZ_ERR_ARG, "hz_ledger_aux_to_idx_dev: null argument");
+    if (!l->have_aux) return set_err(HZ_ERR_ARG, "hz_ledger_aux_to_idx_dev: no successful hz_ledger_apply_l2_addr since the ledger's last other call");
+    *dev = (uint8_t*)l->aux_rows.p;
+    return HZ_OK;
+}
+
+extern "C" double hz_ledger_resolve_ms(const hz_ledger* l) { return l ? l->resolve_ms : 0.0; }

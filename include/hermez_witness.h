@@ -453,8 +453,37 @@ hz_status hz_smt_plan(size_t m, const uint64_t* key, size_t n_sib, uint32_t* dep
  *   7 the signature is rejected (any cause above)       8 max_num_batch != 0 and max_num_batch < current_num_batch
  * HZ_ERR_INPUT: s, r8x, r8y or to_bjj_ay >= r. HZ_ERR_ARG: null sigs, to_eth_addr >= 2^160, chain_id >= 2^16, to_bjj_sign > 1, and
  * everything hz_ledger_apply_l2 refuses as an argument.
- * OUT OF SCOPE: L1 transactions, new accounts, exits, transfers to an address, atomic (rqOffset) fields, batch (random linear
- * combination) verification of signatures, more than one device per ledger. One thread at a time. */
+ * RECEIVERS BY ADDRESS OR KEY. A transaction with to_idx == 0 is transferToEthAddr / transferToBjj: the user signs
+ * to_eth_addr, or the "any" address 2^160 - 1 plus (to_bjj_ay, to_bjj_sign), and the coordinator picks the receiver. The four calls above
+ * keep refusing it; these accept it:
+ *   hz_ledger_apply_l2_addr  hz_ledger_apply_l2 over transactions whose to_idx may be 0. sigs[m] is required: its destination fields are
+ *                       always read; s, r8x, r8y only with HZ_LEDGER_VERIFY_SIGS in flags, and the call then verifies exactly as
+ *                       hz_ledger_apply_l2_signed does (reasons 7 and 8; sig_out as there). Without the flag sig_out must be NULL and
+ *                       chain_id / current_num_batch are not looked at. For an active transaction with to_idx == 0 and amount != 0 the
+ *                       receiver is aux_to_idx[i] when that array is given (the entry must lie inside the state), and otherwise the
+ *                       LOWEST index whose leaf holds to_eth_addr -- or, when to_eth_addr is the "any" address, that address with ay ==
+ *                       to_bjj_ay and sign == to_bjj_sign -- and the token token_id, found on the device in the resident planes as they
+ *                       are before the batch (keys, addresses and tokens never change in an L2 batch, so that is exact). The receiver
+ *                       then behaves as in a plain transfer: it sees the sender's update, and a transfer to one's own address that
+ *                       resolves to the sender sees the new leaf. With amount == 0 processor 2 is a NOP, nothing is looked up, and the
+ *                       leaf-2 rows are what the circuit compares with the signed destination: ethAddr2 = to_eth_addr and, under the
+ *                       "any" address, ay2 = to_bjj_ay and sign2 = to_bjj_sign; tokenID2 = token_id, the rest zero, siblings2 zero.
+ *                       to_idx >= 2 is today's transfer; to_idx == 1 stays HZ_ERR_ARG. The signed to_idx (0) is what txCompressedData,
+ *                       txCompressedDataV2 and the message carry. aux_to_idx_out (may be NULL): auxToIdx as [m][32] elements -- the
+ *                       receiver of a to_idx == 0 transaction with amount != 0, otherwise 0.
+ *   hz_ledger_resolve_l2  the lookup alone: aux_to_idx_out[m], 0 for a NOP, for to_idx != 0 or when nothing matches; a zero amount is
+ *                       still resolved. Changes nothing and refuses nothing.
+ *   hz_ledger_aux_to_idx_dev  the auxToIdx rows as a DEVICE pointer, [m][32] of the last successful hz_ledger_apply_l2_addr, valid until
+ *                       the ledger's next call; fit for hz_set_input_dev
+ *   hz_ledger_resolve_ms  device time of the two lookup kernels of the last hz_ledger_apply_l2_addr / _resolve_l2 (0: none ran)
+ * Further refusal reasons of hz_ledger_apply_l2_addr:
+ *   9 no account holds the signed destination with the transaction's token. The lookup runs before the plan of the batch can exist, so
+ *     reason 9 is reported FIRST: it names the lowest such transaction whatever else is wrong with the batch (a lower transaction with a
+ *     reason of 1 - 8 included).
+ *   10 the receiver's ethAddr != to_eth_addr     11 under the "any" address: the receiver's ay / sign != to_bjj_ay / to_bjj_sign
+ *   10 and 11 are reachable only through a supplied aux_to_idx and rank with 1 - 8: lowest index, then lowest reason.
+ * OUT OF SCOPE: L1 transactions, new accounts, exits, atomic (rqOffset) fields, a resident address index kept across calls, batch (random
+ * linear combination) verification of signatures, more than one device per ledger. One thread at a time. */
 typedef struct hz_ledger hz_ledger;
 typedef struct {
     uint64_t from_idx, to_idx, amount_f /* float40 */, nonce;
@@ -505,6 +534,14 @@ hz_status hz_ledger_verify_l2(hz_ledger* l, size_t m, const hz_l2tx* txs, const 
                               uint8_t* verdict_out /* [m]: 0, 7 or 8 */, const hz_ledger_sig_out* sig_out);
 hz_status hz_ledger_sig_outputs_dev(hz_ledger* l, hz_ledger_sig_out* dev);
 double hz_ledger_sig_ms(const hz_ledger* l);
+#define HZ_LEDGER_VERIFY_SIGS 1u
+hz_status hz_ledger_apply_l2_addr(hz_ledger* l, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, uint32_t flags,
+                                  const uint64_t* aux_to_idx /* [m] or NULL */, uint32_t chain_id, uint32_t current_num_batch, size_t F,
+                                  const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs, size_t n_sib, const hz_ledger_out* out,
+                                  const hz_ledger_sig_out* sig_out, uint8_t* aux_to_idx_out /* [m][32] or NULL */);
+hz_status hz_ledger_resolve_l2(hz_ledger* l, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, uint64_t* aux_to_idx_out /* [m] */);
+hz_status hz_ledger_aux_to_idx_dev(hz_ledger* l, uint8_t** dev);
+double hz_ledger_resolve_ms(const hz_ledger* l);
 
 /* Poseidon batch: n independent permutations of width t = n_inputs + 1 (2..7). ----------------
  * `in`  : [n][t-1] canonical elements; `out`: [n] digests (state[0] after the last round).
