@@ -856,35 +856,8 @@ class BatchBuilder:
 
     # data-availability strings and the global hash (src/hash-inputs.circom:117-184)
     def get_hash_inputs(self):
-        L, F, nTx = self.L, self.F, self.nTx
-        inp = self.input
-        bits = []
-
-        def be(v, n):
-            bits.extend((v >> (n - 1 - k)) & 1 for k in range(n))
-        be(inp["oldLastIdx"], 48); be(self.new_last_idx, 48); be(inp["oldStateRoot"], 256); be(self.new_state_root, 256); be(self.new_exit_root, 256)
-        for i in range(self.maxL1):
-            on = inp["onChain"][i] if i < nTx else 0
-            if on:
-                bjj = sum(b << k for k, b in enumerate(inp["fromBjjCompressed"][i]))
-                txc = inp["txCompressedData"][i]
-                be(inp["fromEthAddr"][i], 160); be(bjj, 256); be((txc >> 48) & ((1 << 48) - 1), 48); be(inp["loadAmountF"][i], 40)
-                be(inp["amountF"][i], 40); be((txc >> 144) & 0xFFFFFFFF, 32); be((txc >> 96) & ((1 << 48) - 1), 48)
-            else:
-                bits.extend([0] * 624)
-        for i in range(nTx):
-            txc = inp["txCompressedData"][i]
-            on = inp["onChain"][i]
-            frm = (txc >> 48) & ((1 << 48) - 1)
-            to = (txc >> 96) & ((1 << 48) - 1)
-            final_to = inp["auxToIdx"][i] if (not on and to == 0) else to
-            be(frm, L); be(final_to, L)
-            be(0 if self.tx_meta[i]["isAmountNullified"] else inp["amountF"][i], 40)
-            be(0 if on else (txc >> 216) & 0xFF, 8)
-        for j in range(F):
-            be(inp["feeIdxs"][j], L)
-        be(inp["globalChainID"], 16); be(inp["currentNumBatch"], 32)
-        return int.from_bytes(sha256_bits(bits), "big") % P
+        return hash_global_inputs(self.input, [m["isAmountNullified"] for m in self.tx_meta], self.new_last_idx, self.new_state_root, self.new_exit_root,
+                                  self.nTx, self.L, self.maxL1, self.F)
 
     # reference test/helpers/helpers.js:45-137 getSingleTxInput
     def get_single_tx_input(self, i):
@@ -917,6 +890,39 @@ class BatchBuilder:
                "newStateRoot": self.tx_meta[i]["stateRoot"], "newExitRoot": self.tx_meta[i]["exitRoot"],
                "isAmountNullified": self.tx_meta[i]["isAmountNullified"]}
         return r, out
+
+
+def hash_global_inputs(inp, nullified, new_last_idx, new_state_root, new_exit_root, n_tx, n_levels, max_l1, max_fee):
+    """hashGlobalInputs of a RollupMain input dictionary (src/hash-inputs.circom:117-184): the data-availability strings and their
+    SHA-256 modulo r. nullified: isAmountNullified per transaction -- L1L2TxsData carries amountF = 0 where it is set."""
+    L, F, nTx = n_levels, max_fee, n_tx
+    bits = []
+
+    def be(v, n):
+        bits.extend((v >> (n - 1 - k)) & 1 for k in range(n))
+    be(inp["oldLastIdx"], 48); be(new_last_idx, 48); be(inp["oldStateRoot"], 256); be(new_state_root, 256); be(new_exit_root, 256)
+    for i in range(max_l1):
+        on = inp["onChain"][i] if i < nTx else 0
+        if on:
+            bjj = sum(b << k for k, b in enumerate(inp["fromBjjCompressed"][i]))
+            txc = inp["txCompressedData"][i]
+            be(inp["fromEthAddr"][i], 160); be(bjj, 256); be((txc >> 48) & ((1 << 48) - 1), 48); be(inp["loadAmountF"][i], 40)
+            be(inp["amountF"][i], 40); be((txc >> 144) & 0xFFFFFFFF, 32); be((txc >> 96) & ((1 << 48) - 1), 48)
+        else:
+            bits.extend([0] * 624)
+    for i in range(nTx):
+        txc = inp["txCompressedData"][i]
+        on = inp["onChain"][i]
+        frm = (txc >> 48) & ((1 << 48) - 1)
+        to = (txc >> 96) & ((1 << 48) - 1)
+        final_to = inp["auxToIdx"][i] if (not on and to == 0) else to
+        be(frm, L); be(final_to, L)
+        be(0 if nullified[i] else inp["amountF"][i], 40)
+        be(0 if on else (txc >> 216) & 0xFF, 8)
+    for j in range(F):
+        be(inp["feeIdxs"][j], L)
+    be(inp["globalChainID"], 16); be(inp["currentNumBatch"], 32)
+    return int.from_bytes(sha256_bits(bits), "big") % P
 
 
 # RollupMain's state-dependent inputs of an all-L2-transfer batch, and where hz_ledger_apply_l2 leaves each (array, first row, rows)
@@ -1010,6 +1016,84 @@ def l2_batch_inputs(ledger, db_like, txs, n_tx, n_levels, max_l1, max_fee, fee_t
     if by_addr:
         inp["auxToIdx"] = ints(out["auxToIdx"])
     return inp, None
+
+
+def ledger_batch_inputs(ledger, db_like, l1_txs, l2_txs, n_tx, n_levels, max_l1, max_fee, fee_tokens, fee_idxs, chain_id, host_outputs=True, verify=False):
+    """The complete RollupMain(n_tx, n_levels, max_l1, max_fee) input dictionary of a batch of L1 transactions on existing accounts
+    (deposit, depositTransfer, forceTransfer: fromIdx, toIdx, amount or amountF, loadAmountF, tokenID, fromEthAddr) followed by L2
+    transfers as l2_batch_inputs takes them, through capi.Ledger.apply_batch (which also applies the batch to the ledger). Rows are the
+    L1 transactions, the L2 transactions, NOPs up to n_tx. The transaction-only signals (onChain, loadAmountF, fromEthAddr, imOnChain, the
+    L1 form of txCompressedData among them) come from this module's helpers, every state-dependent signal and auxToIdx from the ledger;
+    host_outputs=False leaves those on the device as in l2_batch_inputs. verify=True signs and verifies the L2 transactions on the device.
+    -> (inputs, device signals or None, isAmountNullified per row): the last feeds hash_global_inputs, where L1L2TxsData carries
+    amountF = 0 for a nullified L1 transaction; nullifyLoadAmount is bit 0 of the ledger's flag bytes (capi.Ledger.l1_flags_dev has
+    them on the device)."""
+    if len(l1_txs) > max_l1:
+        raise ValueError("too many L1 txs")
+    if len(l1_txs) + len(l2_txs) > n_tx:
+        raise ValueError("batch full")
+    l1_txs, l2_txs = [dict(t) for t in l1_txs], [dict(t) for t in l2_txs]
+    for t in l1_txs + l2_txs:
+        if "amountF" not in t or "amount" in t:
+            t["amountF"] = fix2float(t.get("amount", 0))
+    n_l1 = len(l1_txs)
+    plan = list(fee_tokens) + [0] * (max_fee - len(fee_tokens))
+    idxs = list(fee_idxs) + [0] * (max_fee - len(fee_idxs))
+    padded = l2_txs + [{}] * (n_tx - n_l1 - len(l2_txs))
+    if verify:
+        for t in padded:
+            if t.get("fromIdx", 0) and "signer" in t:
+                t.update(t["signer"].sign_msg(build_hash_sig(t, chain_id)))
+    out = ledger.apply_batch(l1_txs, padded, plan, idxs, chain_id, db_like.num_batch + 1, n_sib=n_levels + 1, verify=verify)
+    flags = [int(x) for x in out["l1_flags"]]
+    inp = {"oldLastIdx": db_like.last_idx, "globalChainID": chain_id, "currentNumBatch": db_like.num_batch + 1, "feePlanTokens": plan, "feeIdxs": idxs}
+    db_like.num_batch += 1
+    names = ("txCompressedData amountF txCompressedDataV2 fromIdx auxFromIdx toIdx auxToIdx toBjjAy toEthAddr maxNumBatch onChain newAccount "
+             "rqOffset rqTxCompressedDataV2 rqToEthAddr rqToBjjAy s r8x r8y loadAmountF fromEthAddr fromBjjCompressed isOld0_1 oldKey1 oldValue1 "
+             "newExit isOld0_2 oldKey2 oldValue2").split()
+    for k in names:
+        inp[k] = []
+    for t in l1_txs:
+        bjj = t.get("fromBjjCompressed", 0)
+        vals = {"txCompressedData": CONST_SIG | (chain_id << 32) | (t.get("fromIdx", 0) << 48) | (t.get("toIdx", 0) << 96) | (t.get("tokenID", 0) << 144),
+                "amountF": t["amountF"], "fromIdx": t.get("fromIdx", 0), "toIdx": t.get("toIdx", 0), "toBjjAy": t.get("toBjjAy", 0), "toEthAddr": t.get("toEthAddr", 0),
+                "maxNumBatch": t.get("maxNumBatch", 0), "onChain": 1, "loadAmountF": t.get("loadAmountF", 0), "fromEthAddr": t.get("fromEthAddr", 0),
+                "fromBjjCompressed": [(bjj >> k) & 1 for k in range(256)]}
+        for k in names:
+            inp[k].append(vals.get(k, 0))
+    for t in padded:
+        sig = {"r8x": 0, "r8y": 0, "s": 0}
+        if t.get("fromIdx", 0):
+            sig = t["signer"].sign_msg(build_hash_sig(t, chain_id)) if "signer" in t and not verify else {k: t.get(k, 0) for k in ("r8x", "r8y", "s")}
+        vals = {"txCompressedData": build_tx_compressed_data(t, chain_id), "amountF": t.get("amountF", 0), "txCompressedDataV2": build_tx_compressed_data_v2(t),
+                "fromIdx": t.get("fromIdx", 0), "toIdx": t.get("toIdx", 0), "toBjjAy": t.get("toBjjAy", 0), "toEthAddr": t.get("toEthAddr", 0),
+                "maxNumBatch": t.get("maxNumBatch", 0), "s": sig["s"], "r8x": sig["r8x"], "r8y": sig["r8y"], "fromBjjCompressed": [0] * 256}
+        for k in names:
+            inp[k].append(vals.get(k, 0))
+    inp["imOnChain"] = inp["onChain"][:n_tx - 1]
+    inp["imExitRoot"] = [0] * (n_tx - 1)
+    inp["imOutIdx"] = [db_like.last_idx] * (n_tx - 1)
+    nullified = [(f >> 1) & 1 for f in flags] + [0] * (n_tx - n_l1)
+    sigs = l2_state_signals(n_tx, max_fee)
+    if not host_outputs:
+        dev = ledger.outputs_dev()
+        devsig = {}
+        for name, (arr, first, rows) in sigs.items():
+            width = {"siblings": n_levels + 1, "imAccFeeOut": max_fee}.get(name.rstrip("123"), 1)
+            devsig[name] = (dev[arr] + first * width * 32, rows * width)
+        del inp["auxToIdx"]
+        devsig["auxToIdx"] = (ledger.aux_to_idx_dev(), n_tx)
+        return inp, devsig, nullified
+
+    def ints(a):
+        if a.ndim == 2:
+            return [int.from_bytes(r.tobytes(), "little") for r in a]
+        return [ints(r) for r in a]
+    for name, (arr, first, rows) in sigs.items():
+        v = ints(out[arr][first:first + rows])
+        inp[name] = v[0] if name in ("imInitStateRootFee", "oldStateRoot") else v
+    inp["auxToIdx"] = ints(out["auxToIdx"])
+    return inp, None, nullified
 
 
 def withdraw_input(batch, idx, n_levels):

@@ -73,6 +73,7 @@ EXPORTS = [
     "hz_ledger_outputs_dev", "hz_ledger_plan_l2", "hz_ledger_device_ms", "hz_ledger_semantic_ms",
     "hz_ledger_apply_l2_signed", "hz_ledger_verify_l2", "hz_ledger_sig_outputs_dev", "hz_ledger_sig_ms",
     "hz_ledger_apply_l2_addr", "hz_ledger_resolve_l2", "hz_ledger_aux_to_idx_dev", "hz_ledger_resolve_ms",
+    "hz_ledger_apply_batch", "hz_ledger_plan_batch", "hz_ledger_l1_flags_dev", "hz_ledger_l1_ms",
 ]
 
 
@@ -110,6 +111,27 @@ def l2sig_array(txs):
             getattr(g, member)[:] = list((int(t.get(key, 0)) % (1 << 256)).to_bytes(32, "little"))
         g.max_num_batch = t.get("maxNumBatch", 0)
         g.to_bjj_sign = min(int(t.get("toBjjSign", 0)), 255)
+    return arr
+
+
+class hz_l1tx(ctypes.Structure):
+    _fields_ = [("from_idx", ctypes.c_uint64), ("to_idx", ctypes.c_uint64), ("amount_f", ctypes.c_uint64), ("load_amount_f", ctypes.c_uint64),
+                ("token_id", ctypes.c_uint32), ("from_eth_addr", ctypes.c_uint8 * 32)]
+
+
+LEDGER_MAX_L1 = 512   # HZ_LEDGER_MAX_L1
+L1_NULLIFY_LOAD, L1_AMOUNT_NULLIFIED = 1, 2   # the bits of hz_ledger_apply_batch's flag bytes
+
+
+def l1tx_array(txs):
+    """[{fromIdx, toIdx, amountF, loadAmountF, tokenID, fromEthAddr}] (builder's L1 transaction dictionaries; missing keys are 0) -> hz_l1tx
+    array. An address that does not fit 256 bits is passed on truncated; one above 160 bits is the library's argument error."""
+    arr = (hz_l1tx * max(len(txs), 1))()
+    for i, t in enumerate(txs):
+        g = arr[i]
+        g.from_idx, g.to_idx, g.amount_f, g.load_amount_f = t.get("fromIdx", 0), t.get("toIdx", 0), t.get("amountF", 0), t.get("loadAmountF", 0)
+        g.token_id = t.get("tokenID", 0)
+        g.from_eth_addr[:] = list((int(t.get("fromEthAddr", 0)) % (1 << 256)).to_bytes(32, "little"))
     return arr
 
 
@@ -271,7 +293,10 @@ class Lib:
         c.hz_ledger_apply_l2_addr.argtypes = [vp, sz, vp, vp, u32, vp, u32, u32, sz, vp, vp, sz, vp, vp, vp]
         c.hz_ledger_resolve_l2.argtypes = [vp, sz, vp, vp, vp]
         c.hz_ledger_aux_to_idx_dev.argtypes = [vp, ctypes.POINTER(vp)]
-        for f in ("hz_ledger_device_ms", "hz_ledger_semantic_ms", "hz_ledger_sig_ms", "hz_ledger_resolve_ms"):
+        c.hz_ledger_apply_batch.argtypes = [vp, sz, vp, sz, vp, vp, u32, vp, u32, u32, sz, vp, vp, sz, vp, vp, vp, vp]
+        c.hz_ledger_plan_batch.argtypes = [sz, vp, sz, vp, sz, vp, vp, ctypes.c_int32, u64, vp, vp, vp, vp, ctypes.POINTER(sz), vp, vp, vp, vp, ctypes.POINTER(sz), vp]
+        c.hz_ledger_l1_flags_dev.argtypes = [vp, ctypes.POINTER(vp)]
+        for f in ("hz_ledger_device_ms", "hz_ledger_semantic_ms", "hz_ledger_sig_ms", "hz_ledger_resolve_ms", "hz_ledger_l1_ms"):
             getattr(c, f).argtypes = [vp]
             getattr(c, f).restype = ctypes.c_double
 
@@ -374,6 +399,30 @@ class Lib:
                                              out["ev_receiver"].ctypes.data, out["fee_slot"].ctypes.data, out["last_event"].ctypes.data, ctypes.byref(n_ev),
                                              acct.ctypes.data, prev.ctypes.data))
         out["account"], out["prev_same"] = acct[:n_ev.value], prev[:n_ev.value]
+        return out
+
+    def ledger_plan_batch(self, l1_txs, txs, fee_plan_tokens, fee_idxs, k, first_idx=256):
+        """hz_ledger_plan_batch, a diagnostic: ledger_plan_l2 over the n_l1 + m rows of a batch (L1 first), plus the local slots of the L1
+        run: l1_slot_sender / l1_slot_receiver [n_l1] (-1: no receiver) and slot_account [slots]"""
+        import numpy as np
+        l1 = l1_txs if isinstance(l1_txs, ctypes.Array) else l1tx_array(l1_txs)
+        arr = txs if isinstance(txs, ctypes.Array) else l2tx_array(txs)
+        n_l1, m = len(l1_txs), len(txs)
+        plan = np.ascontiguousarray(fee_plan_tokens, dtype=np.uint32)
+        idxs = np.ascontiguousarray(fee_idxs, dtype=np.uint64)
+        F = plan.size
+        if idxs.size != F:
+            raise ValueError("fee_plan_tokens and fee_idxs differ in length")
+        R = n_l1 + m
+        out = {n: np.zeros(R, dtype=np.int32) for n in ("ev_sender", "ev_receiver", "fee_slot", "last_event")}
+        out.update({n: np.zeros(n_l1, dtype=np.int32) for n in ("l1_slot_sender", "l1_slot_receiver")})
+        acct, prev, n_ev = np.zeros(2 * R + F, dtype=np.uint64), np.zeros(2 * R + F, dtype=np.int32), ctypes.c_size_t(0)
+        slot_acct, n_slots = np.zeros(max(2 * n_l1, 1), dtype=np.uint64), ctypes.c_size_t(0)
+        self._check(self.c.hz_ledger_plan_batch(n_l1, ctypes.addressof(l1), m, ctypes.addressof(arr), F, plan.ctypes.data, idxs.ctypes.data, k, first_idx,
+                                                out["ev_sender"].ctypes.data, out["ev_receiver"].ctypes.data, out["fee_slot"].ctypes.data,
+                                                out["last_event"].ctypes.data, ctypes.byref(n_ev), acct.ctypes.data, prev.ctypes.data,
+                                                out["l1_slot_sender"].ctypes.data, out["l1_slot_receiver"].ctypes.data, ctypes.byref(n_slots), slot_acct.ctypes.data))
+        out["account"], out["prev_same"], out["slot_account"] = acct[:n_ev.value], prev[:n_ev.value], slot_acct[:n_slots.value]
         return out
 
     def host_alloc(self, nbytes):
@@ -812,8 +861,9 @@ class Ledger(_Resident):
         cols = {"sib": n_sib, "fee": F}
         return [(name, (rows[r], 32) if c is None else (rows[r], cols[c], 32)) for name, r, c in LEDGER_ARRAYS]
 
-    def _l2_args(self, txs, fee_plan_tokens, fee_idxs, n_sib, outputs, into):
-        """what apply_l2 and apply_l2_signed pass on: the hz_l2tx array, the fee arrays, the output arrays by name and their pointers"""
+    def _l2_args(self, txs, fee_plan_tokens, fee_idxs, n_sib, outputs, into, n_l1=0):
+        """what apply_l2 and apply_l2_signed pass on: the hz_l2tx array, the fee arrays, the output arrays by name and their pointers
+        (n_l1: rows of an L1 run in front of the m of the transactions)"""
         import numpy as np
         arr = txs if isinstance(txs, ctypes.Array) else l2tx_array(txs)
         m = len(txs)
@@ -824,7 +874,7 @@ class Ledger(_Resident):
             raise ValueError("fee_plan_tokens and fee_idxs differ in length")
         out, ptrs = {}, (ctypes.c_void_p * len(LEDGER_ARRAYS))()
         if outputs:
-            for i, (name, shape) in enumerate(self.shapes(m, F, min(max(n_sib, 0), 64))):
+            for i, (name, shape) in enumerate(self.shapes(n_l1 + m, F, min(max(n_sib, 0), 64))):
                 out[name] = into[name] if into is not None else np.zeros(shape, dtype=np.uint8)
                 assert out[name].shape == shape and out[name].dtype == np.uint8 and out[name].flags.c_contiguous
                 ptrs[i] = out[name].ctypes.data
@@ -918,6 +968,52 @@ class Ledger(_Resident):
         if outputs:
             out["auxToIdx"] = aux_out
         return out
+
+    def apply_batch(self, l1_txs, txs, fee_plan_tokens, fee_idxs, chain_id, current_num_batch, n_sib=None, verify=False, aux_to_idx=None, outputs=True, into=None,
+                    sigs=None):
+        """a whole batch: the L1 transactions l1_txs (dictionaries with fromIdx, toIdx, amountF, loadAmountF, tokenID, fromEthAddr, or an
+        hz_l1tx array: deposits, depositTransfers and forceTransfers on existing accounts, nullified as the circuit does), then the L2
+        transactions txs exactly as apply_l2_addr takes them. Every per-transaction array has len(l1_txs) + len(txs) rows, L1 first.
+        Returns apply_l2_addr's dictionary plus l1_flags (uint8 [n_l1]: bit 0 nullifyLoadAmount, bit 1 isAmountNullified). sigs=False: no
+        hz_l2sig array is passed at all (allowed when nothing is verified and no L2 transaction names its receiver by address)."""
+        import numpy as np
+        n_sib = self.k if n_sib is None else n_sib
+        l1 = l1_txs if isinstance(l1_txs, ctypes.Array) else l1tx_array(l1_txs)
+        n_l1 = len(l1_txs)
+        arr, m, plan, idxs, F, out, ptrs = self._l2_args(txs, fee_plan_tokens, fee_idxs, n_sib, outputs, into, n_l1=n_l1)
+        if sigs is None:
+            sigs = l2sig_array(txs)
+        sig_out, sig_ptrs = self._sig_out(m, outputs and verify, into)
+        aux = None
+        if aux_to_idx is not None:
+            aux = np.ascontiguousarray(aux_to_idx, dtype=np.uint64)
+            if aux.size != m:
+                raise ValueError("aux_to_idx: one entry per L2 transaction")
+        aux_out = flags = None
+        if outputs:
+            aux_out = into["auxToIdx"] if into is not None and "auxToIdx" in into else np.zeros((n_l1 + m, 32), dtype=np.uint8)
+            assert aux_out.shape == (n_l1 + m, 32) and aux_out.dtype == np.uint8 and aux_out.flags.c_contiguous
+            flags = into["l1_flags"] if into is not None and "l1_flags" in into else np.zeros(n_l1, dtype=np.uint8)
+            assert flags.shape == (n_l1,) and flags.dtype == np.uint8 and flags.flags.c_contiguous
+        self.L._check(self.L.c.hz_ledger_apply_batch(self.h, n_l1, ctypes.addressof(l1), m, ctypes.addressof(arr), ctypes.addressof(sigs) if sigs is not False else None,
+                                                     LEDGER_VERIFY_SIGS if verify else 0, aux.ctypes.data if aux is not None else None, chain_id, current_num_batch,
+                                                     F, plan.ctypes.data, idxs.ctypes.data, n_sib, ctypes.addressof(ptrs) if outputs else None,
+                                                     ctypes.addressof(sig_ptrs) if outputs and verify else None,
+                                                     aux_out.ctypes.data if outputs and n_l1 + m else None, flags.ctypes.data if outputs and n_l1 else None))
+        out.update(sig_out)
+        if outputs:
+            out["auxToIdx"], out["l1_flags"] = aux_out, flags
+        return out
+
+    def l1_flags_dev(self):
+        """device pointer of the [n_l1] flag bytes of the last successful apply_batch; valid until the ledger's next call"""
+        p = ctypes.c_void_p()
+        self.L._check(self.L.c.hz_ledger_l1_flags_dev(self.h, ctypes.byref(p)))
+        return p.value
+
+    def l1_ms(self):
+        """device time of the L1 kernel of the last apply_batch (0.0 without an L1 run)"""
+        return self.L.c.hz_ledger_l1_ms(self.h)
 
     def resolve_l2(self, txs):
         """the lookup alone: the index apply_l2_addr would find for every transaction as a uint64 array -- 0 for a NOP, for toIdx != 0 or

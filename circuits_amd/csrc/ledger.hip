@@ -24,6 +24,12 @@
 // and the pipeline above then runs on the effective receivers, while the uploaded transactions keep the signed to_idx = 0;
 // k_ledger_scan checks the receiver against the signed destination (reasons 10 and 11), k_ledger_pack writes the auxToIdx rows and the
 // leaf-2 rows of a zero-amount transfer to an address.
+// hz_ledger_apply_batch puts a run of L1 transactions in front: the batch has n_l1 + m rows, "transaction" above reads
+// "row", and
+//   k_ledger_l1            (ledger_l1.h) one workgroup: the nullifiers and the ordered recurrence of the L1 run over balances in LDS; it
+//                          leaves the L1 events' deltas where k_ledger_tx leaves those of the L2 rows, and the flag bytes
+// runs before k_ledger_scan, on the same stream and without a synchronise of its own. The scan carries balances through L1 events as
+// through any other, without the token and nonce checks (an invalid L1 transaction is nullified, not refused).
 // Values are plain 256-bit integers in eight 32-bit limbs (the Fc container of fr.h, nothing is reduced modulo r); deltas are
 // two's complement: every true prefix is below 2^220 in magnitude, so a set top bit means "negative"; the arithmetic is u256.h's, shared
 // with ledger_sig.h. Buffers and block offsets are hostutil.h's, the event holder resident.h's; the stream is the tree's (state_stream).
@@ -39,6 +45,7 @@
 #include "resident.h"
 #include "state_internal.h"
 #include "u256.h"
+#include "ledger_l1.h"
 
 #define HZ_LEDGER_MAX_EVENTS 65536u
 #define HZ_LEDGER_MAX_TX (1u << 20)
@@ -62,15 +69,12 @@ struct LedgerPos {
 // ---- kernels ----------------------------------------------------------------------------------------------------------------------------
 // amount = mantissa x 10^exponent (src/lib/decode-float.circom), fee (src/compute-fee.circom); deltas at the events' grouped positions
 __global__ __launch_bounds__(64) void k_ledger_tx(const hz_l2tx* __restrict__ txs, const int32_t* __restrict__ pos_s, const int32_t* __restrict__ pos_r,
-                                                  uint8_t* __restrict__ fee_out, uint8_t* __restrict__ delta, uint32_t m) {
+                                                  uint8_t* __restrict__ fee_out, uint8_t* __restrict__ delta, uint32_t m, uint32_t n_l1) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= m) return;
     Fc fee = fc_zero();
-    if (txs[i].from_idx != 0) {
-        const uint64_t af = txs[i].amount_f;
-        Fc amount = u256_u64(af & ((1ull << 35) - 1));
-        const uint32_t e = (uint32_t)(af >> 35) & 31u;
-        for (uint32_t s = 0; s < e; s++) amount = u256_mul_u32(amount, 10u);
+    if (i >= n_l1 && txs[i].from_idx != 0) {   // an L1 row pays no fee; its deltas are k_ledger_l1's
+        const Fc amount = l1_float40(txs[i].amount_f);
         const uint32_t sel = txs[i].user_fee;
         fee = u256_mul_u64(amount, HZ_FEE_TABLE[sel]);
         if (sel < 192u) fee = u256_shr60(fee);
@@ -117,7 +121,7 @@ __device__ __forceinline__ void ledger_fail(uint32_t* word, uint32_t unit, uint3
 __global__ __launch_bounds__(64) void k_ledger_scan(const LedgerPos* __restrict__ pos, const uint32_t* __restrict__ seg_start, const hz_l2tx* __restrict__ txs,
                                                     const hz_l2sig* __restrict__ sigs, const uint32_t* __restrict__ plan_tok, const uint8_t* __restrict__ delta, const uint8_t* __restrict__ planes,
                                                     uint8_t* __restrict__ before, uint8_t* __restrict__ records, uint32_t* __restrict__ fail_word, uint32_t N,
-                                                    uint32_t G, uint32_t m) {
+                                                    uint32_t G, uint32_t m, uint32_t n_l1) {
     const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= G) return;
     const uint32_t p0 = seg_start[g], p1 = seg_start[g + 1];
@@ -131,13 +135,14 @@ __global__ __launch_bounds__(64) void k_ledger_scan(const LedgerPos* __restrict_
         store_fr(before + (size_t)ev.ev * 64, e0);
         store_fr(before + (size_t)ev.ev * 64 + 32, bal);
         const bool sender = ev.kind == LEDGER_EV_SENDER, fee = ev.kind == LEDGER_EV_FEE;
+        const bool l1 = ev.kind >= LEDGER_EV_L1_SENDER;   // nullified by k_ledger_l1 where L2 is refused: no token check, no nonce
         const uint32_t tok = fee ? plan_tok[ev.unit - m] : txs[ev.unit].token_id;
-        if (e0.v[0] != tok) ledger_fail(fail_word, ev.unit, sender ? 1u : fee ? 6u : 4u);
+        if (!l1 && e0.v[0] != tok) ledger_fail(fail_word, ev.unit, sender ? 1u : fee ? 6u : 4u);
         if (sigs && ev.kind == LEDGER_EV_RECEIVER && txs[ev.unit].to_idx == 0) {   // the signed destination against the receiver's leaf
-            const Fc to_eth = resolve_load32(sigs[ev.unit].to_eth_addr);
+            const hz_l2sig* sig = sigs + (ev.unit - n_l1);   // sigs belong to the L2 rows
+            const Fc to_eth = resolve_load32(sig->to_eth_addr);
             if (!resolve_fc_same(to_eth, eth)) ledger_fail(fail_word, ev.unit, 10u);
-            if (resolve_is_any(to_eth) &&
-                (!resolve_fc_same(resolve_load32(sigs[ev.unit].to_bjj_ay), ay) || (uint32_t)sigs[ev.unit].to_bjj_sign != ((e0.v[2] >> 8) & 1u)))
+            if (resolve_is_any(to_eth) && (!resolve_fc_same(resolve_load32(sig->to_bjj_ay), ay) || (uint32_t)sig->to_bjj_sign != ((e0.v[2] >> 8) & 1u)))
                 ledger_fail(fail_word, ev.unit, 11u);
         }
         if (sender) {
@@ -187,22 +192,24 @@ __device__ __forceinline__ void ledger_put_leaf(const LedgerOutDev& o, int base,
 __global__ __launch_bounds__(64) void k_ledger_pack(const LedgerOutDev o, const hz_l2tx* __restrict__ txs, const hz_l2sig* __restrict__ sigs,
                                                     uint8_t* __restrict__ aux_rows, uint64_t first_idx, const int32_t* __restrict__ ev_s,
                                                     const int32_t* __restrict__ ev_r, const int32_t* __restrict__ ev_fee, const uint32_t* __restrict__ ev_acct,
-                                                    const uint8_t* __restrict__ before, const uint8_t* __restrict__ planes, uint32_t N, uint32_t m, uint32_t F) {
+                                                    const uint8_t* __restrict__ before, const uint8_t* __restrict__ planes, uint32_t N, uint32_t m, uint32_t F,
+                                                    uint32_t n_l1) {
     const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
     if (u >= m + F) return;
     if (u < m) {
-        const bool active = txs[u].from_idx != 0;
+        const bool active = u >= n_l1 && txs[u].from_idx != 0;   // an L2 row; the tokenID2 = token_id row of a NOP processor 2 is L2's only
         ledger_put_leaf(o, LO_TX1, u, ev_s[u], 0u, ev_acct, before, planes, N);
         ledger_put_leaf(o, LO_TX2, u, ev_r[u], active ? txs[u].token_id : 0u, ev_acct, before, planes, N);
         if (sigs) {
             const bool to_addr = active && txs[u].to_idx == 0;
             store_fr(aux_rows + (size_t)u * 32, u256_u64(to_addr && ev_r[u] >= 0 ? first_idx + ev_acct[ev_r[u]] : 0ull));
             if (to_addr && ev_r[u] < 0) {
-                const Fc to_eth = resolve_load32(sigs[u].to_eth_addr);
+                const hz_l2sig* sig = sigs + (u - n_l1);
+                const Fc to_eth = resolve_load32(sig->to_eth_addr);
                 store_fr(o.a[LO_TX2 + 5] + (size_t)u * 32, to_eth);
                 if (resolve_is_any(to_eth)) {
-                    store_fr(o.a[LO_TX2 + 4] + (size_t)u * 32, resolve_load32(sigs[u].to_bjj_ay));
-                    store_fr(o.a[LO_TX2 + 2] + (size_t)u * 32, u256_u64(sigs[u].to_bjj_sign));
+                    store_fr(o.a[LO_TX2 + 4] + (size_t)u * 32, resolve_load32(sig->to_bjj_ay));
+                    store_fr(o.a[LO_TX2 + 2] + (size_t)u * 32, u256_u64(sig->to_bjj_sign));
                 }
             }
         }
@@ -288,7 +295,7 @@ static const char* const LEDGER_REASON[12] = {"", "the sender's token is not the
 // ledger_sig.hip
 hipError_t launch_ledger_sig(const hz_l2tx* d_txs, const hz_l2sig* d_sigs, uint32_t chain_id, uint32_t current_num_batch, uint8_t* d_tcd, uint8_t* d_v2, uint8_t* d_hash,
                              const uint8_t* planes, const void* b8_table, uint32_t N, uint64_t first_idx, uint32_t* d_fail_word, uint8_t* d_verdict, uint32_t m,
-                             hipStream_t s);
+                             hipStream_t s, uint32_t unit_base = 0);
 void ledger_sig_b8_table_host(void* out);
 size_t ledger_sig_b8_table_bytes();
 
@@ -322,10 +329,21 @@ struct hz_ledger {
     bool have_aux = false;
     DevEvent er0, er1;
     double resolve_ms = 0.0;
+    // the L1 run (hz_ledger_apply_batch): the flag bytes
+    DevBuf l1_flags;
+    bool have_l1 = false;
+    DevEvent el0, el1;
+    double l1_ms = 0.0;
     ~hz_ledger() {
         if (tree) hz_state_destroy(tree);
     }
 };
+
+// the device pointers and the L1 time of the last successful call are no longer what the getters may hand out
+static void ledger_forget(hz_ledger* l) {
+    l->have_outputs = l->have_sig_outputs = l->have_aux = l->have_l1 = false;
+    l->l1_ms = 0.0;
+}
 
 static hz_status ledger_ready(const hz_ledger* l, const char* who) {
     if (!l) return set_err(HZ_ERR_ARG, "%s: null ledger", who);
@@ -360,10 +378,46 @@ static hz_status ledger_check_txs(const char* who, size_t m, const hz_l2tx* txs,
     return HZ_OK;
 }
 
+// the L1 run of hz_ledger_apply_batch: its transactions, where the flag bytes go on the host (may be null); is_batch tells the call
+// from hz_ledger_apply_l2_addr, which has none
+struct LedgerL1Run {
+    size_t n = 0;
+    const hz_l1tx* tx = nullptr;
+    uint8_t* flags_out = nullptr;
+    bool is_batch = false;
+};
+
+// the argument checks of an L1 run; -> the events it makes
+static hz_status ledger_check_l1(const char* who, size_t n_l1, const hz_l1tx* l1, uint64_t first_idx, uint64_t N, size_t* events) {
+    *events = 0;
+    if (n_l1 > HZ_LEDGER_MAX_L1) return set_err(HZ_ERR_ARG, "%s: n_l1 = %zu L1 transactions (at most %d)", who, n_l1, HZ_LEDGER_MAX_L1);
+    if (n_l1 && !l1) return set_err(HZ_ERR_ARG, "%s: null l1", who);
+    const uint64_t last = first_idx + N - 1;
+    for (size_t i = 0; i < n_l1; i++) {
+        const hz_l1tx& t = l1[i];
+        if (t.from_idx == 0) return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: from_idx = 0 (creates an account) is not supported yet", who, i);
+        if (!ledger_has(first_idx, N, t.from_idx))
+            return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: from_idx = %llu is outside the state (%llu .. %llu)", who, i, (unsigned long long)t.from_idx,
+                           (unsigned long long)first_idx, (unsigned long long)last);
+        if (t.to_idx == 1) return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: to_idx = 1 (an exit) is not supported yet", who, i);
+        if (t.to_idx != 0 && !ledger_has(first_idx, N, t.to_idx))
+            return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: to_idx = %llu is outside the state (%llu .. %llu)", who, i, (unsigned long long)t.to_idx,
+                           (unsigned long long)first_idx, (unsigned long long)last);
+        if (t.amount_f >> 40) return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: amount_f has more than 40 bits", who, i);
+        if (t.load_amount_f >> 40) return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: load_amount_f has more than 40 bits", who, i);
+        for (int b = 20; b < 32; b++)
+            if (t.from_eth_addr[b]) return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: from_eth_addr has more than 160 bits", who, i);
+        if (ledger_mantissa(t.amount_f) != 0 && t.to_idx == 0)
+            return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: an amount with to_idx = 0 (no receiver)", who, i);
+        *events += 1 + (ledger_mantissa(t.amount_f) != 0);
+    }
+    return HZ_OK;
+}
+
 // the argument checks hz_ledger_apply_l2 and hz_ledger_plan_l2 share; on success the plan is made. by_addr (hz_ledger_apply_l2_addr): the
 // checks alone -- the plan is made later, on the effective receivers
 static hz_status ledger_check_plan(const char* who, size_t m, const hz_l2tx* txs, size_t F, const uint32_t* plan_tokens, const uint64_t* fee_idxs, uint32_t k,
-                                   uint64_t first_idx, LedgerPlan& plan, bool by_addr = false) {
+                                   uint64_t first_idx, LedgerPlan& plan, bool by_addr = false, size_t l1_events = 0) {
     if ((m && !txs) || (F && (!plan_tokens || !fee_idxs))) return set_err(HZ_ERR_ARG, "%s: null argument", who);
     if (F > HZ_LEDGER_MAX_F) return set_err(HZ_ERR_ARG, "%s: F = %zu fee slots (at most %u)", who, F, HZ_LEDGER_MAX_F);
     if (m > HZ_LEDGER_MAX_TX) return set_err(HZ_ERR_ARG, "%s: %zu transactions in one call (at most %u)", who, m, HZ_LEDGER_MAX_TX);
@@ -373,7 +427,7 @@ static hz_status ledger_check_plan(const char* who, size_t m, const hz_l2tx* txs
         if (fee_idxs[j] != 0 && !ledger_has(first_idx, N, fee_idxs[j]))
             return set_err(HZ_ERR_ARG, "%s: fee_idxs[%zu] = %llu is outside the state (%llu .. %llu)", who, j, (unsigned long long)fee_idxs[j],
                            (unsigned long long)first_idx, (unsigned long long)last);
-    size_t events = 0;
+    size_t events = l1_events;
     for (size_t i = 0; i < m; i++)
         if (txs[i].from_idx != 0) events += 1 + (ledger_mantissa(txs[i].amount_f) != 0);
     for (size_t j = 0; j < F; j++) events += fee_idxs[j] != 0;
@@ -414,7 +468,7 @@ extern "C" hz_status hz_ledger_create(int32_t device, int32_t k, uint64_t first_
     HZ_HIP(hipSetDevice(device));
     HZ_HIP(l->planes.alloc((size_t)4 * l->N * 32));
     HZ_HIP(l->h_fail.grow(64));
-    for (DevEvent* e : {&l->e0, &l->e1, &l->e2, &l->es0, &l->es1, &l->er0, &l->er1}) HZ_HIP(e->create());
+    for (DevEvent* e : {&l->e0, &l->e1, &l->e2, &l->es0, &l->es1, &l->er0, &l->er1, &l->el0, &l->el1}) HZ_HIP(e->create());
     *out = l.release();
     return HZ_OK;
 }
@@ -428,7 +482,7 @@ extern "C" void hz_ledger_destroy(hz_ledger* l) {
 
 extern "C" hz_status hz_ledger_load(hz_ledger* l, const uint8_t* e0, const uint8_t* balance, const uint8_t* ay, const uint8_t* eth_addr) {
     if (!l || !e0 || !balance || !ay || !eth_addr) return set_err(HZ_ERR_ARG, "hz_ledger_load: null argument");
-    l->have_outputs = l->have_sig_outputs = l->have_aux = false;
+    ledger_forget(l);
     if (hz_status e = hz_state_load(l->tree, e0, balance, ay, eth_addr)) return e;   // checks every field < r
     const uint8_t* src[4] = {e0, balance, ay, eth_addr};
     hipStream_t s = state_stream(l->tree);
@@ -459,7 +513,7 @@ extern "C" hz_status hz_ledger_accounts(hz_ledger* l, size_t n, const uint64_t* 
         acct[i] = (uint32_t)(idx[i] - l->first_idx);
     }
     HZ_HIP(hipSetDevice(l->device));
-    l->have_outputs = l->have_sig_outputs = l->have_aux = false;   // the call's buffers are reused
+    ledger_forget(l);   // the call's buffers are reused
     hipStream_t s = state_stream(l->tree);
     HZ_HIP(l->ints.grow(n * 4));
     HZ_HIP(l->work.grow(n * 128));
@@ -529,10 +583,13 @@ static hz_status ledger_sig_copy_out(hz_ledger* l, size_t m, const hz_ledger_sig
 // hz_ledger_apply_l2 (sigs == nullptr), hz_ledger_apply_l2_signed and, with eff_txs, hz_ledger_apply_l2_addr: the caller has checked the
 // arguments; eff_txs are the transactions with the effective receivers, which the plan is made of, while txs -- the signed ones, to_idx
 // == 0 where the receiver is named by address -- are what the kernels see; sigs are uploaded for their destination fields whether or
-// not they are verified
+// not they are verified. With an L1 run in front (hz_ledger_apply_batch; the caller has checked it too) the batch has R = n_l1 + m rows:
+// every per-transaction table, kernel and output below is per row, while sigs, sig_out and the signature kernels keep to the m L2 rows
 static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, bool with_sigs, uint32_t chain_id,
                               uint32_t current_num_batch, size_t F, const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs, size_t n_sib, const hz_ledger_out* out,
-                              const hz_ledger_sig_out* sig_out, const hz_l2tx* eff_txs = nullptr, uint8_t* aux_to_idx_out = nullptr) {
+                              const hz_ledger_sig_out* sig_out, const hz_l2tx* eff_txs = nullptr, uint8_t* aux_to_idx_out = nullptr, const LedgerL1Run& run = LedgerL1Run()) {
+    const size_t n_l1 = run.n;
+    const hz_l1tx* l1 = run.tx;
     static_assert(sizeof(hz_ledger_out) == HZ_LEDGER_ARRAYS * sizeof(uint8_t*), "hz_ledger_out is an array of pointers");
     if (hz_status e = ledger_ready(l, who)) return e;
     const uint32_t k = l->k, N = l->N;
@@ -540,31 +597,58 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
     LedgerPlan& p = l->plan;
     const bool by_addr = eff_txs != nullptr;
     if (by_addr) {
-        ledger_plan_l2(m, eff_txs, F, fee_plan_tokens, fee_idxs, p);
+        ledger_plan_batch(n_l1, l1, m, eff_txs, F, fee_plan_tokens, fee_idxs, p);
     } else {
         if (hz_status e = ledger_check_plan(who, m, txs, F, fee_plan_tokens, fee_idxs, k, l->first_idx, p)) return e;
         if (with_sigs)
             if (hz_status e = ledger_check_sigs(who, m, txs, sigs, chain_id)) return e;
     }
-    l->have_outputs = l->have_sig_outputs = l->have_aux = false;
-    const uint32_t m32 = (uint32_t)m, F32 = (uint32_t)F, S = (uint32_t)n_sib;
-    const uint32_t M = (uint32_t)p.account.size(), G = (uint32_t)p.seg_start.size() - 1;
-    const uint32_t n_chunks = m32 ? (m32 + HZ_LEDGER_CHUNK - 1) / HZ_LEDGER_CHUNK : 1u;
+    ledger_forget(l);
+    const size_t R = n_l1 + m;
+    const uint32_t m32 = (uint32_t)m, R32 = (uint32_t)R, L32 = (uint32_t)n_l1, F32 = (uint32_t)F, S = (uint32_t)n_sib;
+    const uint32_t M = (uint32_t)p.account.size(), G = (uint32_t)p.seg_start.size() - 1, n_slots = (uint32_t)p.slot_account.size();
+    const uint32_t n_chunks = R32 ? (R32 + HZ_LEDGER_CHUNK - 1) / HZ_LEDGER_CHUNK : 1u;
     HZ_HIP(hipSetDevice(l->device));
     hipStream_t s = state_stream(l->tree);
 
     // ---- integer tables, one pinned block
     Carve c;
-    const size_t o_tx = c.take(m * sizeof(hz_l2tx)), o_pos_s = c.take(m * 4), o_pos_r = c.take(m * 4), o_ev_s = c.take(m * 4), o_ev_r = c.take(m * 4),
-                 o_slot = c.take(m * 4), o_last = c.take((m + F) * 4), o_ev_fee = c.take(F * 4), o_pos_fee = c.take(F * 4), o_plan = c.take(F * 4),
-                 o_acct = c.take((size_t)M * 4), o_pos = c.take((size_t)M * sizeof(LedgerPos)), o_seg = c.take(((size_t)G + 1) * 4);
+    const size_t o_tx = c.take(R * sizeof(hz_l2tx)), o_pos_s = c.take(R * 4), o_pos_r = c.take(R * 4), o_ev_s = c.take(R * 4), o_ev_r = c.take(R * 4),
+                 o_slot = c.take(R * 4), o_last = c.take((R + F) * 4), o_ev_fee = c.take(F * 4), o_pos_fee = c.take(F * 4), o_plan = c.take(F * 4),
+                 o_acct = c.take((size_t)M * 4), o_pos = c.take((size_t)M * sizeof(LedgerPos)), o_seg = c.take(((size_t)G + 1) * 4),
+                 o_l1 = c.take(n_l1 * sizeof(LedgerL1Dev)), o_slot_acct = c.take((size_t)n_slots * 4);
     const size_t ints_bytes = c.end;   // (G + 1 >= 1: never empty)
     HZ_HIP(l->h_ints.grow(ints_bytes));
     uint8_t* hb = (uint8_t*)l->h_ints.p;
     std::vector<uint32_t> pos_of(M);
     for (uint32_t q = 0; q < M; q++) pos_of[p.perm[q]] = q;
-    if (m) memcpy(hb + o_tx, txs, m * sizeof(hz_l2tx));
-    for (size_t i = 0; i < m; i++) {
+    for (size_t i = 0; i < n_l1; i++) {   // an L1 row as the per-row kernels read it (token_id, to_idx), and as k_ledger_l1 does
+        hz_l2tx row{};
+        row.from_idx = l1[i].from_idx;
+        row.to_idx = l1[i].to_idx;
+        row.amount_f = l1[i].amount_f;
+        row.token_id = l1[i].token_id;
+        ((hz_l2tx*)(hb + o_tx))[i] = row;
+        LedgerL1Dev d{};
+        d.amount_f = l1[i].amount_f;
+        d.load_amount_f = l1[i].load_amount_f;
+        d.token_id = l1[i].token_id;
+        d.acct_s = (uint32_t)(l1[i].from_idx - l->first_idx);
+        d.slot_s = (uint16_t)p.l1_slot_sender[i];
+        d.pos_s = (int32_t)pos_of[p.ev_sender[i]];
+        d.pos_r = -1;
+        d.slot_r = HZ_L1_NO_SLOT;
+        if (p.ev_receiver[i] >= 0) {
+            d.acct_r = (uint32_t)(l1[i].to_idx - l->first_idx);
+            d.slot_r = (uint16_t)p.l1_slot_receiver[i];
+            d.pos_r = (int32_t)pos_of[p.ev_receiver[i]];
+        }
+        memcpy(d.from_eth, l1[i].from_eth_addr, 20);
+        ((LedgerL1Dev*)(hb + o_l1))[i] = d;
+    }
+    for (uint32_t q = 0; q < n_slots; q++) ((uint32_t*)(hb + o_slot_acct))[q] = (uint32_t)(p.slot_account[q] - l->first_idx);
+    if (m) memcpy(hb + o_tx + n_l1 * sizeof(hz_l2tx), txs, m * sizeof(hz_l2tx));
+    for (size_t i = 0; i < R; i++) {
         ((int32_t*)(hb + o_pos_s))[i] = p.ev_sender[i] >= 0 ? (int32_t)pos_of[p.ev_sender[i]] : -1;
         ((int32_t*)(hb + o_pos_r))[i] = p.ev_receiver[i] >= 0 ? (int32_t)pos_of[p.ev_receiver[i]] : -1;
         ((int32_t*)(hb + o_ev_s))[i] = p.ev_sender[i];
@@ -573,7 +657,7 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
         ((int32_t*)(hb + o_last))[i] = p.last_event[i];
     }
     for (size_t j = 0; j < F; j++) {
-        ((int32_t*)(hb + o_last))[m + j] = p.last_event_fee[j];
+        ((int32_t*)(hb + o_last))[R + j] = p.last_event_fee[j];
         ((int32_t*)(hb + o_ev_fee))[j] = p.ev_fee[j];
         ((int32_t*)(hb + o_pos_fee))[j] = p.ev_fee[j] >= 0 ? (int32_t)pos_of[p.ev_fee[j]] : -1;
         ((uint32_t*)(hb + o_plan))[j] = fee_plan_tokens[j];
@@ -588,7 +672,7 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
     // ---- device buffers: work = fee[m] | chunk sums | delta[M] | before[M][2] | failure word; outs = the 27 arrays
     size_t w = 0;
     const size_t w_fee = w;
-    w += (size_t)(m32 ? m32 : 1) * 32;
+    w += (size_t)(R32 ? R32 : 1) * 32;
     const size_t w_chunk = w;
     w += (size_t)n_chunks * (F32 ? F32 : 1) * 32;
     const size_t w_delta = w;
@@ -598,9 +682,9 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
     const size_t w_fail = w;
     w += 64;
     size_t elems[HZ_LEDGER_ARRAYS];
-    for (int a = 0; a < HZ_LEDGER_ARRAYS; a++) elems[a] = a < LO_TX3 ? m : F;
-    elems[LO_SIB1] = elems[LO_SIB2] = m * n_sib;
-    elems[LO_ACC_FEE] = m * F;
+    for (int a = 0; a < HZ_LEDGER_ARRAYS; a++) elems[a] = a < LO_TX3 ? R : F;
+    elems[LO_SIB1] = elems[LO_SIB2] = R * n_sib;
+    elems[LO_ACC_FEE] = R * F;
     elems[LO_SIB3] = F * n_sib;
     elems[LO_OLD_ROOT] = elems[LO_NEW_ROOT] = 1;
     size_t out_bytes = 0;
@@ -631,31 +715,39 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
     if (with_sigs || by_addr)
         if (hz_status e = ledger_sig_prepare(l, m, sigs, s, with_sigs)) return e;
     const hz_l2sig* d_dest = by_addr ? (const hz_l2sig*)l->sig_in.p : nullptr;   // the signed destinations, for reasons 10 and 11 and the zero-amount rows
-    if (by_addr) HZ_HIP(l->aux_rows.grow((m ? m : 1) * 32));
+    if (by_addr) HZ_HIP(l->aux_rows.grow((R ? R : 1) * 32));
+    if (run.is_batch) HZ_HIP(l->l1_flags.grow(n_l1 ? n_l1 : 1));
 
     // ---- the semantic kernels
     HZ_HIP(hipEventRecord(l->e0, s));
-    if (m32) {
-        hipLaunchKernelGGL(k_ledger_tx, dim3((m32 + 63) / 64), dim3(64), 0, s, d_txs, (const int32_t*)(db + o_pos_s), (const int32_t*)(db + o_pos_r), wb + w_fee,
-                           wb + w_delta, m32);
+    if (R32) {
+        hipLaunchKernelGGL(k_ledger_tx, dim3((R32 + 63) / 64), dim3(64), 0, s, d_txs, (const int32_t*)(db + o_pos_s), (const int32_t*)(db + o_pos_r), wb + w_fee,
+                           wb + w_delta, R32, L32);
         HZ_HIP(hipGetLastError());
     }
+    if (L32) {   // the deltas of the L1 events, beside those k_ledger_tx wrote: one workgroup, no synchronise of its own
+        HZ_HIP(hipEventRecord(l->el0, s));
+        hipLaunchKernelGGL(k_ledger_l1, dim3(1), dim3(256), 0, s, (const LedgerL1Dev*)(db + o_l1), (const uint32_t*)(db + o_slot_acct), (const uint8_t*)l->planes.p,
+                           wb + w_delta, (uint8_t*)l->l1_flags.p, N, L32, n_slots);
+        HZ_HIP(hipGetLastError());
+        HZ_HIP(hipEventRecord(l->el1, s));
+    }
     if (F32) {
-        hipLaunchKernelGGL(k_ledger_fee_sum, dim3(n_chunks), dim3(64), 0, s, (const uint8_t*)(wb + w_fee), (const int32_t*)(db + o_slot), wb + w_chunk, m32, F32);
+        hipLaunchKernelGGL(k_ledger_fee_sum, dim3(n_chunks), dim3(64), 0, s, (const uint8_t*)(wb + w_fee), (const int32_t*)(db + o_slot), wb + w_chunk, R32, F32);
         HZ_HIP(hipGetLastError());
         hipLaunchKernelGGL(k_ledger_fee_scan, dim3(n_chunks), dim3(64), 0, s, (const uint8_t*)(wb + w_fee), (const int32_t*)(db + o_slot),
-                           (const uint8_t*)(wb + w_chunk), (const int32_t*)(db + o_pos_fee), od.a[LO_ACC_FEE], od.a[LO_FINAL_FEE], wb + w_delta, m32, F32, n_chunks);
+                           (const uint8_t*)(wb + w_chunk), (const int32_t*)(db + o_pos_fee), od.a[LO_ACC_FEE], od.a[LO_FINAL_FEE], wb + w_delta, R32, F32, n_chunks);
         HZ_HIP(hipGetLastError());
     }
     if (G) {
         hipLaunchKernelGGL(k_ledger_scan, dim3((G + 63) / 64), dim3(64), 0, s, d_pos, d_seg, d_txs, d_dest, (const uint32_t*)(db + o_plan), (const uint8_t*)(wb + w_delta),
-                           (const uint8_t*)l->planes.p, wb + w_before, tb.fields, d_fail, N, G, m32);
+                           (const uint8_t*)l->planes.p, wb + w_before, tb.fields, d_fail, N, G, R32, L32);
         HZ_HIP(hipGetLastError());
     }
     if (with_sigs) {   // they read the planes and the uploads only: any place before the failure-word read would do
         HZ_HIP(hipEventRecord(l->es0, s));
-        HZ_HIP(launch_ledger_sig(d_txs, (const hz_l2sig*)l->sig_in.p, chain_id, current_num_batch, l->sig_dev[0], l->sig_dev[1], l->sig_dev[2],
-                                 (const uint8_t*)l->planes.p, l->b8_table.p, N, l->first_idx, d_fail, nullptr, m32, s));
+        HZ_HIP(launch_ledger_sig(d_txs + n_l1, (const hz_l2sig*)l->sig_in.p, chain_id, current_num_batch, l->sig_dev[0], l->sig_dev[1], l->sig_dev[2],
+                                 (const uint8_t*)l->planes.p, l->b8_table.p, N, l->first_idx, d_fail, nullptr, m32, s, L32));
         HZ_HIP(hipEventRecord(l->es1, s));
     }
     HZ_HIP(hipEventRecord(l->e1, s));
@@ -664,15 +756,18 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
     const uint32_t word = *(const uint32_t*)l->h_fail.p;
     if (word != 0xFFFFFFFFu) {
         const uint32_t unit = word >> 8, reason = word & 0xFFu;
-        if (unit >= m32)
-            return set_err(HZ_ERR_INPUT, "%s: refused at index %u (fee slot %u), reason %u: %s", who, unit, unit - m32, reason, LEDGER_REASON[reason < 12 ? reason : 0]);
+        if (unit >= R32)
+            return set_err(HZ_ERR_INPUT, "%s: refused at index %u (fee slot %u), reason %u: %s", who, unit, unit - R32, reason, LEDGER_REASON[reason < 12 ? reason : 0]);
+        if (L32)
+            return set_err(HZ_ERR_INPUT, "%s: refused at index %u (%s transaction %u), reason %u: %s", who, unit, unit < L32 ? "L1" : "L2", unit < L32 ? unit : unit - L32,
+                           reason, LEDGER_REASON[reason < 12 ? reason : 0]);
         return set_err(HZ_ERR_INPUT, "%s: refused at index %u (transaction %u), reason %u: %s", who, unit, unit, reason, LEDGER_REASON[reason < 12 ? reason : 0]);
     }
 
     // ---- outputs, tree, resident planes
-    if (m32 + F32) {
-        hipLaunchKernelGGL(k_ledger_pack, dim3((m32 + F32 + 63) / 64), dim3(64), 0, s, od, d_txs, d_dest, (uint8_t*)l->aux_rows.p, l->first_idx, (const int32_t*)(db + o_ev_s),
-                           (const int32_t*)(db + o_ev_r), (const int32_t*)(db + o_ev_fee), (const uint32_t*)(db + o_acct), (const uint8_t*)(wb + w_before), (const uint8_t*)l->planes.p, N, m32, F32);
+    if (R32 + F32) {
+        hipLaunchKernelGGL(k_ledger_pack, dim3((R32 + F32 + 63) / 64), dim3(64), 0, s, od, d_txs, d_dest, (uint8_t*)l->aux_rows.p, l->first_idx, (const int32_t*)(db + o_ev_s),
+                           (const int32_t*)(db + o_ev_r), (const int32_t*)(db + o_ev_fee), (const uint32_t*)(db + o_acct), (const uint8_t*)(wb + w_before), (const uint8_t*)l->planes.p, N, R32, F32, L32);
         HZ_HIP(hipGetLastError());
     }
     const uint8_t* root0 = state_root_dev(l->tree);
@@ -682,10 +777,10 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
     }
     HZ_HIP(hipMemcpyAsync(od.a[LO_OLD_ROOT], root0, 32, hipMemcpyDeviceToDevice, s));
     HZ_HIP(hipMemcpyAsync(od.a[LO_NEW_ROOT], M ? tb.new_root + (size_t)(M - 1) * 32 : root0, 32, hipMemcpyDeviceToDevice, s));
-    if (m32 + F32) {
-        const size_t threads = (size_t)(m32 + F32) * (S + 1);
+    if (R32 + F32) {
+        const size_t threads = (size_t)(R32 + F32) * (S + 1);
         hipLaunchKernelGGL(k_ledger_gather, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, od, (const int32_t*)(db + o_ev_s), (const int32_t*)(db + o_ev_r),
-                           (const int32_t*)(db + o_ev_fee), (const int32_t*)(db + o_last), (const uint8_t*)tb.siblings, (const uint8_t*)tb.new_root, root0, k, S, m32,
+                           (const int32_t*)(db + o_ev_fee), (const int32_t*)(db + o_last), (const uint8_t*)tb.siblings, (const uint8_t*)tb.new_root, root0, k, S, R32,
                            F32);
         HZ_HIP(hipGetLastError());
     }
@@ -701,7 +796,8 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
     }
     if (with_sigs)
         if (hz_status e = ledger_sig_copy_out(l, m, sig_out, s)) return e;
-    if (by_addr && aux_to_idx_out && m) HZ_HIP(hipMemcpyAsync(aux_to_idx_out, l->aux_rows.p, m * 32, hipMemcpyDeviceToHost, s));
+    if (by_addr && aux_to_idx_out && R) HZ_HIP(hipMemcpyAsync(aux_to_idx_out, l->aux_rows.p, R * 32, hipMemcpyDeviceToHost, s));
+    if (run.flags_out && n_l1) HZ_HIP(hipMemcpyAsync(run.flags_out, l->l1_flags.p, n_l1, hipMemcpyDeviceToHost, s));
     if (M) {
         if (hz_status e = state_apply_finish(l->tree)) return e;
     } else {
@@ -715,6 +811,11 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
     l->out_dev = od;
     l->have_outputs = true;
     l->have_aux = by_addr;
+    l->have_l1 = run.is_batch;
+    if (L32) {
+        HZ_HIP(hipEventElapsedTime(&ms, l->el0, l->el1));
+        l->l1_ms = ms;
+    }
     if (with_sigs) {
         HZ_HIP(hipEventElapsedTime(&ms, l->es0, l->es1));
         l->sig_ms = ms;
@@ -742,7 +843,7 @@ extern "C" hz_status hz_ledger_verify_l2(hz_ledger* l, size_t m, const hz_l2tx* 
     if (m > HZ_LEDGER_MAX_TX) return set_err(HZ_ERR_ARG, "%s: %zu transactions in one call (at most %u)", who, m, HZ_LEDGER_MAX_TX);
     if (hz_status e = ledger_check_txs(who, m, txs, l->first_idx, l->N)) return e;
     if (hz_status e = ledger_check_sigs(who, m, txs, sigs, chain_id)) return e;
-    l->have_outputs = l->have_sig_outputs = l->have_aux = false;
+    ledger_forget(l);
     HZ_HIP(hipSetDevice(l->device));
     hipStream_t s = state_stream(l->tree);
     HZ_HIP(l->ints.grow((m ? m : 1) * sizeof(hz_l2tx)));
@@ -831,16 +932,28 @@ extern "C" hz_status hz_ledger_resolve_l2(hz_ledger* l, size_t m, const hz_l2tx*
     return ledger_resolve(l, m, txs, sigs, false, aux_to_idx_out);
 }
 
-extern "C" hz_status hz_ledger_apply_l2_addr(hz_ledger* l, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, uint32_t flags, const uint64_t* aux_to_idx,
-                                             uint32_t chain_id, uint32_t current_num_batch, size_t F, const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs,
-                                             size_t n_sib, const hz_ledger_out* out, const hz_ledger_sig_out* sig_out, uint8_t* aux_to_idx_out) {
-    const char* who = "hz_ledger_apply_l2_addr";
+// hz_ledger_apply_l2_addr, and hz_ledger_apply_batch (is_batch) with its L1 run in front
+static hz_status ledger_apply_addr(hz_ledger* l, const char* who, const LedgerL1Run& run, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, uint32_t flags,
+                                   const uint64_t* aux_to_idx, uint32_t chain_id, uint32_t current_num_batch, size_t F, const uint32_t* fee_plan_tokens,
+                                   const uint64_t* fee_idxs, size_t n_sib, const hz_ledger_out* out, const hz_ledger_sig_out* sig_out, uint8_t* aux_to_idx_out) {
     if (hz_status e = ledger_ready(l, who)) return e;
+    const size_t n_l1 = run.n;
+    const hz_l1tx* l1 = run.tx;
+    if (run.is_batch) l->l1_ms = 0.0;   // the time of THIS call, whatever becomes of it
     const bool verify = (flags & HZ_LEDGER_VERIFY_SIGS) != 0;
     if (flags & ~HZ_LEDGER_VERIFY_SIGS) return set_err(HZ_ERR_ARG, "%s: flags = %#x", who, flags);
     if (!verify && sig_out) return set_err(HZ_ERR_ARG, "%s: sig_out without HZ_LEDGER_VERIFY_SIGS", who);
     if (n_sib < l->k || n_sib > 64) return set_err(HZ_ERR_ARG, "%s: n_sib = %zu (%u .. 64)", who, n_sib, l->k);
-    if (hz_status e = ledger_check_plan(who, m, txs, F, fee_plan_tokens, fee_idxs, l->k, l->first_idx, l->plan, true)) return e;
+    size_t l1_events = 0;
+    if (hz_status e = ledger_check_l1(who, n_l1, l1, l->first_idx, l->N, &l1_events)) return e;
+    if (hz_status e = ledger_check_plan(who, m, txs, F, fee_plan_tokens, fee_idxs, l->k, l->first_idx, l->plan, true, l1_events)) return e;
+    std::vector<hz_l2sig> no_sigs;
+    if (run.is_batch && !sigs && m && !verify) {   // no destination is signed: zero entries stand in, and the call is hz_ledger_apply_l2_addr's
+        for (size_t i = 0; i < m; i++)
+            if (txs[i].from_idx != 0 && txs[i].to_idx == 0) return set_err(HZ_ERR_ARG, "%s: null sigs with tx %zu to an address", who, i);
+        no_sigs.assign(m, hz_l2sig{});
+        sigs = no_sigs.data();
+    }
     if (hz_status e = ledger_check_sigs(who, m, txs, sigs, chain_id, verify)) return e;
     std::vector<hz_l2tx> eff(m ? m : 1);   // (never empty: its address tells ledger_apply which call this is)
     if (m) memcpy(eff.data(), txs, m * sizeof(hz_l2tx));
@@ -856,17 +969,82 @@ extern "C" hz_status hz_ledger_apply_l2_addr(hz_ledger* l, size_t m, const hz_l2
         l->resolve_ms = 0.0;
     } else {
         std::vector<uint64_t> found(m ? m : 1);
-        l->have_outputs = l->have_sig_outputs = l->have_aux = false;
+        ledger_forget(l);
         if (hz_status e = ledger_resolve(l, m, txs, sigs, true, found.data())) return e;
         for (size_t i = 0; i < m; i++) {
             if (!wants_receiver(i)) continue;
             if (found[i] == 0)   // before the plan can exist: reported whatever else is wrong with the batch
-                return set_err(HZ_ERR_INPUT, "%s: refused at index %zu (transaction %zu), reason 9: %s", who, i, i, LEDGER_REASON[9]);
+                return set_err(HZ_ERR_INPUT, "%s: refused at index %zu (%stransaction %zu), reason 9: %s", who, n_l1 + i, n_l1 ? "L2 " : "", i, LEDGER_REASON[9]);
             eff[i].to_idx = found[i];
         }
     }
-    return ledger_apply(l, who, m, txs, sigs, verify, chain_id, current_num_batch, F, fee_plan_tokens, fee_idxs, n_sib, out, sig_out, eff.data(), aux_to_idx_out);
+    return ledger_apply(l, who, m, txs, sigs, verify, chain_id, current_num_batch, F, fee_plan_tokens, fee_idxs, n_sib, out, sig_out, eff.data(), aux_to_idx_out,
+                        run);
 }
+
+extern "C" hz_status hz_ledger_apply_l2_addr(hz_ledger* l, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, uint32_t flags, const uint64_t* aux_to_idx,
+                                             uint32_t chain_id, uint32_t current_num_batch, size_t F, const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs,
+                                             size_t n_sib, const hz_ledger_out* out, const hz_ledger_sig_out* sig_out, uint8_t* aux_to_idx_out) {
+    return ledger_apply_addr(l, "hz_ledger_apply_l2_addr", LedgerL1Run(), m, txs, sigs, flags, aux_to_idx, chain_id, current_num_batch, F, fee_plan_tokens,
+                             fee_idxs, n_sib, out, sig_out, aux_to_idx_out);
+}
+
+// ---- an L1 run in front of the L2 transactions ---------------------------------------------------------------------------
+extern "C" hz_status hz_ledger_apply_batch(hz_ledger* l, size_t n_l1, const hz_l1tx* l1, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, uint32_t flags,
+                                           const uint64_t* aux_to_idx, uint32_t chain_id, uint32_t current_num_batch, size_t F, const uint32_t* fee_plan_tokens,
+                                           const uint64_t* fee_idxs, size_t n_sib, const hz_ledger_out* out, const hz_ledger_sig_out* sig_out,
+                                           uint8_t* aux_to_idx_out, uint8_t* l1_flags_out) {
+    LedgerL1Run run;
+    run.n = n_l1;
+    run.tx = l1;
+    run.flags_out = l1_flags_out;
+    run.is_batch = true;
+    return ledger_apply_addr(l, "hz_ledger_apply_batch", run, m, txs, sigs, flags, aux_to_idx, chain_id, current_num_batch, F, fee_plan_tokens, fee_idxs, n_sib, out,
+                             sig_out, aux_to_idx_out);
+}
+
+extern "C" hz_status hz_ledger_plan_batch(size_t n_l1, const hz_l1tx* l1, size_t m, const hz_l2tx* txs, size_t F, const uint32_t* fee_plan_tokens,
+                                          const uint64_t* fee_idxs, int32_t k, uint64_t first_idx, int32_t* ev_sender_out, int32_t* ev_receiver_out,
+                                          int32_t* fee_slot_out, int32_t* last_event_out, size_t* n_events_out, uint64_t* ev_account_out, int32_t* ev_prev_out,
+                                          int32_t* l1_slot_sender_out, int32_t* l1_slot_receiver_out, size_t* n_slots_out, uint64_t* slot_account_out) {
+    const char* who = "hz_ledger_plan_batch";
+    if (k < 4 || k > 24) return set_err(HZ_ERR_ARG, "%s: k = %d (4 .. 24)", who, k);
+    LedgerPlan p;
+    size_t l1_events = 0;
+    if (hz_status e = ledger_check_l1(who, n_l1, l1, first_idx, 1ull << k, &l1_events)) return e;
+    if (hz_status e = ledger_check_plan(who, m, txs, F, fee_plan_tokens, fee_idxs, (uint32_t)k, first_idx, p, true, l1_events)) return e;
+    for (size_t i = 0; i < m; i++)   // the planner is given receivers: a transfer to an address has none before the lookup
+        if (txs[i].from_idx != 0 && txs[i].to_idx == 0) return set_err(HZ_ERR_ARG, "%s: tx %zu: to_idx = 0 (a transfer to an address) is not supported yet", who, i);
+    ledger_plan_batch(n_l1, l1, m, txs, F, fee_plan_tokens, fee_idxs, p);
+    for (size_t i = 0; i < n_l1 + m; i++) {
+        if (ev_sender_out) ev_sender_out[i] = p.ev_sender[i];
+        if (ev_receiver_out) ev_receiver_out[i] = p.ev_receiver[i];
+        if (fee_slot_out) fee_slot_out[i] = p.fee_slot[i];
+        if (last_event_out) last_event_out[i] = p.last_event[i];
+    }
+    if (n_events_out) *n_events_out = p.account.size();
+    for (size_t e = 0; e < p.account.size(); e++) {
+        if (ev_account_out) ev_account_out[e] = p.account[e];
+        if (ev_prev_out) ev_prev_out[e] = p.prev_same[e];
+    }
+    for (size_t i = 0; i < n_l1; i++) {
+        if (l1_slot_sender_out) l1_slot_sender_out[i] = p.l1_slot_sender[i];
+        if (l1_slot_receiver_out) l1_slot_receiver_out[i] = p.l1_slot_receiver[i];
+    }
+    if (n_slots_out) *n_slots_out = p.slot_account.size();
+    for (size_t q = 0; q < p.slot_account.size(); q++)
+        if (slot_account_out) slot_account_out[q] = p.slot_account[q];
+    return HZ_OK;
+}
+
+extern "C" hz_status hz_ledger_l1_flags_dev(hz_ledger* l, uint8_t** dev) {
+    if (!l || !dev) return set_err(HZ_ERR_ARG, "hz_ledger_l1_flags_dev: null argument");
+    if (!l->have_l1) return set_err(HZ_ERR_ARG, "hz_ledger_l1_flags_dev: no successful hz_ledger_apply_batch since the ledger's last other call");
+    *dev = (uint8_t*)l->l1_flags.p;
+    return HZ_OK;
+}
+
+extern "C" double hz_ledger_l1_ms(const hz_ledger* l) { return l ? l->l1_ms : 0.0; }
 
 extern "C" hz_status hz_ledger_aux_to_idx_dev(hz_ledger* l, uint8_t** dev) {
     if (!l || !dev) return set_err(HZ_ERR_ARG, "hz_ledger_aux_to_idx_dev: null argument");

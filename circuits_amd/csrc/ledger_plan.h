@@ -6,6 +6,11 @@
 // not zero: integer work), a RECEIVER event right after it; after the last transaction every fee slot j with fee_idxs[j] != 0 makes a
 // FEE event, in slot order. The events in that order are the updates of one hz_state apply. Events of one account are grouped, in order
 // (perm / seg_start): a device lane walks a group and carries the account's balance and nonce through it.
+// A batch (ledger_plan_batch) puts n_l1 L1 transactions in front: row i < n_l1 is L1 transaction i, row n_l1 + i is L2
+// transaction i, and "transaction" above reads "row". An L1 row makes an L1_SENDER event and, when its amount is not zero, an
+// L1_RECEIVER event; it has no fee slot. The accounts the L1 run touches are numbered as dense local slots by first appearance
+// (sender before receiver) -- the first groups of the grouping, since the L1 events come first: the L1 kernel keeps one balance per
+// slot in LDS.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -14,10 +19,10 @@
 
 namespace hz {
 
-enum : uint8_t { LEDGER_EV_SENDER = 0, LEDGER_EV_RECEIVER = 1, LEDGER_EV_FEE = 2 };
+enum : uint8_t { LEDGER_EV_SENDER = 0, LEDGER_EV_RECEIVER = 1, LEDGER_EV_FEE = 2, LEDGER_EV_L1_SENDER = 3, LEDGER_EV_L1_RECEIVER = 4 };
 
 struct LedgerPlan {
-    // per transaction
+    // per row (transaction)
     std::vector<int32_t> ev_sender, ev_receiver;   // event numbers, -1: none
     std::vector<int32_t> fee_slot;                  // first slot whose plan token is the transaction's, -1: none (or a NOP)
     std::vector<int32_t> last_event;                // the last event made by transactions 0 .. i, -1: none yet
@@ -30,15 +35,23 @@ struct LedgerPlan {
     std::vector<uint8_t> kind;
     // grouping: the events of group g are perm[seg_start[g] .. seg_start[g + 1]), ascending
     std::vector<uint32_t> perm, seg_start;
+    // the L1 run: the local slot of every L1 transaction's sender and receiver (-1: no receiver), the account of every slot
+    std::vector<int32_t> l1_slot_sender, l1_slot_receiver;
+    std::vector<uint64_t> slot_account;
 };
 
 inline uint64_t ledger_mantissa(uint64_t amount_f) { return amount_f & ((1ull << 35) - 1); }
 
-inline void ledger_plan_l2(size_t m, const hz_l2tx* txs, size_t F, const uint32_t* plan_tokens, const uint64_t* fee_idxs, LedgerPlan& p) {
-    p.ev_sender.assign(m, -1);
-    p.ev_receiver.assign(m, -1);
-    p.fee_slot.assign(m, -1);
-    p.last_event.assign(m, -1);
+inline void ledger_plan_batch(size_t n_l1, const hz_l1tx* l1, size_t m, const hz_l2tx* txs, size_t F, const uint32_t* plan_tokens, const uint64_t* fee_idxs,
+                              LedgerPlan& p) {
+    const size_t R = n_l1 + m;
+    p.ev_sender.assign(R, -1);
+    p.ev_receiver.assign(R, -1);
+    p.fee_slot.assign(R, -1);
+    p.last_event.assign(R, -1);
+    p.l1_slot_sender.assign(n_l1, -1);
+    p.l1_slot_receiver.assign(n_l1, -1);
+    p.slot_account.clear();
     p.ev_fee.assign(F, -1);
     p.last_event_fee.assign(F, -1);
     p.account.clear();
@@ -50,21 +63,28 @@ inline void ledger_plan_l2(size_t m, const hz_l2tx* txs, size_t F, const uint32_
         p.kind.push_back(kind);
         return (int32_t)(p.account.size() - 1);
     };
+    for (size_t i = 0; i < n_l1; i++) {
+        const hz_l1tx& t = l1[i];
+        p.ev_sender[i] = event(t.from_idx, i, LEDGER_EV_L1_SENDER);
+        if (ledger_mantissa(t.amount_f) != 0) p.ev_receiver[i] = event(t.to_idx, i, LEDGER_EV_L1_RECEIVER);
+        p.last_event[i] = (int32_t)p.account.size() - 1;
+    }
     for (size_t i = 0; i < m; i++) {
         const hz_l2tx& t = txs[i];
+        const size_t row = n_l1 + i;
         if (t.from_idx != 0) {
-            p.ev_sender[i] = event(t.from_idx, i, LEDGER_EV_SENDER);
-            if (ledger_mantissa(t.amount_f) != 0) p.ev_receiver[i] = event(t.to_idx, i, LEDGER_EV_RECEIVER);
+            p.ev_sender[row] = event(t.from_idx, row, LEDGER_EV_SENDER);
+            if (ledger_mantissa(t.amount_f) != 0) p.ev_receiver[row] = event(t.to_idx, row, LEDGER_EV_RECEIVER);
             for (size_t s = 0; s < F; s++)
                 if (plan_tokens[s] == t.token_id) {
-                    p.fee_slot[i] = (int32_t)s;
+                    p.fee_slot[row] = (int32_t)s;
                     break;
                 }
         }
-        p.last_event[i] = (int32_t)p.account.size() - 1;
+        p.last_event[row] = (int32_t)p.account.size() - 1;
     }
     for (size_t j = 0; j < F; j++) {
-        if (fee_idxs[j] != 0) p.ev_fee[j] = event(fee_idxs[j], m + j, LEDGER_EV_FEE);
+        if (fee_idxs[j] != 0) p.ev_fee[j] = event(fee_idxs[j], R + j, LEDGER_EV_FEE);
         p.last_event_fee[j] = (int32_t)p.account.size() - 1;
     }
 
@@ -95,6 +115,19 @@ inline void ledger_plan_l2(size_t m, const hz_l2tx* txs, size_t F, const uint32_
     std::vector<uint32_t> at(p.seg_start.begin(), p.seg_start.end() - 1);
     p.perm.resize(M);
     for (uint32_t e = 0; e < M; e++) p.perm[at[ev_group[e]]++] = e;
+    // groups are numbered by first appearance and the L1 events come first: the groups of the L1 run are its local slots
+    for (size_t i = 0; i < n_l1; i++) {
+        p.l1_slot_sender[i] = (int32_t)ev_group[p.ev_sender[i]];
+        if (p.ev_receiver[i] >= 0) p.l1_slot_receiver[i] = (int32_t)ev_group[p.ev_receiver[i]];
+    }
+    size_t n_slots = 0;
+    for (int32_t e = 0; n_l1 && e <= p.last_event[n_l1 - 1]; e++)
+        if (ev_group[e] + 1 > n_slots) n_slots = ev_group[e] + 1;
+    for (size_t q = 0; q < n_slots; q++) p.slot_account.push_back(p.account[p.perm[p.seg_start[q]]]);
+}
+
+inline void ledger_plan_l2(size_t m, const hz_l2tx* txs, size_t F, const uint32_t* plan_tokens, const uint64_t* fee_idxs, LedgerPlan& p) {
+    ledger_plan_batch(0, nullptr, m, txs, F, plan_tokens, fee_idxs, p);
 }
 
 }  // namespace hz

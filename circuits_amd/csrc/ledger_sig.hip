@@ -25,7 +25,7 @@ __device__ __forceinline__ Fc sig_load32(const uint8_t* p) {
 
 __global__ __launch_bounds__(64) void k_ledger_sig_msg(const hz_l2tx* __restrict__ txs, const hz_l2sig* __restrict__ sigs, uint32_t chain_id, uint32_t current_num_batch,
                                                        uint8_t* __restrict__ out_tcd, uint8_t* __restrict__ out_v2, uint8_t* __restrict__ out_hash,
-                                                       uint32_t* __restrict__ fail_word, uint8_t* __restrict__ verdict, uint32_t m) {
+                                                       uint32_t* __restrict__ fail_word, uint8_t* __restrict__ verdict, uint32_t m, uint32_t unit_base) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= m) return;
     const bool active = txs[i].from_idx != 0;
@@ -51,12 +51,12 @@ __global__ __launch_bounds__(64) void k_ledger_sig_msg(const hz_l2tx* __restrict
     store_fr(out_hash + (size_t)i * 32, sig_message(tcd, t, poseidon_consts<7>()));
     const bool expired = active && sig_batch_expired(t.max_num_batch, current_num_batch);
     if (verdict) verdict[i] = expired ? 8u : 0u;
-    if (expired && fail_word) atomicMin(fail_word, (i << 8) | 8u);
+    if (expired && fail_word) atomicMin(fail_word, ((unit_base + i) << 8) | 8u);
 }
 
 __global__ __launch_bounds__(64) void k_ledger_sig_verify(const hz_l2tx* __restrict__ txs, const hz_l2sig* __restrict__ sigs, const uint8_t* __restrict__ msg_hash,
                                                           const uint8_t* __restrict__ planes, const Fr* __restrict__ b8_table, uint32_t N, uint64_t first_idx,
-                                                          uint32_t* __restrict__ fail_word, uint8_t* __restrict__ verdict, uint32_t m) {
+                                                          uint32_t* __restrict__ fail_word, uint8_t* __restrict__ verdict, uint32_t m, uint32_t unit_base) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= m) return;
     const uint64_t from = txs[i].from_idx;
@@ -69,18 +69,18 @@ __global__ __launch_bounds__(64) void k_ledger_sig_verify(const hz_l2tx* __restr
                                poseidon_consts<6>(), b8_table);
     if (!ok) {
         if (verdict) verdict[i] = 7u;
-        if (fail_word) atomicMin(fail_word, (i << 8) | 7u);
+        if (fail_word) atomicMin(fail_word, ((unit_base + i) << 8) | 7u);
     }
 }
 
 hipError_t launch_ledger_sig(const hz_l2tx* d_txs, const hz_l2sig* d_sigs, uint32_t chain_id, uint32_t current_num_batch, uint8_t* d_tcd, uint8_t* d_v2, uint8_t* d_hash,
                              const uint8_t* planes, const void* b8_table, uint32_t N, uint64_t first_idx, uint32_t* d_fail_word, uint8_t* d_verdict, uint32_t m,
-                             hipStream_t s) {
+                             hipStream_t s, uint32_t unit_base) {
     if (m == 0) return hipSuccess;
     const dim3 grid((m + 63) / 64), block(64);
-    hipLaunchKernelGGL(k_ledger_sig_msg, grid, block, 0, s, d_txs, d_sigs, chain_id, current_num_batch, d_tcd, d_v2, d_hash, d_fail_word, d_verdict, m);
+    hipLaunchKernelGGL(k_ledger_sig_msg, grid, block, 0, s, d_txs, d_sigs, chain_id, current_num_batch, d_tcd, d_v2, d_hash, d_fail_word, d_verdict, m, unit_base);
     if (hipError_t e = hipGetLastError()) return e;
-    hipLaunchKernelGGL(k_ledger_sig_verify, grid, block, 0, s, d_txs, d_sigs, (const uint8_t*)d_hash, planes, (const Fr*)b8_table, N, first_idx, d_fail_word, d_verdict, m);
+    hipLaunchKernelGGL(k_ledger_sig_verify, grid, block, 0, s, d_txs, d_sigs, (const uint8_t*)d_hash, planes, (const Fr*)b8_table, N, first_idx, d_fail_word, d_verdict, m, unit_base);
     return hipGetLastError();
 }
 

@@ -482,8 +482,47 @@ hz_status hz_smt_plan(size_t m, const uint64_t* key, size_t n_sib, uint32_t* dep
  *     reason of 1 - 8 included).
  *   10 the receiver's ethAddr != to_eth_addr     11 under the "any" address: the receiver's ay / sign != to_bjj_ay / to_bjj_sign
  *   10 and 11 are reachable only through a supplied aux_to_idx and rank with 1 - 8: lowest index, then lowest reason.
- * OUT OF SCOPE: L1 transactions, new accounts, exits, atomic (rqOffset) fields, a resident address index kept across calls, batch (random
- * linear combination) verification of signatures, more than one device per ledger. One thread at a time. */
+ * L1 TRANSACTIONS. A batch RollupMain proves is a run of L1 transactions followed by L2 transactions; the calls above take
+ * the L2 part alone. An hz_l1tx is a deposit, depositTransfer or forceTransfer on EXISTING accounts: from_idx != 0, to_idx 0 (no transfer)
+ * or >= 2, amount_f and load_amount_f float40, token_id, from_eth_addr as 32 little-endian bytes below 2^160. An invalid L1 transaction
+ * is not refused, it is NULLIFIED (src/rollup-tx-states.circom:244-313, src/balance-updater.circom:56-100; the onChain branch of
+ * BatchBuilder.build is the checker). From the leaves as they are before the batch:
+ *   null_tok1 = token_id != sender.tokenID          null_load = null_tok1 && loadAmount != 0
+ *   null_eth  = amount != 0 && from_eth_addr != sender.ethAddr     null_tok2 = amount != 0 && token_id != receiver.tokenID
+ *   null_amount = null_eth || null_tok2 || (null_tok1 && amount != 0)
+ * and then, in order over the L1 transactions, on the balances as the earlier ones left them:
+ *   eff_load = null_load ? 0 : loadAmount           eff2 = null_amount ? 0 : amount
+ *   underflow_ok = balance[sender] + eff_load - eff2 >= 0          eff3 = underflow_ok ? eff2 : 0
+ *   balance[sender] += eff_load - eff3, then balance[receiver] += eff3 (a self-transfer sees the sender's new leaf)
+ *   isAmountNullified = !(!null_amount && underflow_ok)
+ * No fee, no nonce check or increment, no signature. Whenever amount != 0 (the float40's mantissa is not zero), nullified or not,
+ * processor 2 is an UPDATE of the receiver with delta eff3: its before-leaf and siblings are written; with amount == 0 it is a NOP and
+ * all six leaf-2 rows are zero (tokenID2 too). So what a receiver gets depends on its sender's balance at that moment, which depends on
+ * whether earlier transfers into that sender were nullified: the device walks the L1 run in order over balances held in LDS.
+ *   hz_ledger_apply_batch  n_l1 L1 transactions (n_l1 <= HZ_LEDGER_MAX_L1), then m L2 transactions exactly as hz_ledger_apply_l2_addr
+ *                       takes them (flags, aux_to_idx[m], sig_out[m] belong to the L2 rows; sigs may be NULL when
+ *                       HZ_LEDGER_VERIFY_SIGS is not set and no L2 transaction has to_idx == 0). The batch has n_l1 + m rows, L1 first:
+ *                       every [m] array of `out` has n_l1 + m rows, acc_fee_after rows of the L1 run are zero, aux_to_idx_out is
+ *                       [n_l1 + m][32] with zero L1 rows. l1_flags_out (may be NULL): one byte per L1 transaction, bit 0
+ *                       nullifyLoadAmount, bit 1 isAmountNullified. Refusals name the ROW (n_l1 + i for L2 transaction i). Reasons 1 - 4
+ *                       never fire for an L1 row; reason 5 can, through loadAmount, and stays a refusal (the circuit's Num2Bits(193)
+ *                       rejects it). An L2 transaction funded by an L1 deposit is accepted; one that counted on a nullified L1 transfer
+ *                       is refused with reason 3 at its own row. Reason 9 keeps its precedence. With n_l1 == 0 every output equals
+ *                       hz_ledger_apply_l2_addr's byte for byte. HZ_ERR_ARG beyond that call's: L1 from_idx == 0 (creates an
+ *                       account), L1 to_idx == 1 (exit), an index outside the state, amount_f or load_amount_f >= 2^40, from_eth_addr
+ *                       >= 2^160, an L1 amount != 0 with to_idx == 0 (no receiver to update), n_l1 > HZ_LEDGER_MAX_L1, too many updates
+ *                       (the L1 events count towards the 65536).
+ *   hz_ledger_plan_batch  DIAGNOSTIC, no device: hz_ledger_plan_l2's outputs over the n_l1 + m rows (events of an L1 row: sender, then
+ *                       receiver when amount != 0; fee_slot -1), plus the dense local slots of the accounts the L1 run touches, numbered
+ *                       by first appearance: l1_slot_sender_out / l1_slot_receiver_out [n_l1] (-1: no receiver), *n_slots_out,
+ *                       slot_account_out (room for 2 n_l1). Every output may be NULL
+ *   hz_ledger_l1_flags_dev  the flag bytes as a DEVICE pointer, [n_l1] of the last successful hz_ledger_apply_batch, valid until the
+ *                       ledger's next call
+ *   hz_ledger_l1_ms     device time of the L1 kernel of the last hz_ledger_apply_batch (0: n_l1 was 0, the call did not succeed, or the
+ *                       ledger has been used otherwise since)
+ * OUT OF SCOPE: L1 transactions that create accounts or exit, an L1 amount with to_idx == 0 (no receiver), L2 exits, atomic (rqOffset)
+ * fields, a resident address index kept across calls, batch (random linear combination) verification of signatures, more than one
+ * device per ledger. One thread at a time. */
 typedef struct hz_ledger hz_ledger;
 typedef struct {
     uint64_t from_idx, to_idx, amount_f /* float40 */, nonce;
@@ -542,6 +581,23 @@ hz_status hz_ledger_apply_l2_addr(hz_ledger* l, size_t m, const hz_l2tx* txs, co
 hz_status hz_ledger_resolve_l2(hz_ledger* l, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, uint64_t* aux_to_idx_out /* [m] */);
 hz_status hz_ledger_aux_to_idx_dev(hz_ledger* l, uint8_t** dev);
 double hz_ledger_resolve_ms(const hz_ledger* l);
+typedef struct {
+    uint64_t from_idx, to_idx, amount_f /* float40 */, load_amount_f /* float40 */;
+    uint32_t token_id;
+    uint8_t from_eth_addr[32]; /* little-endian, below 2^160 */
+} hz_l1tx;
+#define HZ_LEDGER_MAX_L1 512
+hz_status hz_ledger_apply_batch(hz_ledger* l, size_t n_l1, const hz_l1tx* l1, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, uint32_t flags,
+                                const uint64_t* aux_to_idx /* [m] or NULL */, uint32_t chain_id, uint32_t current_num_batch, size_t F,
+                                const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs, size_t n_sib, const hz_ledger_out* out /* n_l1 + m rows */,
+                                const hz_ledger_sig_out* sig_out /* [m], L2 rows */, uint8_t* aux_to_idx_out /* [n_l1 + m][32] or NULL */,
+                                uint8_t* l1_flags_out /* [n_l1] or NULL: bit 0 nullifyLoadAmount, bit 1 isAmountNullified */);
+hz_status hz_ledger_plan_batch(size_t n_l1, const hz_l1tx* l1, size_t m, const hz_l2tx* txs, size_t F, const uint32_t* fee_plan_tokens,
+                               const uint64_t* fee_idxs, int32_t k, uint64_t first_idx, int32_t* ev_sender_out, int32_t* ev_receiver_out,
+                               int32_t* fee_slot_out, int32_t* last_event_out, size_t* n_events_out, uint64_t* ev_account_out, int32_t* ev_prev_out,
+                               int32_t* l1_slot_sender_out, int32_t* l1_slot_receiver_out, size_t* n_slots_out, uint64_t* slot_account_out);
+hz_status hz_ledger_l1_flags_dev(hz_ledger* l, uint8_t** dev);
+double hz_ledger_l1_ms(const hz_ledger* l);
 
 /* Poseidon batch: n independent permutations of width t = n_inputs + 1 (2..7). ----------------
  * `in`  : [n][t-1] canonical elements; `out`: [n] digests (state[0] after the last round).
