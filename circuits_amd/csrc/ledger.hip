@@ -45,12 +45,14 @@
 #include "resident.h"
 #include "state_internal.h"
 #include "u256.h"
+#include "ledger_fee.h"
 #include "ledger_l1.h"
 
 #define HZ_LEDGER_MAX_EVENTS 65536u
 #define HZ_LEDGER_MAX_TX (1u << 20)
 #define HZ_LEDGER_MAX_F 64u
 #define HZ_LEDGER_CHUNK 64u   // transactions per lane of the fee scan
+#define HZ_LEDGER_REASONS 13u   // refusal reasons 1 .. 12; 0 is none
 
 namespace hz {
 
@@ -76,8 +78,7 @@ __global__ __launch_bounds__(64) void k_ledger_tx(const hz_l2tx* __restrict__ tx
     if (i >= n_l1 && txs[i].from_idx != 0) {   // an L1 row pays no fee; its deltas are k_ledger_l1's
         const Fc amount = l1_float40(txs[i].amount_f);
         const uint32_t sel = txs[i].user_fee;
-        fee = u256_mul_u64(amount, HZ_FEE_TABLE[sel]);
-        if (sel < 192u) fee = u256_shr60(fee);
+        fee = ledger_fee(amount, sel);
         store_fr(delta + (size_t)pos_s[i] * 32, u256_neg(u256_add(amount, fee)));
         if (pos_r[i] >= 0) store_fr(delta + (size_t)pos_r[i] * 32, amount);
     }
@@ -148,9 +149,10 @@ __global__ __launch_bounds__(64) void k_ledger_scan(const LedgerPos* __restrict_
         if (sender) {
             const uint64_t nonce = (uint64_t)e0.v[1] | ((uint64_t)(e0.v[2] & 0xFFu) << 32);
             if (nonce != txs[ev.unit].nonce) ledger_fail(fail_word, ev.unit, 2u);
-            const uint64_t next = (nonce + 1) & ((1ull << 40) - 1);
+            const uint64_t next = nonce + 1;   // not wrapped: the circuit feeds nonce + 1 into the state hash (rollup-tx.circom:519)
+            if (next >> 40) ledger_fail(fail_word, ev.unit, 12u);
             e0.v[1] = (uint32_t)next;
-            e0.v[2] = (e0.v[2] & ~0xFFu) | (uint32_t)(next >> 32);
+            e0.v[2] = (e0.v[2] & ~0xFFu) | ((uint32_t)(next >> 32) & 0xFFu);
         }
         bal = u256_add(bal, load_fr(delta + (size_t)p * 32));
         if (bal.v[7] >> 31)
@@ -285,12 +287,13 @@ __global__ __launch_bounds__(64) void k_ledger_resolve_pick(const int32_t* __res
     out[i] = a != HZ_RESOLVE_NONE ? first_idx + a : 0ull;
 }
 
-static const char* const LEDGER_REASON[12] = {"", "the sender's token is not the transaction's", "the nonce is not the sender's current nonce",
+static const char* const LEDGER_REASON[HZ_LEDGER_REASONS] = {"", "the sender's token is not the transaction's", "the nonce is not the sender's current nonce",
                                              "the sender's balance is below amount + fee", "the receiver's token is not the transaction's",
                                              "a new balance reaches 2^192", "the fee account's token is not the slot's plan token",
                                              "the signature is rejected", "max_num_batch has expired",
                                               "no account holds the signed destination with the transaction's token",
-                                              "the receiver's ethAddr is not the signed to_eth_addr", "the receiver's key is not the signed to_bjj_ay / to_bjj_sign"};
+                                              "the receiver's ethAddr is not the signed to_eth_addr", "the receiver's key is not the signed to_bjj_ay / to_bjj_sign",
+                                              "the sender's nonce is 2^40 - 1: the next nonce is not a leaf field"};
 
 // ledger_sig.hip
 hipError_t launch_ledger_sig(const hz_l2tx* d_txs, const hz_l2sig* d_sigs, uint32_t chain_id, uint32_t current_num_batch, uint8_t* d_tcd, uint8_t* d_v2, uint8_t* d_hash,
@@ -480,8 +483,23 @@ extern "C" void hz_ledger_destroy(hz_ledger* l) {
     delete l;
 }
 
+// any byte set from `from` to the end of a 32-byte little-endian element
+static bool ledger_bytes_from(const uint8_t* p, int from) {
+    uint8_t d = 0;
+    for (int b = from; b < 32; b++) d |= p[b];
+    return d != 0;
+}
+
 extern "C" hz_status hz_ledger_load(hz_ledger* l, const uint8_t* e0, const uint8_t* balance, const uint8_t* ay, const uint8_t* eth_addr) {
     if (!l || !e0 || !balance || !ay || !eth_addr) return set_err(HZ_ERR_ARG, "hz_ledger_load: null argument");
+    // a leaf's ranges, which every kernel assumes: before the tree or the planes are touched, so a refused load leaves a loaded ledger as it was
+    for (size_t i = 0; i < l->N; i++) {
+        const char* bad = nullptr;
+        if (ledger_bytes_from(balance + i * 32, 24)) bad = "balance >= 2^192";
+        else if (ledger_bytes_from(e0 + i * 32, 10) || e0[i * 32 + 9] > 1) bad = "e0 >= 2^73";
+        else if (ledger_bytes_from(eth_addr + i * 32, 20)) bad = "ethAddr >= 2^160";
+        if (bad) return set_err(HZ_ERR_INPUT, "hz_ledger_load: account %llu (row %zu) is not a leaf: %s", (unsigned long long)(l->first_idx + i), i, bad);
+    }
     ledger_forget(l);
     if (hz_status e = hz_state_load(l->tree, e0, balance, ay, eth_addr)) return e;   // checks every field < r
     const uint8_t* src[4] = {e0, balance, ay, eth_addr};
@@ -757,11 +775,11 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
     if (word != 0xFFFFFFFFu) {
         const uint32_t unit = word >> 8, reason = word & 0xFFu;
         if (unit >= R32)
-            return set_err(HZ_ERR_INPUT, "%s: refused at index %u (fee slot %u), reason %u: %s", who, unit, unit - R32, reason, LEDGER_REASON[reason < 12 ? reason : 0]);
+            return set_err(HZ_ERR_INPUT, "%s: refused at index %u (fee slot %u), reason %u: %s", who, unit, unit - R32, reason, LEDGER_REASON[reason < HZ_LEDGER_REASONS ? reason : 0]);
         if (L32)
             return set_err(HZ_ERR_INPUT, "%s: refused at index %u (%s transaction %u), reason %u: %s", who, unit, unit < L32 ? "L1" : "L2", unit < L32 ? unit : unit - L32,
-                           reason, LEDGER_REASON[reason < 12 ? reason : 0]);
-        return set_err(HZ_ERR_INPUT, "%s: refused at index %u (transaction %u), reason %u: %s", who, unit, unit, reason, LEDGER_REASON[reason < 12 ? reason : 0]);
+                           reason, LEDGER_REASON[reason < HZ_LEDGER_REASONS ? reason : 0]);
+        return set_err(HZ_ERR_INPUT, "%s: refused at index %u (transaction %u), reason %u: %s", who, unit, unit, reason, LEDGER_REASON[reason < HZ_LEDGER_REASONS ? reason : 0]);
     }
 
     // ---- outputs, tree, resident planes

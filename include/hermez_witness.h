@@ -400,7 +400,10 @@ hz_status hz_smt_plan(size_t m, const uint64_t* key, size_t n_sib, uint32_t* dep
  * circuits_amd/builder.py (its L2 branch is the checker), then the tree update of hz_state_apply on the new leaves, without a host
  * round trip for any 256-bit value. The outputs are every state-dependent input RollupMain wants for such a batch.
  *   hz_ledger_create / _destroy   as hz_state_create (4 <= k <= 24)
- *   hz_ledger_load      as hz_state_load, but the planes stay resident
+ *   hz_ledger_load      as hz_state_load, but the planes stay resident. The planes must be LEAVES: balance < 2^192, e0 < 2^73 (tokenID |
+ *                       nonce << 32 | sign << 72), ethAddr < 2^160 -- every kernel assumes it. Anything else is HZ_ERR_INPUT with the
+ *                       first offending account named, before the tree or the planes are touched: a ledger that was loaded before
+ *                       keeps its root and fields
  *   hz_ledger_root      the current root
  *   hz_ledger_accounts  the resident leaf fields of n accounts: fields_out [n][4][32]
  *   hz_ledger_tree      the tree, borrowed: hz_state_proofs / _download / _root work on it (hz_state_apply / _load on it would leave the
@@ -430,6 +433,9 @@ hz_status hz_smt_plan(size_t m, const uint64_t* key, size_t n_sib, uint32_t* dep
  *   1 the sender's token != token_id          2 nonce != the sender's current nonce      3 the sender's balance < amount + fee
  *   4 the receiver's token != token_id (only when amount != 0)       5 a new balance >= 2^192
  *   6 fee slot j: the account's token != fee_plan_tokens[j], reported with index m + j, after every transaction
+ *   12 the sender's nonce is 2^40 - 1: the next nonce is not a leaf field. The circuit does not wrap (src/rollup-tx.circom:519 feeds
+ *      nonce + 1 into the state hash), so neither does the ledger. It ranks like 1 - 8 (lowest index, then lowest reason) in every call
+ *      that applies L2 transactions. A transaction nonce of 2^40 or more never equals a resident nonce: that is reason 2
  * builder.py raises for 1, 3 and 6 and builds inputs the circuit rejects for 2 and 4; the ledger refuses those two as well. A refused
  * call changes nothing (fields, tree, root), writes none of its outputs and leaves no work in flight; the one exception is hz_smt_apply's:
  * a HIP failure reported after the write-back was queued. HZ_ERR_ARG: null arguments, an index outside the state, to_idx 0 or 1 (transfer

@@ -147,6 +147,8 @@ def scheme_model(leaf_of, txs, plan_tokens, fee_idxs):
             if kind == 0:
                 if leaf["nonce"] != txs[unit].get("nonce", 0):
                     bad.append(2)
+                if leaf["nonce"] == (1 << 40) - 1:   # reason 12: nonce + 1 is not a leaf field, and the circuit does not wrap
+                    bad.append(12)
                 leaf["nonce"] += 1
             leaf["balance"] += delta[e]
             if leaf["balance"] < 0:
