@@ -110,14 +110,28 @@ __global__ __launch_bounds__(HZ_BLOCK) void k_hi_prep(const HashInputsArgs a) {
             newStateRoot = hio.in_c(o.i_newStateRoot); newExitRoot = hio.in_c(o.i_newExitRoot); chainID = hio.in_c(o.i_globalChainID);
             batch = hio.in_c(o.i_currentNumBatch);
         }
-        auto idx48 = [&](uint32_t off, const Fc& v) __attribute__((always_inline)) {
-            num2bits_dev(hio, off, v, 48, C_HI_N2B);
+        // Every range check of HashInputs is reported from here, in the template's order (oldLastIdx, newLastIdx, the fee slots,
+        // globalChainID, currentNumBatch): they share unit 0 and two constraint ids, and among equal keys the first report of ONE
+        // lane is the one that is kept -- reports of the fee lanes would race with this lane's (or, with prep_part = 1 and 2,
+        // always come first). The fee lanes store their bits; this lane reads the slots again for the checks alone: first all of
+        // them for "anything wrong" (value >= 2^L: independent loads, no call between them), then the few that are, in order.
+        auto range48 = [&](const Fc& v) __attribute__((always_inline)) {
+            if (!c_fits(v, 48)) report_fail(hio.err, bt, 0, C_HI_N2B, fr_from_canon(c_extract(v, 0, 48)), fr_from_canon(v));
             uint32_t pad = 0;
             for (uint32_t i = L; i < 48; i++) pad += c_bit(v, i);
             if (pad) report_fail(hio.err, bt, 0, C_HI_PAD, fr_from_u64(pad), fr_zero());
         };
-        idx48(o.n2bOldLastIdx, oldLastIdx);
-        idx48(o.n2bNewLastIdx, newLastIdx);
+        put_bits(hio, o.n2bOldLastIdx, oldLastIdx, 48); range48(oldLastIdx);
+        put_bits(hio, o.n2bNewLastIdx, newLastIdx, 48); range48(newLastIdx);
+        auto fee_slot = [&](uint32_t u) __attribute__((always_inline)) {
+            return a.is_main ? load_fr(a.fee_base + ((size_t)a.fi_feeIdxs * feeU + fee0 + u) * 32) : hio.in_c(o.i_feeTxsData + u);
+        };
+        for (uint32_t u0 = 0; u0 < Fn; u0 += 32) {
+            const uint32_t n = min(32u, Fn - u0);
+            uint32_t bad = 0;
+            for (uint32_t k = 0; k < n; k++) bad |= (c_fits(fee_slot(u0 + k), (int)L) ? 0u : 1u) << k;
+            for (; bad; bad &= bad - 1) range48(fee_slot(u0 + (uint32_t)__ffs((int)bad) - 1u));
+        }
         // Num2Bits(256) of a field element never fails (value < r < 2^254)
         for (int k = 0; k < 256; k++) { hio.put_bit(o.n2bOldStateRoot + k, c_bit(oldStateRoot, k)); hio.put_bit(o.n2bNewStateRoot + k, c_bit(newStateRoot, k));
                                         hio.put_bit(o.n2bNewExitRoot + k, c_bit(newExitRoot, k)); }
@@ -160,10 +174,7 @@ __global__ __launch_bounds__(HZ_BLOCK) void k_hi_prep(const HashInputsArgs a) {
     u -= nTx;
     {
         const Fc v = a.is_main ? load_fr(a.fee_base + ((size_t)a.fi_feeIdxs * feeU + fee0 + u) * 32) : hio.in_c(o.i_feeTxsData + u);
-        num2bits_dev(hio, o.n2bFee + 48 * u, v, 48, C_HI_N2B);
-        uint32_t pad = 0;
-        for (uint32_t i = L; i < 48; i++) pad += c_bit(v, i);
-        if (pad) report_fail(hio.err, bt, 0, C_HI_PAD, fr_from_u64(pad), fr_zero());
+        put_bits(hio, o.n2bFee + 48 * u, v, 48);   // its range checks: the header lane
         msg_put_be(msgw, offFee + (uint64_t)u * L, v, (int)L);
     }
 }

@@ -307,17 +307,19 @@ extern "C" int orc_run(void* h, int32_t* err_inst, int32_t* err_unit, int32_t* e
     }
     else if (c->lo.p.tmpl == T_HASH_INPUTS) {
         const Layout& lo = c->lo;
-        W w{&lo, &c->vals, &c->written, &c->fail, 0, 0, 0, 0};
         const HashInputsOff& o = lo.hi;
-        HashInputsIn in;
-        in.oldLastIdx = w.get(o.i_oldLastIdx); in.newLastIdx = w.get(o.i_newLastIdx); in.oldStateRoot = w.get(o.i_oldStateRoot);
-        in.newStateRoot = w.get(o.i_newStateRoot); in.newExitRoot = w.get(o.i_newExitRoot); in.globalChainID = w.get(o.i_globalChainID);
-        in.currentNumBatch = w.get(o.i_currentNumBatch);
-        for (int i = 0; i < lo.p.maxL1 * hzl::L1FULL_BITS; i++) in.L1TxsFullData.push_back(w.get(o.i_L1TxsFullData + i));
-        for (int i = 0; i < lo.p.nTx * (2 * lo.p.L + 48); i++) in.L1L2TxsData.push_back(w.get(o.i_L1L2TxsData + i));
-        for (int i = 0; i < lo.p.F; i++) in.feeTxsData.push_back(w.get(o.i_feeTxsData + i));
-        w.set(o.one, F(1));
-        hash_inputs(w, o, lo.p.L, lo.p.nTx, lo.p.maxL1, lo.p.F, in);
+        for (uint32_t u = 0; u < lo.n_inst; u++) {   // one unit per instance, like run_instanced
+            W w{&lo, &c->vals, &c->written, &c->fail, 0, u, u, 0};
+            HashInputsIn in;
+            in.oldLastIdx = w.get(o.i_oldLastIdx); in.newLastIdx = w.get(o.i_newLastIdx); in.oldStateRoot = w.get(o.i_oldStateRoot);
+            in.newStateRoot = w.get(o.i_newStateRoot); in.newExitRoot = w.get(o.i_newExitRoot); in.globalChainID = w.get(o.i_globalChainID);
+            in.currentNumBatch = w.get(o.i_currentNumBatch);
+            for (int i = 0; i < lo.p.maxL1 * hzl::L1FULL_BITS; i++) in.L1TxsFullData.push_back(w.get(o.i_L1TxsFullData + i));
+            for (int i = 0; i < lo.p.nTx * (2 * lo.p.L + 48); i++) in.L1L2TxsData.push_back(w.get(o.i_L1L2TxsData + i));
+            for (int i = 0; i < lo.p.F; i++) in.feeTxsData.push_back(w.get(o.i_feeTxsData + i));
+            w.set(o.one, F(1));
+            hash_inputs(w, o, lo.p.L, lo.p.nTx, lo.p.maxL1, lo.p.F, in);
+        }
     } else run_instanced(c);
     if (c->fail.failed) {
         if (err_inst) *err_inst = c->fail.inst;

@@ -142,8 +142,9 @@ def mutate(rng, base, sibling_fields=(), key_fields=(), key_bits=None, bit_field
 
 
 # ---- evaluation ----------------------------------------------------------------------------------------------------------------
-def run_oracle_threads(template, shape, cases, n_threads=None):
-    """the oracle over `cases`, one context per thread (contiguous slices). Returns [(ctx, first, count)], the contexts already run."""
+def run_oracle_threads(template, shape, cases, n_threads=None, set_case=None):
+    """the oracle over `cases`, one context per thread (contiguous slices). Returns [(ctx, first, count)], the contexts already run.
+    set_case(ctx, i, k): another way than set_inputs to give instance k of a context the inputs of case i (set_packed_case)."""
     import os
     n = len(cases)
     if n_threads is None:
@@ -167,7 +168,10 @@ def run_oracle_threads(template, shape, cases, n_threads=None):
             lo, hi = bounds[t], bounds[t + 1]
             o = OracleCtx(template, *shape, n_instances=hi - lo)
             for i in range(lo, hi):
-                o.set_inputs(cases[i], instance=i - lo)
+                if set_case is None:
+                    o.set_inputs(cases[i], instance=i - lo)
+                else:
+                    set_case(o, i, i - lo)
             o.run_result = o.run()
             parts[t] = (o, lo, hi - lo)
         except Exception as e:   # pragma: no cover
@@ -205,6 +209,32 @@ def set_all_inputs(g, cases):
     """every input of every instance of a product context, one call per signal (instance = -1)"""
     for name, _ in g.input_names():
         g.set_input(name, [c[name] for c in cases], instance=-1)
+
+
+_FR_0, _FR_1 = bytes(32), (1).to_bytes(32, "little")
+
+
+def pack_case(case):
+    """{input name: (its values as 32-byte little-endian records, their number)} of one input object. Inputs that are mostly bits
+    (HashInputs: 10^4 per instance) cost a tenth of fr_to_bytes over flatten, and the records serve the product and the oracle alike."""
+    out = {}
+    for name, v in case.items():
+        flat = v if isinstance(v, list) and not any(isinstance(x, (list, tuple)) for x in v) else flatten(v)
+        out[name] = (b"".join([_FR_1 if x == 1 else _FR_0 if x == 0 else int(x % P).to_bytes(32, "little") for x in flat]), len(flat))
+    return out
+
+
+def set_packed_case(ctx, packed, instance):
+    """pack_case's records into one instance of an oracle context (run_oracle_threads' set_case)"""
+    for name, (raw, cnt) in packed.items():
+        rc = ctx.o.c.orc_set_input(ctx.h, instance, name.encode(), raw, cnt)
+        assert rc == 0, "oracle rejected input %s (rc %d)" % (name, rc)
+
+
+def set_all_packed(g, packed):
+    """set_all_inputs from pack_case's records: every input of every instance of a product context, one call per signal"""
+    for name, _ in g.input_names():
+        g.L._check(g.L.c.hz_set_input(g.h, -1, name.encode(), b"".join(pk[name][0] for pk in packed), sum(pk[name][1] for pk in packed)))
 
 
 def compare_instanced(g, parts, n, rows_per_chunk=512):
@@ -380,6 +410,99 @@ def rollup_main_cases(n, shape, seed):
     bits = [(f, (i,)) for f in ("onChain", "newAccount", "isOld0_1", "isOld0_2", "newExit") for i in range(nTx)] + [("fromBjjCompressed", (i, rng.randrange(256))) for i in range(nTx)]
     keys = [(f, (i,)) for f in ("auxFromIdx", "auxToIdx", "oldKey1", "oldKey2") for i in range(nTx)]
     return [mutate(rng, valid[rng.randrange(len(valid))], sibling_fields=sib, key_fields=keys, key_bits=L, bit_fields=bits) for _ in range(n)]
+
+
+# ---- HashInputs as main component ------------------------------------------------------------------------------------------------
+L1_FULL_BITS = 2 * 48 + 32 + 40 + 40 + 256 + 160   # bits of one L1TxsFullData slot (reference src/hash-inputs.circom)
+
+
+def hash_inputs_valid(rng, shape, fill=None):
+    """one valid input object of HashInputs(nLevels, nTx, maxL1Tx, maxFeeTx) as main component, shape = (nTx, nLevels, maxL1Tx,
+    maxFeeTx): the two data-availability arrays as random bits (fill = 0 / 1: all zero / all one), every scalar random inside its range"""
+    nTx, L, m1, F = shape
+
+    def bits(n):
+        if fill is not None:
+            return [fill] * n
+        return [int(c) for c in bin(rng.getrandbits(n) | (1 << n))[3:]] if n else []
+    return {"oldLastIdx": rng.randrange(1 << L), "newLastIdx": rng.randrange(1 << L), "oldStateRoot": rng.randrange(P), "newStateRoot": rng.randrange(P),
+            "newExitRoot": rng.randrange(P), "L1TxsFullData": bits(m1 * L1_FULL_BITS), "L1L2TxsData": bits(nTx * (2 * L + 48)),
+            "feeTxsData": [rng.randrange(1 << L) for _ in range(F)], "globalChainID": rng.randrange(1 << 16), "currentNumBatch": rng.randrange(1 << 32)}
+
+
+def hash_inputs_checked(d, shape):
+    """the range-checked elements of a HashInputs input object in the template's evaluation order (reference src/hash-inputs.circom):
+    [(name, path, value, bits of its Num2Bits, padded)] -- padded: the bits from nLevels up to 48 must be zero as well"""
+    F = shape[3]
+    return ([("oldLastIdx", (), d["oldLastIdx"], 48, True), ("newLastIdx", (), d["newLastIdx"], 48, True)] +
+            [("feeTxsData", (j,), d["feeTxsData"][j], 48, True) for j in range(F)] +
+            [("globalChainID", (), d["globalChainID"], 16, False), ("currentNumBatch", (), d["currentNumBatch"], 32, False)])
+
+
+def hash_inputs_lowest_failures(d, shape):
+    """how many elements of an input object fail the constraint that is the object's first failure -- "Num2Bits sum" (value >= 2^n)
+    where any element fails it, "index padding" (a bit between nLevels and 48 in the value's low 48 bits) otherwise. 0: valid;
+    2 or more: a double failure with equal keys, whose reported operands are those of the first such element."""
+    L = shape[1]
+    n2b = pad = 0
+    for _, _, v, n, padded in hash_inputs_checked(d, shape):
+        v %= P
+        n2b += v >> n != 0
+        pad += padded and ((v & ((1 << 48) - 1)) >> L) != 0
+    return n2b or pad
+
+
+def hash_inputs_cases(n, shape, seed, sample=16, p_scalar=0.12, p_double=0.4):
+    """standalone HashInputs inputs for the differential fuzz: valid random inputs (hash_inputs_valid), then
+      * `mutate` over `sample` random positions of each of the two bit arrays as bit_fields (non-bits -- 2, r - 1, random -- of which the
+        hash takes the least significant bit; walking all 10^4 bits of every case for one to four edits would be the generator's whole cost),
+      * every scalar and fee index replaced by `garbage(..., key_bits=nLevels)` with probability p_scalar,
+      * with probability p_double a deliberate double failure: two or three of {oldLastIdx, newLastIdx, several feeTxsData[j],
+        globalChainID, currentNumBatch} out of range at once -- all >= 2^n ("Num2Bits sum"), all below 2^48 with bits at or above nLevels
+        ("index padding", a different number of bits each so that the operands tell the elements apart), the earlier ones padding and the
+        later ones Num2Bits, or a random mix. The reference reports the first element in its evaluation order among equal keys."""
+    rng = random.Random(seed)
+    nTx, L, m1, F = shape
+    out = []
+    for _ in range(n):
+        d = hash_inputs_valid(rng, shape, fill=(None, None, None, 0, 1)[rng.randrange(5)])
+        for name in ("L1TxsFullData", "L1L2TxsData"):
+            pos = rng.sample(range(len(d[name])), min(sample, len(d[name])))
+            proxy = mutate(rng, {name: [d[name][q] for q in pos]}, bit_fields=[(name, (k,)) for k in range(len(pos))])
+            for k, q in enumerate(pos):
+                d[name][q] = proxy[name][k]
+        checked = hash_inputs_checked(d, shape)
+        for name, path, v, _, _ in checked:
+            if rng.random() < p_scalar:
+                _set(d, name, path, garbage(rng, v, key_bits=L))
+        for name in ("oldStateRoot", "newStateRoot", "newExitRoot"):
+            if rng.random() < p_scalar:
+                d[name] = garbage(rng, d[name])
+        if rng.random() < p_double:
+            idx = [c for c in checked if c[4]]
+            mode = rng.randrange(4) if L < 48 else 0
+            pool = idx if mode == 1 else checked
+            chosen = sorted(rng.sample(range(len(pool)), min(len(pool), rng.randrange(2, 4))))
+            for k, c in enumerate(chosen):
+                name, path, v, nb, padded = pool[c]
+                v = _get(d, name, path) % (1 << nb)
+                if mode == 0:
+                    n2b = True
+                elif mode == 1:
+                    n2b = False
+                elif mode == 2:   # the earlier elements fail the padding, the last one Num2Bits
+                    n2b = k == len(chosen) - 1 or not padded
+                else:
+                    n2b = not padded or rng.random() < 0.5
+                if n2b:
+                    v = (v + (1 << rng.randrange(nb, 253))) % P if rng.random() < 0.7 else rng.randrange(1 << nb, P)
+                else:
+                    v &= (1 << L) - 1
+                    for b in rng.sample(range(L, 48), min(48 - L, k + 1)):
+                        v |= 1 << b
+                _set(d, name, path, v)
+        out.append(d)
+    return out
 
 
 # ---- signature edges -------------------------------------------------------------------------------------------------------------
