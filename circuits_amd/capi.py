@@ -66,7 +66,7 @@ EXPORTS = [
     "hz_symmap_create", "hz_symmap_create_r1cs", "hz_symmap_solved", "hz_symmap_check_r1cs", "hz_symmap_save", "hz_symmap_load", "hz_symmap_destroy", "hz_symmap_nvars", "hz_symmap_unresolved", "hz_symmap_derived", "hz_witness_read_sym", "hz_witness_write_wtns_sym", "hz_witness_gather",
     "hz_symmap_from_index", "hz_component_major_index", "hz_symmap_upload", "hz_witness_export_dev", "hz_witness_export_range_dev", "hz_witness_export_host", "hz_symmap_dev_index", "hz_witness_derive_dev",
     "hz_symbol_count", "hz_symbol_get", "hz_symbol_lookup", "hz_constraint_name", "hz_poseidon_batch",
-    "hz_poseidon_batch_dev", "hz_shard_range", "hz_set_inputs_json", "hz_witness_write_json", "hz_witness_write_wtns", "hz_symbols_write_sym", "hz_fr_ops", "hz_poseidon_dag",
+    "hz_poseidon_batch_dev", "hz_shard_range", "hz_set_inputs_json", "hz_witness_write_json", "hz_witness_write_wtns", "hz_symbols_write_sym", "hz_fr_ops", "hz_fr_raw_ops", "hz_poseidon_dag",
     "hz_state_create", "hz_state_destroy", "hz_state_load", "hz_state_root", "hz_state_apply", "hz_state_proofs", "hz_state_download", "hz_state_device_ms",
     "hz_smt_create", "hz_smt_destroy", "hz_smt_reset", "hz_smt_root", "hz_smt_size", "hz_smt_device_ms", "hz_smt_apply", "hz_smt_proofs", "hz_smt_plan",
     "hz_ledger_create", "hz_ledger_destroy", "hz_ledger_load", "hz_ledger_root", "hz_ledger_accounts", "hz_ledger_tree", "hz_ledger_apply_l2",
@@ -161,6 +161,7 @@ class Lib:
         c.hz_poseidon_dag.argtypes = [ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
         c.hz_fr_ops.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]
+        c.hz_fr_raw_ops.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
         c.hz_shard_range.argtypes = [ctypes.c_int32] * 3 + [ctypes.POINTER(ctypes.c_int32)] * 2
         c.hz_shard_range.restype = None
         vp, u64 = ctypes.c_void_p, ctypes.c_uint64
@@ -343,6 +344,16 @@ class Lib:
         out = ctypes.create_string_buffer(32 * max(n, 1))
         self._check(self.c.hz_fr_ops(device, op, n, fr_to_bytes(a), fr_to_bytes(b) if b is not None else None, out))
         return fr_from_bytes(out.raw[:32 * n])
+
+    def fr_raw_ops(self, op, form, operands, device=0):
+        """One fr.h routine on raw limbs (hz_fr_raw_ops, a self test): operands uint32[n_operands, n, 9] -> uint32[n, 9]. Element i runs
+        on thread i of 256-thread workgroups (lane i % 64). form 0: the kernel built with HZ_FR_INLINE, 1: without it."""
+        import numpy as np
+        assert operands.dtype == np.uint32 and operands.ndim == 3 and operands.shape[2] == 9 and operands.flags.c_contiguous
+        n = operands.shape[1]
+        out = np.zeros((n, 9), dtype=np.uint32)
+        self._check(self.c.hz_fr_raw_ops(device, op, form, n, operands.ctypes.data_as(ctypes.c_void_p), operands.shape[0], out.ctypes.data_as(ctypes.c_void_p)))
+        return out
 
     def poseidon_dag(self, vals, job_in, job_out, seg_t, seg_first, seg_count, device=0):
         """vals: bytearray of 32-byte elements (known values in, digests out); job_in uint32[n,6], job_out uint32[n];

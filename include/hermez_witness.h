@@ -618,6 +618,28 @@ enum { HZ_FR_ADD = 0, HZ_FR_SUB = 1, HZ_FR_MUL = 2, HZ_FR_SQR = 3, HZ_FR_INV = 4
        HZ_FR_SQRT = 7 /* circomlib pointbits.circom sqrt(): the root <= (r-1)/2 of a, 0 when a is a non-residue (AySign2Ax, src/lib/utils-bjj.circom:37-58) */ };
 hz_status hz_fr_ops(int32_t device, int32_t op, size_t n, const uint8_t* a, const uint8_t* b, uint8_t* out);
 
+/* Field self test on raw limbs: ONE routine of circuits_amd/csrc/fr.h per call, on operands given as 9 x 29-bit limbs exactly as the
+ * routine sees them (tests/test_fr_contract.py: every routine at the edges of its stated operand range). A self test, used by tests/
+ * only; no reference counterpart.
+ *   operands  uint32[n_operands][n][9], plain limb arrays. NO range validation: the caller owns the routine's preconditions.
+ *             An Fc operand (HZ_FRR_FROM_CANON; the exponent of HZ_FRR_POW) is 8 x u32 in words 0..7, a u64 (HZ_FRR_FROM_U64) words 0..1.
+ *   out       uint32[n][9]: an Fr result as its 9 limbs; an Fc result in words 0..7 with word 8 zero; a boolean in word 0, the rest zero.
+ *   form      0: the kernel is built with HZ_FR_INLINE, as every kernel of the step is; 1: built without it, so fr_mul, fr_sqr,
+ *             fr_to_canon and fr_inv are the out-of-line bodies that the gadget mains call. The same kernel body otherwise.
+ *   mapping   256-thread workgroups, element i runs on thread i of the launch (workgroup i / 256, wavefront (i % 256) / 64, lane
+ *             i % 64) for n <= 2048 * 256; a grid-stride loop only beyond that. The tests place values on chosen lanes of chosen
+ *             wavefronts through this mapping (fr_cond_sub_p_rare's and fr_inv's wave-uniform branches).
+ * One kernel instantiation per op: a routine's code does not depend on the others that share the entry point.
+ * Operands per op, in order -- HZ_FRR_SUB3: m a b c; HZ_FRR_SUB_A_2X: s a x; HZ_FRR_MULADD: a b s; HZ_FRR_MULADD2: a0 b0 a1 b1 s;
+ * HZ_FRR_DOT1 + (N-1): a0 b0 .. a(N-1) b(N-1); HZ_FRR_DOT1_ADD + (N-1): the same and the addend; HZ_FRR_POW: a, exponent.
+ * HZ_ERR_ARG for a bad op or form, an n_operands that is not the op's, or a null pointer with n > 0; n = 0 is HZ_OK. */
+enum { HZ_FRR_ADD = 0, HZ_FRR_SUB, HZ_FRR_NEG, HZ_FRR_DBL, HZ_FRR_SUB_LAZY, HZ_FRR_DBL_LAZY, HZ_FRR_ADD_LAZY, HZ_FRR_SUB2_LAZY, HZ_FRR_3A_B_C_LAZY,
+       HZ_FRR_SUB3, HZ_FRR_SUB_A_2X, HZ_FRR_COND_SUB_2P, HZ_FRR_COND_SUB_4P, HZ_FRR_COND_SUB_P, HZ_FRR_COND_SUB_P_RARE, HZ_FRR_IS_ZERO, HZ_FRR_EQ,
+       HZ_FRR_MUL, HZ_FRR_SQR, HZ_FRR_MULADD, HZ_FRR_MULADD2, HZ_FRR_DOT1 /* .. HZ_FRR_DOT1 + 5: fr_dot<6> */, HZ_FRR_DOT1_ADD = HZ_FRR_DOT1 + 6 /* .. + 5 */,
+       HZ_FRR_FROM_CANON = HZ_FRR_DOT1_ADD + 6, HZ_FRR_FROM_U64, HZ_FRR_TO_CANON, HZ_FRR_CANON_LIMBS, HZ_FRR_PACK_CANON, HZ_FRR_INV, HZ_FRR_INV_FERMAT,
+       HZ_FRR_POW, HZ_FRR_COUNT };
+hz_status hz_fr_raw_ops(int32_t device, int32_t op, int32_t form, size_t n, const uint32_t* operands, int32_t n_operands, uint32_t* out);
+
 /* multi-GPU, one process per GPU (reference src/rollup-main.circom:93-99: every DecodeTx / RollupTx is
  * independent given the im* inputs). A RollupMain batch is sharded by transaction index:
  *   hz_shard_range      contiguous range of a rank
