@@ -1028,6 +1028,25 @@ def ledger_batch_inputs(ledger, db_like, l1_txs, l2_txs, n_tx, n_levels, max_l1,
     -> (inputs, device signals or None, isAmountNullified per row): the last feeds hash_global_inputs, where L1L2TxsData carries
     amountF = 0 for a nullified L1 transaction; nullifyLoadAmount is bit 0 of the ledger's flag bytes (capi.Ledger.l1_flags_dev has
     them on the device)."""
+    return _ledger_batch_inputs(ledger, db_like, l1_txs, l2_txs, n_tx, n_levels, max_l1, max_fee, fee_tokens, fee_idxs, chain_id, host_outputs, verify, False)[:3]
+
+
+# RollupMain's exit-side inputs, and where hz_ledger_apply_batch_exits leaves each (array, first row, rows)
+def exit_signals(n_tx):
+    return {"newExit": ("new_exit", 0, n_tx), "isOld0_2": ("is_old0_2", 0, n_tx), "oldKey2": ("old_key2", 0, n_tx), "oldValue2": ("old_value2", 0, n_tx),
+            "imExitRoot": ("exit_root_after", 0, n_tx - 1)}
+
+
+def ledger_exit_batch_inputs(ledger, db_like, l1_txs, l2_txs, n_tx, n_levels, max_l1, max_fee, fee_tokens, fee_idxs, chain_id, host_outputs=True, verify=False):
+    """ledger_batch_inputs over rows that may be exits (toIdx == 1: an L2 exit, an L1 forceExit), through capi.Ledger.apply_batch_exits:
+    newExit, isOld0_2, oldKey2, oldValue2 and imExitRoot are the ledger's (device signals too with host_outputs=False) instead of zeros.
+    -> (inputs, device signals or None, isAmountNullified per row, the new exit root): the last is hash_global_inputs' new_exit_root.
+    LedgerExits(ledger) afterwards is what withdraw_input reads the batch's exit tree through."""
+    return _ledger_batch_inputs(ledger, db_like, l1_txs, l2_txs, n_tx, n_levels, max_l1, max_fee, fee_tokens, fee_idxs, chain_id, host_outputs, verify, True)
+
+
+def _ledger_batch_inputs(ledger, db_like, l1_txs, l2_txs, n_tx, n_levels, max_l1, max_fee, fee_tokens, fee_idxs, chain_id, host_outputs, verify, exits):
+    """ledger_batch_inputs (exits=False) and ledger_exit_batch_inputs (exits=True) -> (inputs, device signals, nullified, new exit root)"""
     if len(l1_txs) > max_l1:
         raise ValueError("too many L1 txs")
     if len(l1_txs) + len(l2_txs) > n_tx:
@@ -1044,7 +1063,8 @@ def ledger_batch_inputs(ledger, db_like, l1_txs, l2_txs, n_tx, n_levels, max_l1,
         for t in padded:
             if t.get("fromIdx", 0) and "signer" in t:
                 t.update(t["signer"].sign_msg(build_hash_sig(t, chain_id)))
-    out = ledger.apply_batch(l1_txs, padded, plan, idxs, chain_id, db_like.num_batch + 1, n_sib=n_levels + 1, verify=verify)
+    apply = ledger.apply_batch_exits if exits else ledger.apply_batch
+    out = apply(l1_txs, padded, plan, idxs, chain_id, db_like.num_batch + 1, n_sib=n_levels + 1, verify=verify)
     flags = [int(x) for x in out["l1_flags"]]
     inp = {"oldLastIdx": db_like.last_idx, "globalChainID": chain_id, "currentNumBatch": db_like.num_batch + 1, "feePlanTokens": plan, "feeIdxs": idxs}
     db_like.num_batch += 1
@@ -1075,6 +1095,7 @@ def ledger_batch_inputs(ledger, db_like, l1_txs, l2_txs, n_tx, n_levels, max_l1,
     inp["imOutIdx"] = [db_like.last_idx] * (n_tx - 1)
     nullified = [(f >> 1) & 1 for f in flags] + [0] * (n_tx - n_l1)
     sigs = l2_state_signals(n_tx, max_fee)
+    new_exit_root = int.from_bytes(out["new_exit_root"][0].tobytes(), "little") if exits else 0
     if not host_outputs:
         dev = ledger.outputs_dev()
         devsig = {}
@@ -1083,7 +1104,12 @@ def ledger_batch_inputs(ledger, db_like, l1_txs, l2_txs, n_tx, n_levels, max_l1,
             devsig[name] = (dev[arr] + first * width * 32, rows * width)
         del inp["auxToIdx"]
         devsig["auxToIdx"] = (ledger.aux_to_idx_dev(), n_tx)
-        return inp, devsig, nullified
+        if exits:
+            exit_dev = ledger.exit_outputs_dev()
+            for name, (arr, first, rows) in exit_signals(n_tx).items():
+                del inp[name]
+                devsig[name] = (exit_dev[arr] + first * 32, rows)
+        return inp, devsig, nullified, new_exit_root
 
     def ints(a):
         if a.ndim == 2:
@@ -1093,7 +1119,10 @@ def ledger_batch_inputs(ledger, db_like, l1_txs, l2_txs, n_tx, n_levels, max_l1,
         v = ints(out[arr][first:first + rows])
         inp[name] = v[0] if name in ("imInitStateRootFee", "oldStateRoot") else v
     inp["auxToIdx"] = ints(out["auxToIdx"])
-    return inp, None, nullified
+    if exits:
+        for name, (arr, first, rows) in exit_signals(n_tx).items():
+            inp[name] = ints(out[arr][first:first + rows])
+    return inp, None, nullified, new_exit_root
 
 
 def withdraw_input(batch, idx, n_levels):
@@ -1133,6 +1162,23 @@ class DeviceSMT:
             return {"found": True, "siblings": sib, "foundValue": int.from_bytes(p["value"][0].tobytes(), "little"), "isOld0": False}
         return {"found": False, "siblings": sib, "notFoundKey": int(p["not_found_key"][0]),
                 "notFoundValue": int.from_bytes(p["not_found_value"][0].tobytes(), "little"), "isOld0": bool(p["is_old0"][0])}
+
+
+class LedgerExits:
+    """The exit tree and exit leaves of the batch a capi.Ledger applied last (apply_batch_exits), as withdraw_input reads them off a built
+    BatchBuilder: exit_tree is a DeviceSMT over the ledger's tree, exit_leaves[idx] the leaf's fields read from the device. Valid until
+    the ledger's next batch."""
+
+    class _Leaves:
+        def __init__(self, ledger):
+            self.ledger = ledger
+
+        def __getitem__(self, idx):
+            e0, balance, ay, eth = (int.from_bytes(r.tobytes(), "little") for r in self.ledger.exit_accounts([idx])[0])
+            return {"tokenID": e0 & 0xFFFFFFFF, "nonce": (e0 >> 32) & ((1 << 40) - 1), "sign": (e0 >> 72) & 1, "balance": balance, "ay": ay, "ethAddr": eth}
+
+    def __init__(self, ledger):
+        self.exit_tree, self.exit_leaves = DeviceSMT(ledger.exit_tree()), self._Leaves(ledger)
 
 
 class ExitTreeFixture:

@@ -74,6 +74,7 @@ EXPORTS = [
     "hz_ledger_apply_l2_signed", "hz_ledger_verify_l2", "hz_ledger_sig_outputs_dev", "hz_ledger_sig_ms",
     "hz_ledger_apply_l2_addr", "hz_ledger_resolve_l2", "hz_ledger_aux_to_idx_dev", "hz_ledger_resolve_ms",
     "hz_ledger_apply_batch", "hz_ledger_plan_batch", "hz_ledger_l1_flags_dev", "hz_ledger_l1_ms",
+    "hz_ledger_apply_batch_exits", "hz_ledger_exit_outputs_dev", "hz_ledger_exit_tree", "hz_ledger_exit_accounts", "hz_ledger_plan_exits", "hz_ledger_exit_ms",
 ]
 
 
@@ -121,6 +122,10 @@ class hz_l1tx(ctypes.Structure):
 
 LEDGER_MAX_L1 = 512   # HZ_LEDGER_MAX_L1
 L1_NULLIFY_LOAD, L1_AMOUNT_NULLIFIED = 1, 2   # the bits of hz_ledger_apply_batch's flag bytes
+
+
+# hz_ledger_exit_out's arrays in order: [rows, 32] each, the last [1, 32]
+LEDGER_EXIT_ARRAYS = ("new_exit", "is_old0_2", "old_key2", "old_value2", "exit_root_after", "new_exit_root")
 
 
 def l1tx_array(txs):
@@ -297,7 +302,14 @@ class Lib:
         c.hz_ledger_apply_batch.argtypes = [vp, sz, vp, sz, vp, vp, u32, vp, u32, u32, sz, vp, vp, sz, vp, vp, vp, vp]
         c.hz_ledger_plan_batch.argtypes = [sz, vp, sz, vp, sz, vp, vp, ctypes.c_int32, u64, vp, vp, vp, vp, ctypes.POINTER(sz), vp, vp, vp, vp, ctypes.POINTER(sz), vp]
         c.hz_ledger_l1_flags_dev.argtypes = [vp, ctypes.POINTER(vp)]
-        for f in ("hz_ledger_device_ms", "hz_ledger_semantic_ms", "hz_ledger_sig_ms", "hz_ledger_resolve_ms", "hz_ledger_l1_ms"):
+        c.hz_ledger_apply_batch_exits.argtypes = [vp, sz, vp, sz, vp, vp, u32, vp, u32, u32, sz, vp, vp, sz, vp, vp, vp, vp, vp]
+        c.hz_ledger_exit_outputs_dev.argtypes = [vp, vp]
+        c.hz_ledger_exit_tree.argtypes = [vp]
+        c.hz_ledger_exit_tree.restype = vp
+        c.hz_ledger_exit_accounts.argtypes = [vp, sz, vp, vp]
+        c.hz_ledger_plan_exits.argtypes = [sz, vp, sz, vp, sz, vp, vp, ctypes.c_int32, u64, sz, vp, vp, vp, ctypes.POINTER(sz), vp, vp, vp, ctypes.POINTER(sz), vp, vp,
+                                           vp, vp, vp, vp, vp]
+        for f in ("hz_ledger_device_ms", "hz_ledger_semantic_ms", "hz_ledger_sig_ms", "hz_ledger_resolve_ms", "hz_ledger_l1_ms", "hz_ledger_exit_ms"):
             getattr(c, f).argtypes = [vp]
             getattr(c, f).restype = ctypes.c_double
 
@@ -434,6 +446,34 @@ class Lib:
                                                 out["last_event"].ctypes.data, ctypes.byref(n_ev), acct.ctypes.data, prev.ctypes.data,
                                                 out["l1_slot_sender"].ctypes.data, out["l1_slot_receiver"].ctypes.data, ctypes.byref(n_slots), slot_acct.ctypes.data))
         out["account"], out["prev_same"], out["slot_account"] = acct[:n_ev.value], prev[:n_ev.value], slot_acct[:n_slots.value]
+        return out
+
+    def ledger_plan_exits(self, l1_txs, txs, fee_plan_tokens, fee_idxs, k, n_sib=None, first_idx=256):
+        """hz_ledger_plan_exits, a diagnostic: the plan of a batch whose rows may be exits (toIdx == 1), no device needed. An exit row makes
+        its sender event and no receiver event; its operation on the exit tree is in a second ordered list. -> dictionary of numpy arrays:
+        ev_sender / ev_receiver / last_event / ev_exit / last_exit [rows] (-1: none), account [events], and per exit operation exit_row,
+        exit_key, exit_prev (-1: the operation is the insert), exit_perm (grouped by key), exit_insert, exit_is_old0, exit_old_key"""
+        import numpy as np
+        l1 = l1_txs if isinstance(l1_txs, ctypes.Array) else l1tx_array(l1_txs)
+        arr = txs if isinstance(txs, ctypes.Array) else l2tx_array(txs)
+        n_l1, m = len(l1_txs), len(txs)
+        plan = np.ascontiguousarray(fee_plan_tokens, dtype=np.uint32)
+        idxs = np.ascontiguousarray(fee_idxs, dtype=np.uint64)
+        F = plan.size
+        if idxs.size != F:
+            raise ValueError("fee_plan_tokens and fee_idxs differ in length")
+        R = n_l1 + m
+        out = {n: np.zeros(R, dtype=np.int32) for n in ("ev_sender", "ev_receiver", "last_event", "ev_exit", "last_exit")}
+        acct, n_ev, n_x = np.zeros(2 * R + F, dtype=np.uint64), ctypes.c_size_t(0), ctypes.c_size_t(0)
+        per_op = {"exit_row": np.uint32, "exit_key": np.uint64, "exit_prev": np.int32, "exit_perm": np.uint32, "exit_insert": np.uint8, "exit_is_old0": np.uint8,
+                  "exit_old_key": np.uint64}
+        ops = {n: np.zeros(max(R, 1), dtype=t) for n, t in per_op.items()}
+        self._check(self.c.hz_ledger_plan_exits(n_l1, ctypes.addressof(l1), m, ctypes.addressof(arr), F, plan.ctypes.data, idxs.ctypes.data, k, first_idx,
+                                                k + 1 if n_sib is None else n_sib, out["ev_sender"].ctypes.data, out["ev_receiver"].ctypes.data,
+                                                out["last_event"].ctypes.data, ctypes.byref(n_ev), acct.ctypes.data, out["ev_exit"].ctypes.data,
+                                                out["last_exit"].ctypes.data, ctypes.byref(n_x), *[ops[n].ctypes.data for n in per_op]))
+        out["account"] = acct[:n_ev.value]
+        out.update({n: a[:n_x.value] for n, a in ops.items()})
         return out
 
     def host_alloc(self, nbytes):
@@ -1016,6 +1056,69 @@ class Ledger(_Resident):
             out["auxToIdx"], out["l1_flags"] = aux_out, flags
         return out
 
+    def apply_batch_exits(self, l1_txs, txs, fee_plan_tokens, fee_idxs, chain_id, current_num_batch, n_sib=None, verify=False, aux_to_idx=None, outputs=True,
+                          into=None, sigs=None):
+        """apply_batch over rows that may be exits (toIdx == 1: an L2 exit, an L1 forceExit): the amount goes into the batch's exit tree at
+        key fromIdx, an insert the first time and an update after. Returns apply_batch's dictionary plus new_exit, is_old0_2, old_key2,
+        old_value2, exit_root_after ([rows, 32]) and new_exit_root ([1, 32]). exit_tree() and exit_accounts() read the tree and its leaves
+        until the ledger's next batch."""
+        import numpy as np
+        n_sib = self.k if n_sib is None else n_sib
+        l1 = l1_txs if isinstance(l1_txs, ctypes.Array) else l1tx_array(l1_txs)
+        n_l1 = len(l1_txs)
+        arr, m, plan, idxs, F, out, ptrs = self._l2_args(txs, fee_plan_tokens, fee_idxs, n_sib, outputs, into, n_l1=n_l1)
+        if sigs is None:
+            sigs = l2sig_array(txs)
+        sig_out, sig_ptrs = self._sig_out(m, outputs and verify, into)
+        aux = None
+        if aux_to_idx is not None:
+            aux = np.ascontiguousarray(aux_to_idx, dtype=np.uint64)
+            if aux.size != m:
+                raise ValueError("aux_to_idx: one entry per L2 transaction")
+        R = n_l1 + m
+        aux_out = flags = None
+        exit_out, exit_ptrs = {}, (ctypes.c_void_p * len(LEDGER_EXIT_ARRAYS))()
+        if outputs:
+            shapes = {"auxToIdx": (R, 32), "l1_flags": (n_l1,)}
+            shapes.update({name: (R if name != "new_exit_root" else 1, 32) for name in LEDGER_EXIT_ARRAYS})
+            for name, shape in shapes.items():
+                exit_out[name] = into[name] if into is not None and name in into else np.zeros(shape, dtype=np.uint8)
+                assert exit_out[name].shape == shape and exit_out[name].dtype == np.uint8 and exit_out[name].flags.c_contiguous
+            aux_out, flags = exit_out["auxToIdx"], exit_out["l1_flags"]
+            for i, name in enumerate(LEDGER_EXIT_ARRAYS):
+                exit_ptrs[i] = exit_out[name].ctypes.data
+        self.L._check(self.L.c.hz_ledger_apply_batch_exits(self.h, n_l1, ctypes.addressof(l1), m, ctypes.addressof(arr), ctypes.addressof(sigs) if sigs is not False else None,
+                                                           LEDGER_VERIFY_SIGS if verify else 0, aux.ctypes.data if aux is not None else None, chain_id, current_num_batch,
+                                                           F, plan.ctypes.data, idxs.ctypes.data, n_sib, ctypes.addressof(ptrs) if outputs else None,
+                                                           ctypes.addressof(sig_ptrs) if outputs and verify else None,
+                                                           aux_out.ctypes.data if outputs and R else None, flags.ctypes.data if outputs and n_l1 else None,
+                                                           ctypes.addressof(exit_ptrs) if outputs else None))
+        out.update(sig_out)
+        out.update(exit_out)
+        return out
+
+    def exit_outputs_dev(self):
+        """device pointers of the six exit arrays of the last successful apply_batch_exits, by name; valid until the ledger's next call"""
+        ptrs = (ctypes.c_void_p * len(LEDGER_EXIT_ARRAYS))()
+        self.L._check(self.L.c.hz_ledger_exit_outputs_dev(self.h, ctypes.addressof(ptrs)))
+        return {name: ptrs[i] for i, name in enumerate(LEDGER_EXIT_ARRAYS)}
+
+    def exit_tree(self):
+        """the exit tree of the last batch as a capi.SparseTree, borrowed: proofs / root / size"""
+        return _BorrowedSparseTree(self.L, self.L.c.hz_ledger_exit_tree(self.h))
+
+    def exit_accounts(self, keys):
+        """the fields (e0, balance, ay, ethAddr) of the exit leaves at keys -> [n, 4, 32]; a key that is not in the exit tree raises"""
+        import numpy as np
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        out = np.zeros((keys.size, 4, 32), dtype=np.uint8)
+        self.L._check(self.L.c.hz_ledger_exit_accounts(self.h, keys.size, keys.ctypes.data, out.ctypes.data))
+        return out
+
+    def exit_ms(self):
+        """device time of the exit kernels plus the exit tree's update of the last apply_batch_exits (0.0 without an exit operation)"""
+        return self.L.c.hz_ledger_exit_ms(self.h)
+
     def l1_flags_dev(self):
         """device pointer of the [n_l1] flag bytes of the last successful apply_batch; valid until the ledger's next call"""
         p = ctypes.c_void_p()
@@ -1110,6 +1213,17 @@ class SparseTree(_Resident):
     def device_ms(self):
         """device time of the last apply"""
         return self.L.c.hz_smt_device_ms(self.h)
+
+
+class _BorrowedSparseTree(SparseTree):
+    """the hz_smt inside a Ledger, its exit tree: proofs / root / size work on it; the ledger owns it"""
+
+    def __init__(self, L, h):
+        self.L, self.h = L, ctypes.c_void_p(h)
+        self.n_sib_max = 64
+
+    def close(self):
+        self.h = ctypes.c_void_p()
 
 
 class SymMap:

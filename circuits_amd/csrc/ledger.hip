@@ -30,13 +30,20 @@
 //                          leaves the L1 events' deltas where k_ledger_tx leaves those of the L2 rows, and the flag bytes
 // runs before k_ledger_scan, on the same stream and without a synchronise of its own. The scan carries balances through L1 events as
 // through any other, without the token and nonce checks (an invalid L1 transaction is nullified, not refused).
+// hz_ledger_apply_batch_exits accepts to_idx == 1, an L2 exit or an L1 forceExit: the row keeps its sender event, has no
+// receiver event, and its amount goes into the batch's exit tree, an hz_smt the ledger owns (ledger_exit.h, smt_internal.h):
+//   k_ledger_exit_scan     a lane per exit key, before the one synchronise: the exit leaf before and after each of its operations
+//   the exit tree's update smt_apply_launch on that tree's own stream behind an event, beside the state tree's update
+//   k_ledger_exit_pack / _gather   the leaf-2 rows, newExit, isOld0_2, oldKey2, oldValue2, siblings2 and the exit root after every row
 // Values are plain 256-bit integers in eight 32-bit limbs (the Fc container of fr.h, nothing is reduced modulo r); deltas are
 // two's complement: every true prefix is below 2^220 in magnitude, so a set top bit means "negative"; the arithmetic is u256.h's, shared
 // with ledger_sig.h. Buffers and block offsets are hostutil.h's, the event holder resident.h's; the stream is the tree's (state_stream).
 #define HZ_FR_INLINE 1
 #include <hip/hip_runtime.h>
 #include <string.h>
+#include <algorithm>
 #include <memory>
+#include <utility>
 #include <vector>
 #include "../../include/hermez_witness.h"
 #include "devcommon.h"
@@ -47,6 +54,9 @@
 #include "u256.h"
 #include "ledger_fee.h"
 #include "ledger_l1.h"
+#include "ledger_exit.h"
+#include "smt_internal.h"
+#include "smt_plan.h"
 
 #define HZ_LEDGER_MAX_EVENTS 65536u
 #define HZ_LEDGER_MAX_TX (1u << 20)
@@ -71,7 +81,8 @@ struct LedgerPos {
 // ---- kernels ----------------------------------------------------------------------------------------------------------------------------
 // amount = mantissa x 10^exponent (src/lib/decode-float.circom), fee (src/compute-fee.circom); deltas at the events' grouped positions
 __global__ __launch_bounds__(64) void k_ledger_tx(const hz_l2tx* __restrict__ txs, const int32_t* __restrict__ pos_s, const int32_t* __restrict__ pos_r,
-                                                  uint8_t* __restrict__ fee_out, uint8_t* __restrict__ delta, uint32_t m, uint32_t n_l1) {
+                                                  uint8_t* __restrict__ fee_out, uint8_t* __restrict__ delta, const int32_t* __restrict__ pos_x,
+                                                  uint8_t* __restrict__ exit_amt, uint32_t m, uint32_t n_l1) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= m) return;
     Fc fee = fc_zero();
@@ -81,6 +92,7 @@ __global__ __launch_bounds__(64) void k_ledger_tx(const hz_l2tx* __restrict__ tx
         fee = ledger_fee(amount, sel);
         store_fr(delta + (size_t)pos_s[i] * 32, u256_neg(u256_add(amount, fee)));
         if (pos_r[i] >= 0) store_fr(delta + (size_t)pos_r[i] * 32, amount);
+        if (pos_x && pos_x[i] >= 0) store_fr(exit_amt + (size_t)pos_x[i] * 32, amount);   // an exit: no receiver delta (pos_x == NULL: the call takes none)
     }
     store_fr(fee_out + (size_t)i * 32, fee);
 }
@@ -337,14 +349,39 @@ struct hz_ledger {
     bool have_l1 = false;
     DevEvent el0, el1;
     double l1_ms = 0.0;
+    // exits (hz_ledger_apply_batch_exits): the batch's exit tree, the six exit arrays, the leaf every exit key ends with (plane-major,
+    // [4][exit_keys.size()]) and which key lies where
+    hz_smt* exit = nullptr;
+    DevBuf exit_outs, exit_final;
+    uint8_t* exit_dev[HZ_LEDGER_EXIT_ARRAYS] = {};
+    std::vector<std::pair<uint64_t, uint32_t>> exit_keys;   // (key, its place in exit_final), ascending
+    bool have_exit_outputs = false;
+    DevEvent ex0, ex1, ex2, ex3, ex_tree;   // around the scan, around pack and gather (the tree's stream); after the exit tree's update (its own)
+    double exit_ms = 0.0;
     ~hz_ledger() {
+        if (exit) hz_smt_destroy(exit);
         if (tree) hz_state_destroy(tree);
+    }
+};
+
+// the exit tree and the exit leaves are those of the last successful call: every call that applies a batch starts from the empty tree
+static void ledger_exit_reset(hz_ledger* l) {
+    smt_clear(l->exit);   // (no synchronise: every update of this tree ends in smt_apply_finish or smt_apply_abort)
+    l->exit_keys.clear();
+    l->exit_ms = 0.0;
+}
+
+// a prepared update of the exit tree that does not reach smt_apply_finish did not happen
+struct LedgerExitGuard {
+    hz_smt* t = nullptr;
+    ~LedgerExitGuard() {
+        if (t) smt_apply_abort(t);
     }
 };
 
 // the device pointers and the L1 time of the last successful call are no longer what the getters may hand out
 static void ledger_forget(hz_ledger* l) {
-    l->have_outputs = l->have_sig_outputs = l->have_aux = l->have_l1 = false;
+    l->have_outputs = l->have_sig_outputs = l->have_aux = l->have_l1 = l->have_exit_outputs = false;
     l->l1_ms = 0.0;
 }
 
@@ -357,8 +394,8 @@ static hz_status ledger_ready(const hz_ledger* l, const char* who) {
 static bool ledger_has(uint64_t first_idx, uint64_t N, uint64_t idx) { return idx >= first_idx && idx - first_idx < N; }
 
 // the per-transaction argument checks of every call that takes transactions; a NOP (from_idx == 0) is not looked at. by_addr: to_idx == 0
-// (a receiver named by address or key) passes
-static hz_status ledger_check_txs(const char* who, size_t m, const hz_l2tx* txs, uint64_t first_idx, uint64_t N, bool by_addr = false) {
+// (a receiver named by address or key) passes; exits: to_idx == 1 does
+static hz_status ledger_check_txs(const char* who, size_t m, const hz_l2tx* txs, uint64_t first_idx, uint64_t N, bool by_addr = false, bool exits = false) {
     const uint64_t last = first_idx + N - 1;
     for (size_t i = 0; i < m; i++) {
         const hz_l2tx& t = txs[i];
@@ -366,7 +403,7 @@ static hz_status ledger_check_txs(const char* who, size_t m, const hz_l2tx* txs,
         if (!ledger_has(first_idx, N, t.from_idx))
             return set_err(HZ_ERR_ARG, "%s: tx %zu: from_idx = %llu is outside the state (%llu .. %llu)", who, i, (unsigned long long)t.from_idx,
                            (unsigned long long)first_idx, (unsigned long long)last);
-        if (t.to_idx == 0 && by_addr) {
+        if ((t.to_idx == 0 && by_addr) || (t.to_idx == HZ_LEDGER_EXIT_IDX && exits)) {
             if (t.amount_f >> 40) return set_err(HZ_ERR_ARG, "%s: tx %zu: amount_f has more than 40 bits", who, i);
             continue;
         }
@@ -388,10 +425,13 @@ struct LedgerL1Run {
     const hz_l1tx* tx = nullptr;
     uint8_t* flags_out = nullptr;
     bool is_batch = false;
+    // hz_ledger_apply_batch_exits: to_idx == 1 is taken in L1 and L2 rows; where the exit arrays go on the host (may be null)
+    bool exits = false;
+    const hz_ledger_exit_out* exit_out = nullptr;
 };
 
 // the argument checks of an L1 run; -> the events it makes
-static hz_status ledger_check_l1(const char* who, size_t n_l1, const hz_l1tx* l1, uint64_t first_idx, uint64_t N, size_t* events) {
+static hz_status ledger_check_l1(const char* who, size_t n_l1, const hz_l1tx* l1, uint64_t first_idx, uint64_t N, size_t* events, bool exits = false) {
     *events = 0;
     if (n_l1 > HZ_LEDGER_MAX_L1) return set_err(HZ_ERR_ARG, "%s: n_l1 = %zu L1 transactions (at most %d)", who, n_l1, HZ_LEDGER_MAX_L1);
     if (n_l1 && !l1) return set_err(HZ_ERR_ARG, "%s: null l1", who);
@@ -402,8 +442,8 @@ static hz_status ledger_check_l1(const char* who, size_t n_l1, const hz_l1tx* l1
         if (!ledger_has(first_idx, N, t.from_idx))
             return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: from_idx = %llu is outside the state (%llu .. %llu)", who, i, (unsigned long long)t.from_idx,
                            (unsigned long long)first_idx, (unsigned long long)last);
-        if (t.to_idx == 1) return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: to_idx = 1 (an exit) is not supported yet", who, i);
-        if (t.to_idx != 0 && !ledger_has(first_idx, N, t.to_idx))
+        if (t.to_idx == HZ_LEDGER_EXIT_IDX && !exits) return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: to_idx = 1 (an exit) is not supported yet", who, i);
+        if (t.to_idx > HZ_LEDGER_EXIT_IDX && !ledger_has(first_idx, N, t.to_idx))
             return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: to_idx = %llu is outside the state (%llu .. %llu)", who, i, (unsigned long long)t.to_idx,
                            (unsigned long long)first_idx, (unsigned long long)last);
         if (t.amount_f >> 40) return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: amount_f has more than 40 bits", who, i);
@@ -420,12 +460,12 @@ static hz_status ledger_check_l1(const char* who, size_t n_l1, const hz_l1tx* l1
 // the argument checks hz_ledger_apply_l2 and hz_ledger_plan_l2 share; on success the plan is made. by_addr (hz_ledger_apply_l2_addr): the
 // checks alone -- the plan is made later, on the effective receivers
 static hz_status ledger_check_plan(const char* who, size_t m, const hz_l2tx* txs, size_t F, const uint32_t* plan_tokens, const uint64_t* fee_idxs, uint32_t k,
-                                   uint64_t first_idx, LedgerPlan& plan, bool by_addr = false, size_t l1_events = 0) {
+                                   uint64_t first_idx, LedgerPlan& plan, bool by_addr = false, size_t l1_events = 0, bool exits = false) {
     if ((m && !txs) || (F && (!plan_tokens || !fee_idxs))) return set_err(HZ_ERR_ARG, "%s: null argument", who);
     if (F > HZ_LEDGER_MAX_F) return set_err(HZ_ERR_ARG, "%s: F = %zu fee slots (at most %u)", who, F, HZ_LEDGER_MAX_F);
     if (m > HZ_LEDGER_MAX_TX) return set_err(HZ_ERR_ARG, "%s: %zu transactions in one call (at most %u)", who, m, HZ_LEDGER_MAX_TX);
     const uint64_t N = 1ull << k, last = first_idx + N - 1;
-    if (hz_status e = ledger_check_txs(who, m, txs, first_idx, N, by_addr)) return e;
+    if (hz_status e = ledger_check_txs(who, m, txs, first_idx, N, by_addr, exits)) return e;
     for (size_t j = 0; j < F; j++)
         if (fee_idxs[j] != 0 && !ledger_has(first_idx, N, fee_idxs[j]))
             return set_err(HZ_ERR_ARG, "%s: fee_idxs[%zu] = %llu is outside the state (%llu .. %llu)", who, j, (unsigned long long)fee_idxs[j],
@@ -464,6 +504,7 @@ extern "C" hz_status hz_ledger_create(int32_t device, int32_t k, uint64_t first_
     *out = nullptr;
     std::unique_ptr<hz_ledger> l(new hz_ledger);
     if (hz_status e = hz_state_create(device, k, first_idx, &l->tree)) return e;
+    if (hz_status e = hz_smt_create(device, HZ_SMT_MAX_DEPTH, &l->exit)) return e;
     l->device = device;
     l->k = (uint32_t)k;
     l->N = 1u << k;
@@ -471,7 +512,8 @@ extern "C" hz_status hz_ledger_create(int32_t device, int32_t k, uint64_t first_
     HZ_HIP(hipSetDevice(device));
     HZ_HIP(l->planes.alloc((size_t)4 * l->N * 32));
     HZ_HIP(l->h_fail.grow(64));
-    for (DevEvent* e : {&l->e0, &l->e1, &l->e2, &l->es0, &l->es1, &l->er0, &l->er1, &l->el0, &l->el1}) HZ_HIP(e->create());
+    for (DevEvent* e : {&l->e0, &l->e1, &l->e2, &l->es0, &l->es1, &l->er0, &l->er1, &l->el0, &l->el1, &l->ex0, &l->ex1, &l->ex2, &l->ex3, &l->ex_tree})
+        HZ_HIP(e->create());
     *out = l.release();
     return HZ_OK;
 }
@@ -480,6 +522,7 @@ extern "C" void hz_ledger_destroy(hz_ledger* l) {
     if (!l) return;
     (void)hipSetDevice(l->device);
     (void)hipStreamSynchronize(state_stream(l->tree));
+    (void)hipStreamSynchronize(smt_stream(l->exit));
     delete l;
 }
 
@@ -610,12 +653,13 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
     const hz_l1tx* l1 = run.tx;
     static_assert(sizeof(hz_ledger_out) == HZ_LEDGER_ARRAYS * sizeof(uint8_t*), "hz_ledger_out is an array of pointers");
     if (hz_status e = ledger_ready(l, who)) return e;
+    ledger_exit_reset(l);
     const uint32_t k = l->k, N = l->N;
     if (n_sib < k || n_sib > 64) return set_err(HZ_ERR_ARG, "%s: n_sib = %zu (%u .. 64)", who, n_sib, k);
     LedgerPlan& p = l->plan;
     const bool by_addr = eff_txs != nullptr;
     if (by_addr) {
-        ledger_plan_batch(n_l1, l1, m, eff_txs, F, fee_plan_tokens, fee_idxs, p);
+        ledger_plan_rows(n_l1, l1, m, eff_txs, F, fee_plan_tokens, fee_idxs, run.exits, p);
     } else {
         if (hz_status e = ledger_check_plan(who, m, txs, F, fee_plan_tokens, fee_idxs, k, l->first_idx, p)) return e;
         if (with_sigs)
@@ -626,20 +670,33 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
     const uint32_t m32 = (uint32_t)m, R32 = (uint32_t)R, L32 = (uint32_t)n_l1, F32 = (uint32_t)F, S = (uint32_t)n_sib;
     const uint32_t M = (uint32_t)p.account.size(), G = (uint32_t)p.seg_start.size() - 1, n_slots = (uint32_t)p.slot_account.size();
     const uint32_t n_chunks = R32 ? (R32 + HZ_LEDGER_CHUNK - 1) / HZ_LEDGER_CHUNK : 1u;
+    const uint32_t X = (uint32_t)p.exit_row.size(), GX = (uint32_t)p.exit_seg_start.size() - 1;   // exit operations, exit keys
     HZ_HIP(hipSetDevice(l->device));
     hipStream_t s = state_stream(l->tree);
+    // the exit tree's plan comes first: a leaf it cannot hold refuses the call before anything is launched, and the pack kernel's
+    // integers are the planner's
+    SmtCallBufs xb{};
+    LedgerExitGuard exit_guard;
+    if (X) {
+        if (hz_status e = smt_apply_prepare(l->exit, who, HZ_ERR_ARG, X, p.exit_key.data(), (uint32_t)n_sib, true, &xb)) return e;
+        exit_guard.t = l->exit;
+    }
 
     // ---- integer tables, one pinned block
     Carve c;
     const size_t o_tx = c.take(R * sizeof(hz_l2tx)), o_pos_s = c.take(R * 4), o_pos_r = c.take(R * 4), o_ev_s = c.take(R * 4), o_ev_r = c.take(R * 4),
                  o_slot = c.take(R * 4), o_last = c.take((R + F) * 4), o_ev_fee = c.take(F * 4), o_pos_fee = c.take(F * 4), o_plan = c.take(F * 4),
                  o_acct = c.take((size_t)M * 4), o_pos = c.take((size_t)M * sizeof(LedgerPos)), o_seg = c.take(((size_t)G + 1) * 4),
-                 o_l1 = c.take(n_l1 * sizeof(LedgerL1Dev)), o_slot_acct = c.take((size_t)n_slots * 4);
+                 o_l1 = c.take(n_l1 * sizeof(LedgerL1Dev)), o_slot_acct = c.take((size_t)n_slots * 4), o_ev_x = c.take(X ? R * 4 : 0),
+                 o_pos_x = c.take(X ? R * 4 : 0), o_last_x = c.take(X ? R * 4 : 0), o_xpos = c.take((size_t)X * sizeof(LedgerExitPos)),
+                 o_xseg = c.take(X ? ((size_t)GX + 1) * 4 : 0), o_xop = c.take((size_t)X * sizeof(LedgerExitOp));
     const size_t ints_bytes = c.end;   // (G + 1 >= 1: never empty)
     HZ_HIP(l->h_ints.grow(ints_bytes));
     uint8_t* hb = (uint8_t*)l->h_ints.p;
     std::vector<uint32_t> pos_of(M);
     for (uint32_t q = 0; q < M; q++) pos_of[p.perm[q]] = q;
+    std::vector<uint32_t> xpos_of(X);
+    for (uint32_t q = 0; q < X; q++) xpos_of[p.exit_perm[q]] = q;
     for (size_t i = 0; i < n_l1; i++) {   // an L1 row as the per-row kernels read it (token_id, to_idx), and as k_ledger_l1 does
         hz_l2tx row{};
         row.from_idx = l1[i].from_idx;
@@ -656,6 +713,7 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
         d.pos_s = (int32_t)pos_of[p.ev_sender[i]];
         d.pos_r = -1;
         d.slot_r = HZ_L1_NO_SLOT;
+        d.pos_x = p.ev_exit[i] >= 0 ? (int32_t)xpos_of[p.ev_exit[i]] : -1;
         if (p.ev_receiver[i] >= 0) {
             d.acct_r = (uint32_t)(l1[i].to_idx - l->first_idx);
             d.slot_r = (uint16_t)p.l1_slot_receiver[i];
@@ -686,8 +744,24 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
         ((LedgerPos*)(hb + o_pos))[q] = LedgerPos{e, p.unit[e], p.kind[e], (uint32_t)(p.account[e] - l->first_idx)};
     }
     for (uint32_t g = 0; g <= G; g++) ((uint32_t*)(hb + o_seg))[g] = p.seg_start[g];
+    if (X) {
+        for (size_t i = 0; i < R; i++) {
+            ((int32_t*)(hb + o_ev_x))[i] = p.ev_exit[i];
+            ((int32_t*)(hb + o_pos_x))[i] = p.ev_exit[i] >= 0 ? (int32_t)xpos_of[p.ev_exit[i]] : -1;
+            ((int32_t*)(hb + o_last_x))[i] = p.last_exit[i];
+        }
+        for (uint32_t q = 0; q < X; q++) {
+            const uint32_t x = p.exit_perm[q];
+            ((LedgerExitPos*)(hb + o_xpos))[q] = LedgerExitPos{x, p.exit_row[x], (uint32_t)(p.exit_key[x] - l->first_idx)};
+        }
+        for (uint32_t x = 0; x < X; x++)
+            ((LedgerExitOp*)(hb + o_xop))[x] = LedgerExitOp{xb.old_key[x], (uint32_t)(p.exit_key[x] - l->first_idx),
+                                                            (xb.fnc[x] ? EXIT_OP_INSERT : 0u) | (xb.is_old0[x] ? EXIT_OP_IS_OLD0 : 0u)};
+        for (uint32_t g = 0; g <= GX; g++) ((uint32_t*)(hb + o_xseg))[g] = p.exit_seg_start[g];
+    }
 
-    // ---- device buffers: work = fee[m] | chunk sums | delta[M] | before[M][2] | failure word; outs = the 27 arrays
+    // ---- device buffers: work = fee[m] | chunk sums | delta[M] | before[M][2] | failure word | exit amounts[X] | exit before[X][2];
+    // outs = the 27 arrays; exit_outs = the six exit arrays
     size_t w = 0;
     const size_t w_fee = w;
     w += (size_t)(R32 ? R32 : 1) * 32;
@@ -699,6 +773,10 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
     w += (size_t)(M ? M : 1) * 64;
     const size_t w_fail = w;
     w += 64;
+    const size_t w_xamt = w;
+    w += (size_t)X * 32;
+    const size_t w_xbefore = w;
+    w += (size_t)X * 64;
     size_t elems[HZ_LEDGER_ARRAYS];
     for (int a = 0; a < HZ_LEDGER_ARRAYS; a++) elems[a] = a < LO_TX3 ? R : F;
     elems[LO_SIB1] = elems[LO_SIB2] = R * n_sib;
@@ -710,6 +788,13 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
     HZ_HIP(l->ints.grow(ints_bytes));
     HZ_HIP(l->work.grow(w));
     HZ_HIP(l->outs.grow(out_bytes));
+    const size_t exit_out_bytes = ((size_t)(HZ_LEDGER_EXIT_ARRAYS - 1) * R + 1) * 32;   // five arrays per row, the new exit root
+    uint8_t* xd[HZ_LEDGER_EXIT_ARRAYS] = {};
+    if (run.exits) {
+        HZ_HIP(l->exit_outs.grow(exit_out_bytes));
+        HZ_HIP(l->exit_final.grow((size_t)4 * (GX ? GX : 1) * 32));
+        for (int a = 0; a < HZ_LEDGER_EXIT_ARRAYS; a++) xd[a] = (uint8_t*)l->exit_outs.p + (size_t)a * R * 32;
+    }
     LedgerOutDev od;
     {
         uint8_t* at = (uint8_t*)l->outs.p;
@@ -740,13 +825,13 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
     HZ_HIP(hipEventRecord(l->e0, s));
     if (R32) {
         hipLaunchKernelGGL(k_ledger_tx, dim3((R32 + 63) / 64), dim3(64), 0, s, d_txs, (const int32_t*)(db + o_pos_s), (const int32_t*)(db + o_pos_r), wb + w_fee,
-                           wb + w_delta, R32, L32);
+                           wb + w_delta, X ? (const int32_t*)(db + o_pos_x) : (const int32_t*)nullptr, wb + w_xamt, R32, L32);
         HZ_HIP(hipGetLastError());
     }
     if (L32) {   // the deltas of the L1 events, beside those k_ledger_tx wrote: one workgroup, no synchronise of its own
         HZ_HIP(hipEventRecord(l->el0, s));
         hipLaunchKernelGGL(k_ledger_l1, dim3(1), dim3(256), 0, s, (const LedgerL1Dev*)(db + o_l1), (const uint32_t*)(db + o_slot_acct), (const uint8_t*)l->planes.p,
-                           wb + w_delta, (uint8_t*)l->l1_flags.p, N, L32, n_slots);
+                           wb + w_delta, wb + w_xamt, (uint8_t*)l->l1_flags.p, N, L32, n_slots);
         HZ_HIP(hipGetLastError());
         HZ_HIP(hipEventRecord(l->el1, s));
     }
@@ -761,6 +846,13 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
         hipLaunchKernelGGL(k_ledger_scan, dim3((G + 63) / 64), dim3(64), 0, s, d_pos, d_seg, d_txs, d_dest, (const uint32_t*)(db + o_plan), (const uint8_t*)(wb + w_delta),
                            (const uint8_t*)l->planes.p, wb + w_before, tb.fields, d_fail, N, G, R32, L32);
         HZ_HIP(hipGetLastError());
+    }
+    if (X) {   // the exit leaves: it reads the amounts k_ledger_tx and k_ledger_l1 left and the planes, and writes per-call buffers only
+        HZ_HIP(hipEventRecord(l->ex0, s));
+        hipLaunchKernelGGL(k_ledger_exit_scan, dim3((GX + 63) / 64), dim3(64), 0, s, (const LedgerExitPos*)(db + o_xpos), (const uint32_t*)(db + o_xseg),
+                           (const uint8_t*)(wb + w_xamt), (const uint8_t*)l->planes.p, wb + w_xbefore, xb.fields, (uint8_t*)l->exit_final.p, d_fail, N, GX);
+        HZ_HIP(hipGetLastError());
+        HZ_HIP(hipEventRecord(l->ex1, s));
     }
     if (with_sigs) {   // they read the planes and the uploads only: any place before the failure-word read would do
         HZ_HIP(hipEventRecord(l->es0, s));
@@ -783,6 +875,12 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
     }
 
     // ---- outputs, tree, resident planes
+    if (X) {   // the exit tree's update depends on the scan alone: on its own stream, beside everything below
+        HZ_HIP(hipStreamWaitEvent(smt_stream(l->exit), l->ex1, 0));
+        if (hz_status e = smt_apply_launch(l->exit, X, S, true)) return e;
+        HZ_HIP(hipEventRecord(l->ex_tree, smt_stream(l->exit)));
+    }
+    if (run.exits) HZ_HIP(hipMemsetAsync(l->exit_outs.p, 0, exit_out_bytes, s));
     if (R32 + F32) {
         hipLaunchKernelGGL(k_ledger_pack, dim3((R32 + F32 + 63) / 64), dim3(64), 0, s, od, d_txs, d_dest, (uint8_t*)l->aux_rows.p, l->first_idx, (const int32_t*)(db + o_ev_s),
                            (const int32_t*)(db + o_ev_r), (const int32_t*)(db + o_ev_fee), (const uint32_t*)(db + o_acct), (const uint8_t*)(wb + w_before), (const uint8_t*)l->planes.p, N, R32, F32, L32);
@@ -806,7 +904,31 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
         hipLaunchKernelGGL(k_ledger_writeback, dim3((G + 63) / 64), dim3(64), 0, s, d_pos, d_seg, (const uint8_t*)tb.fields, (uint8_t*)l->planes.p, N, G);
         HZ_HIP(hipGetLastError());
     }
+    if (X) {   // the exit rows, once the exit tree's update is through: leaf-2 rows and siblings2 over what k_ledger_pack / _gather left there
+        LedgerExitOutDev xo;
+        for (int q = 0; q < 6; q++) xo.tx2[q] = od.a[LO_TX2 + q];
+        xo.sib2 = od.a[LO_SIB2];
+        for (int a = 0; a < HZ_LEDGER_EXIT_ARRAYS; a++) xo.x[a] = xd[a];
+        HZ_HIP(hipStreamWaitEvent(s, l->ex_tree, 0));
+        HZ_HIP(hipEventRecord(l->ex2, s));
+        hipLaunchKernelGGL(k_ledger_exit_pack, dim3((R32 + 63) / 64), dim3(64), 0, s, xo, (const int32_t*)(db + o_ev_x), (const LedgerExitOp*)(db + o_xop),
+                           (const uint8_t*)(wb + w_xbefore), (const uint8_t*)xb.old_value, (const uint8_t*)l->planes.p, N, R32);
+        HZ_HIP(hipGetLastError());
+        const size_t threads = (size_t)R32 * (S + 1);
+        hipLaunchKernelGGL(k_ledger_exit_gather, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, xo, (const int32_t*)(db + o_ev_x),
+                           (const int32_t*)(db + o_last_x), (const uint8_t*)xb.siblings, (const uint8_t*)xb.roots, S, R32);
+        HZ_HIP(hipGetLastError());
+        HZ_HIP(hipMemcpyAsync(xd[XO_NEW_ROOT], xb.roots + (size_t)X * 32, 32, hipMemcpyDeviceToDevice, s));
+        HZ_HIP(hipEventRecord(l->ex3, s));
+    }
     HZ_HIP(hipEventRecord(l->e2, s));
+    if (run.exit_out) {
+        uint8_t* const* h = (uint8_t* const*)run.exit_out;
+        for (int a = 0; a < HZ_LEDGER_EXIT_ARRAYS; a++) {
+            const size_t rows = a == XO_NEW_ROOT ? 1 : R;
+            if (h[a] && rows) HZ_HIP(hipMemcpyAsync(h[a], xd[a], rows * 32, hipMemcpyDeviceToHost, s));
+        }
+    }
     if (out) {
         uint8_t* const* h = (uint8_t* const*)out;
         for (int a = 0; a < HZ_LEDGER_ARRAYS; a++)
@@ -822,6 +944,24 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
         HZ_HIP(hipStreamSynchronize(s));
     }
     float ms = 0;
+    if (X) {
+        exit_guard.t = nullptr;
+        if (hz_status e = smt_apply_finish(l->exit)) {
+            smt_apply_abort(l->exit);
+            return e;
+        }
+        l->exit_ms = hz_smt_device_ms(l->exit);
+        HZ_HIP(hipEventElapsedTime(&ms, l->ex0, l->ex1));
+        l->exit_ms += ms;
+        HZ_HIP(hipEventElapsedTime(&ms, l->ex2, l->ex3));
+        l->exit_ms += ms;
+        for (uint32_t g = 0; g < GX; g++) l->exit_keys.push_back({p.exit_key[p.exit_perm[p.exit_seg_start[g]]], g});
+        std::sort(l->exit_keys.begin(), l->exit_keys.end());
+    }
+    if (run.exits) {
+        for (int a = 0; a < HZ_LEDGER_EXIT_ARRAYS; a++) l->exit_dev[a] = xd[a];
+        l->have_exit_outputs = true;
+    }
     HZ_HIP(hipEventElapsedTime(&ms, l->e0, l->e1));
     l->semantic_ms = ms;
     HZ_HIP(hipEventElapsedTime(&ms, l->e0, l->e2));
@@ -955,6 +1095,7 @@ static hz_status ledger_apply_addr(hz_ledger* l, const char* who, const LedgerL1
                                    const uint64_t* aux_to_idx, uint32_t chain_id, uint32_t current_num_batch, size_t F, const uint32_t* fee_plan_tokens,
                                    const uint64_t* fee_idxs, size_t n_sib, const hz_ledger_out* out, const hz_ledger_sig_out* sig_out, uint8_t* aux_to_idx_out) {
     if (hz_status e = ledger_ready(l, who)) return e;
+    ledger_exit_reset(l);
     const size_t n_l1 = run.n;
     const hz_l1tx* l1 = run.tx;
     if (run.is_batch) l->l1_ms = 0.0;   // the time of THIS call, whatever becomes of it
@@ -963,8 +1104,8 @@ static hz_status ledger_apply_addr(hz_ledger* l, const char* who, const LedgerL1
     if (!verify && sig_out) return set_err(HZ_ERR_ARG, "%s: sig_out without HZ_LEDGER_VERIFY_SIGS", who);
     if (n_sib < l->k || n_sib > 64) return set_err(HZ_ERR_ARG, "%s: n_sib = %zu (%u .. 64)", who, n_sib, l->k);
     size_t l1_events = 0;
-    if (hz_status e = ledger_check_l1(who, n_l1, l1, l->first_idx, l->N, &l1_events)) return e;
-    if (hz_status e = ledger_check_plan(who, m, txs, F, fee_plan_tokens, fee_idxs, l->k, l->first_idx, l->plan, true, l1_events)) return e;
+    if (hz_status e = ledger_check_l1(who, n_l1, l1, l->first_idx, l->N, &l1_events, run.exits)) return e;
+    if (hz_status e = ledger_check_plan(who, m, txs, F, fee_plan_tokens, fee_idxs, l->k, l->first_idx, l->plan, true, l1_events, run.exits)) return e;
     std::vector<hz_l2sig> no_sigs;
     if (run.is_batch && !sigs && m && !verify) {   // no destination is signed: zero entries stand in, and the call is hz_ledger_apply_l2_addr's
         for (size_t i = 0; i < m; i++)
@@ -1072,3 +1213,106 @@ extern "C" hz_status hz_ledger_aux_to_idx_dev(hz_ledger* l, uint8_t** dev) {
 }
 
 extern "C" double hz_ledger_resolve_ms(const hz_ledger* l) { return l ? l->resolve_ms : 0.0; }
+
+// ---- exits into the batch's exit tree ------------------------------------------------------------------------------------
+extern "C" hz_status hz_ledger_apply_batch_exits(hz_ledger* l, size_t n_l1, const hz_l1tx* l1, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, uint32_t flags,
+                                                 const uint64_t* aux_to_idx, uint32_t chain_id, uint32_t current_num_batch, size_t F, const uint32_t* fee_plan_tokens,
+                                                 const uint64_t* fee_idxs, size_t n_sib, const hz_ledger_out* out, const hz_ledger_sig_out* sig_out,
+                                                 uint8_t* aux_to_idx_out, uint8_t* l1_flags_out, const hz_ledger_exit_out* exit_out) {
+    static_assert(sizeof(hz_ledger_exit_out) == HZ_LEDGER_EXIT_ARRAYS * sizeof(uint8_t*), "hz_ledger_exit_out is an array of pointers");
+    LedgerL1Run run;
+    run.n = n_l1;
+    run.tx = l1;
+    run.flags_out = l1_flags_out;
+    run.is_batch = true;
+    run.exits = true;
+    run.exit_out = exit_out;
+    return ledger_apply_addr(l, "hz_ledger_apply_batch_exits", run, m, txs, sigs, flags, aux_to_idx, chain_id, current_num_batch, F, fee_plan_tokens, fee_idxs, n_sib,
+                             out, sig_out, aux_to_idx_out);
+}
+
+extern "C" hz_status hz_ledger_exit_outputs_dev(hz_ledger* l, hz_ledger_exit_out* dev) {
+    if (!l || !dev) return set_err(HZ_ERR_ARG, "hz_ledger_exit_outputs_dev: null argument");
+    if (!l->have_exit_outputs)
+        return set_err(HZ_ERR_ARG, "hz_ledger_exit_outputs_dev: no successful hz_ledger_apply_batch_exits since the ledger's last other call");
+    uint8_t** d = (uint8_t**)dev;
+    for (int a = 0; a < HZ_LEDGER_EXIT_ARRAYS; a++) d[a] = l->exit_dev[a];
+    return HZ_OK;
+}
+
+extern "C" hz_smt* hz_ledger_exit_tree(hz_ledger* l) { return l ? l->exit : nullptr; }
+extern "C" double hz_ledger_exit_ms(const hz_ledger* l) { return l ? l->exit_ms : 0.0; }
+
+extern "C" hz_status hz_ledger_exit_accounts(hz_ledger* l, size_t n, const uint64_t* key, uint8_t* fields_out) {
+    const char* who = "hz_ledger_exit_accounts";
+    if (hz_status e = ledger_ready(l, who)) return e;
+    if (n == 0) return HZ_OK;
+    if (!key || !fields_out) return set_err(HZ_ERR_ARG, "%s: null argument", who);
+    if (n > HZ_LEDGER_MAX_EVENTS) return set_err(HZ_ERR_ARG, "%s: %zu leaves in one call (at most %u)", who, n, HZ_LEDGER_MAX_EVENTS);
+    const uint32_t GX = (uint32_t)l->exit_keys.size();
+    std::vector<uint32_t> at(n);
+    for (size_t i = 0; i < n; i++) {
+        const auto it = std::lower_bound(l->exit_keys.begin(), l->exit_keys.end(), std::make_pair(key[i], 0u));
+        if (it == l->exit_keys.end() || it->first != key[i])
+            return set_err(HZ_ERR_ARG, "%s: key[%zu] = %llu is not in the exit tree of the last batch", who, i, (unsigned long long)key[i]);
+        at[i] = it->second;
+    }
+    HZ_HIP(hipSetDevice(l->device));
+    ledger_forget(l);   // the call's buffers are reused
+    hipStream_t s = state_stream(l->tree);
+    HZ_HIP(l->ints.grow(n * 4));
+    HZ_HIP(l->work.grow(n * 128));
+    HZ_HIP(hipMemcpyAsync(l->ints.p, at.data(), n * 4, hipMemcpyHostToDevice, s));
+    // the final leaves lie plane-major, [4][GX], as the resident planes do: the same gather
+    hipLaunchKernelGGL(k_ledger_accounts, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, s, (const uint32_t*)l->ints.p, (const uint8_t*)l->exit_final.p,
+                       (uint8_t*)l->work.p, GX, (uint32_t)n);
+    HZ_HIP(hipGetLastError());
+    HZ_HIP(hipMemcpyAsync(fields_out, l->work.p, n * 128, hipMemcpyDeviceToHost, s));
+    HZ_HIP(hipStreamSynchronize(s));
+    return HZ_OK;
+}
+
+extern "C" hz_status hz_ledger_plan_exits(size_t n_l1, const hz_l1tx* l1, size_t m, const hz_l2tx* txs, size_t F, const uint32_t* fee_plan_tokens,
+                                          const uint64_t* fee_idxs, int32_t k, uint64_t first_idx, size_t n_sib, int32_t* ev_sender_out, int32_t* ev_receiver_out,
+                                          int32_t* last_event_out, size_t* n_events_out, uint64_t* ev_account_out, int32_t* ev_exit_out, int32_t* last_exit_out,
+                                          size_t* n_exits_out, uint32_t* exit_row_out, uint64_t* exit_key_out, int32_t* exit_prev_out, uint32_t* exit_perm_out,
+                                          uint8_t* exit_insert_out, uint8_t* exit_is_old0_out, uint64_t* exit_old_key_out) {
+    const char* who = "hz_ledger_plan_exits";
+    if (k < 4 || k > 24) return set_err(HZ_ERR_ARG, "%s: k = %d (4 .. 24)", who, k);
+    if (n_sib < (size_t)k || n_sib > 64) return set_err(HZ_ERR_ARG, "%s: n_sib = %zu (%d .. 64)", who, n_sib, k);
+    LedgerPlan p;
+    size_t l1_events = 0;
+    if (hz_status e = ledger_check_l1(who, n_l1, l1, first_idx, 1ull << k, &l1_events, true)) return e;
+    if (hz_status e = ledger_check_plan(who, m, txs, F, fee_plan_tokens, fee_idxs, (uint32_t)k, first_idx, p, true, l1_events, true)) return e;
+    for (size_t i = 0; i < m; i++)   // the planner is given receivers: a transfer to an address has none before the lookup
+        if (txs[i].from_idx != 0 && txs[i].to_idx == 0) return set_err(HZ_ERR_ARG, "%s: tx %zu: to_idx = 0 (a transfer to an address) is not supported yet", who, i);
+    ledger_plan_exits(n_l1, l1, m, txs, F, fee_plan_tokens, fee_idxs, p);
+    const size_t X = p.exit_row.size();
+    SmtShape sh;   // the exit tree of a batch starts empty
+    sh.begin();
+    for (size_t x = 0; x < X; x++)
+        if (sh.add(p.exit_key[x], (uint32_t)n_sib) != SMT_PLAN_OK)
+            return set_err(HZ_ERR_ARG, "%s: op %zu (key %llu) would have its leaf at depth >= n_sib = %zu: SMTProcessor(%zu) cannot express it", who, x,
+                           (unsigned long long)p.exit_key[x], n_sib, n_sib);
+    for (size_t i = 0; i < n_l1 + m; i++) {
+        if (ev_sender_out) ev_sender_out[i] = p.ev_sender[i];
+        if (ev_receiver_out) ev_receiver_out[i] = p.ev_receiver[i];
+        if (last_event_out) last_event_out[i] = p.last_event[i];
+        if (ev_exit_out) ev_exit_out[i] = p.ev_exit[i];
+        if (last_exit_out) last_exit_out[i] = p.last_exit[i];
+    }
+    if (n_events_out) *n_events_out = p.account.size();
+    for (size_t e = 0; e < p.account.size(); e++)
+        if (ev_account_out) ev_account_out[e] = p.account[e];
+    if (n_exits_out) *n_exits_out = X;
+    for (size_t x = 0; x < X; x++) {
+        if (exit_row_out) exit_row_out[x] = p.exit_row[x];
+        if (exit_key_out) exit_key_out[x] = p.exit_key[x];
+        if (exit_prev_out) exit_prev_out[x] = p.exit_prev[x];
+        if (exit_perm_out) exit_perm_out[x] = p.exit_perm[x];
+        if (exit_insert_out) exit_insert_out[x] = sh.fnc[x];
+        if (exit_is_old0_out) exit_is_old0_out[x] = sh.is_old0[x];
+        if (exit_old_key_out) exit_old_key_out[x] = sh.old_key[x];
+    }
+    return HZ_OK;
+}

@@ -13,6 +13,9 @@
 //                buffer k_ledger_scan reads, and the flag byte (bit 0 nullifyLoadAmount, bit 1 isAmountNullified)
 // k_ledger_scan then treats the L1 events like any other: it carries the balance through the deltas (no token or nonce check; reason 5
 // stays), so an L2 transaction sees exactly the balances the L1 run left.
+// A forceExit (to_idx == 1) is a transfer whose receiver needs no slot: nothing ever depends on an exit leaf's balance. Its
+// receiver's token is the sender's (the exit leaf is made of the sender's), so null_tok2 adds nothing; phase 3 leaves eff3 in the
+// exit-amount buffer at pos_x, where k_ledger_tx leaves the amount of an L2 exit.
 // LDS (L1Lds below), limb-major so that the parallel phases are free of bank conflicts: balances [8][1024] u32 = 32768 B; eff_load and
 // eff2 / eff3 [5][512] u32 each (an amount is below 2^35 x 10^31 < 2^138) = 20480 B; the two slots of a transaction [512] u16 each =
 // 2048 B; flags [512] = 512 B: 55808 B of the 65536 a workgroup may have.
@@ -35,6 +38,7 @@ struct LedgerL1Dev {
     uint32_t acct_s, acct_r;   // account - first_idx; acct_r is read only when the amount is not zero
     uint16_t slot_s, slot_r;   // local slots; slot_r == HZ_L1_NO_SLOT: no receiver event
     int32_t pos_s, pos_r;      // grouped positions of the two events in the delta buffer; pos_r < 0: none
+    int32_t pos_x;             // a forceExit with an amount: the grouped position of its operation in the exit-amount buffer; else < 0
     uint32_t from_eth[5];      // 160 bits
 };
 
@@ -103,7 +107,8 @@ static_assert(sizeof(L1Lds) == 55808 && sizeof(L1Lds) <= 65536, "k_ledger_l1's L
 
 // one workgroup; n <= HZ_L1_MAX_TX, n_slots <= HZ_L1_MAX_SLOTS (the host checks both)
 __global__ __launch_bounds__(256) void k_ledger_l1(const LedgerL1Dev* __restrict__ l1, const uint32_t* __restrict__ slot_acct, const uint8_t* __restrict__ planes,
-                                                   uint8_t* __restrict__ delta, uint8_t* __restrict__ flags_out, uint32_t N, uint32_t n, uint32_t n_slots) {
+                                                   uint8_t* __restrict__ delta, uint8_t* __restrict__ exit_amt, uint8_t* __restrict__ flags_out, uint32_t N,
+                                                   uint32_t n, uint32_t n_slots) {
     __shared__ L1Lds lds;
     // ---- 1: the static part of every transaction, the balance of every slot
     for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
@@ -112,6 +117,7 @@ __global__ __launch_bounds__(256) void k_ledger_l1(const LedgerL1Dev* __restrict
         const Fc eth_s = load_fr(planes + ((size_t)3 * N + t.acct_s) * 32);
         uint32_t tok_r = 0u;
         if (t.slot_r != HZ_L1_NO_SLOT) tok_r = load_fr(planes + (size_t)t.acct_r * 32).v[0];
+        if (t.pos_x >= 0) tok_r = e0_s.v[0];   // the exit leaf holds the sender's token
         const L1Static st = l1_static(t.amount_f, t.load_amount_f, t.token_id, t.from_eth, e0_s.v[0], eth_s, tok_r);
 #pragma unroll
         for (int q = 0; q < 5; q++) {
@@ -168,9 +174,10 @@ __global__ __launch_bounds__(256) void k_ledger_l1(const LedgerL1Dev* __restrict
             eff_load.v[q] = lds.load[q][i];
             eff3.v[q] = lds.amt[q][i];
         }
-        const int32_t pos_s = l1[i].pos_s, pos_r = l1[i].pos_r;
+        const int32_t pos_s = l1[i].pos_s, pos_r = l1[i].pos_r, pos_x = l1[i].pos_x;
         store_fr(delta + (size_t)pos_s * 32, l1_sender_delta(eff_load, eff3));
         if (pos_r >= 0) store_fr(delta + (size_t)pos_r * 32, eff3);
+        if (pos_x >= 0) store_fr(exit_amt + (size_t)pos_x * 32, eff3);
         flags_out[i] = lds.flag[i];
     }
 }

@@ -1,0 +1,36 @@
+// hz_smt from the inside: the ordered inserts and updates of hz_smt_apply for callers in this library whose leaf fields are already in
+// device memory (ledger.hip's exit tree). The counterpart of state_internal.h; smt_tree.hip defines everything declared here.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "../../include/hermez_witness.h"
+
+namespace hz {
+
+// device buffers of one apply, valid until the tree's next call: the [M][4][32] records the update reads, and what it leaves behind
+struct SmtCallBufs {
+    uint8_t* fields;      // in:  [M][4][32], written by the caller between prepare and launch; the launch must be ordered behind that write
+    uint8_t* siblings;    // out: [M][n_sib][32], zero-padded (NULL when the caller asked for none)
+    uint8_t* roots;       // out: [M + 1][32], the root before operation j (so [j + 1]: after it)
+    uint8_t* old_value;   // out: [M][32]
+    // the planner's integers of the M operations, the host's: valid until finish / abort
+    const uint64_t* old_key;
+    const uint8_t *is_old0, *fnc;
+};
+
+// Plans the M keys on the host (SmtShape::add), grows pools and buffers, and queues the upload of the call's integer tables on the
+// tree's stream. A key the planner refuses leaves the tree as it was: HZ_ERR_INPUT, or depth_status for a leaf at depth >= n_sib.
+// The tree must be usable and 1 <= M <= 65536, 1 <= n_sib <= n_sib_max (the callers check).
+hz_status smt_apply_prepare(hz_smt* t, const char* who, hz_status depth_status, uint32_t M, const uint64_t* key, uint32_t n_sib, bool want_siblings, SmtCallBufs* out);
+// the kernels, on the tree's stream: leaf, one level launch per depth, gather, write-back
+hz_status smt_apply_launch(hz_smt* t, uint32_t M, uint32_t n_sib, bool want_siblings);
+// synchronises the tree's stream, records the device time of the launch and lets the call stand
+hz_status smt_apply_finish(hz_smt* t);
+// the prepared call did not happen, or failed: nothing stays in flight, the shape is rolled back; after a queued write-back the tree
+// is poisoned (hz_smt_apply's rule)
+void smt_apply_abort(hz_smt* t);
+// the empty tree again without a synchronise: for an owner whose every call on the tree ended in finish or abort
+void smt_clear(hz_smt* t);
+hipStream_t smt_stream(const hz_smt* t);
+
+}  // namespace hz

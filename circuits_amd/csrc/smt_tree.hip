@@ -16,6 +16,7 @@
 #include "../../include/hermez_witness.h"
 #include "devcommon.h"
 #include "resident.h"
+#include "smt_internal.h"
 #include "smt_plan.h"
 #include "state_dev.h"
 
@@ -92,6 +93,9 @@ struct hz_smt {
     Resident r;               // device, stream, device time of the last apply
     bool wb_queued = false;   // the call in progress has queued its write-back: the pools may have changed
     bool poisoned = false;    // a call failed after that point: shape and pools may disagree until hz_smt_reset
+    // the prepared call (smt_internal.h): where its tables lie in the integer block
+    size_t o_keys = 0, o_ops = 0, o_gather = 0, o_wb = 0, n_gather = 0, n_wb = 0;
+    uint32_t first[HZ_SMT_MAX_DEPTH] = {};
 };
 
 // a pool that holds `used` entries gets room for `want`: a larger buffer and a device-to-device copy
@@ -135,10 +139,10 @@ static hz_status smt_usable(const hz_smt* t, const char* who) {
     return HZ_OK;
 }
 
-static hz_status smt_plan_err(const char* who, SmtPlanError e, size_t j, uint64_t key, size_t n_sib) {
+static hz_status smt_plan_err(const char* who, SmtPlanError e, size_t j, uint64_t key, size_t n_sib, hz_status depth_status = HZ_ERR_INPUT) {
     if (e == SMT_PLAN_KEY) return set_err(HZ_ERR_INPUT, "%s: key[%zu] = %llu >= 2^48 (the circuits' idx has 48 bits)", who, j, (unsigned long long)key);
     if (e == SMT_PLAN_DEPTH)
-        return set_err(HZ_ERR_INPUT, "%s: op %zu (key %llu) would have its leaf at depth >= n_sib = %zu: SMTProcessor(%zu) cannot express it", who, j,
+        return set_err(depth_status, "%s: op %zu (key %llu) would have its leaf at depth >= n_sib = %zu: SMTProcessor(%zu) cannot express it", who, j,
                        (unsigned long long)key, n_sib, n_sib);
     return set_err(HZ_ERR_ARG, "%s: op %zu: the tree is full (2^28 keys)", who, j);
 }
@@ -191,81 +195,126 @@ extern "C" hz_status hz_smt_root(hz_smt* t, uint8_t* out32) {
     return HZ_OK;
 }
 
-// the device's part of a planned call; the shape is rolled back by the caller when this fails
-static hz_status smt_apply_device(hz_smt* t, uint32_t M, const uint64_t* key, const uint8_t* fields, uint32_t n_sib, uint8_t* siblings_out, uint8_t* old_value_out,
-                                  uint8_t* old_root_out, uint8_t* new_root_out) {
+// ---- one apply in three steps (smt_internal.h): hz_smt_apply below, and the ledger's exit tree ---------------------------------------------
+hz_status hz::smt_apply_prepare(hz_smt* t, const char* who, hz_status depth_status, uint32_t M, const uint64_t* key, uint32_t n_sib, bool want_siblings,
+                                SmtCallBufs* bufs) {
     SmtShape& sh = t->shape;
-    HZ_HIP(hipSetDevice(t->r.device));
-    if (hz_status e = smt_pool(t, t->node, sh.nodes0, sh.nodes())) return e;
-    if (hz_status e = smt_pool(t, t->leaf, sh.leaves0, sh.leaves())) return e;
-    if (hz_status e = smt_pool(t, t->value, sh.leaves0, sh.leaves())) return e;
-    uint32_t first[HZ_SMT_MAX_DEPTH];
-    sh.firsts(first);
-    const size_t V = sh.versions();
-    // what the gather reads: roots [m + 1] | old values [m]; what the write-back scatters
-    const size_t G = (size_t)2 * M + 1, W = sh.touched_nodes.size() + 2 * sh.touched_leaves.size();
-    // the integer tables of the call, one pinned block: bases [8] (at offset 0) | keys u64[m] | level ops [V] | gather list [G] | write-back list [W]
-    Carve c;
-    c.take(64);
-    const size_t o_keys = c.take((size_t)M * 8), o_ops = c.take(V * sizeof(SmtLevelOp)), o_gather = c.take(G * sizeof(SmtCopy)), o_wb = c.take(W * sizeof(SmtCopy));
-    const size_t ints_bytes = c.end;
-    HZ_HIP(t->h_ints.grow(ints_bytes));
-    HZ_HIP(t->ints.grow(ints_bytes));
-    HZ_HIP(t->fields.grow((size_t)M * 128));
-    HZ_HIP(t->lv.grow((size_t)M * 32));
-    HZ_HIP(t->lh.grow((size_t)M * 32));
-    HZ_HIP(t->ver.grow((V + 1) * 32));
-    HZ_HIP(t->out.grow(G * 32));
-    if (siblings_out) HZ_HIP(t->sib.grow((size_t)M * n_sib * 32));
-    uint8_t* hb = (uint8_t*)t->h_ints.p;
-    smt_bases(t, (const void**)hb);
-    uint64_t* h_keys = (uint64_t*)(hb + o_keys);
-    for (uint32_t j = 0; j < M; j++) h_keys[j] = key[j];
-    SmtLevelOp* h_ops = (SmtLevelOp*)(hb + o_ops);
-    for (uint32_t d = 0; d < sh.max_depth; d++)
-        for (size_t i = 0; i < sh.level[d].size(); i++) {
-            const SmtLevelOp& o = sh.level[d][i];
-            h_ops[first[d] + i] = {sh.flat_src(o.own, first), sh.flat_src(o.other, first), o.meta};
+    sh.begin();
+    for (uint32_t j = 0; j < M; j++)
+        if (const SmtPlanError e = sh.add(key[j], n_sib)) {
+            sh.rollback();
+            return smt_plan_err(who, e, j, key[j], n_sib, depth_status);
         }
-    SmtCopy* h_gather = (SmtCopy*)(hb + o_gather);
-    for (uint32_t j = 0; j <= M; j++) h_gather[j] = {sh.flat_src(sh.root_src[j], first), j};
-    for (uint32_t j = 0; j < M; j++) h_gather[M + 1 + j] = {sh.old_value_src[j], M + 1 + j};
-    SmtCopy* h_wb = (SmtCopy*)(hb + o_wb);
-    size_t w = 0;
-    for (uint32_t n : sh.touched_nodes) h_wb[w++] = {smt_src(SMT_VER, sh.global_ver((uint32_t)sh.node_ver[n], first)), smt_src(SMT_NODE, n)};
-    for (uint32_t l : sh.touched_leaves) {
-        h_wb[w++] = {smt_src(SMT_CALL_LH, (uint32_t)sh.leaf_op[l]), smt_src(SMT_LEAF, l)};
-        h_wb[w++] = {smt_src(SMT_CALL_LV, (uint32_t)sh.leaf_op[l]), smt_src(SMT_VALUE, l)};
+    t->wb_queued = false;
+    const hz_status st = [&]() -> hz_status {
+        HZ_HIP(hipSetDevice(t->r.device));
+        if (hz_status e = smt_pool(t, t->node, sh.nodes0, sh.nodes())) return e;
+        if (hz_status e = smt_pool(t, t->leaf, sh.leaves0, sh.leaves())) return e;
+        if (hz_status e = smt_pool(t, t->value, sh.leaves0, sh.leaves())) return e;
+        uint32_t* first = t->first;
+        sh.firsts(first);
+        const size_t V = sh.versions();
+        // what the gather reads: roots [m + 1] | old values [m]; what the write-back scatters
+        const size_t G = (size_t)2 * M + 1, W = sh.touched_nodes.size() + 2 * sh.touched_leaves.size();
+        // the integer tables of the call, one pinned block: bases [8] (at offset 0) | keys u64[m] | level ops [V] | gather list [G] | write-back list [W]
+        Carve c;
+        c.take(64);
+        const size_t o_keys = c.take((size_t)M * 8), o_ops = c.take(V * sizeof(SmtLevelOp)), o_gather = c.take(G * sizeof(SmtCopy)), o_wb = c.take(W * sizeof(SmtCopy));
+        const size_t ints_bytes = c.end;
+        t->o_keys = o_keys, t->o_ops = o_ops, t->o_gather = o_gather, t->o_wb = o_wb, t->n_gather = G, t->n_wb = W;
+        HZ_HIP(t->h_ints.grow(ints_bytes));
+        HZ_HIP(t->ints.grow(ints_bytes));
+        HZ_HIP(t->fields.grow((size_t)M * 128));
+        HZ_HIP(t->lv.grow((size_t)M * 32));
+        HZ_HIP(t->lh.grow((size_t)M * 32));
+        HZ_HIP(t->ver.grow((V + 1) * 32));
+        HZ_HIP(t->out.grow(G * 32));
+        if (want_siblings) HZ_HIP(t->sib.grow((size_t)M * n_sib * 32));
+        uint8_t* hb = (uint8_t*)t->h_ints.p;
+        smt_bases(t, (const void**)hb);
+        uint64_t* h_keys = (uint64_t*)(hb + o_keys);
+        for (uint32_t j = 0; j < M; j++) h_keys[j] = key[j];
+        SmtLevelOp* h_ops = (SmtLevelOp*)(hb + o_ops);
+        for (uint32_t d = 0; d < sh.max_depth; d++)
+            for (size_t i = 0; i < sh.level[d].size(); i++) {
+                const SmtLevelOp& o = sh.level[d][i];
+                h_ops[first[d] + i] = {sh.flat_src(o.own, first), sh.flat_src(o.other, first), o.meta};
+            }
+        SmtCopy* h_gather = (SmtCopy*)(hb + o_gather);
+        for (uint32_t j = 0; j <= M; j++) h_gather[j] = {sh.flat_src(sh.root_src[j], first), j};
+        for (uint32_t j = 0; j < M; j++) h_gather[M + 1 + j] = {sh.old_value_src[j], M + 1 + j};
+        SmtCopy* h_wb = (SmtCopy*)(hb + o_wb);
+        size_t w = 0;
+        for (uint32_t n : sh.touched_nodes) h_wb[w++] = {smt_src(SMT_VER, sh.global_ver((uint32_t)sh.node_ver[n], first)), smt_src(SMT_NODE, n)};
+        for (uint32_t l : sh.touched_leaves) {
+            h_wb[w++] = {smt_src(SMT_CALL_LH, (uint32_t)sh.leaf_op[l]), smt_src(SMT_LEAF, l)};
+            h_wb[w++] = {smt_src(SMT_CALL_LV, (uint32_t)sh.leaf_op[l]), smt_src(SMT_VALUE, l)};
+        }
+        HZ_HIP(hipMemcpyAsync(t->ints.p, t->h_ints.p, ints_bytes, hipMemcpyHostToDevice, t->r.s));
+        return HZ_OK;
+    }();
+    if (st) {
+        smt_apply_abort(t);
+        return st;
     }
+    bufs->fields = (uint8_t*)t->fields.p;
+    bufs->siblings = want_siblings ? (uint8_t*)t->sib.p : nullptr;
+    bufs->roots = (uint8_t*)t->out.p;
+    bufs->old_value = (uint8_t*)t->out.p + ((size_t)M + 1) * 32;
+    bufs->old_key = sh.old_key.data();
+    bufs->is_old0 = sh.is_old0.data();
+    bufs->fnc = sh.fnc.data();
+    return HZ_OK;
+}
 
+hz_status hz::smt_apply_launch(hz_smt* t, uint32_t M, uint32_t n_sib, bool want_siblings) {
+    const SmtShape& sh = t->shape;
+    const uint32_t* first = t->first;
+    const size_t G = t->n_gather, W = t->n_wb;
+    HZ_HIP(hipSetDevice(t->r.device));
     const uint8_t* db = (const uint8_t*)t->ints.p;
     const uint8_t* const* d_bases = (const uint8_t* const*)db;
     hipStream_t s = t->r.s;
-    HZ_HIP(hipMemcpyAsync(t->ints.p, t->h_ints.p, ints_bytes, hipMemcpyHostToDevice, s));
-    HZ_HIP(hipMemcpyAsync(t->fields.p, fields, (size_t)M * 128, hipMemcpyHostToDevice, s));
-    if (siblings_out) HZ_HIP(hipMemsetAsync(t->sib.p, 0, (size_t)M * n_sib * 32, s));
+    if (want_siblings) HZ_HIP(hipMemsetAsync(t->sib.p, 0, (size_t)M * n_sib * 32, s));
     HZ_HIP(t->r.begin());
-    hipLaunchKernelGGL(k_smt_leaf, dim3((M + 63) / 64), dim3(64), 0, s, (const uint64_t*)(db + o_keys), (const uint8_t*)t->fields.p, (uint8_t*)t->lv.p, (uint8_t*)t->lh.p, M);
+    hipLaunchKernelGGL(k_smt_leaf, dim3((M + 63) / 64), dim3(64), 0, s, (const uint64_t*)(db + t->o_keys), (const uint8_t*)t->fields.p, (uint8_t*)t->lv.p, (uint8_t*)t->lh.p, M);
     HZ_HIP(hipGetLastError());
     for (uint32_t d = sh.max_depth; d-- > 0;) {
         const uint32_t n = (uint32_t)sh.level[d].size();
-        hipLaunchKernelGGL(k_smt_level, dim3((4 * n + 63) / 64), dim3(64), 0, s, (const SmtLevelOp*)(db + o_ops) + first[d], d_bases,
-                           (uint8_t*)t->ver.p + (size_t)first[d] * 32, siblings_out ? (uint8_t*)t->sib.p : (uint8_t*)nullptr, (const Fr*)t->pos3.p, n_sib, n);
+        hipLaunchKernelGGL(k_smt_level, dim3((4 * n + 63) / 64), dim3(64), 0, s, (const SmtLevelOp*)(db + t->o_ops) + first[d], d_bases,
+                           (uint8_t*)t->ver.p + (size_t)first[d] * 32, want_siblings ? (uint8_t*)t->sib.p : (uint8_t*)nullptr, (const Fr*)t->pos3.p, n_sib, n);
         HZ_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_smt_gather, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, s, (const SmtCopy*)(db + o_gather), d_bases, (uint8_t*)t->out.p, (uint32_t)G);
+    hipLaunchKernelGGL(k_smt_gather, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, s, (const SmtCopy*)(db + t->o_gather), d_bases, (uint8_t*)t->out.p, (uint32_t)G);
     HZ_HIP(hipGetLastError());
     t->wb_queued = true;
-    hipLaunchKernelGGL(k_smt_writeback, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, s, (const SmtCopy*)(db + o_wb), d_bases, (uint32_t)W);
+    hipLaunchKernelGGL(k_smt_writeback, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, s, (const SmtCopy*)(db + t->o_wb), d_bases, (uint32_t)W);
     HZ_HIP(hipGetLastError());
     HZ_HIP(t->r.end());
-    const uint8_t* out = (const uint8_t*)t->out.p;
-    if (old_root_out) HZ_HIP(hipMemcpyAsync(old_root_out, out, (size_t)M * 32, hipMemcpyDeviceToHost, s));
-    if (new_root_out) HZ_HIP(hipMemcpyAsync(new_root_out, out + 32, (size_t)M * 32, hipMemcpyDeviceToHost, s));
-    if (old_value_out) HZ_HIP(hipMemcpyAsync(old_value_out, out + ((size_t)M + 1) * 32, (size_t)M * 32, hipMemcpyDeviceToHost, s));
-    if (siblings_out) HZ_HIP(hipMemcpyAsync(siblings_out, t->sib.p, (size_t)M * n_sib * 32, hipMemcpyDeviceToHost, s));
-    return t->r.finish();
+    return HZ_OK;
 }
+
+hz_status hz::smt_apply_finish(hz_smt* t) {
+    if (hz_status e = t->r.finish()) return e;
+    t->shape.commit();
+    return HZ_OK;
+}
+
+// nothing of the call stays in flight (its copies read the pinned block and the caller's buffers). Before the write-back was queued the
+// pools are as they were and the roll-back is exact; after it they may not be, and the tree says so from now on
+void hz::smt_apply_abort(hz_smt* t) {
+    (void)hipStreamSynchronize(t->r.s);
+    t->shape.rollback();
+    t->poisoned = t->wb_queued;
+    t->wb_queued = false;
+}
+
+void hz::smt_clear(hz_smt* t) {
+    t->shape.clear();
+    t->poisoned = false;
+}
+
+hipStream_t hz::smt_stream(const hz_smt* t) { return t->r.s; }
 
 extern "C" hz_status hz_smt_apply(hz_smt* t, size_t m, const uint64_t* key, const uint8_t* fields, size_t n_sib, uint8_t* siblings_out, uint64_t* old_key_out,
                                   uint8_t* old_value_out, uint8_t* is_old0_out, uint8_t* fnc_out, uint8_t* old_root_out, uint8_t* new_root_out) {
@@ -276,29 +325,30 @@ extern "C" hz_status hz_smt_apply(hz_smt* t, size_t m, const uint64_t* key, cons
     if (m > HZ_SMT_MAX_M) return set_err(HZ_ERR_ARG, "hz_smt_apply: %zu ops in one call (at most %u)", m, HZ_SMT_MAX_M);
     for (size_t i = 0; i < m * 4; i++)
         if (!canon_lt_p(fields + i * 32)) return set_err(HZ_ERR_INPUT, "hz_smt_apply: field %zu of op %zu >= r", i & 3, i >> 2);
-    SmtShape& sh = t->shape;
-    sh.begin();
-    for (size_t j = 0; j < m; j++)
-        if (const SmtPlanError e = sh.add(key[j], (uint32_t)n_sib)) {
-            sh.rollback();
-            return smt_plan_err("hz_smt_apply", e, j, key[j], n_sib);
-        }
-    t->wb_queued = false;
-    if (hz_status e = smt_apply_device(t, (uint32_t)m, key, fields, (uint32_t)n_sib, siblings_out, old_value_out, old_root_out, new_root_out)) {
-        // nothing of the call stays in flight (its copies read the pinned block and the caller's buffers). Before the write-back was
-        // queued the pools are as they were and the roll-back is exact; after it they may not be, and the tree says so from now on
-        (void)hipStreamSynchronize(t->r.s);
-        sh.rollback();
-        t->poisoned = t->wb_queued;
-        return e;
+    const uint32_t M = (uint32_t)m;
+    SmtCallBufs b{};
+    if (hz_status e = smt_apply_prepare(t, "hz_smt_apply", HZ_ERR_INPUT, M, key, (uint32_t)n_sib, siblings_out != nullptr, &b)) return e;
+    const hz_status st = [&]() -> hz_status {
+        hipStream_t s = t->r.s;
+        HZ_HIP(hipMemcpyAsync(b.fields, fields, (size_t)M * 128, hipMemcpyHostToDevice, s));
+        if (hz_status e = smt_apply_launch(t, M, (uint32_t)n_sib, siblings_out != nullptr)) return e;
+        if (old_root_out) HZ_HIP(hipMemcpyAsync(old_root_out, b.roots, (size_t)M * 32, hipMemcpyDeviceToHost, s));
+        if (new_root_out) HZ_HIP(hipMemcpyAsync(new_root_out, b.roots + 32, (size_t)M * 32, hipMemcpyDeviceToHost, s));
+        if (old_value_out) HZ_HIP(hipMemcpyAsync(old_value_out, b.old_value, (size_t)M * 32, hipMemcpyDeviceToHost, s));
+        if (siblings_out) HZ_HIP(hipMemcpyAsync(siblings_out, b.siblings, (size_t)M * n_sib * 32, hipMemcpyDeviceToHost, s));
+        HZ_HIP(hipStreamSynchronize(s));
+        return HZ_OK;
+    }();
+    if (st) {
+        smt_apply_abort(t);
+        return st;
     }
     for (size_t j = 0; j < m; j++) {
-        if (old_key_out) old_key_out[j] = sh.old_key[j];
-        if (is_old0_out) is_old0_out[j] = sh.is_old0[j];
-        if (fnc_out) fnc_out[j] = sh.fnc[j];
+        if (old_key_out) old_key_out[j] = b.old_key[j];
+        if (is_old0_out) is_old0_out[j] = b.is_old0[j];
+        if (fnc_out) fnc_out[j] = b.fnc[j];
     }
-    sh.commit();
-    return HZ_OK;
+    return smt_apply_finish(t);
 }
 
 // the device's part of hz_smt_proofs: the gather over t->copies and the copies out

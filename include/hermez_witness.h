@@ -526,9 +526,49 @@ hz_status hz_smt_plan(size_t m, const uint64_t* key, size_t n_sib, uint32_t* dep
  *                       ledger's next call
  *   hz_ledger_l1_ms     device time of the L1 kernel of the last hz_ledger_apply_batch (0: n_l1 was 0, the call did not succeed, or the
  *                       ledger has been used otherwise since)
- * OUT OF SCOPE: L1 transactions that create accounts or exit, an L1 amount with to_idx == 0 (no receiver), L2 exits, atomic (rqOffset)
- * fields, a resident address index kept across calls, batch (random linear combination) verification of signatures, more than one
- * device per ledger. One thread at a time. */
+ * EXITS. A row with to_idx == 1 is an exit: an L2 exit, or an L1 forceExit. The five apply calls above keep refusing it
+ * with HZ_ERR_ARG; hz_ledger_apply_batch_exits accepts it. The sender side of an exit is exactly that of a transfer (L2: reasons 1, 2, 3
+ * and 12, the fee to its slot, nonce + 1; L1: the nullifiers above, no fee, no nonce), and the state root after the row is the root after
+ * the sender's update. Processor 2 works on the batch's EXIT TREE, an hz_smt the ledger owns, empty at the start of every batch, at key
+ * from_idx:
+ *   amount == 0 (the float40's mantissa is zero): a NOP, no exit-tree operation; the leaf-2 rows are as in a transfer (tokenID2 = token_id
+ *                       for L2, all zero for L1), newExit = 0
+ *   amount != 0, key not yet in the exit tree: INSERT, newExit = 1. The new leaf is {tokenID, sign, ay, ethAddr} of the SENDER's leaf, nonce
+ *                       0, balance eff3 -- the amount for L2, eff3 above for L1 (0 when the amount is nullified; the insert still
+ *                       happens). All six leaf-2 rows are zero; isOld0_2, oldKey2, oldValue2 are the tree's, as hz_smt_apply reports them
+ *                       (oldKey2 = oldValue2 = 0 where isOld0_2 = 1)
+ *   amount != 0, key present: UPDATE, newExit = 0. The leaf-2 rows are the exit leaf before; balance += eff3; isOld0_2 = oldKey2 = oldValue2 = 0
+ * The receiver's token of an exit is the sender's: null_amount = null_eth || (null_tok1 && amount != 0) for a forceExit, and reason 4 cannot
+ * fire on an L2 exit. Reason 5 holds for the exit leaf too: a new exit balance >= 2^192 refuses the batch at that row. siblings2 of an
+ * exit row are the exit tree's, zero-padded to n_sib. txCompressedData, txCompressedDataV2 and the signed message carry to_idx = 1.
+ *   hz_ledger_apply_batch_exits  hz_ledger_apply_batch with to_idx == 1 accepted in L1 and L2 rows, plus exit_out (may be NULL; nullable host
+ *                       pointers): new_exit, is_old0_2, old_key2, old_value2 and exit_root_after as [n_l1 + m] 32-byte elements,
+ *                       new_exit_root [1]. exit_root_after is the exit root after every row -- 0 until the first insert, unchanged
+ *                       across rows without an exit operation; its first rows - 1 entries are imExitRoot. With no exit row every
+ *                       output of hz_ledger_apply_batch is equal byte for byte and the exit arrays are zero. Exit operations count
+ *                       towards the 65536 updates. HZ_ERR_ARG beyond hz_ledger_apply_batch's: an exit leaf that would lie at depth
+ *                       >= n_sib (found by the planner, before anything is launched)
+ *   hz_ledger_exit_outputs_dev  exit_out's arrays as DEVICE pointers of the last successful hz_ledger_apply_batch_exits, valid until the
+ *                       ledger's next call; fit for hz_set_input_dev
+ *   hz_ledger_exit_tree the exit tree, borrowed: hz_smt_proofs / _root / _size work on it (hz_smt_apply / _reset on it would leave the
+ *                       exit leaves behind: do not)
+ *   hz_ledger_exit_accounts  the fields (e0, balance, ay, ethAddr) of n exit leaves by key: fields_out [n][4][32]; a key that is not in
+ *                       the exit tree is HZ_ERR_ARG
+ *   hz_ledger_plan_exits  DIAGNOSTIC, no device: the plan of such a batch. An exit row makes its sender event and NO receiver event
+ *                       (ev_receiver -1; last_event counts state events only); the exit operations are a second ordered list: per row
+ *                       ev_exit_out (operation or -1) and last_exit_out (the last operation of rows 0 .. i, -1 none yet), per operation
+ *                       (room for n_l1 + m) exit_row_out, exit_key_out, exit_prev_out (the previous operation on the same key, -1: the
+ *                       operation is the insert), exit_perm_out (the operations grouped by key, groups by first appearance), and the
+ *                       exit tree's own plan: exit_insert_out, exit_is_old0_out, exit_old_key_out. Every output may be NULL
+ *   hz_ledger_exit_ms   device time of the exit kernels plus the exit tree's update of the last hz_ledger_apply_batch_exits (0: no exit
+ *                       operation, or the call did not succeed). The update runs on the exit tree's own stream beside the state
+ *                       tree's: the time is not a part of hz_ledger_device_ms that could be subtracted
+ * LIFETIME. The exit tree and the exit leaves are those of the last successful call that applied a batch: every apply call (all six)
+ * starts by emptying them, so after a refused call, and after a call of the other five, the tree is empty. A refused call leaves root,
+ * planes and state tree untouched, as above.
+ * OUT OF SCOPE: L1 transactions that create accounts or exit through a call other than hz_ledger_apply_batch_exits, an L1 amount with
+ * to_idx == 0 (no receiver), exit trees of earlier batches kept resident, atomic (rqOffset) fields, a resident address index kept across
+ * calls, batch (random linear combination) verification of signatures, more than one device per ledger. One thread at a time. */
 typedef struct hz_ledger hz_ledger;
 typedef struct {
     uint64_t from_idx, to_idx, amount_f /* float40 */, nonce;
@@ -604,6 +644,26 @@ hz_status hz_ledger_plan_batch(size_t n_l1, const hz_l1tx* l1, size_t m, const h
                                int32_t* l1_slot_sender_out, int32_t* l1_slot_receiver_out, size_t* n_slots_out, uint64_t* slot_account_out);
 hz_status hz_ledger_l1_flags_dev(hz_ledger* l, uint8_t** dev);
 double hz_ledger_l1_ms(const hz_ledger* l);
+#define HZ_LEDGER_EXIT_ARRAYS 6
+typedef struct {
+    uint8_t *new_exit, *is_old0_2, *old_key2, *old_value2; /* [n_l1 + m]: zero for a row without an exit operation */
+    uint8_t* exit_root_after;                              /* [n_l1 + m]: its first n_l1 + m - 1 rows are imExitRoot */
+    uint8_t* new_exit_root;                                /* [1] */
+} hz_ledger_exit_out;
+hz_status hz_ledger_apply_batch_exits(hz_ledger* l, size_t n_l1, const hz_l1tx* l1, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, uint32_t flags,
+                                      const uint64_t* aux_to_idx /* [m] or NULL */, uint32_t chain_id, uint32_t current_num_batch, size_t F,
+                                      const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs, size_t n_sib, const hz_ledger_out* out,
+                                      const hz_ledger_sig_out* sig_out, uint8_t* aux_to_idx_out, uint8_t* l1_flags_out,
+                                      const hz_ledger_exit_out* exit_out /* or NULL */);
+hz_status hz_ledger_exit_outputs_dev(hz_ledger* l, hz_ledger_exit_out* dev);
+hz_smt* hz_ledger_exit_tree(hz_ledger* l);
+hz_status hz_ledger_exit_accounts(hz_ledger* l, size_t n, const uint64_t* key, uint8_t* fields_out /* [n][4][32] */);
+hz_status hz_ledger_plan_exits(size_t n_l1, const hz_l1tx* l1, size_t m, const hz_l2tx* txs, size_t F, const uint32_t* fee_plan_tokens,
+                               const uint64_t* fee_idxs, int32_t k, uint64_t first_idx, size_t n_sib, int32_t* ev_sender_out, int32_t* ev_receiver_out,
+                               int32_t* last_event_out, size_t* n_events_out, uint64_t* ev_account_out, int32_t* ev_exit_out, int32_t* last_exit_out,
+                               size_t* n_exits_out, uint32_t* exit_row_out, uint64_t* exit_key_out, int32_t* exit_prev_out, uint32_t* exit_perm_out,
+                               uint8_t* exit_insert_out, uint8_t* exit_is_old0_out, uint64_t* exit_old_key_out);
+double hz_ledger_exit_ms(const hz_ledger* l);
 
 /* Poseidon batch: n independent permutations of width t = n_inputs + 1 (2..7). ----------------
  * `in`  : [n][t-1] canonical elements; `out`: [n] digests (state[0] after the last round).
