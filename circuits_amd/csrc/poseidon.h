@@ -4,24 +4,36 @@
 // EdDSAPoseidonVerifier n=5). x^5 S-box, R_F = 8, R_P(t) = {56,57,56,60,60,63}[t-2],
 // state[0] = 0 (capacity first), state[1..] = inputs, out = state[0] after the last Mix.
 //
-// One permutation per lane. The partial rounds are evaluated in the sparse form derived in
-// tools/poseidon_sparse.py: only lane 0 receives a constant and passes the S-box, lanes 1..T-1 are
-// updated with one product each, and lane 0's S-box inputs and outputs -- the only partial-round
-// values the witness holds -- are bit-identical to the circuit's dense evaluation (2T-1 constant
-// products per round instead of T^2). The oracle keeps the dense form.
+// One permutation per lane. The partial rounds are evaluated in one of the two forms derived in
+// tools/poseidon_sparse.py, chosen per width by PoseidonCfg<T>::REC:
+//   pair form (REC = false): only lane 0 receives a constant and passes the S-box, lanes 1..T-1 are
+//     updated with one product each and reduced once per pair of rounds: 4T-1 products and T+1
+//     reductions per pair;
+//   linear recurrence (REC = true): between the first and the last partial round lanes 1..T-1 are a
+//     linear system driven by one scalar a round, and by Cayley-Hamilton lane 0's next S-box input is
+//     a fixed combination of its last T-1 inputs and last T S-box outputs plus a per-round constant:
+//     2T-1 products and ONE lazily reduced sum per round (two or three sums for T >= 4, where the row
+//     has more than six terms), lanes 1..T-1 not touched at all. The first T-1 partial rounds run in
+//     the single-round sparse form to fill the window; the lanes come back once, from the window,
+//     through a constant (T-1) x 2(T-1) matrix.
+// In both, lane 0's S-box inputs and outputs -- the only partial-round values the witness holds --
+// are bit-identical to the circuit's dense evaluation (field arithmetic is exact). The oracle keeps
+// the dense form.
 #pragma once
 #include "fr.h"
 
 namespace hz {
 
+// RP: number of partial rounds. REC: partial rounds as a linear recurrence (true) or in the pair form (false); the one switch --
+// tools/gen_constants.py reads it from here and appends the recurrence's constants to the block of a REC width.
 template <int T>
 struct PoseidonCfg;
-template <> struct PoseidonCfg<2> { static constexpr int RP = 56; };
-template <> struct PoseidonCfg<3> { static constexpr int RP = 57; };
-template <> struct PoseidonCfg<4> { static constexpr int RP = 56; };
-template <> struct PoseidonCfg<5> { static constexpr int RP = 60; };
-template <> struct PoseidonCfg<6> { static constexpr int RP = 60; };
-template <> struct PoseidonCfg<7> { static constexpr int RP = 63; };
+template <> struct PoseidonCfg<2> { static constexpr int RP = 56; static constexpr bool REC = false; };
+template <> struct PoseidonCfg<3> { static constexpr int RP = 57; static constexpr bool REC = true; };
+template <> struct PoseidonCfg<4> { static constexpr int RP = 56; static constexpr bool REC = false; };
+template <> struct PoseidonCfg<5> { static constexpr int RP = 60; static constexpr bool REC = false; };
+template <> struct PoseidonCfg<6> { static constexpr int RP = 60; static constexpr bool REC = false; };
+template <> struct PoseidonCfg<7> { static constexpr int RP = 63; static constexpr bool REC = false; };
 
 template <int T> constexpr int poseidon_rounds() { return 8 + PoseidonCfg<T>::RP; }
 template <int T> constexpr int poseidon_nsbox() { return 8 * T + PoseidonCfg<T>::RP; }
@@ -38,6 +50,13 @@ template <int T> constexpr int poseidon_nsbox() { return 8 * T + PoseidonCfg<T>:
 //   CF     T-1       lanes 1.. of the full round that follows (c*R^2, pushed constants folded in)
 //   TAIL   3T        Ark constants of the last three full rounds (c*R^2)
 //   M      T*T       MDS matrix, row-major (Montgomery form)
+// A REC width (n = T-1) has, appended to the block (PART, DENSE and CF stay: the pair form of the width still evaluates from it):
+//   ENTRY  partial rounds 0..n-1, 2T Fr each: row[T], eNext, col[T-1] (the last round has no col: its lanes are not used)
+//   REC    2T-1      the recurrence's row over the window, oldest first: gamma_{n+1}..gamma_1 (on the S-box outputs
+//                    y_{k-n-1}..y_{k-1}), alpha_n..alpha_1 (on the S-box inputs x_{k-n}..x_{k-1}); Montgomery form
+//   E      RP-n      e_k for k = T..RP as c*R^2 (e_RP belongs to lane 0 of the full round that follows)
+//   EXIT   2(T-1)^2  row i over (y_{RP-n}..y_{RP-1}, x_{RP-n+1}..x_RP) yields lane 1+i of the full round that follows
+//   CX     T-1       the exit's constants (c*R^2)
 template <int T> constexpr int poseidon_k_e0() { return 4 * T; }
 template <int T> constexpr int poseidon_k_part() { return 4 * T + 1; }
 template <int T> constexpr int poseidon_k_dense() {
@@ -46,8 +65,13 @@ template <int T> constexpr int poseidon_k_dense() {
 template <int T> constexpr int poseidon_k_cf() { return poseidon_k_dense<T>() + (T - 1) * (T - 1); }
 template <int T> constexpr int poseidon_k_tail() { return poseidon_k_cf<T>() + (T - 1); }
 template <int T> constexpr int poseidon_k_m() { return poseidon_k_tail<T>() + 3 * T; }
+template <int T> constexpr int poseidon_k_entry() { return poseidon_k_m<T>() + T * T; }
+template <int T> constexpr int poseidon_k_rec() { return poseidon_k_entry<T>() + (T - 1) * 2 * T - (T - 1); }
+template <int T> constexpr int poseidon_k_e() { return poseidon_k_rec<T>() + 2 * T - 1; }
+template <int T> constexpr int poseidon_k_exit() { return poseidon_k_e<T>() + PoseidonCfg<T>::RP - (T - 1); }
+template <int T> constexpr int poseidon_k_cx() { return poseidon_k_exit<T>() + 2 * (T - 1) * (T - 1); }
 // number of Fr the constant block of width T occupies
-template <int T> constexpr int poseidon_const_frs() { return poseidon_k_m<T>() + T * T; }
+template <int T> constexpr int poseidon_const_frs() { return PoseidonCfg<T>::REC ? poseidon_k_cx<T>() + T - 1 : poseidon_k_entry<T>(); }
 
 HZ_HD constexpr int poseidon_nsbox_rt(int t) {
     return 8 * t + (t == 2 ? 56 : t == 3 ? 57 : t == 4 ? 56 : t == 5 ? 60 : t == 6 ? 60 : 63);
@@ -87,13 +111,17 @@ HZ_HD Fr poseidon_sbox(const Fr& x, int k, Sink& sink) {
 }
 
 // one row of a constant matrix times the state, plus an optional c*R^2 addend, one reduction
-// (rows of more than 6 terms are split in two)
+// (rows of more than 6 terms are split in two, of more than 8 in a head of six and the rest).
+// row[i] < p (constants), st[i] normalised and below 2^257, addend < p; the result is normalised and below 2p: a single fr_dot of
+// operands below 2p returns less than 1.08 p, and fr_add takes two such sums (or one and an fr_add's result: below 4p together).
 template <int N>
 HZ_HD Fr poseidon_row(const Fr* row, const Fr* st, const Fr* addend) {
     if constexpr (N <= 6) {
         return fr_dot<N>(row, st, addend);
-    } else {
+    } else if constexpr (N <= 8) {
         return fr_add(fr_dot<4>(row, st, addend), fr_dot<N - 4>(row + 4, st + 4));   // N <= 8
+    } else {
+        return fr_add(fr_dot<6>(row, st, addend), poseidon_row<N - 6>(row + 6, st + 6, nullptr));   // N <= 13
     }
 }
 
@@ -112,6 +140,14 @@ HZ_HD void poseidon_rotate_in(Fr (&a)[T], const Fr& v) {
 #pragma unroll
     for (int i = 0; i + 1 < T; i++) a[i] = a[i + 1];
     a[T - 1] = v;
+}
+// the same on the places FROM .. FROM+LEN-1 of a longer array: the window of the recurrence holds two such queues
+template <int FROM, int LEN, int N>
+HZ_HD void poseidon_window_in(Fr (&a)[N], const Fr& v) {
+    static_assert(FROM + LEN <= N, "queue inside the array");
+#pragma unroll
+    for (int i = FROM; i + 1 < FROM + LEN; i++) a[i] = a[i + 1];
+    a[FROM + LEN - 1] = v;
 }
 template <int T, int NC>
 HZ_HD void poseidon_mix_ark(Fr (&st)[T], const Fr* M, const Fr* Cn) {
@@ -135,6 +171,58 @@ template <int T, class Sink>
 HZ_HD void poseidon_sbox_layer(Fr (&st)[T], int k, Sink& sink) {
 #pragma unroll 1
     for (int j = 0; j < T; j++) poseidon_rotate_in<T>(st, poseidon_sbox(st[0], k + j, sink));
+}
+
+// The partial rounds of a REC width: st holds lane 0's first S-box input and lanes 1.. on entry, the state of the full round that
+// follows (constants added) on exit; k counts the S-boxes.
+template <int T, class Sink>
+HZ_HD void poseidon_partial_rec(Fr (&st)[T], const Fr* K, int& k, Sink& sink) {
+    constexpr int RP = PoseidonCfg<T>::RP;
+    // Partial rounds as a linear recurrence. w = the window, oldest first: the S-box outputs y_{k-n}..y_k (n + 1 places), then the
+    // S-box inputs x_{k-n+1}..x_k (n places), n = T-1. Both queues rotate (constant indices only: the window stays in registers).
+    // Ranges: every x is a poseidon_row (below 2p), every y an S-box output (below 1.03 p, canonical for a kCanon sink); all of them
+    // only feed products and rows, which take operands below 2^257. Lanes 1.. gain at most 1.01 p in each of the n-1 entry rounds
+    // that update them (fr_muladd: addend below 8p; 2p + 5 x 1.01 p at T = 7) and are dropped after the entry.
+    constexpr int N = T - 1;
+    Fr w[2 * N + 1];
+#pragma unroll
+    for (int i = 0; i < 2 * N + 1; i++) w[i] = st[0];   // (places the entry does not fill are rotated out before a row reads them)
+    const Fr* S = K + poseidon_k_entry<T>();
+#pragma unroll 1
+    for (int r = 0; r < N; r++) {   // entry: y_0..y_{n-1}, x_1..x_n in the single-round sparse form
+        st[0] = poseidon_sbox(st[0], k, sink);
+        k += 1;
+        poseidon_window_in<0, N + 1>(w, st[0]);
+        const Fr x = poseidon_row<T>(S, st, S + T);
+        poseidon_window_in<N + 1, N>(w, x);
+        if (r + 1 < N) {
+#pragma unroll
+            for (int j = 1; j < T; j++) st[j] = fr_muladd(S[T + j], st[0], st[j]);
+        }
+        st[0] = x;
+        S += 2 * T;
+    }
+    const Fr* E = K + poseidon_k_e<T>();
+#pragma unroll 1
+    for (int r = N; r < RP; r++) {   // y_r = S-box(x_r), then x_{r+1}: one row over the whole window
+        poseidon_window_in<0, N + 1>(w, poseidon_sbox(w[2 * N], k, sink));
+        k += 1;
+        poseidon_window_in<N + 1, N>(w, poseidon_row<2 * N + 1>(K + poseidon_k_rec<T>(), w, E));
+        E += 1;
+    }
+    {
+        // exit: lane 0 is x_RP; lanes 1.. of the full round that follows from the last n outputs and inputs (w without its oldest
+        // place), constants included (rolled over the rows, rotating like the mix)
+        st[0] = w[2 * N];
+        Fr o[N];
+#pragma unroll
+        for (int i = 0; i < N; i++) o[i] = st[i + 1];
+#pragma unroll 1
+        for (int i = 0; i < N; i++)
+            poseidon_rotate_in<N>(o, poseidon_row<2 * N>(K + poseidon_k_exit<T>() + i * 2 * N, w + 1, K + poseidon_k_cx<T>() + i));
+#pragma unroll
+        for (int i = 1; i < T; i++) st[i] = o[i - 1];
+    }
 }
 
 // Full permutation; `in` are the T-1 inputs (Montgomery), K the constant block (layout above) in the form the sink asks for:
@@ -161,53 +249,57 @@ HZ_HD Fr poseidon_hash(const Fr* in, const Fr* K, Sink& sink) {
     poseidon_sbox_layer<T>(st, k, sink);
     k += T;
     poseidon_mix_ark<T, 1>(st, M, K + poseidon_k_e0<T>());
-    // Partial rounds, sparse form: lane 0 <- row . (y, lanes) + next constant ; lane i <- lane i + col[i] * y. Two rounds
-    // per iteration so that lanes 1.. are reduced once per pair: round b's row is applied to the lanes as they were before
-    // round a (its constants absorb colA through beta * yA), then lane i <- lane i + colA[i]*yA + colB[i]*yB in one
-    // reduction. Lanes 1.. grow by at most ~1.02 p per pair (two products of values below p, the reduction's multiple of p) and are
-    // brought back below 4p after every THIRD pair: fr_muladd2 takes an addend below 8p, and 4p + 3 x 1.02 p stays under it (the
-    // conditional subtraction is 45 instructions per lane: after every pair it was 2 % of a permutation).
-    const Fr* S = K + poseidon_k_part<T>();
-    int lazy = 0;
+    if constexpr (PoseidonCfg<T>::REC) {
+        poseidon_partial_rec<T>(st, K, k, sink);
+    } else {
+        // Partial rounds, pair form: lane 0 <- row . (y, lanes) + next constant ; lane i <- lane i + col[i] * y. Two rounds
+        // per iteration so that lanes 1.. are reduced once per pair: round b's row is applied to the lanes as they were before
+        // round a (its constants absorb colA through beta * yA), then lane i <- lane i + colA[i]*yA + colB[i]*yB in one
+        // reduction. Lanes 1.. grow by at most ~1.02 p per pair (two products of values below p, the reduction's multiple of p) and are
+        // brought back below 4p after every THIRD pair: fr_muladd2 takes an addend below 8p, and 4p + 3 x 1.02 p stays under it (the
+        // conditional subtraction is 45 instructions per lane: after every pair it was 2 % of a permutation).
+        const Fr* S = K + poseidon_k_part<T>();
+        int lazy = 0;
 #pragma unroll 1
-    for (int r = 0; r + 1 < RP; r += 2) {
-        Fr v[T + 1];
-        v[0] = poseidon_sbox(st[0], k, sink);
+        for (int r = 0; r + 1 < RP; r += 2) {
+            Fr v[T + 1];
+            v[0] = poseidon_sbox(st[0], k, sink);
 #pragma unroll
-        for (int j = 1; j < T; j++) v[j] = st[j];
-        const Fr sa = poseidon_row<T>(S, v, S + T);
-        v[T] = v[0];                                   // yA, multiplied by beta
-        v[0] = poseidon_sbox(sa, k + 1, sink);         // yB
-        k += 2;
-        st[0] = poseidon_row<T + 1>(S + T + 1, v, S + 2 * T + 2);
-        const Fr* CA = S + 2 * T + 3;
+            for (int j = 1; j < T; j++) v[j] = st[j];
+            const Fr sa = poseidon_row<T>(S, v, S + T);
+            v[T] = v[0];                                   // yA, multiplied by beta
+            v[0] = poseidon_sbox(sa, k + 1, sink);         // yB
+            k += 2;
+            st[0] = poseidon_row<T + 1>(S + T + 1, v, S + 2 * T + 2);
+            const Fr* CA = S + 2 * T + 3;
 #pragma unroll
-        for (int j = 1; j < T; j++) st[j] = fr_muladd2(CA[j - 1], v[T], CA[T - 1 + j - 1], v[0], st[j]);
-        if (++lazy == 3) {   // (a branch around the subtraction only: two copies of the products cost the batch kernel twice its registers)
-            lazy = 0;
+            for (int j = 1; j < T; j++) st[j] = fr_muladd2(CA[j - 1], v[T], CA[T - 1 + j - 1], v[0], st[j]);
+            if (++lazy == 3) {   // (a branch around the subtraction only: two copies of the products cost the batch kernel twice its registers)
+                lazy = 0;
 #pragma unroll
-            for (int j = 1; j < T; j++) st[j] = fr_cond_sub_4p(st[j]);
+                for (int j = 1; j < T; j++) st[j] = fr_cond_sub_4p(st[j]);
+            }
+            S += 4 * T + 1;
         }
-        S += 4 * T + 1;
-    }
-    if constexpr (RP % 2 == 1) {
-        st[0] = poseidon_sbox(st[0], k, sink);
-        k += 1;
-        const Fr s0 = poseidon_row<T>(S, st, S + 2 * T - 1);
+        if constexpr (RP % 2 == 1) {
+            st[0] = poseidon_sbox(st[0], k, sink);
+            k += 1;
+            const Fr s0 = poseidon_row<T>(S, st, S + 2 * T - 1);
 #pragma unroll
-        for (int j = 1; j < T; j++) st[j] = fr_muladd(S[T + j - 1], st[0], st[j]);
-        st[0] = s0;
-    }
-    {
-        // pending lanes-1.. matrix, with the constants of the following full round (rolled over the rows, rotating like the mix)
-        Fr o[T - 1];
+            for (int j = 1; j < T; j++) st[j] = fr_muladd(S[T + j - 1], st[0], st[j]);
+            st[0] = s0;
+        }
+        {
+            // pending lanes-1.. matrix, with the constants of the following full round (rolled over the rows, rotating like the mix)
+            Fr o[T - 1];
 #pragma unroll
-        for (int i = 0; i + 1 < T; i++) o[i] = st[i + 1];
+            for (int i = 0; i + 1 < T; i++) o[i] = st[i + 1];
 #pragma unroll 1
-        for (int i = 0; i + 1 < T; i++)
-            poseidon_rotate_in<T - 1>(o, poseidon_row<T - 1>(K + poseidon_k_dense<T>() + i * (T - 1), st + 1, K + poseidon_k_cf<T>() + i));
+            for (int i = 0; i + 1 < T; i++)
+                poseidon_rotate_in<T - 1>(o, poseidon_row<T - 1>(K + poseidon_k_dense<T>() + i * (T - 1), st + 1, K + poseidon_k_cf<T>() + i));
 #pragma unroll
-        for (int i = 1; i < T; i++) st[i] = o[i - 1];
+            for (int i = 1; i < T; i++) st[i] = o[i - 1];
+        }
     }
 #pragma unroll 1
     for (int r = 0; r < 3; r++) {

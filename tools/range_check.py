@@ -237,17 +237,22 @@ def poseidon_sbox(x, witness):
 
 def poseidon_row(row, st, addend):
     src("circuits_amd/csrc/poseidon.h", "        return fr_add(fr_dot<4>(row, st, addend), fr_dot<N - 4>(row + 4, st + 4));   // N <= 8")
+    src("circuits_amd/csrc/poseidon.h", "        return fr_add(fr_dot<6>(row, st, addend), poseidon_row<N - 6>(row + 6, st + 6, nullptr));   // N <= 13")
     n = len(st)
+    need(n <= 13 and len(row) >= n, "poseidon_row<%d>: at most 13 terms" % n)
     if n <= 6:
         return fr_dot(row[:n], st, addend, "poseidon_row<%d>" % n)
-    return fr_add(fr_dot(row[:4], st[:4], addend, "poseidon_row lo"), fr_dot(row[4:n], st[4:], None, "poseidon_row hi"))
+    if n <= 8:
+        return fr_add(fr_dot(row[:4], st[:4], addend, "poseidon_row lo"), fr_dot(row[4:n], st[4:], None, "poseidon_row hi"))
+    return fr_add(fr_dot(row[:6], st[:6], addend, "poseidon_row head"), poseidon_row(row[6:n], st[6:], None))
 
 
 def poseidon_hash(T, witness, in_ub=2 * P, report=None, trim_every=3):
+    """poseidon_hash<T> with the partial rounds in the pair form (PoseidonCfg<T>::REC = false); poseidon_hash_rec is the other form"""
     from gen_constants import poseidon_block
     from poseidon_params import N_ROUNDS_P
     RP = N_ROUNDS_P[T - 2]
-    K = [const(x, "K[%d]" % i) for i, x in enumerate(poseidon_block(T, witness))]
+    K = [const(x, "K[%d]" % i) for i, x in enumerate(poseidon_block(T, witness, rec=False))]
     e0 = 4 * T
     part = 4 * T + 1
     dense = part + (RP // 2) * (4 * T + 1) + (RP % 2) * 2 * T
@@ -303,6 +308,68 @@ def poseidon_hash(T, witness, in_ub=2 * P, report=None, trim_every=3):
         report.append("poseidon_hash<%d> %s: lanes beside the S-box lane peak at %.3f p (addend limit 8 p), digest below %.3f p" % (
             T, "witness" if witness else "digest ", worst_lane / P, out.ub / P))
     need(out.ub <= 2 * P, "poseidon_hash<%d>: digest %r not below 2p" % (T, out))
+    return out
+
+
+def poseidon_hash_rec(T, witness, in_ub=2 * P, report=None):
+    """poseidon_hash<T> with the partial rounds as a linear recurrence (PoseidonCfg<T>::REC = true): the window of S-box outputs and
+    inputs only feeds rows, the lanes beside the S-box lane live through the T-2 updates of the entry alone"""
+    from gen_constants import poseidon_block
+    from poseidon_params import N_ROUNDS_P
+    RP = N_ROUNDS_P[T - 2]
+    N = T - 1
+    K = [const(x, "K[%d]" % i) for i, x in enumerate(poseidon_block(T, witness, rec=True))]
+    e0 = 4 * T
+    tail = 4 * T + 1 + (RP // 2) * (4 * T + 1) + (RP % 2) * 2 * T + N * N + N
+    mo = tail + 3 * T
+    part = mo + T * T          # the entry rounds: the first of the appended constants
+    rec = part + N * 2 * T - N
+    eo = rec + 2 * T - 1
+    dense = eo + RP - N
+    cf = dense + 2 * N * N
+    need(len(K) == cf + N, "constant block layout (recurrence)")
+    M = K[mo:mo + T * T]
+    st = [K[0]] + [fr_add(V(in_ub, name="input"), K[j]) for j in range(1, T)]
+
+    def sbox_layer(st):
+        return [poseidon_sbox(x, witness) for x in st]
+
+    def mix_ark(st, Cn, nc):
+        return [poseidon_row(M[i * T:(i + 1) * T], st, Cn[i] if i < nc else None) for i in range(T)]
+    for r in range(3):
+        st = mix_ark(sbox_layer(st), K[T * (r + 1):T * (r + 2)], T)
+    st = mix_ark(sbox_layer(st), K[e0:e0 + 1], 1)
+    src("circuits_amd/csrc/poseidon.h", "            for (int j = 1; j < T; j++) st[j] = fr_muladd(S[T + j], st[0], st[j]);")
+    src("circuits_amd/csrc/poseidon.h", "        poseidon_window_in<N + 1, N>(w, poseidon_row<2 * N + 1>(K + poseidon_k_rec<T>(), w, E));")
+    w = [st[0]] * (2 * N + 1)
+    S = part
+    worst_lane = max(x.ub for x in st[1:])
+    for r in range(N):
+        st = [poseidon_sbox(st[0], witness)] + st[1:]
+        w = w[1:N + 1] + [st[0]] + w[N + 1:]
+        x = poseidon_row(K[S:S + T], st, K[S + T])
+        w = w[:N + 1] + w[N + 2:] + [x]
+        if r + 1 < N:
+            st = [st[0]] + [fr_muladd(K[S + T + j], st[0], st[j], "entry lane") for j in range(1, T)]
+            worst_lane = max([worst_lane] + [x.ub for x in st[1:]])
+        st = [x] + st[1:]
+        S += 2 * T
+    worst_x = 0
+    for r in range(N, RP):
+        w = w[1:N + 1] + [poseidon_sbox(w[2 * N], witness)] + w[N + 1:]
+        x = poseidon_row(K[rec:rec + 2 * N + 1], w, K[eo + r - N])
+        worst_x = max(worst_x, x.ub)
+        w = w[:N + 1] + w[N + 2:] + [x]
+    src("circuits_amd/csrc/poseidon.h", "poseidon_row<2 * N>(K + poseidon_k_exit<T>() + i * 2 * N, w + 1, K + poseidon_k_cx<T>() + i));")
+    st = [w[2 * N]] + [poseidon_row(K[dense + i * 2 * N:dense + (i + 1) * 2 * N], w[1:], K[cf + i]) for i in range(N)]
+    for r in range(3):
+        st = mix_ark(sbox_layer(st), K[tail + T * r:tail + T * (r + 1)], T)
+    st = sbox_layer(st)
+    out = poseidon_row(M[:T], st, None)
+    if report is not None:
+        report.append("poseidon_hash<%d> %s, recurrence: entry lanes below %.3f p (addend limit 8 p), S-box inputs below %.3f p, digest below %.3f p" % (
+            T, "witness" if witness else "digest ", worst_lane / P, worst_x / P, out.ub / P))
+    need(out.ub <= 2 * P, "poseidon_hash<%d> (recurrence): digest %r not below 2p" % (T, out))
     return out
 
 
@@ -437,10 +504,13 @@ def check_sources():
     return missing
 
 
-def run(report=None):
+def run(report=None, report_rec=None):
+    """both forms of the partial rounds for every width: poseidon.h holds both and switches per width (`report_rec`: the lines of
+    the recurrence form, kept apart from the pair form's)"""
     for T in range(2, 8):
         for witness in (False, True):
             poseidon_hash(T, witness, report=report)
+            poseidon_hash_rec(T, witness, report=report_rec)
     for G in (1, 2, 3, 4):
         seg_any_step(G, report)
     for G in (1, 8):
@@ -450,9 +520,9 @@ def run(report=None):
 
 
 if __name__ == "__main__":
-    rep = []
-    missing = run(rep)
-    print("\n".join(rep))
+    rep, rep_rec = [], []
+    missing = run(rep, rep_rec)
+    print("\n".join(rep + rep_rec))
     for path, text in missing:
         print("STALE TRANSCRIPTION: %s no longer contains: %s" % (path, text))
     print("range check:", "FAILED (source drifted)" if missing else "all bounds hold")
