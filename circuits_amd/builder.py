@@ -288,6 +288,12 @@ class DenseState:
         lg.load(*self.leaf_fields())
         return lg
 
+    def to_growing_ledger(self, lib, capacity, n_sib_max=33, device=0):
+        """this state as a capi.GrowingLedger with room for `capacity` accounts: tree and leaf fields resident, L1 rows may create accounts"""
+        lg = lib.ledger_growing(capacity, first_idx=self.first_idx, n_sib_max=n_sib_max, device=device)
+        lg.load_accounts(*self.leaf_fields())
+        return lg
+
     @staticmethod
     def from_device(state, like):
         """the consolidated arrays of a capi.State as a DenseState (for hzb_db_set_base, or save). `like`: the DenseState the device
@@ -1045,8 +1051,24 @@ def ledger_exit_batch_inputs(ledger, db_like, l1_txs, l2_txs, n_tx, n_levels, ma
     return _ledger_batch_inputs(ledger, db_like, l1_txs, l2_txs, n_tx, n_levels, max_l1, max_fee, fee_tokens, fee_idxs, chain_id, host_outputs, verify, True)
 
 
-def _ledger_batch_inputs(ledger, db_like, l1_txs, l2_txs, n_tx, n_levels, max_l1, max_fee, fee_tokens, fee_idxs, chain_id, host_outputs, verify, exits):
-    """ledger_batch_inputs (exits=False) and ledger_exit_batch_inputs (exits=True) -> (inputs, device signals, nullified, new exit root)"""
+# RollupMain's create-side inputs, and where hz_ledger_apply_batch_creates leaves each (array, first row, rows)
+def create_signals(n_tx):
+    return {"auxFromIdx": ("aux_from_idx", 0, n_tx), "isOld0_1": ("is_old0_1", 0, n_tx), "oldKey1": ("old_key1", 0, n_tx), "oldValue1": ("old_value1", 0, n_tx),
+            "imOutIdx": ("out_idx_after", 0, n_tx - 1)}
+
+
+def ledger_create_batch_inputs(ledger, db_like, l1_txs, l2_txs, n_tx, n_levels, max_l1, max_fee, fee_tokens, fee_idxs, chain_id, host_outputs=True, verify=False):
+    """ledger_exit_batch_inputs over L1 rows that may create accounts (fromIdx == 0, the key in fromBjjCompressed), through
+    capi.GrowingLedger.apply_batch_creates: newAccount is 1 on those rows, and auxFromIdx, isOld0_1, oldKey1, oldValue1 and imOutIdx are
+    the ledger's (device signals too with host_outputs=False) instead of zeros and the constant last idx. db_like.last_idx is advanced.
+    -> (inputs, device signals or None, isAmountNullified per row, the new exit root, the new last idx): the last two feed
+    hash_global_inputs."""
+    return _ledger_batch_inputs(ledger, db_like, l1_txs, l2_txs, n_tx, n_levels, max_l1, max_fee, fee_tokens, fee_idxs, chain_id, host_outputs, verify, True, True)
+
+
+def _ledger_batch_inputs(ledger, db_like, l1_txs, l2_txs, n_tx, n_levels, max_l1, max_fee, fee_tokens, fee_idxs, chain_id, host_outputs, verify, exits, creates=False):
+    """ledger_batch_inputs (exits=False), ledger_exit_batch_inputs (exits=True) and ledger_create_batch_inputs (creates=True)
+    -> (inputs, device signals, nullified, new exit root[, new last idx])"""
     if len(l1_txs) > max_l1:
         raise ValueError("too many L1 txs")
     if len(l1_txs) + len(l2_txs) > n_tx:
@@ -1063,7 +1085,7 @@ def _ledger_batch_inputs(ledger, db_like, l1_txs, l2_txs, n_tx, n_levels, max_l1
         for t in padded:
             if t.get("fromIdx", 0) and "signer" in t:
                 t.update(t["signer"].sign_msg(build_hash_sig(t, chain_id)))
-    apply = ledger.apply_batch_exits if exits else ledger.apply_batch
+    apply = ledger.apply_batch_creates if creates else ledger.apply_batch_exits if exits else ledger.apply_batch
     out = apply(l1_txs, padded, plan, idxs, chain_id, db_like.num_batch + 1, n_sib=n_levels + 1, verify=verify)
     flags = [int(x) for x in out["l1_flags"]]
     inp = {"oldLastIdx": db_like.last_idx, "globalChainID": chain_id, "currentNumBatch": db_like.num_batch + 1, "feePlanTokens": plan, "feeIdxs": idxs}
@@ -1077,7 +1099,7 @@ def _ledger_batch_inputs(ledger, db_like, l1_txs, l2_txs, n_tx, n_levels, max_l1
         bjj = t.get("fromBjjCompressed", 0)
         vals = {"txCompressedData": CONST_SIG | (chain_id << 32) | (t.get("fromIdx", 0) << 48) | (t.get("toIdx", 0) << 96) | (t.get("tokenID", 0) << 144),
                 "amountF": t["amountF"], "fromIdx": t.get("fromIdx", 0), "toIdx": t.get("toIdx", 0), "toBjjAy": t.get("toBjjAy", 0), "toEthAddr": t.get("toEthAddr", 0),
-                "maxNumBatch": t.get("maxNumBatch", 0), "onChain": 1, "loadAmountF": t.get("loadAmountF", 0), "fromEthAddr": t.get("fromEthAddr", 0),
+                "maxNumBatch": t.get("maxNumBatch", 0), "onChain": 1, "newAccount": 1 if creates and not t.get("fromIdx", 0) else 0, "loadAmountF": t.get("loadAmountF", 0), "fromEthAddr": t.get("fromEthAddr", 0),
                 "fromBjjCompressed": [(bjj >> k) & 1 for k in range(256)]}
         for k in names:
             inp[k].append(vals.get(k, 0))
@@ -1096,6 +1118,10 @@ def _ledger_batch_inputs(ledger, db_like, l1_txs, l2_txs, n_tx, n_levels, max_l1
     nullified = [(f >> 1) & 1 for f in flags] + [0] * (n_tx - n_l1)
     sigs = l2_state_signals(n_tx, max_fee)
     new_exit_root = int.from_bytes(out["new_exit_root"][0].tobytes(), "little") if exits else 0
+    tail = (nullified, new_exit_root)
+    if creates:
+        db_like.last_idx = ledger.last_idx()
+        tail += (db_like.last_idx,)
     if not host_outputs:
         dev = ledger.outputs_dev()
         devsig = {}
@@ -1109,7 +1135,12 @@ def _ledger_batch_inputs(ledger, db_like, l1_txs, l2_txs, n_tx, n_levels, max_l1
             for name, (arr, first, rows) in exit_signals(n_tx).items():
                 del inp[name]
                 devsig[name] = (exit_dev[arr] + first * 32, rows)
-        return inp, devsig, nullified, new_exit_root
+        if creates:
+            create_dev = ledger.create_outputs_dev()
+            for name, (arr, first, rows) in create_signals(n_tx).items():
+                del inp[name]
+                devsig[name] = (create_dev[arr] + first * 32, rows)
+        return (inp, devsig) + tail
 
     def ints(a):
         if a.ndim == 2:
@@ -1122,7 +1153,10 @@ def _ledger_batch_inputs(ledger, db_like, l1_txs, l2_txs, n_tx, n_levels, max_l1
     if exits:
         for name, (arr, first, rows) in exit_signals(n_tx).items():
             inp[name] = ints(out[arr][first:first + rows])
-    return inp, None, nullified, new_exit_root
+    if creates:
+        for name, (arr, first, rows) in create_signals(n_tx).items():
+            inp[name] = ints(out[arr][first:first + rows])
+    return (inp, None) + tail
 
 
 def withdraw_input(batch, idx, n_levels):

@@ -75,6 +75,8 @@ EXPORTS = [
     "hz_ledger_apply_l2_addr", "hz_ledger_resolve_l2", "hz_ledger_aux_to_idx_dev", "hz_ledger_resolve_ms",
     "hz_ledger_apply_batch", "hz_ledger_plan_batch", "hz_ledger_l1_flags_dev", "hz_ledger_l1_ms",
     "hz_ledger_apply_batch_exits", "hz_ledger_exit_outputs_dev", "hz_ledger_exit_tree", "hz_ledger_exit_accounts", "hz_ledger_plan_exits", "hz_ledger_exit_ms",
+    "hz_ledger_create_growing", "hz_ledger_load_accounts", "hz_ledger_size", "hz_ledger_last_idx", "hz_ledger_state_smt", "hz_ledger_apply_batch_creates",
+    "hz_ledger_create_outputs_dev", "hz_ledger_create_ms", "hz_ledger_plan_creates",
 ]
 
 
@@ -126,6 +128,19 @@ L1_NULLIFY_LOAD, L1_AMOUNT_NULLIFIED = 1, 2   # the bits of hz_ledger_apply_batc
 
 # hz_ledger_exit_out's arrays in order: [rows, 32] each, the last [1, 32]
 LEDGER_EXIT_ARRAYS = ("new_exit", "is_old0_2", "old_key2", "old_value2", "exit_root_after", "new_exit_root")
+
+
+# hz_ledger_create_out's arrays in order: [rows, 32] each, the last [1, 32]
+LEDGER_CREATE_ARRAYS = ("aux_from_idx", "is_old0_1", "old_key1", "old_value1", "out_idx_after", "new_last_idx")
+
+
+def from_bjj_array(l1_txs):
+    """fromBjjCompressed of every L1 transaction dictionary as [n_l1, 32] little-endian bytes (missing: 0), or None when no row creates an
+    account (fromIdx == 0)"""
+    import numpy as np
+    if not any(not t.get("fromIdx", 0) for t in l1_txs):
+        return None
+    return np.frombuffer(b"".join((int(t.get("fromBjjCompressed", 0)) % (1 << 256)).to_bytes(32, "little") for t in l1_txs), dtype=np.uint8).reshape(-1, 32).copy()
 
 
 def l1tx_array(txs):
@@ -309,7 +324,17 @@ class Lib:
         c.hz_ledger_exit_accounts.argtypes = [vp, sz, vp, vp]
         c.hz_ledger_plan_exits.argtypes = [sz, vp, sz, vp, sz, vp, vp, ctypes.c_int32, u64, sz, vp, vp, vp, ctypes.POINTER(sz), vp, vp, vp, ctypes.POINTER(sz), vp, vp,
                                            vp, vp, vp, vp, vp]
-        for f in ("hz_ledger_device_ms", "hz_ledger_semantic_ms", "hz_ledger_sig_ms", "hz_ledger_resolve_ms", "hz_ledger_l1_ms", "hz_ledger_exit_ms"):
+        c.hz_ledger_create_growing.argtypes = [ctypes.c_int32, u64, u64, ctypes.c_int32, ctypes.POINTER(vp)]
+        c.hz_ledger_load_accounts.argtypes = [vp, u64, vp, vp, vp, vp]
+        for f in ("hz_ledger_size", "hz_ledger_last_idx"):
+            getattr(c, f).argtypes = [vp]
+            getattr(c, f).restype = u64
+        c.hz_ledger_state_smt.argtypes = [vp]
+        c.hz_ledger_state_smt.restype = vp
+        c.hz_ledger_apply_batch_creates.argtypes = [vp, sz, vp, vp, sz, vp, vp, u32, vp, u32, u32, sz, vp, vp, sz, vp, vp, vp, vp, vp, vp]
+        c.hz_ledger_create_outputs_dev.argtypes = [vp, vp]
+        c.hz_ledger_plan_creates.argtypes = [sz, vp, vp, sz, vp, sz, vp, vp, ctypes.c_int32, u64, u64, u64, vp, vp, ctypes.POINTER(sz)]
+        for f in ("hz_ledger_device_ms", "hz_ledger_semantic_ms", "hz_ledger_sig_ms", "hz_ledger_resolve_ms", "hz_ledger_l1_ms", "hz_ledger_exit_ms", "hz_ledger_create_ms"):
             getattr(c, f).argtypes = [vp]
             getattr(c, f).restype = ctypes.c_double
 
@@ -403,6 +428,27 @@ class Lib:
 
     def ledger(self, k, first_idx=256, device=0):
         return Ledger(self, k, first_idx=first_idx, device=device)
+
+    def ledger_growing(self, capacity, first_idx=256, n_sib_max=33, device=0):
+        """a ledger that takes L1 rows which create accounts: room for `capacity` accounts, the state tree a sparse tree of n_sib_max"""
+        return GrowingLedger(self, capacity, first_idx=first_idx, n_sib_max=n_sib_max, device=device)
+
+    def ledger_plan_creates(self, l1_txs, txs, fee_plan_tokens, fee_idxs, capacity, size, first_idx=256, growing=True):
+        """hz_ledger_plan_creates, a diagnostic: the running index of a batch whose L1 rows may create accounts (fromIdx == 0), and the
+        argument errors of apply_batch_creates but the depth, for a ledger of `capacity` that holds `size` accounts; no device needed.
+        -> {"aux_from_idx": [rows], "out_idx_after": [rows], "n_creates": int}"""
+        import numpy as np
+        l1, arr = l1tx_array(l1_txs), l2tx_array(txs)
+        bjj = from_bjj_array(l1_txs)
+        n_l1, m = len(l1_txs), len(txs)
+        plan = np.ascontiguousarray(fee_plan_tokens, dtype=np.uint32)
+        idxs = np.ascontiguousarray(fee_idxs, dtype=np.uint64)
+        aux, after = np.zeros(max(n_l1 + m, 1), dtype=np.uint64), np.zeros(max(n_l1 + m, 1), dtype=np.uint64)
+        n = ctypes.c_size_t(0)
+        self._check(self.c.hz_ledger_plan_creates(n_l1, ctypes.addressof(l1), bjj.ctypes.data if bjj is not None else None, m, ctypes.addressof(arr), plan.size,
+                                                  plan.ctypes.data, idxs.ctypes.data, 1 if growing else 0, capacity, first_idx, size, aux.ctypes.data,
+                                                  after.ctypes.data, ctypes.byref(n)))
+        return {"aux_from_idx": aux[:n_l1 + m].tolist(), "out_idx_after": after[:n_l1 + m].tolist(), "n_creates": n.value}
 
     def ledger_plan_l2(self, txs, fee_plan_tokens, fee_idxs, k, first_idx=256):
         """hz_ledger_plan_l2, a diagnostic: the host planner alone (integers only, no device needed). txs: transaction dictionaries or an
@@ -1097,6 +1143,71 @@ class Ledger(_Resident):
         out.update(exit_out)
         return out
 
+    def apply_batch_creates(self, l1_txs, txs, fee_plan_tokens, fee_idxs, chain_id, current_num_batch, n_sib=None, verify=False, aux_to_idx=None, outputs=True,
+                            into=None, sigs=None, from_bjj=None):
+        """apply_batch_exits over L1 rows that may create accounts (fromIdx == 0, the key in fromBjjCompressed): a growing ledger makes
+        account last_idx + 1 for each, in row order, and every later row may name it. Returns apply_batch_exits' dictionary plus
+        aux_from_idx, is_old0_1, old_key1, old_value1, out_idx_after ([rows, 32]) and new_last_idx ([1, 32]). from_bjj: the keys as a
+        prebuilt [n_l1, 32] array (from_bjj_array) to go with a prebuilt hz_l1tx array."""
+        import numpy as np
+        n_sib = self.k if n_sib is None else n_sib
+        prebuilt = isinstance(l1_txs, ctypes.Array)
+        l1 = l1_txs if prebuilt else l1tx_array(l1_txs)
+        bjj = from_bjj if from_bjj is not None or prebuilt else from_bjj_array(l1_txs)
+        n_l1 = len(l1_txs)
+        arr, m, plan, idxs, F, out, ptrs = self._l2_args(txs, fee_plan_tokens, fee_idxs, n_sib, outputs, into, n_l1=n_l1)
+        if sigs is None:
+            sigs = l2sig_array(txs)
+        sig_out, sig_ptrs = self._sig_out(m, outputs and verify, into)
+        aux = None
+        if aux_to_idx is not None:
+            aux = np.ascontiguousarray(aux_to_idx, dtype=np.uint64)
+            if aux.size != m:
+                raise ValueError("aux_to_idx: one entry per L2 transaction")
+        R = n_l1 + m
+        aux_out = flags = None
+        more, exit_ptrs, create_ptrs = {}, (ctypes.c_void_p * len(LEDGER_EXIT_ARRAYS))(), (ctypes.c_void_p * len(LEDGER_CREATE_ARRAYS))()
+        if outputs:
+            shapes = {"auxToIdx": (R, 32), "l1_flags": (n_l1,)}
+            shapes.update({name: (R if name != "new_exit_root" else 1, 32) for name in LEDGER_EXIT_ARRAYS})
+            shapes.update({name: (R if name != "new_last_idx" else 1, 32) for name in LEDGER_CREATE_ARRAYS})
+            for name, shape in shapes.items():
+                more[name] = into[name] if into is not None and name in into else np.zeros(shape, dtype=np.uint8)
+                assert more[name].shape == shape and more[name].dtype == np.uint8 and more[name].flags.c_contiguous
+            aux_out, flags = more["auxToIdx"], more["l1_flags"]
+            for i, name in enumerate(LEDGER_EXIT_ARRAYS):
+                exit_ptrs[i] = more[name].ctypes.data
+            for i, name in enumerate(LEDGER_CREATE_ARRAYS):
+                create_ptrs[i] = more[name].ctypes.data
+        self.L._check(self.L.c.hz_ledger_apply_batch_creates(self.h, n_l1, ctypes.addressof(l1), bjj.ctypes.data if bjj is not None else None, m, ctypes.addressof(arr),
+                                                             ctypes.addressof(sigs) if sigs is not False else None, LEDGER_VERIFY_SIGS if verify else 0,
+                                                             aux.ctypes.data if aux is not None else None, chain_id, current_num_batch, F, plan.ctypes.data,
+                                                             idxs.ctypes.data, n_sib, ctypes.addressof(ptrs) if outputs else None,
+                                                             ctypes.addressof(sig_ptrs) if outputs and verify else None, aux_out.ctypes.data if outputs and R else None,
+                                                             flags.ctypes.data if outputs and n_l1 else None, ctypes.addressof(exit_ptrs) if outputs else None,
+                                                             ctypes.addressof(create_ptrs) if outputs else None))
+        out.update(sig_out)
+        out.update(more)
+        return out
+
+    def create_outputs_dev(self):
+        """device pointers of the six create arrays of the last successful apply_batch_creates, by name; valid until the ledger's next call"""
+        ptrs = (ctypes.c_void_p * len(LEDGER_CREATE_ARRAYS))()
+        self.L._check(self.L.c.hz_ledger_create_outputs_dev(self.h, ctypes.addressof(ptrs)))
+        return {name: ptrs[i] for i, name in enumerate(LEDGER_CREATE_ARRAYS)}
+
+    def create_ms(self):
+        """device time of the two create kernels of the last apply_batch_creates"""
+        return self.L.c.hz_ledger_create_ms(self.h)
+
+    def size(self):
+        """live accounts"""
+        return self.L.c.hz_ledger_size(self.h)
+
+    def last_idx(self):
+        """first_idx + size - 1; first_idx - 1 when the ledger is empty"""
+        return self.L.c.hz_ledger_last_idx(self.h)
+
     def exit_outputs_dev(self):
         """device pointers of the six exit arrays of the last successful apply_batch_exits, by name; valid until the ledger's next call"""
         ptrs = (ctypes.c_void_p * len(LEDGER_EXIT_ARRAYS))()
@@ -1160,6 +1271,42 @@ class Ledger(_Resident):
     def semantic_ms(self):
         """device time of the last apply_l2's semantic kernels alone (first kernel to the failure-word read)"""
         return self.L.c.hz_ledger_semantic_ms(self.h)
+
+
+class GrowingLedger(Ledger):
+    """hz_ledger_create_growing: a ledger whose state tree is a sparse tree and whose planes have room for `capacity` accounts, so that L1
+    rows may create accounts (apply_batch_creates). Every call of Ledger works on it, over its live accounts; n_sib defaults to n_sib_max."""
+    _create = "hz_ledger_create_growing"
+
+    def __init__(self, L, capacity, first_idx=256, n_sib_max=33, device=0):
+        self._open(L, device, capacity, first_idx, n_sib_max)
+        self.capacity, self.first_idx, self.n_sib_max = capacity, first_idx, n_sib_max
+        self.k = n_sib_max   # what the calls take as their default n_sib
+
+    @property
+    def N(self):
+        return self.size()
+
+    def load(self, *cols):
+        raise TypeError("a growing ledger is loaded with load_accounts")
+
+    def load_accounts(self, e0, balance, ay, eth_addr):
+        """consecutive accounts from first_idx: four [n, 32] arrays, 0 <= n <= capacity (n == 0: the genesis state)"""
+        import numpy as np
+        cols = [np.ascontiguousarray(a, dtype=np.uint8).reshape(-1, 32) for a in (e0, balance, ay, eth_addr)]
+        n = cols[0].shape[0]
+        if any(c.shape != (n, 32) for c in cols):
+            raise ValueError("load_accounts: four [n, 32] arrays")
+        self.L._check(self.L.c.hz_ledger_load_accounts(self.h, n, *[c.ctypes.data for c in cols]))
+
+    def tree(self):
+        raise TypeError("a growing ledger has no dense tree: state_smt()")
+
+    def state_smt(self):
+        """the state tree as a capi.SparseTree, borrowed: proofs / root / size"""
+        t = _BorrowedSparseTree(self.L, self.L.c.hz_ledger_state_smt(self.h))
+        t.n_sib_max = self.n_sib_max
+        return t
 
 
 class SparseTree(_Resident):

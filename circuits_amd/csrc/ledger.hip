@@ -35,6 +35,12 @@
 //   k_ledger_exit_scan     a lane per exit key, before the one synchronise: the exit leaf before and after each of its operations
 //   the exit tree's update smt_apply_launch on that tree's own stream behind an event, beside the state tree's update
 //   k_ledger_exit_pack / _gather   the leaf-2 rows, newExit, isOld0_2, oldKey2, oldValue2, siblings2 and the exit root after every row
+// hz_ledger_create_growing makes a ledger whose state tree is an hz_smt and whose planes are [capacity][32]: N below is
+// then the plane stride and `live` the number of accounts, the tree update is smt_apply_prepare / _launch / _finish on the same record
+// buffer, and hz_ledger_apply_batch_creates accepts from_idx == 0 in L1 rows (ledger_create.h):
+//   k_ledger_create        a lane per create row, before everything else of the call: the new account's static fields into its plane
+//                          slot beyond `live`. From there the pipeline above sees a deposit on auxFromIdx; the tree's planner makes it an insert
+//   k_ledger_create_pack   a lane per row, behind the tree update: auxFromIdx, isOld0_1, oldKey1, oldValue1, the last idx after the row
 // Values are plain 256-bit integers in eight 32-bit limbs (the Fc container of fr.h, nothing is reduced modulo r); deltas are
 // two's complement: every true prefix is below 2^220 in magnitude, so a set top bit means "negative"; the arithmetic is u256.h's, shared
 // with ledger_sig.h. Buffers and block offsets are hostutil.h's, the event holder resident.h's; the stream is the tree's (state_stream).
@@ -55,6 +61,7 @@
 #include "ledger_fee.h"
 #include "ledger_l1.h"
 #include "ledger_exit.h"
+#include "ledger_create.h"
 #include "smt_internal.h"
 #include "smt_plan.h"
 
@@ -276,9 +283,9 @@ __global__ __launch_bounds__(256) void k_ledger_accounts(const uint32_t* __restr
 
 // a lane per account: its key probed in the table of the batch's queries; a hit lowers the slot's result to the lowest account
 __global__ __launch_bounds__(256) void k_ledger_resolve(const uint8_t* __restrict__ planes, const ResolveKey* __restrict__ table, uint32_t* __restrict__ result,
-                                                        uint32_t slots, uint32_t N) {
+                                                        uint32_t slots, uint32_t N, uint32_t n) {
     const uint32_t a = blockIdx.x * blockDim.x + threadIdx.x;
-    if (a >= N) return;
+    if (a >= n) return;   // n accounts to scan, N the plane stride (equal on a dense ledger)
     const Fc e0 = load_fr(planes + (size_t)a * 32);
     const Fc eth = load_fr(planes + ((size_t)3 * N + a) * 32);
     Fc ay = fc_zero();
@@ -358,11 +365,26 @@ struct hz_ledger {
     bool have_exit_outputs = false;
     DevEvent ex0, ex1, ex2, ex3, ex_tree;   // around the scan, around pack and gather (the tree's stream); after the exit tree's update (its own)
     double exit_ms = 0.0;
+    // a growing ledger (hz_ledger_create_growing): the state tree is an hz_smt, tree == nullptr, N is the capacity -- the
+    // plane stride -- and live the number of accounts; a dense ledger has live == N for good
+    hz_smt* smt = nullptr;
+    uint64_t live = 0;
+    uint32_t n_sib_max = 0;
+    bool loaded = false;
+    DevBuf create_in, create_outs, root_buf;
+    PinnedBuf h_create;
+    uint8_t* create_dev[HZ_LEDGER_CREATE_ARRAYS] = {};
+    bool have_create_outputs = false;
+    DevEvent ec0, ec1, ec2, ec3;   // around k_ledger_create, around k_ledger_create_pack
+    double create_ms = 0.0;
     ~hz_ledger() {
         if (exit) hz_smt_destroy(exit);
+        if (smt) hz_smt_destroy(smt);
         if (tree) hz_state_destroy(tree);
     }
 };
+
+static hipStream_t ledger_stream(const hz_ledger* l) { return l->smt ? smt_stream(l->smt) : state_stream(l->tree); }
 
 // the exit tree and the exit leaves are those of the last successful call: every call that applies a batch starts from the empty tree
 static void ledger_exit_reset(hz_ledger* l) {
@@ -371,7 +393,7 @@ static void ledger_exit_reset(hz_ledger* l) {
     l->exit_ms = 0.0;
 }
 
-// a prepared update of the exit tree that does not reach smt_apply_finish did not happen
+// a prepared update of the exit tree -- or of a growing ledger's state tree -- that does not reach smt_apply_finish did not happen
 struct LedgerExitGuard {
     hz_smt* t = nullptr;
     ~LedgerExitGuard() {
@@ -381,17 +403,34 @@ struct LedgerExitGuard {
 
 // the device pointers and the L1 time of the last successful call are no longer what the getters may hand out
 static void ledger_forget(hz_ledger* l) {
-    l->have_outputs = l->have_sig_outputs = l->have_aux = l->have_l1 = l->have_exit_outputs = false;
+    l->have_outputs = l->have_sig_outputs = l->have_aux = l->have_l1 = l->have_exit_outputs = l->have_create_outputs = false;
     l->l1_ms = 0.0;
+    l->create_ms = 0.0;
 }
 
 static hz_status ledger_ready(const hz_ledger* l, const char* who) {
     if (!l) return set_err(HZ_ERR_ARG, "%s: null ledger", who);
+    if (l->smt) {
+        if (!l->loaded) return set_err(HZ_ERR_ARG, "%s: the ledger has not been loaded yet (hz_ledger_load_accounts)", who);
+        if (smt_poisoned(l->smt))
+            return set_err(HZ_ERR_HIP, "%s: an earlier call failed on the device after the state tree's write-back was queued; hz_ledger_load_accounts makes the ledger usable again", who);
+        return HZ_OK;
+    }
     if (!state_loaded(l->tree)) return set_err(HZ_ERR_ARG, "%s: the ledger holds no accounts yet (hz_ledger_load)", who);
     return HZ_OK;
 }
 
 static bool ledger_has(uint64_t first_idx, uint64_t N, uint64_t idx) { return idx >= first_idx && idx - first_idx < N; }
+
+// a dense ledger's tree has k levels; a growing one's depth is the planner's to judge (a leaf at depth >= n_sib is HZ_ERR_ARG there)
+static hz_status ledger_n_sib(const hz_ledger* l, const char* who, size_t n_sib) {
+    if (l->smt) {
+        if (n_sib < 1 || n_sib > 64 || n_sib > l->n_sib_max) return set_err(HZ_ERR_ARG, "%s: n_sib = %zu (1 .. %u, the ledger's n_sib_max)", who, n_sib, l->n_sib_max);
+        return HZ_OK;
+    }
+    if (n_sib < l->k || n_sib > 64) return set_err(HZ_ERR_ARG, "%s: n_sib = %zu (%u .. 64)", who, n_sib, l->k);
+    return HZ_OK;
+}
 
 // the per-transaction argument checks of every call that takes transactions; a NOP (from_idx == 0) is not looked at. by_addr: to_idx == 0
 // (a receiver named by address or key) passes; exits: to_idx == 1 does
@@ -418,6 +457,16 @@ static hz_status ledger_check_txs(const char* who, size_t m, const hz_l2tx* txs,
     return HZ_OK;
 }
 
+// the checks of an L1 row that do not depend on which accounts exist
+static hz_status ledger_check_l1_fields(const char* who, size_t i, const hz_l1tx& t) {
+    if (t.amount_f >> 40) return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: amount_f has more than 40 bits", who, i);
+    if (t.load_amount_f >> 40) return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: load_amount_f has more than 40 bits", who, i);
+    for (int b = 20; b < 32; b++)
+        if (t.from_eth_addr[b]) return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: from_eth_addr has more than 160 bits", who, i);
+    if (ledger_mantissa(t.amount_f) != 0 && t.to_idx == 0) return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: an amount with to_idx = 0 (no receiver)", who, i);
+    return HZ_OK;
+}
+
 // the L1 run of hz_ledger_apply_batch: its transactions, where the flag bytes go on the host (may be null); is_batch tells the call
 // from hz_ledger_apply_l2_addr, which has none
 struct LedgerL1Run {
@@ -428,7 +477,55 @@ struct LedgerL1Run {
     // hz_ledger_apply_batch_exits: to_idx == 1 is taken in L1 and L2 rows; where the exit arrays go on the host (may be null)
     bool exits = false;
     const hz_ledger_exit_out* exit_out = nullptr;
+    // hz_ledger_apply_batch_creates: from_idx == 0 is taken in L1 rows; the compressed keys of those rows; where the create arrays go on
+    // the host (may be null). Once the rows are checked: tx are the rows with auxFromIdx in from_idx's place, aux_from / idx_after [n]
+    // the running index, n_creates the accounts the call makes
+    bool creates = false;
+    const uint8_t* from_bjj = nullptr;
+    const hz_ledger_create_out* create_out = nullptr;
+    const uint64_t *aux_from = nullptr, *idx_after = nullptr;
+    size_t n_creates = 0;
 };
+
+// the argument checks of an L1 run that may create accounts; -> the events it makes, the rows as the pipeline takes them
+// (eff: from_idx = auxFromIdx on a create row), auxFromIdx (0: the row creates nothing) and the last idx after every row
+static hz_status ledger_check_creates(const char* who, bool growing, uint64_t capacity, uint64_t first_idx, uint64_t size, size_t n_l1, const hz_l1tx* l1,
+                                      const uint8_t* from_bjj, size_t* events, std::vector<hz_l1tx>& eff, std::vector<uint64_t>& aux_from,
+                                      std::vector<uint64_t>& idx_after, size_t* n_creates) {
+    *events = 0;
+    *n_creates = 0;
+    if (n_l1 > HZ_LEDGER_MAX_L1) return set_err(HZ_ERR_ARG, "%s: n_l1 = %zu L1 transactions (at most %d)", who, n_l1, HZ_LEDGER_MAX_L1);
+    if (n_l1 && !l1) return set_err(HZ_ERR_ARG, "%s: null l1", who);
+    eff.assign(l1, l1 + n_l1);
+    aux_from.assign(n_l1, 0);
+    idx_after.assign(n_l1, 0);
+    uint64_t last = first_idx + size - 1;   // first_idx - 1 on an empty ledger
+    for (size_t i = 0; i < n_l1; i++) {
+        const hz_l1tx& t = l1[i];
+        const bool creates = t.from_idx == 0;
+        if (creates) {
+            if (!growing) return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: from_idx = 0 (creates an account) on a ledger that cannot grow (hz_ledger_create_growing)", who, i);
+            if (!from_bjj) return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: from_idx = 0 (creates an account) with from_bjj == NULL", who, i);
+            if (size + *n_creates + 1 > capacity)
+                return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: the ledger is full (capacity %llu accounts)", who, i, (unsigned long long)capacity);
+            *n_creates += 1;
+            last = create_next_idx(last, true);
+            aux_from[i] = last;
+            eff[i].from_idx = last;
+            if (t.to_idx == HZ_LEDGER_EXIT_IDX) return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: a row that creates an account with to_idx = 1 (an exit)", who, i);
+        } else if (!(t.from_idx >= first_idx && t.from_idx <= last && last >= first_idx)) {
+            return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: from_idx = %llu does not exist at its row (%llu .. %lld)", who, i, (unsigned long long)t.from_idx,
+                           (unsigned long long)first_idx, (long long)last);
+        }
+        idx_after[i] = last;
+        if (t.to_idx > HZ_LEDGER_EXIT_IDX && !(t.to_idx >= first_idx && t.to_idx <= last && last >= first_idx))
+            return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: to_idx = %llu does not exist at its row (%llu .. %lld)", who, i, (unsigned long long)t.to_idx,
+                           (unsigned long long)first_idx, (long long)last);
+        if (hz_status e = ledger_check_l1_fields(who, i, t)) return e;
+        *events += 1 + (ledger_mantissa(t.amount_f) != 0);
+    }
+    return HZ_OK;
+}
 
 // the argument checks of an L1 run; -> the events it makes
 static hz_status ledger_check_l1(const char* who, size_t n_l1, const hz_l1tx* l1, uint64_t first_idx, uint64_t N, size_t* events, bool exits = false) {
@@ -446,12 +543,7 @@ static hz_status ledger_check_l1(const char* who, size_t n_l1, const hz_l1tx* l1
         if (t.to_idx > HZ_LEDGER_EXIT_IDX && !ledger_has(first_idx, N, t.to_idx))
             return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: to_idx = %llu is outside the state (%llu .. %llu)", who, i, (unsigned long long)t.to_idx,
                            (unsigned long long)first_idx, (unsigned long long)last);
-        if (t.amount_f >> 40) return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: amount_f has more than 40 bits", who, i);
-        if (t.load_amount_f >> 40) return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: load_amount_f has more than 40 bits", who, i);
-        for (int b = 20; b < 32; b++)
-            if (t.from_eth_addr[b]) return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: from_eth_addr has more than 160 bits", who, i);
-        if (ledger_mantissa(t.amount_f) != 0 && t.to_idx == 0)
-            return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: an amount with to_idx = 0 (no receiver)", who, i);
+        if (hz_status e = ledger_check_l1_fields(who, i, t)) return e;
         *events += 1 + (ledger_mantissa(t.amount_f) != 0);
     }
     return HZ_OK;
@@ -459,12 +551,12 @@ static hz_status ledger_check_l1(const char* who, size_t n_l1, const hz_l1tx* l1
 
 // the argument checks hz_ledger_apply_l2 and hz_ledger_plan_l2 share; on success the plan is made. by_addr (hz_ledger_apply_l2_addr): the
 // checks alone -- the plan is made later, on the effective receivers
-static hz_status ledger_check_plan(const char* who, size_t m, const hz_l2tx* txs, size_t F, const uint32_t* plan_tokens, const uint64_t* fee_idxs, uint32_t k,
+static hz_status ledger_check_plan(const char* who, size_t m, const hz_l2tx* txs, size_t F, const uint32_t* plan_tokens, const uint64_t* fee_idxs, uint64_t N,
                                    uint64_t first_idx, LedgerPlan& plan, bool by_addr = false, size_t l1_events = 0, bool exits = false) {
     if ((m && !txs) || (F && (!plan_tokens || !fee_idxs))) return set_err(HZ_ERR_ARG, "%s: null argument", who);
     if (F > HZ_LEDGER_MAX_F) return set_err(HZ_ERR_ARG, "%s: F = %zu fee slots (at most %u)", who, F, HZ_LEDGER_MAX_F);
     if (m > HZ_LEDGER_MAX_TX) return set_err(HZ_ERR_ARG, "%s: %zu transactions in one call (at most %u)", who, m, HZ_LEDGER_MAX_TX);
-    const uint64_t N = 1ull << k, last = first_idx + N - 1;
+    const uint64_t last = first_idx + N - 1;
     if (hz_status e = ledger_check_txs(who, m, txs, first_idx, N, by_addr, exits)) return e;
     for (size_t j = 0; j < F; j++)
         if (fee_idxs[j] != 0 && !ledger_has(first_idx, N, fee_idxs[j]))
@@ -484,7 +576,7 @@ extern "C" hz_status hz_ledger_plan_l2(size_t m, const hz_l2tx* txs, size_t F, c
                                        size_t* n_events_out, uint64_t* ev_account_out, int32_t* ev_prev_out) {
     if (k < 4 || k > 24) return set_err(HZ_ERR_ARG, "hz_ledger_plan_l2: k = %d (4 .. 24)", k);
     LedgerPlan p;
-    if (hz_status e = ledger_check_plan("hz_ledger_plan_l2", m, txs, F, fee_plan_tokens, fee_idxs, (uint32_t)k, first_idx, p)) return e;
+    if (hz_status e = ledger_check_plan("hz_ledger_plan_l2", m, txs, F, fee_plan_tokens, fee_idxs, 1ull << k, first_idx, p)) return e;
     for (size_t i = 0; i < m; i++) {
         if (ev_sender_out) ev_sender_out[i] = p.ev_sender[i];
         if (ev_receiver_out) ev_receiver_out[i] = p.ev_receiver[i];
@@ -499,6 +591,19 @@ extern "C" hz_status hz_ledger_plan_l2(size_t m, const hz_l2tx* txs, size_t F, c
     return HZ_OK;
 }
 
+#define HZ_LEDGER_MAX_CAPACITY (1ull << 24)
+
+// what both kinds of ledger own once device, N and the trees are set: the planes, the failure word's pinned home, the events
+static hz_status ledger_open(hz_ledger* l) {
+    HZ_HIP(hipSetDevice(l->device));
+    HZ_HIP(l->planes.alloc((size_t)4 * l->N * 32));
+    HZ_HIP(l->h_fail.grow(64));
+    for (DevEvent* e : {&l->e0, &l->e1, &l->e2, &l->es0, &l->es1, &l->er0, &l->er1, &l->el0, &l->el1, &l->ex0, &l->ex1, &l->ex2, &l->ex3, &l->ex_tree, &l->ec0,
+                        &l->ec1, &l->ec2, &l->ec3})
+        HZ_HIP(e->create());
+    return HZ_OK;
+}
+
 extern "C" hz_status hz_ledger_create(int32_t device, int32_t k, uint64_t first_idx, hz_ledger** out) {
     if (!out) return set_err(HZ_ERR_ARG, "hz_ledger_create: null argument");
     *out = nullptr;
@@ -508,12 +613,29 @@ extern "C" hz_status hz_ledger_create(int32_t device, int32_t k, uint64_t first_
     l->device = device;
     l->k = (uint32_t)k;
     l->N = 1u << k;
+    l->live = l->N;
     l->first_idx = first_idx;
-    HZ_HIP(hipSetDevice(device));
-    HZ_HIP(l->planes.alloc((size_t)4 * l->N * 32));
-    HZ_HIP(l->h_fail.grow(64));
-    for (DevEvent* e : {&l->e0, &l->e1, &l->e2, &l->es0, &l->es1, &l->er0, &l->er1, &l->el0, &l->el1, &l->ex0, &l->ex1, &l->ex2, &l->ex3, &l->ex_tree})
-        HZ_HIP(e->create());
+    if (hz_status e = ledger_open(l.get())) return e;
+    *out = l.release();
+    return HZ_OK;
+}
+
+extern "C" hz_status hz_ledger_create_growing(int32_t device, uint64_t capacity, uint64_t first_idx, int32_t n_sib_max, hz_ledger** out) {
+    const char* who = "hz_ledger_create_growing";
+    if (!out) return set_err(HZ_ERR_ARG, "%s: null argument", who);
+    *out = nullptr;
+    if (capacity < 1 || capacity > HZ_LEDGER_MAX_CAPACITY) return set_err(HZ_ERR_ARG, "%s: capacity = %llu accounts (1 .. 2^24)", who, (unsigned long long)capacity);
+    if (first_idx < 2 || (first_idx + capacity) >> HZ_SMT_KEY_BITS)
+        return set_err(HZ_ERR_ARG, "%s: first_idx = %llu (0 and 1 are not accounts; the circuits' idx has 48 bits)", who, (unsigned long long)first_idx);
+    std::unique_ptr<hz_ledger> l(new hz_ledger);
+    if (hz_status e = hz_smt_create(device, n_sib_max, &l->smt)) return e;
+    if (hz_status e = hz_smt_create(device, HZ_SMT_MAX_DEPTH, &l->exit)) return e;
+    l->device = device;
+    l->N = (uint32_t)capacity;
+    l->n_sib_max = (uint32_t)n_sib_max;
+    l->first_idx = first_idx;
+    if (hz_status e = ledger_open(l.get())) return e;
+    HZ_HIP(l->root_buf.alloc(32));
     *out = l.release();
     return HZ_OK;
 }
@@ -521,7 +643,7 @@ extern "C" hz_status hz_ledger_create(int32_t device, int32_t k, uint64_t first_
 extern "C" void hz_ledger_destroy(hz_ledger* l) {
     if (!l) return;
     (void)hipSetDevice(l->device);
-    (void)hipStreamSynchronize(state_stream(l->tree));
+    (void)hipStreamSynchronize(ledger_stream(l));
     (void)hipStreamSynchronize(smt_stream(l->exit));
     delete l;
 }
@@ -533,28 +655,92 @@ static bool ledger_bytes_from(const uint8_t* p, int from) {
     return d != 0;
 }
 
-extern "C" hz_status hz_ledger_load(hz_ledger* l, const uint8_t* e0, const uint8_t* balance, const uint8_t* ay, const uint8_t* eth_addr) {
-    if (!l || !e0 || !balance || !ay || !eth_addr) return set_err(HZ_ERR_ARG, "hz_ledger_load: null argument");
-    // a leaf's ranges, which every kernel assumes: before the tree or the planes are touched, so a refused load leaves a loaded ledger as it was
-    for (size_t i = 0; i < l->N; i++) {
+// the first account whose fields are not a leaf's, named
+static hz_status ledger_check_leaves(const char* who, uint64_t first_idx, size_t n, const uint8_t* e0, const uint8_t* balance, const uint8_t* eth_addr) {
+    for (size_t i = 0; i < n; i++) {
         const char* bad = nullptr;
         if (ledger_bytes_from(balance + i * 32, 24)) bad = "balance >= 2^192";
         else if (ledger_bytes_from(e0 + i * 32, 10) || e0[i * 32 + 9] > 1) bad = "e0 >= 2^73";
         else if (ledger_bytes_from(eth_addr + i * 32, 20)) bad = "ethAddr >= 2^160";
-        if (bad) return set_err(HZ_ERR_INPUT, "hz_ledger_load: account %llu (row %zu) is not a leaf: %s", (unsigned long long)(l->first_idx + i), i, bad);
+        if (bad) return set_err(HZ_ERR_INPUT, "%s: account %llu (row %zu) is not a leaf: %s", who, (unsigned long long)(first_idx + i), i, bad);
     }
+    return HZ_OK;
+}
+
+extern "C" hz_status hz_ledger_load(hz_ledger* l, const uint8_t* e0, const uint8_t* balance, const uint8_t* ay, const uint8_t* eth_addr) {
+    if (!l || !e0 || !balance || !ay || !eth_addr) return set_err(HZ_ERR_ARG, "hz_ledger_load: null argument");
+    if (l->smt) return set_err(HZ_ERR_ARG, "hz_ledger_load: a growing ledger is loaded with hz_ledger_load_accounts");
+    // a leaf's ranges, which every kernel assumes: before the tree or the planes are touched, so a refused load leaves a loaded ledger as it was
+    if (hz_status e = ledger_check_leaves("hz_ledger_load", l->first_idx, l->N, e0, balance, eth_addr)) return e;
     ledger_forget(l);
     if (hz_status e = hz_state_load(l->tree, e0, balance, ay, eth_addr)) return e;   // checks every field < r
     const uint8_t* src[4] = {e0, balance, ay, eth_addr};
-    hipStream_t s = state_stream(l->tree);
+    hipStream_t s = ledger_stream(l);
     HZ_HIP(hipSetDevice(l->device));
     for (int f = 0; f < 4; f++) HZ_HIP(hipMemcpyAsync((uint8_t*)l->planes.p + (size_t)f * l->N * 32, src[f], (size_t)l->N * 32, hipMemcpyHostToDevice, s));
     HZ_HIP(hipStreamSynchronize(s));
     return HZ_OK;
 }
 
+// n consecutive accounts from first_idx into a growing ledger (n == 0: the genesis state, root 0): the planes by copy, the tree by ordered
+// inserts through smt_internal.h, at most 65536 a call, on records a kernel makes of the planes
+extern "C" hz_status hz_ledger_load_accounts(hz_ledger* l, uint64_t n, const uint8_t* e0, const uint8_t* balance, const uint8_t* ay, const uint8_t* eth_addr) {
+    const char* who = "hz_ledger_load_accounts";
+    if (!l) return set_err(HZ_ERR_ARG, "%s: null ledger", who);
+    if (!l->smt) return set_err(HZ_ERR_ARG, "%s: a dense ledger is loaded with hz_ledger_load", who);
+    if (n > l->N) return set_err(HZ_ERR_ARG, "%s: n = %llu accounts (the capacity is %u)", who, (unsigned long long)n, l->N);
+    if (n && (!e0 || !balance || !ay || !eth_addr)) return set_err(HZ_ERR_ARG, "%s: null argument", who);
+    if (hz_status e = ledger_check_leaves(who, l->first_idx, n, e0, balance, eth_addr)) return e;
+    const uint8_t* src[4] = {e0, balance, ay, eth_addr};
+    static const char* const name[4] = {"e0", "balance", "ay", "ethAddr"};
+    for (int f = 0; f < 4; f++)
+        for (size_t i = 0; i < n; i++)
+            if (!canon_lt_p(src[f] + i * 32))
+                return set_err(HZ_ERR_INPUT, "%s: %s of account %llu (row %zu) is not below the field's modulus", who, name[f], (unsigned long long)(l->first_idx + i), i);
+    // a depth the tree cannot express is found before anything is touched: the shape of n consecutive keys, planned alone
+    {
+        SmtShape sh;
+        sh.begin();
+        for (uint64_t i = 0; i < n; i++)
+            if (sh.add(l->first_idx + i, l->n_sib_max) != SMT_PLAN_OK)
+                return set_err(HZ_ERR_ARG, "%s: account %llu would have its leaf at depth >= n_sib_max = %u", who, (unsigned long long)(l->first_idx + i), l->n_sib_max);
+    }
+    ledger_forget(l);
+    ledger_exit_reset(l);
+    HZ_HIP(hipSetDevice(l->device));
+    if (hz_status e = hz_smt_reset(l->smt)) return e;   // synchronises the stream
+    l->live = 0;
+    l->loaded = false;
+    hipStream_t s = ledger_stream(l);
+    for (int f = 0; f < 4 && n; f++) HZ_HIP(hipMemcpyAsync((uint8_t*)l->planes.p + (size_t)f * l->N * 32, src[f], (size_t)n * 32, hipMemcpyHostToDevice, s));
+    std::vector<uint64_t> keys;
+    for (uint64_t base = 0; base < n; base += HZ_LEDGER_MAX_EVENTS) {
+        const uint32_t M = (uint32_t)std::min<uint64_t>(HZ_LEDGER_MAX_EVENTS, n - base);
+        keys.resize(M);
+        for (uint32_t j = 0; j < M; j++) keys[j] = l->first_idx + base + j;
+        SmtCallBufs sb{};
+        if (hz_status e = smt_apply_prepare(l->smt, who, HZ_ERR_ARG, M, keys.data(), l->n_sib_max, false, &sb)) return e;
+        LedgerExitGuard guard;
+        guard.t = l->smt;
+        hipLaunchKernelGGL(k_ledger_load_records, dim3((M + 255) / 256), dim3(256), 0, s, (const uint8_t*)l->planes.p, sb.fields, l->N, (uint32_t)base, M);
+        HZ_HIP(hipGetLastError());
+        if (hz_status e = smt_apply_launch(l->smt, M, l->n_sib_max, false)) return e;
+        if (hz_status e = smt_apply_finish(l->smt)) return e;
+        guard.t = nullptr;
+    }
+    HZ_HIP(hipStreamSynchronize(s));
+    l->live = n;
+    l->loaded = true;
+    return HZ_OK;
+}
+
+extern "C" uint64_t hz_ledger_size(const hz_ledger* l) { return l ? l->live : 0; }
+extern "C" uint64_t hz_ledger_last_idx(const hz_ledger* l) { return l ? l->first_idx + l->live - 1 : 0; }
+extern "C" hz_smt* hz_ledger_state_smt(hz_ledger* l) { return l ? l->smt : nullptr; }
+
 extern "C" hz_status hz_ledger_root(hz_ledger* l, uint8_t* out32) {
     if (hz_status e = ledger_ready(l, "hz_ledger_root")) return e;
+    if (l->smt) return hz_smt_root(l->smt, out32);
     return hz_state_root(l->tree, out32);
 }
 
@@ -566,16 +752,16 @@ extern "C" hz_status hz_ledger_accounts(hz_ledger* l, size_t n, const uint64_t* 
     if (hz_status e = ledger_ready(l, "hz_ledger_accounts")) return e;
     if (n == 0) return HZ_OK;
     if (!idx || !fields_out) return set_err(HZ_ERR_ARG, "hz_ledger_accounts: null argument");
-    if (n > l->N) return set_err(HZ_ERR_ARG, "hz_ledger_accounts: %zu accounts in one call (the state holds %u)", n, l->N);
+    if (n > l->live) return set_err(HZ_ERR_ARG, "hz_ledger_accounts: %zu accounts in one call (the state holds %u)", n, (unsigned)l->live);
     std::vector<uint32_t> acct(n);
     for (size_t i = 0; i < n; i++) {
-        if (!ledger_has(l->first_idx, l->N, idx[i]))
+        if (!ledger_has(l->first_idx, l->live, idx[i]))
             return set_err(HZ_ERR_ARG, "hz_ledger_accounts: idx[%zu] = %llu is outside the state", i, (unsigned long long)idx[i]);
         acct[i] = (uint32_t)(idx[i] - l->first_idx);
     }
     HZ_HIP(hipSetDevice(l->device));
     ledger_forget(l);   // the call's buffers are reused
-    hipStream_t s = state_stream(l->tree);
+    hipStream_t s = ledger_stream(l);
     HZ_HIP(l->ints.grow(n * 4));
     HZ_HIP(l->work.grow(n * 128));
     HZ_HIP(hipMemcpyAsync(l->ints.p, acct.data(), n * 4, hipMemcpyHostToDevice, s));
@@ -654,14 +840,16 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
     static_assert(sizeof(hz_ledger_out) == HZ_LEDGER_ARRAYS * sizeof(uint8_t*), "hz_ledger_out is an array of pointers");
     if (hz_status e = ledger_ready(l, who)) return e;
     ledger_exit_reset(l);
-    const uint32_t k = l->k, N = l->N;
-    if (n_sib < k || n_sib > 64) return set_err(HZ_ERR_ARG, "%s: n_sib = %zu (%u .. 64)", who, n_sib, k);
+    const bool growing = l->smt != nullptr;
+    if (hz_status e = ledger_n_sib(l, who, n_sib)) return e;
+    // N is the plane stride; a growing ledger's tree hands out siblings zero-padded to n_sib, so the gather reads all of them
+    const uint32_t N = l->N, k = growing ? (uint32_t)n_sib : l->k;
     LedgerPlan& p = l->plan;
     const bool by_addr = eff_txs != nullptr;
     if (by_addr) {
         ledger_plan_rows(n_l1, l1, m, eff_txs, F, fee_plan_tokens, fee_idxs, run.exits, p);
     } else {
-        if (hz_status e = ledger_check_plan(who, m, txs, F, fee_plan_tokens, fee_idxs, k, l->first_idx, p)) return e;
+        if (hz_status e = ledger_check_plan(who, m, txs, F, fee_plan_tokens, fee_idxs, l->live, l->first_idx, p)) return e;
         if (with_sigs)
             if (hz_status e = ledger_check_sigs(who, m, txs, sigs, chain_id)) return e;
     }
@@ -672,7 +860,7 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
     const uint32_t n_chunks = R32 ? (R32 + HZ_LEDGER_CHUNK - 1) / HZ_LEDGER_CHUNK : 1u;
     const uint32_t X = (uint32_t)p.exit_row.size(), GX = (uint32_t)p.exit_seg_start.size() - 1;   // exit operations, exit keys
     HZ_HIP(hipSetDevice(l->device));
-    hipStream_t s = state_stream(l->tree);
+    hipStream_t s = ledger_stream(l);
     // the exit tree's plan comes first: a leaf it cannot hold refuses the call before anything is launched, and the pack kernel's
     // integers are the planner's
     SmtCallBufs xb{};
@@ -689,7 +877,8 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
                  o_acct = c.take((size_t)M * 4), o_pos = c.take((size_t)M * sizeof(LedgerPos)), o_seg = c.take(((size_t)G + 1) * 4),
                  o_l1 = c.take(n_l1 * sizeof(LedgerL1Dev)), o_slot_acct = c.take((size_t)n_slots * 4), o_ev_x = c.take(X ? R * 4 : 0),
                  o_pos_x = c.take(X ? R * 4 : 0), o_last_x = c.take(X ? R * 4 : 0), o_xpos = c.take((size_t)X * sizeof(LedgerExitPos)),
-                 o_xseg = c.take(X ? ((size_t)GX + 1) * 4 : 0), o_xop = c.take((size_t)X * sizeof(LedgerExitOp));
+                 o_xseg = c.take(X ? ((size_t)GX + 1) * 4 : 0), o_xop = c.take((size_t)X * sizeof(LedgerExitOp)),
+                 o_crow = c.take(run.creates ? R * sizeof(LedgerCreateRow) : 0);
     const size_t ints_bytes = c.end;   // (G + 1 >= 1: never empty)
     HZ_HIP(l->h_ints.grow(ints_bytes));
     uint8_t* hb = (uint8_t*)l->h_ints.p;
@@ -790,6 +979,12 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
     HZ_HIP(l->outs.grow(out_bytes));
     const size_t exit_out_bytes = ((size_t)(HZ_LEDGER_EXIT_ARRAYS - 1) * R + 1) * 32;   // five arrays per row, the new exit root
     uint8_t* xd[HZ_LEDGER_EXIT_ARRAYS] = {};
+    const size_t create_out_bytes = ((size_t)(HZ_LEDGER_CREATE_ARRAYS - 1) * R + 1) * 32;   // five arrays per row, the new last idx
+    LedgerCreateOutDev cd{};
+    if (run.creates) {
+        HZ_HIP(l->create_outs.grow(create_out_bytes));
+        for (int a = 0; a < HZ_LEDGER_CREATE_ARRAYS; a++) cd.a[a] = (uint8_t*)l->create_outs.p + (size_t)a * R * 32;
+    }
     if (run.exits) {
         HZ_HIP(l->exit_outs.grow(exit_out_bytes));
         HZ_HIP(l->exit_final.grow((size_t)4 * (GX ? GX : 1) * 32));
@@ -810,9 +1005,36 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
     const uint32_t* d_seg = (const uint32_t*)(db + o_seg);
     uint32_t* d_fail = (uint32_t*)(wb + w_fail);
 
+    // the state tree's update: hz_state's on a dense ledger; on a growing one hz_smt's, whose planner turns the first event of a key the
+    // tree does not hold -- a create row's sender event -- into an INSERT and refuses a leaf at depth >= n_sib before anything of the
+    // update is launched
     StateCallBufs tb{};
-    if (M)
+    SmtCallBufs sb{};
+    LedgerExitGuard tree_guard;
+    if (M && growing) {
+        if (hz_status e = smt_apply_prepare(l->smt, who, HZ_ERR_ARG, M, p.account.data(), S, true, &sb)) return e;
+        tree_guard.t = l->smt;
+        tb.fields = sb.fields;
+        tb.siblings = sb.siblings;
+        tb.old_value = sb.old_value;
+        tb.old_root = sb.roots;
+        tb.new_root = sb.roots + 32;
+    } else if (M) {
         if (hz_status e = state_apply_prepare(l->tree, M, p.account.data(), S, &tb)) return e;
+    }
+    const uint64_t new_last = l->first_idx + l->live + run.n_creates - 1;
+    if (run.creates)
+        for (size_t i = 0; i < R; i++) {   // the create arrays' integers: the running index, and what the tree's planner says of the insert
+            LedgerCreateRow row{};
+            row.idx_after = i < n_l1 ? run.idx_after[i] : new_last;
+            row.ev = p.ev_sender[i];
+            if (i < n_l1 && run.aux_from[i]) {
+                row.aux_from = run.aux_from[i];
+                row.old_key = sb.old_key[row.ev];
+                row.flags = CREATE_ROW | (sb.is_old0[row.ev] ? CREATE_IS_OLD0 : 0u);
+            }
+            ((LedgerCreateRow*)(hb + o_crow))[i] = row;
+        }
     HZ_HIP(hipMemcpyAsync(l->ints.p, l->h_ints.p, ints_bytes, hipMemcpyHostToDevice, s));
     HZ_HIP(hipMemsetAsync(d_fail, 0xFF, 4, s));
     if (with_sigs || by_addr)
@@ -886,10 +1108,23 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
                            (const int32_t*)(db + o_ev_r), (const int32_t*)(db + o_ev_fee), (const uint32_t*)(db + o_acct), (const uint8_t*)(wb + w_before), (const uint8_t*)l->planes.p, N, R32, F32, L32);
         HZ_HIP(hipGetLastError());
     }
-    const uint8_t* root0 = state_root_dev(l->tree);
+    const uint8_t* root0 = nullptr;
     if (M) {
-        if (hz_status e = state_apply_launch(l->tree, M, S, false)) return e;
+        if (hz_status e = growing ? smt_apply_launch(l->smt, M, S, true) : state_apply_launch(l->tree, M, S, false)) return e;
         root0 = tb.old_root;
+    } else if (growing) {   // no update at all: the root as it stands, through the host
+        uint8_t r32[32];
+        if (hz_status e = hz_smt_root(l->smt, r32)) return e;
+        HZ_HIP(hipMemcpy(l->root_buf.p, r32, 32, hipMemcpyHostToDevice));
+        root0 = (const uint8_t*)l->root_buf.p;
+    } else {
+        root0 = state_root_dev(l->tree);
+    }
+    if (run.creates) {   // behind the tree's update: oldValue1 is its old-value buffer's
+        HZ_HIP(hipEventRecord(l->ec2, s));
+        hipLaunchKernelGGL(k_ledger_create_pack, dim3((R32 + 64) / 64), dim3(64), 0, s, cd, (const LedgerCreateRow*)(db + o_crow), (const uint8_t*)tb.old_value, new_last, R32);
+        HZ_HIP(hipGetLastError());
+        HZ_HIP(hipEventRecord(l->ec3, s));
     }
     HZ_HIP(hipMemcpyAsync(od.a[LO_OLD_ROOT], root0, 32, hipMemcpyDeviceToDevice, s));
     HZ_HIP(hipMemcpyAsync(od.a[LO_NEW_ROOT], M ? tb.new_root + (size_t)(M - 1) * 32 : root0, 32, hipMemcpyDeviceToDevice, s));
@@ -922,6 +1157,13 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
         HZ_HIP(hipEventRecord(l->ex3, s));
     }
     HZ_HIP(hipEventRecord(l->e2, s));
+    if (run.create_out) {
+        uint8_t* const* h = (uint8_t* const*)run.create_out;
+        for (int a = 0; a < HZ_LEDGER_CREATE_ARRAYS; a++) {
+            const size_t rows = a == CO_NEW_LAST ? 1 : R;
+            if (h[a] && rows) HZ_HIP(hipMemcpyAsync(h[a], cd.a[a], rows * 32, hipMemcpyDeviceToHost, s));
+        }
+    }
     if (run.exit_out) {
         uint8_t* const* h = (uint8_t* const*)run.exit_out;
         for (int a = 0; a < HZ_LEDGER_EXIT_ARRAYS; a++) {
@@ -938,7 +1180,14 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
         if (hz_status e = ledger_sig_copy_out(l, m, sig_out, s)) return e;
     if (by_addr && aux_to_idx_out && R) HZ_HIP(hipMemcpyAsync(aux_to_idx_out, l->aux_rows.p, R * 32, hipMemcpyDeviceToHost, s));
     if (run.flags_out && n_l1) HZ_HIP(hipMemcpyAsync(run.flags_out, l->l1_flags.p, n_l1, hipMemcpyDeviceToHost, s));
-    if (M) {
+    if (M && growing) {
+        tree_guard.t = nullptr;
+        if (hz_status e = smt_apply_finish(l->smt)) {
+            smt_apply_abort(l->smt);
+            return e;
+        }
+        l->live += run.n_creates;   // the tree holds them: from here the created accounts exist
+    } else if (M) {
         if (hz_status e = state_apply_finish(l->tree)) return e;
     } else {
         HZ_HIP(hipStreamSynchronize(s));
@@ -970,6 +1219,16 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
     l->have_outputs = true;
     l->have_aux = by_addr;
     l->have_l1 = run.is_batch;
+    if (run.creates) {
+        for (int a = 0; a < HZ_LEDGER_CREATE_ARRAYS; a++) l->create_dev[a] = cd.a[a];
+        l->have_create_outputs = true;
+        HZ_HIP(hipEventElapsedTime(&ms, l->ec2, l->ec3));
+        l->create_ms = ms;
+        if (run.n_creates) {
+            HZ_HIP(hipEventElapsedTime(&ms, l->ec0, l->ec1));
+            l->create_ms += ms;
+        }
+    }
     if (L32) {
         HZ_HIP(hipEventElapsedTime(&ms, l->el0, l->el1));
         l->l1_ms = ms;
@@ -999,11 +1258,11 @@ extern "C" hz_status hz_ledger_verify_l2(hz_ledger* l, size_t m, const hz_l2tx* 
     if (hz_status e = ledger_ready(l, who)) return e;
     if (m && (!txs || !verdict_out)) return set_err(HZ_ERR_ARG, "%s: null argument", who);
     if (m > HZ_LEDGER_MAX_TX) return set_err(HZ_ERR_ARG, "%s: %zu transactions in one call (at most %u)", who, m, HZ_LEDGER_MAX_TX);
-    if (hz_status e = ledger_check_txs(who, m, txs, l->first_idx, l->N)) return e;
+    if (hz_status e = ledger_check_txs(who, m, txs, l->first_idx, l->live)) return e;
     if (hz_status e = ledger_check_sigs(who, m, txs, sigs, chain_id)) return e;
     ledger_forget(l);
     HZ_HIP(hipSetDevice(l->device));
-    hipStream_t s = state_stream(l->tree);
+    hipStream_t s = ledger_stream(l);
     HZ_HIP(l->ints.grow((m ? m : 1) * sizeof(hz_l2tx)));
     if (m) HZ_HIP(hipMemcpyAsync(l->ints.p, txs, m * sizeof(hz_l2tx), hipMemcpyHostToDevice, s));
     if (hz_status e = ledger_sig_prepare(l, m, sigs, s)) return e;
@@ -1037,7 +1296,7 @@ extern "C" double hz_ledger_sig_ms(const hz_ledger* l) { return l ? l->sig_ms : 
 // The lookup: out[i] is the lowest account that holds transaction i's signed destination and its token, 0 for a NOP, for to_idx != 0, for
 // a zero amount when skip_zero (processor 2 is a NOP then: no receiver is needed), or when no account matches. Host: the distinct
 // queries into the table; device: one pass over the planes, then a lane per transaction; one copy back and a synchronise.
-static hz_status ledger_resolve(hz_ledger* l, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, bool skip_zero, uint64_t* out) {
+static hz_status ledger_resolve(hz_ledger* l, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, bool skip_zero, uint64_t* out, uint64_t count) {
     l->resolve_ms = 0.0;
     size_t queries = 0;
     for (size_t i = 0; i < m; i++) {
@@ -1063,11 +1322,11 @@ static hz_status ledger_resolve(hz_ledger* l, size_t m, const hz_l2tx* txs, cons
                                   resolve_key(txs[i].token_id, resolve_load32(sigs[i].to_eth_addr), resolve_load32(sigs[i].to_bjj_ay), sigs[i].to_bjj_sign));
         ((int32_t*)(hb + o_slot))[i] = slot;
     }
-    hipStream_t s = state_stream(l->tree);
+    hipStream_t s = ledger_stream(l);
     HZ_HIP(hipMemcpyAsync(db, hb, up_bytes, hipMemcpyHostToDevice, s));
     HZ_HIP(hipEventRecord(l->er0, s));
-    hipLaunchKernelGGL(k_ledger_resolve, dim3((l->N + 255) / 256), dim3(256), 0, s, (const uint8_t*)l->planes.p, (const ResolveKey*)(db + o_table),
-                       (uint32_t*)(db + o_result), slots, l->N);
+    hipLaunchKernelGGL(k_ledger_resolve, dim3(((uint32_t)count + 255) / 256), dim3(256), 0, s, (const uint8_t*)l->planes.p, (const ResolveKey*)(db + o_table),
+                       (uint32_t*)(db + o_result), slots, l->N, (uint32_t)count);
     HZ_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_ledger_resolve_pick, dim3((m32 + 63) / 64), dim3(64), 0, s, (const int32_t*)(db + o_slot), (const uint32_t*)(db + o_result),
                        (uint64_t*)(db + o_out), l->first_idx, m32);
@@ -1087,11 +1346,37 @@ extern "C" hz_status hz_ledger_resolve_l2(hz_ledger* l, size_t m, const hz_l2tx*
     if (hz_status e = ledger_ready(l, who)) return e;
     if (m && (!txs || !sigs || !aux_to_idx_out)) return set_err(HZ_ERR_ARG, "%s: null argument", who);
     if (m > HZ_LEDGER_MAX_TX) return set_err(HZ_ERR_ARG, "%s: %zu transactions in one call (at most %u)", who, m, HZ_LEDGER_MAX_TX);
-    return ledger_resolve(l, m, txs, sigs, false, aux_to_idx_out);
+    return ledger_resolve(l, m, txs, sigs, false, aux_to_idx_out, l->live);
+}
+
+// k_ledger_create on the ledger's stream: every slot lies at or beyond the ledger's size and below its capacity (ledger_check_creates)
+static hz_status ledger_create_launch(hz_ledger* l, const LedgerL1Run& run) {
+    const uint32_t n = (uint32_t)run.n_creates;
+    HZ_HIP(hipSetDevice(l->device));
+    HZ_HIP(l->h_create.grow((size_t)n * sizeof(LedgerCreateDev)));
+    HZ_HIP(l->create_in.grow((size_t)n * sizeof(LedgerCreateDev)));
+    LedgerCreateDev* h = (LedgerCreateDev*)l->h_create.p;
+    uint32_t q = 0;
+    for (size_t i = 0; i < run.n; i++) {
+        if (!run.aux_from[i]) continue;
+        LedgerCreateDev c{};
+        c.acct = (uint32_t)(run.aux_from[i] - l->first_idx);
+        c.token_id = run.tx[i].token_id;
+        memcpy(c.bjj, run.from_bjj + i * 32, 32);
+        memcpy(c.from_eth, run.tx[i].from_eth_addr, 20);
+        h[q++] = c;
+    }
+    hipStream_t s = ledger_stream(l);
+    HZ_HIP(hipMemcpyAsync(l->create_in.p, h, (size_t)n * sizeof(LedgerCreateDev), hipMemcpyHostToDevice, s));
+    HZ_HIP(hipEventRecord(l->ec0, s));
+    hipLaunchKernelGGL(k_ledger_create, dim3((n + 63) / 64), dim3(64), 0, s, (const LedgerCreateDev*)l->create_in.p, (uint8_t*)l->planes.p, l->N, n);
+    HZ_HIP(hipGetLastError());
+    HZ_HIP(hipEventRecord(l->ec1, s));
+    return HZ_OK;
 }
 
 // hz_ledger_apply_l2_addr, and hz_ledger_apply_batch (is_batch) with its L1 run in front
-static hz_status ledger_apply_addr(hz_ledger* l, const char* who, const LedgerL1Run& run, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, uint32_t flags,
+static hz_status ledger_apply_addr(hz_ledger* l, const char* who, LedgerL1Run run, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, uint32_t flags,
                                    const uint64_t* aux_to_idx, uint32_t chain_id, uint32_t current_num_batch, size_t F, const uint32_t* fee_plan_tokens,
                                    const uint64_t* fee_idxs, size_t n_sib, const hz_ledger_out* out, const hz_ledger_sig_out* sig_out, uint8_t* aux_to_idx_out) {
     if (hz_status e = ledger_ready(l, who)) return e;
@@ -1102,10 +1387,22 @@ static hz_status ledger_apply_addr(hz_ledger* l, const char* who, const LedgerL1
     const bool verify = (flags & HZ_LEDGER_VERIFY_SIGS) != 0;
     if (flags & ~HZ_LEDGER_VERIFY_SIGS) return set_err(HZ_ERR_ARG, "%s: flags = %#x", who, flags);
     if (!verify && sig_out) return set_err(HZ_ERR_ARG, "%s: sig_out without HZ_LEDGER_VERIFY_SIGS", who);
-    if (n_sib < l->k || n_sib > 64) return set_err(HZ_ERR_ARG, "%s: n_sib = %zu (%u .. 64)", who, n_sib, l->k);
+    if (hz_status e = ledger_n_sib(l, who, n_sib)) return e;
     size_t l1_events = 0;
-    if (hz_status e = ledger_check_l1(who, n_l1, l1, l->first_idx, l->N, &l1_events, run.exits)) return e;
-    if (hz_status e = ledger_check_plan(who, m, txs, F, fee_plan_tokens, fee_idxs, l->k, l->first_idx, l->plan, true, l1_events, run.exits)) return e;
+    std::vector<hz_l1tx> eff_l1;
+    std::vector<uint64_t> aux_from, idx_after;
+    if (run.creates) {   // the rows as the pipeline takes them: a create row is a deposit on auxFromIdx
+        if (hz_status e = ledger_check_creates(who, l->smt != nullptr, l->N, l->first_idx, l->live, n_l1, l1, run.from_bjj, &l1_events, eff_l1, aux_from, idx_after,
+                                               &run.n_creates))
+            return e;
+        run.tx = eff_l1.data();
+        run.aux_from = aux_from.data();
+        run.idx_after = idx_after.data();
+    } else if (hz_status e = ledger_check_l1(who, n_l1, l1, l->first_idx, l->live, &l1_events, run.exits)) {
+        return e;
+    }
+    const uint64_t count = l->live + run.n_creates;   // the accounts an L2 row or a fee slot may name: live plus created
+    if (hz_status e = ledger_check_plan(who, m, txs, F, fee_plan_tokens, fee_idxs, count, l->first_idx, l->plan, true, l1_events, run.exits)) return e;
     std::vector<hz_l2sig> no_sigs;
     if (run.is_batch && !sigs && m && !verify) {   // no destination is signed: zero entries stand in, and the call is hz_ledger_apply_l2_addr's
         for (size_t i = 0; i < m; i++)
@@ -1114,22 +1411,24 @@ static hz_status ledger_apply_addr(hz_ledger* l, const char* who, const LedgerL1
         sigs = no_sigs.data();
     }
     if (hz_status e = ledger_check_sigs(who, m, txs, sigs, chain_id, verify)) return e;
+    if (run.n_creates)   // before everything else of the call, the lookup included: the new accounts' static fields into their plane slots
+        if (hz_status e = ledger_create_launch(l, run)) return e;
     std::vector<hz_l2tx> eff(m ? m : 1);   // (never empty: its address tells ledger_apply which call this is)
     if (m) memcpy(eff.data(), txs, m * sizeof(hz_l2tx));
     auto wants_receiver = [&](size_t i) { return txs[i].from_idx != 0 && txs[i].to_idx == 0 && ledger_mantissa(txs[i].amount_f) != 0; };
     if (aux_to_idx) {
         for (size_t i = 0; i < m; i++) {
             if (!wants_receiver(i)) continue;
-            if (!ledger_has(l->first_idx, l->N, aux_to_idx[i]))
+            if (!ledger_has(l->first_idx, count, aux_to_idx[i]))
                 return set_err(HZ_ERR_ARG, "%s: tx %zu: aux_to_idx = %llu is outside the state (%llu .. %llu)", who, i, (unsigned long long)aux_to_idx[i],
-                               (unsigned long long)l->first_idx, (unsigned long long)(l->first_idx + l->N - 1));
+                               (unsigned long long)l->first_idx, (unsigned long long)(l->first_idx + count - 1));
             eff[i].to_idx = aux_to_idx[i];
         }
         l->resolve_ms = 0.0;
     } else {
         std::vector<uint64_t> found(m ? m : 1);
         ledger_forget(l);
-        if (hz_status e = ledger_resolve(l, m, txs, sigs, true, found.data())) return e;
+        if (hz_status e = ledger_resolve(l, m, txs, sigs, true, found.data(), count)) return e;
         for (size_t i = 0; i < m; i++) {
             if (!wants_receiver(i)) continue;
             if (found[i] == 0)   // before the plan can exist: reported whatever else is wrong with the batch
@@ -1171,7 +1470,7 @@ extern "C" hz_status hz_ledger_plan_batch(size_t n_l1, const hz_l1tx* l1, size_t
     LedgerPlan p;
     size_t l1_events = 0;
     if (hz_status e = ledger_check_l1(who, n_l1, l1, first_idx, 1ull << k, &l1_events)) return e;
-    if (hz_status e = ledger_check_plan(who, m, txs, F, fee_plan_tokens, fee_idxs, (uint32_t)k, first_idx, p, true, l1_events)) return e;
+    if (hz_status e = ledger_check_plan(who, m, txs, F, fee_plan_tokens, fee_idxs, 1ull << k, first_idx, p, true, l1_events)) return e;
     for (size_t i = 0; i < m; i++)   // the planner is given receivers: a transfer to an address has none before the lookup
         if (txs[i].from_idx != 0 && txs[i].to_idx == 0) return set_err(HZ_ERR_ARG, "%s: tx %zu: to_idx = 0 (a transfer to an address) is not supported yet", who, i);
     ledger_plan_batch(n_l1, l1, m, txs, F, fee_plan_tokens, fee_idxs, p);
@@ -1259,7 +1558,7 @@ extern "C" hz_status hz_ledger_exit_accounts(hz_ledger* l, size_t n, const uint6
     }
     HZ_HIP(hipSetDevice(l->device));
     ledger_forget(l);   // the call's buffers are reused
-    hipStream_t s = state_stream(l->tree);
+    hipStream_t s = ledger_stream(l);
     HZ_HIP(l->ints.grow(n * 4));
     HZ_HIP(l->work.grow(n * 128));
     HZ_HIP(hipMemcpyAsync(l->ints.p, at.data(), n * 4, hipMemcpyHostToDevice, s));
@@ -1283,7 +1582,7 @@ extern "C" hz_status hz_ledger_plan_exits(size_t n_l1, const hz_l1tx* l1, size_t
     LedgerPlan p;
     size_t l1_events = 0;
     if (hz_status e = ledger_check_l1(who, n_l1, l1, first_idx, 1ull << k, &l1_events, true)) return e;
-    if (hz_status e = ledger_check_plan(who, m, txs, F, fee_plan_tokens, fee_idxs, (uint32_t)k, first_idx, p, true, l1_events, true)) return e;
+    if (hz_status e = ledger_check_plan(who, m, txs, F, fee_plan_tokens, fee_idxs, 1ull << k, first_idx, p, true, l1_events, true)) return e;
     for (size_t i = 0; i < m; i++)   // the planner is given receivers: a transfer to an address has none before the lookup
         if (txs[i].from_idx != 0 && txs[i].to_idx == 0) return set_err(HZ_ERR_ARG, "%s: tx %zu: to_idx = 0 (a transfer to an address) is not supported yet", who, i);
     ledger_plan_exits(n_l1, l1, m, txs, F, fee_plan_tokens, fee_idxs, p);
@@ -1314,5 +1613,59 @@ extern "C" hz_status hz_ledger_plan_exits(size_t n_l1, const hz_l1tx* l1, size_t
         if (exit_is_old0_out) exit_is_old0_out[x] = sh.is_old0[x];
         if (exit_old_key_out) exit_old_key_out[x] = sh.old_key[x];
     }
+    return HZ_OK;
+}
+
+// ---- L1 rows that create accounts, on a growing ledger -------------------------------------------------------------------
+extern "C" hz_status hz_ledger_apply_batch_creates(hz_ledger* l, size_t n_l1, const hz_l1tx* l1, const uint8_t* from_bjj, size_t m, const hz_l2tx* txs,
+                                                   const hz_l2sig* sigs, uint32_t flags, const uint64_t* aux_to_idx, uint32_t chain_id, uint32_t current_num_batch,
+                                                   size_t F, const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs, size_t n_sib, const hz_ledger_out* out,
+                                                   const hz_ledger_sig_out* sig_out, uint8_t* aux_to_idx_out, uint8_t* l1_flags_out, const hz_ledger_exit_out* exit_out,
+                                                   const hz_ledger_create_out* create_out) {
+    static_assert(sizeof(hz_ledger_create_out) == HZ_LEDGER_CREATE_ARRAYS * sizeof(uint8_t*), "hz_ledger_create_out is an array of pointers");
+    LedgerL1Run run;
+    run.n = n_l1;
+    run.tx = l1;
+    run.flags_out = l1_flags_out;
+    run.is_batch = true;
+    run.exits = true;
+    run.exit_out = exit_out;
+    run.creates = true;
+    run.from_bjj = from_bjj;
+    run.create_out = create_out;
+    return ledger_apply_addr(l, "hz_ledger_apply_batch_creates", run, m, txs, sigs, flags, aux_to_idx, chain_id, current_num_batch, F, fee_plan_tokens, fee_idxs, n_sib,
+                             out, sig_out, aux_to_idx_out);
+}
+
+extern "C" hz_status hz_ledger_create_outputs_dev(hz_ledger* l, hz_ledger_create_out* dev) {
+    if (!l || !dev) return set_err(HZ_ERR_ARG, "hz_ledger_create_outputs_dev: null argument");
+    if (!l->have_create_outputs)
+        return set_err(HZ_ERR_ARG, "hz_ledger_create_outputs_dev: no successful hz_ledger_apply_batch_creates since the ledger's last other call");
+    uint8_t** d = (uint8_t**)dev;
+    for (int a = 0; a < HZ_LEDGER_CREATE_ARRAYS; a++) d[a] = l->create_dev[a];
+    return HZ_OK;
+}
+
+extern "C" double hz_ledger_create_ms(const hz_ledger* l) { return l ? l->create_ms : 0.0; }
+
+extern "C" hz_status hz_ledger_plan_creates(size_t n_l1, const hz_l1tx* l1, const uint8_t* from_bjj, size_t m, const hz_l2tx* txs, size_t F,
+                                            const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs, int32_t growing, uint64_t capacity, uint64_t first_idx,
+                                            uint64_t size, uint64_t* aux_from_idx_out, uint64_t* out_idx_after_out, size_t* n_creates_out) {
+    const char* who = "hz_ledger_plan_creates";
+    if (capacity < 1 || capacity > HZ_LEDGER_MAX_CAPACITY || size > capacity || first_idx < 2)
+        return set_err(HZ_ERR_ARG, "%s: capacity = %llu, size = %llu, first_idx = %llu", who, (unsigned long long)capacity, (unsigned long long)size,
+                       (unsigned long long)first_idx);
+    size_t l1_events = 0, n_creates = 0;
+    std::vector<hz_l1tx> eff_l1;
+    std::vector<uint64_t> aux_from, idx_after;
+    if (hz_status e = ledger_check_creates(who, growing != 0, capacity, first_idx, size, n_l1, l1, from_bjj, &l1_events, eff_l1, aux_from, idx_after, &n_creates)) return e;
+    LedgerPlan p;
+    if (hz_status e = ledger_check_plan(who, m, txs, F, fee_plan_tokens, fee_idxs, size + n_creates, first_idx, p, true, l1_events, true)) return e;
+    const uint64_t last = first_idx + size + n_creates - 1;
+    for (size_t i = 0; i < n_l1 + m; i++) {
+        if (aux_from_idx_out) aux_from_idx_out[i] = i < n_l1 ? aux_from[i] : 0;
+        if (out_idx_after_out) out_idx_after_out[i] = i < n_l1 ? idx_after[i] : last;
+    }
+    if (n_creates_out) *n_creates_out = n_creates;
     return HZ_OK;
 }

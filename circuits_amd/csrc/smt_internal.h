@@ -32,5 +32,7 @@ void smt_apply_abort(hz_smt* t);
 // the empty tree again without a synchronise: for an owner whose every call on the tree ended in finish or abort
 void smt_clear(hz_smt* t);
 hipStream_t smt_stream(const hz_smt* t);
+// a call failed on the device behind its queued write-back: every public call answers HZ_ERR_HIP until hz_smt_reset
+bool smt_poisoned(const hz_smt* t);
 
 }  // namespace hz

@@ -315,6 +315,7 @@ void hz::smt_clear(hz_smt* t) {
 }
 
 hipStream_t hz::smt_stream(const hz_smt* t) { return t->r.s; }
+bool hz::smt_poisoned(const hz_smt* t) { return t->poisoned; }
 
 extern "C" hz_status hz_smt_apply(hz_smt* t, size_t m, const uint64_t* key, const uint8_t* fields, size_t n_sib, uint8_t* siblings_out, uint64_t* old_key_out,
                                   uint8_t* old_value_out, uint8_t* is_old0_out, uint8_t* fnc_out, uint8_t* old_root_out, uint8_t* new_root_out) {

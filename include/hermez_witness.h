@@ -566,7 +566,44 @@ hz_status hz_smt_plan(size_t m, const uint64_t* key, size_t n_sib, uint32_t* dep
  * LIFETIME. The exit tree and the exit leaves are those of the last successful call that applied a batch: every apply call (all six)
  * starts by emptying them, so after a refused call, and after a call of the other five, the tree is empty. A refused call leaves root,
  * planes and state tree untouched, as above.
- * OUT OF SCOPE: L1 transactions that create accounts or exit through a call other than hz_ledger_apply_batch_exits, an L1 amount with
+ * CREATES. An L1 row with from_idx == 0 creates an account: createAccount, createAccountDeposit,
+ * createAccountDepositTransfer, and the coordinator's L1 transactions. The state tree's shape changes, so only a GROWING ledger takes one:
+ *   hz_ledger_create_growing  a ledger of up to `capacity` accounts (1 .. 2^24; first_idx >= 2) whose state tree is an hz_smt of n_sib_max siblings it
+ *                       owns. The four planes are allocated once, [capacity][32] each; they do not grow by reallocation. hz_ledger_tree
+ *                       is NULL for it, hz_ledger_state_smt the tree. n_sib of every call: 1 .. n_sib_max; there is no k <= n_sib
+ *                       rule -- a leaf that would lie at depth >= n_sib is HZ_ERR_ARG from the tree's planner, before the update is launched
+ *   hz_ledger_load_accounts  0 <= n <= capacity consecutive accounts first_idx .. first_idx + n - 1 (n == 0: the genesis state, root 0).
+ *                       hz_ledger_load's leaf-range checks, first offender named, nothing touched; every field below r. A reload
+ *                       resets the tree first. hz_ledger_load is for dense ledgers, this call for growing ones
+ *   hz_ledger_size / _last_idx  live accounts; first_idx + size - 1 (first_idx - 1 when empty). Both kinds of ledger
+ *   hz_ledger_state_smt the state tree, borrowed: hz_smt_proofs / _root / _size work on it; NULL on a dense ledger
+ * All apply / verify / resolve calls above work on a growing ledger, over its live accounts, and keep refusing from_idx == 0; on the same
+ * 2^k accounts every output equals the dense ledger's byte for byte. After a HIP failure reported behind the state tree's queued
+ * write-back a growing ledger answers HZ_ERR_HIP until it is loaded again (hz_smt_apply's rule).
+ *   hz_ledger_apply_batch_creates  hz_ledger_apply_batch_exits with from_idx == 0 accepted in L1 rows. from_bjj[n_l1][32]: fromBjjCompressed
+ *                       of every L1 row, little-endian, read only where from_idx == 0 (NULL when no row creates). Row i creates account
+ *                       auxFromIdx = last idx + 1, last idx running over the rows. The new leaf: tokenID = token_id, nonce 0, ethAddr =
+ *                       from_eth_addr, sign = bit 255 of the key, ay = its bits 0 .. 253 reduced once modulo r (bit 254 is not read),
+ *                       balance 0. No nullifier applies to the load or the sender side; then the L1 arithmetic above runs from balance 0:
+ *                       eff_load = loadAmount, null_amount = amount != 0 && token_id != receiver's tokenID, underflow_ok, eff3,
+ *                       isAmountNullified as above. Processor 1 is an INSERT of the leaf after the row; the leaf-1 rows are the new
+ *                       leaf with balance 0, siblings1 those of the walk before the insert. Processor 2 is the L1 run's. A created
+ *                       account exists for every later row and for its own row's to_idx (a self-transfer): later L1 rows, L2 senders
+ *                       (signature verified against the new key), L2 receivers by index, address or key (the lowest index over live
+ *                       plus created accounts wins), L2 exits, fee slots. create_out (may be NULL; nullable host pointers):
+ *                       aux_from_idx, is_old0_1, old_key1, old_value1 [n_l1 + m] (zero for a row that creates nothing; old_key1 =
+ *                       old_value1 = 0 where is_old0_1 = 1), out_idx_after [n_l1 + m] (its first rows - 1 entries are imOutIdx),
+ *                       new_last_idx [1]. With no create row every output equals hz_ledger_apply_batch_exits' byte for byte, on either
+ *                       kind of ledger. A refused call does not raise the size. HZ_ERR_ARG beyond hz_ledger_apply_batch_exits': a create
+ *                       row on a dense ledger, from_bjj == NULL with a create row, size + creates > capacity, an L1 from_idx or to_idx
+ *                       above the row's current last idx (a create row: above its own new idx), a create row with to_idx == 1 or
+ *                       with an amount and to_idx == 0, a leaf at depth >= n_sib
+ *   hz_ledger_create_outputs_dev  create_out's arrays as DEVICE pointers of the last successful hz_ledger_apply_batch_creates
+ *   hz_ledger_create_ms device time of the two create kernels of the last hz_ledger_apply_batch_creates
+ *   hz_ledger_plan_creates  DIAGNOSTIC, no device: aux_from_idx_out / out_idx_after_out [n_l1 + m], *n_creates_out, and the argument errors
+ *                       above but the depth, for a ledger of `capacity` that holds `size` accounts (growing == 0: a dense one)
+ * OUT OF SCOPE: L1 transactions that create accounts or exit through a call other than hz_ledger_apply_batch_exits (creates:
+ * hz_ledger_apply_batch_creates on a growing ledger), an L1 amount with
  * to_idx == 0 (no receiver), exit trees of earlier batches kept resident, atomic (rqOffset) fields, a resident address index kept across
  * calls, batch (random linear combination) verification of signatures, more than one device per ledger. One thread at a time. */
 typedef struct hz_ledger hz_ledger;
@@ -664,6 +701,28 @@ hz_status hz_ledger_plan_exits(size_t n_l1, const hz_l1tx* l1, size_t m, const h
                                size_t* n_exits_out, uint32_t* exit_row_out, uint64_t* exit_key_out, int32_t* exit_prev_out, uint32_t* exit_perm_out,
                                uint8_t* exit_insert_out, uint8_t* exit_is_old0_out, uint64_t* exit_old_key_out);
 double hz_ledger_exit_ms(const hz_ledger* l);
+hz_status hz_ledger_create_growing(int32_t device, uint64_t capacity, uint64_t first_idx, int32_t n_sib_max, hz_ledger** out);
+hz_status hz_ledger_load_accounts(hz_ledger* l, uint64_t n, const uint8_t* e0, const uint8_t* balance, const uint8_t* ay, const uint8_t* eth_addr);
+uint64_t hz_ledger_size(const hz_ledger* l);
+uint64_t hz_ledger_last_idx(const hz_ledger* l);
+hz_smt* hz_ledger_state_smt(hz_ledger* l);
+#define HZ_LEDGER_CREATE_ARRAYS 6
+typedef struct {
+    uint8_t *aux_from_idx, *is_old0_1, *old_key1, *old_value1; /* [n_l1 + m]: zero for a row that creates nothing */
+    uint8_t* out_idx_after;                                    /* [n_l1 + m]: its first n_l1 + m - 1 rows are imOutIdx */
+    uint8_t* new_last_idx;                                     /* [1] */
+} hz_ledger_create_out;
+hz_status hz_ledger_apply_batch_creates(hz_ledger* l, size_t n_l1, const hz_l1tx* l1, const uint8_t* from_bjj /* [n_l1][32] or NULL */, size_t m,
+                                        const hz_l2tx* txs, const hz_l2sig* sigs, uint32_t flags, const uint64_t* aux_to_idx /* [m] or NULL */,
+                                        uint32_t chain_id, uint32_t current_num_batch, size_t F, const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs,
+                                        size_t n_sib, const hz_ledger_out* out, const hz_ledger_sig_out* sig_out, uint8_t* aux_to_idx_out,
+                                        uint8_t* l1_flags_out, const hz_ledger_exit_out* exit_out /* or NULL */,
+                                        const hz_ledger_create_out* create_out /* or NULL */);
+hz_status hz_ledger_create_outputs_dev(hz_ledger* l, hz_ledger_create_out* dev);
+double hz_ledger_create_ms(const hz_ledger* l);
+hz_status hz_ledger_plan_creates(size_t n_l1, const hz_l1tx* l1, const uint8_t* from_bjj, size_t m, const hz_l2tx* txs, size_t F,
+                                 const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs, int32_t growing, uint64_t capacity, uint64_t first_idx,
+                                 uint64_t size, uint64_t* aux_from_idx_out, uint64_t* out_idx_after_out, size_t* n_creates_out);
 
 /* Poseidon batch: n independent permutations of width t = n_inputs + 1 (2..7). ----------------
  * `in`  : [n][t-1] canonical elements; `out`: [n] digests (state[0] after the last round).
