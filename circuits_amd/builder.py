@@ -1066,9 +1066,22 @@ def ledger_create_batch_inputs(ledger, db_like, l1_txs, l2_txs, n_tx, n_levels, 
     return _ledger_batch_inputs(ledger, db_like, l1_txs, l2_txs, n_tx, n_levels, max_l1, max_fee, fee_tokens, fee_idxs, chain_id, host_outputs, verify, True, True)
 
 
-def _ledger_batch_inputs(ledger, db_like, l1_txs, l2_txs, n_tx, n_levels, max_l1, max_fee, fee_tokens, fee_idxs, chain_id, host_outputs, verify, exits, creates=False):
-    """ledger_batch_inputs (exits=False), ledger_exit_batch_inputs (exits=True) and ledger_create_batch_inputs (creates=True)
-    -> (inputs, device signals, nullified, new exit root[, new last idx])"""
+def ledger_atomic_batch_inputs(ledger, db_like, l1_txs, l2_txs, n_tx, n_levels, max_l1, max_fee, fee_tokens, fee_idxs, chain_id, host_outputs=True, verify=False):
+    """ledger_create_batch_inputs over L2 transactions that may be linked (rqOffset), through capi.Ledger.apply_batch_atomic: rqOffset,
+    rqTxCompressedDataV2, rqToEthAddr and rqToBjjAy are the transactions' instead of zeros, the message signed and verified holds them, and
+    the ledger refuses a batch whose links the circuit would reject (reason 13). As in BatchBuilder.build, a transaction with rqOffset and
+    no explicit rq fields gets them from its target before it is signed; explicit ones are kept as given. With no linked transaction the
+    result is ledger_create_batch_inputs'."""
+    return _ledger_batch_inputs(ledger, db_like, l1_txs, l2_txs, n_tx, n_levels, max_l1, max_fee, fee_tokens, fee_idxs, chain_id, host_outputs, verify, True, True, True)
+
+
+RQ_SIGNALS = ("rqOffset", "rqTxCompressedDataV2", "rqToEthAddr", "rqToBjjAy")
+
+
+def _ledger_batch_inputs(ledger, db_like, l1_txs, l2_txs, n_tx, n_levels, max_l1, max_fee, fee_tokens, fee_idxs, chain_id, host_outputs, verify, exits, creates=False,
+                         atomic=False):
+    """ledger_batch_inputs (exits=False), ledger_exit_batch_inputs (exits=True), ledger_create_batch_inputs (creates=True) and
+    ledger_atomic_batch_inputs (atomic=True) -> (inputs, device signals, nullified, new exit root[, new last idx])"""
     if len(l1_txs) > max_l1:
         raise ValueError("too many L1 txs")
     if len(l1_txs) + len(l2_txs) > n_tx:
@@ -1081,11 +1094,22 @@ def _ledger_batch_inputs(ledger, db_like, l1_txs, l2_txs, n_tx, n_levels, max_l1
     plan = list(fee_tokens) + [0] * (max_fee - len(fee_tokens))
     idxs = list(fee_idxs) + [0] * (max_fee - len(fee_idxs))
     padded = l2_txs + [{}] * (n_tx - n_l1 - len(l2_txs))
+    if atomic:   # the rq fields a signer commits to, from the target as it stands in the batch (BatchBuilder.build does the same)
+        rows = l1_txs + l2_txs
+        for i, t in enumerate(l2_txs, n_l1):
+            k = t.get("rqOffset", 0)
+            if k and "rqTxCompressedDataV2" not in t:
+                j = i + k if k <= 3 else i - (8 - k)
+                if not (n_l1 <= j < len(rows)):
+                    raise ValueError("rqOffset %d of tx %d does not point at an L2 tx of this batch" % (k, i))
+                t["rqTxCompressedDataV2"] = build_tx_compressed_data_v2(rows[j])
+                t["rqToEthAddr"] = rows[j].get("toEthAddr", 0)
+                t["rqToBjjAy"] = rows[j].get("toBjjAy", 0)
     if verify:
         for t in padded:
             if t.get("fromIdx", 0) and "signer" in t:
                 t.update(t["signer"].sign_msg(build_hash_sig(t, chain_id)))
-    apply = ledger.apply_batch_creates if creates else ledger.apply_batch_exits if exits else ledger.apply_batch
+    apply = ledger.apply_batch_atomic if atomic else ledger.apply_batch_creates if creates else ledger.apply_batch_exits if exits else ledger.apply_batch
     out = apply(l1_txs, padded, plan, idxs, chain_id, db_like.num_batch + 1, n_sib=n_levels + 1, verify=verify)
     flags = [int(x) for x in out["l1_flags"]]
     inp = {"oldLastIdx": db_like.last_idx, "globalChainID": chain_id, "currentNumBatch": db_like.num_batch + 1, "feePlanTokens": plan, "feeIdxs": idxs}
@@ -1110,6 +1134,8 @@ def _ledger_batch_inputs(ledger, db_like, l1_txs, l2_txs, n_tx, n_levels, max_l1
         vals = {"txCompressedData": build_tx_compressed_data(t, chain_id), "amountF": t.get("amountF", 0), "txCompressedDataV2": build_tx_compressed_data_v2(t),
                 "fromIdx": t.get("fromIdx", 0), "toIdx": t.get("toIdx", 0), "toBjjAy": t.get("toBjjAy", 0), "toEthAddr": t.get("toEthAddr", 0),
                 "maxNumBatch": t.get("maxNumBatch", 0), "s": sig["s"], "r8x": sig["r8x"], "r8y": sig["r8y"], "fromBjjCompressed": [0] * 256}
+        if atomic and t.get("fromIdx", 0):
+            vals.update({k: t.get(k, 0) for k in RQ_SIGNALS})
         for k in names:
             inp[k].append(vals.get(k, 0))
     inp["imOnChain"] = inp["onChain"][:n_tx - 1]

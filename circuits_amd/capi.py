@@ -77,6 +77,7 @@ EXPORTS = [
     "hz_ledger_apply_batch_exits", "hz_ledger_exit_outputs_dev", "hz_ledger_exit_tree", "hz_ledger_exit_accounts", "hz_ledger_plan_exits", "hz_ledger_exit_ms",
     "hz_ledger_create_growing", "hz_ledger_load_accounts", "hz_ledger_size", "hz_ledger_last_idx", "hz_ledger_state_smt", "hz_ledger_apply_batch_creates",
     "hz_ledger_create_outputs_dev", "hz_ledger_create_ms", "hz_ledger_plan_creates",
+    "hz_ledger_apply_batch_atomic", "hz_ledger_verify_l2_atomic", "hz_ledger_plan_atomic", "hz_ledger_rq_ms",
 ]
 
 
@@ -114,6 +115,38 @@ def l2sig_array(txs):
             getattr(g, member)[:] = list((int(t.get(key, 0)) % (1 << 256)).to_bytes(32, "little"))
         g.max_num_batch = t.get("maxNumBatch", 0)
         g.to_bjj_sign = min(int(t.get("toBjjSign", 0)), 255)
+    return arr
+
+
+class hz_l2rq(ctypes.Structure):
+    _fields_ = [("rq_tx_compressed_data_v2", ctypes.c_uint8 * 32), ("rq_to_eth_addr", ctypes.c_uint8 * 32), ("rq_to_bjj_ay", ctypes.c_uint8 * 32),
+                ("rq_offset", ctypes.c_uint8)]
+
+
+LEDGER_RQ_REASON = 13   # the rq fields of a row are not its target's link fields
+
+
+def l2rq_array(txs):
+    """[{rqOffset, rqTxCompressedDataV2, rqToEthAddr, rqToBjjAy}] (builder's transaction dictionaries; missing keys are 0) -> hz_l2rq array,
+    or None when no transaction holds any of them (the library then checks no link). The fields are passed on as given: explicit, never
+    derived from a neighbour. A value that does not fit its member -- a field outside 0 .. 2^256 - 1, an offset outside 0 .. 255 -- raises
+    ValueError: nothing is reduced or clamped on the way. What fits and is not valid (a field >= r, an offset above 7) is the library's
+    to refuse."""
+    keys = (("rq_tx_compressed_data_v2", "rqTxCompressedDataV2"), ("rq_to_eth_addr", "rqToEthAddr"), ("rq_to_bjj_ay", "rqToBjjAy"))
+    if not any(t.get("rqOffset", 0) or any(t.get(key, 0) for _, key in keys) for t in txs):
+        return None
+    arr = (hz_l2rq * max(len(txs), 1))()
+    for i, t in enumerate(txs):
+        g = arr[i]
+        for member, key in keys:
+            v = int(t.get(key, 0))
+            if not 0 <= v < 1 << 256:
+                raise ValueError("tx %d: %s = %d does not fit 32 bytes" % (i, key, v))
+            getattr(g, member)[:] = list(v.to_bytes(32, "little"))
+        k = int(t.get("rqOffset", 0))
+        if not 0 <= k <= 255:
+            raise ValueError("tx %d: rqOffset = %d does not fit a byte" % (i, k))
+        g.rq_offset = k
     return arr
 
 
@@ -334,7 +367,11 @@ class Lib:
         c.hz_ledger_apply_batch_creates.argtypes = [vp, sz, vp, vp, sz, vp, vp, u32, vp, u32, u32, sz, vp, vp, sz, vp, vp, vp, vp, vp, vp]
         c.hz_ledger_create_outputs_dev.argtypes = [vp, vp]
         c.hz_ledger_plan_creates.argtypes = [sz, vp, vp, sz, vp, sz, vp, vp, ctypes.c_int32, u64, u64, u64, vp, vp, ctypes.POINTER(sz)]
-        for f in ("hz_ledger_device_ms", "hz_ledger_semantic_ms", "hz_ledger_sig_ms", "hz_ledger_resolve_ms", "hz_ledger_l1_ms", "hz_ledger_exit_ms", "hz_ledger_create_ms"):
+        c.hz_ledger_apply_batch_atomic.argtypes = [vp, sz, vp, vp, sz, vp, vp, vp, u32, vp, u32, u32, sz, vp, vp, sz, vp, vp, vp, vp, vp, vp]
+        c.hz_ledger_verify_l2_atomic.argtypes = [vp, sz, vp, vp, vp, u32, u32, vp, vp]
+        c.hz_ledger_plan_atomic.argtypes = [sz, sz, vp, vp, vp, vp, vp]
+        for f in ("hz_ledger_device_ms", "hz_ledger_semantic_ms", "hz_ledger_sig_ms", "hz_ledger_resolve_ms", "hz_ledger_l1_ms", "hz_ledger_exit_ms", "hz_ledger_create_ms",
+                  "hz_ledger_rq_ms"):
             getattr(c, f).argtypes = [vp]
             getattr(c, f).restype = ctypes.c_double
 
@@ -449,6 +486,20 @@ class Lib:
                                                   plan.ctypes.data, idxs.ctypes.data, 1 if growing else 0, capacity, first_idx, size, aux.ctypes.data,
                                                   after.ctypes.data, ctypes.byref(n)))
         return {"aux_from_idx": aux[:n_l1 + m].tolist(), "out_idx_after": after[:n_l1 + m].tolist(), "n_creates": n.value}
+
+    def ledger_plan_atomic(self, n_l1, txs, rq=None):
+        """hz_ledger_plan_atomic, a diagnostic: where the atomic link of every L2 transaction points in a batch of n_l1 L1 rows and the
+        transactions txs, and whether it holds; no device needed. txs: transaction dictionaries with the signed destination and rqOffset,
+        rqTxCompressedDataV2, rqToEthAddr, rqToBjjAy; rq: a prebuilt hz_l2rq array instead. -> {"target_row": [m] (-1: the comparison is
+        against zeros), "verdict": [m] (0 or 13)}"""
+        import numpy as np
+        arr, sigs = l2tx_array(txs), l2sig_array(txs)
+        rq = l2rq_array(txs) if rq is None else rq
+        m = len(txs)
+        target, verdict = np.zeros(max(m, 1), dtype=np.int64), np.zeros(max(m, 1), dtype=np.uint8)
+        self._check(self.c.hz_ledger_plan_atomic(n_l1, m, ctypes.addressof(arr), ctypes.addressof(sigs), ctypes.addressof(rq) if rq is not None else None,
+                                                 target.ctypes.data, verdict.ctypes.data))
+        return {"target_row": target[:m].tolist(), "verdict": verdict[:m].tolist()}
 
     def ledger_plan_l2(self, txs, fee_plan_tokens, fee_idxs, k, first_idx=256):
         """hz_ledger_plan_l2, a diagnostic: the host planner alone (integers only, no device needed). txs: transaction dictionaries or an
@@ -1021,13 +1072,27 @@ class Ledger(_Resident):
     def verify_l2(self, txs, chain_id, current_num_batch, outputs=False):
         """the mempool filter: one verdict per transaction against the resident keys -- 0 accepted (or a NOP), 7 signature rejected, 8
         maxNumBatch expired -- as a uint8 array; nothing resident changes. outputs=True: (verdicts, the three signature arrays)"""
+        return self._verify_l2(txs, chain_id, current_num_batch, outputs, False)
+
+    def verify_l2_atomic(self, txs, chain_id, current_num_batch, outputs=False, rq=None):
+        """verify_l2 over transactions that carry atomic links (rqOffset, rqTxCompressedDataV2, rqToEthAddr, rqToBjjAy): the list is a
+        batch of its own, row i is transaction i, and 13 marks a transaction whose rq fields are not the link fields of the row its offset
+        names; 7 and 8 come first where they hold. The message hashed is the one with the rq fields. rq: a prebuilt hz_l2rq array."""
+        return self._verify_l2(txs, chain_id, current_num_batch, outputs, True, rq)
+
+    def _verify_l2(self, txs, chain_id, current_num_batch, outputs, atomic, rq=None):
         import numpy as np
         arr, sigs = l2tx_array(txs), l2sig_array(txs)
         m = len(txs)
         verdict = np.zeros(max(m, 1), dtype=np.uint8)
         sig_out, sig_ptrs = self._sig_out(m, outputs, None)
-        self.L._check(self.L.c.hz_ledger_verify_l2(self.h, m, ctypes.addressof(arr), ctypes.addressof(sigs), chain_id, current_num_batch, verdict.ctypes.data,
-                                                   ctypes.addressof(sig_ptrs) if outputs else None))
+        if atomic:
+            rq = l2rq_array(txs) if rq is None else rq
+            self.L._check(self.L.c.hz_ledger_verify_l2_atomic(self.h, m, ctypes.addressof(arr), ctypes.addressof(sigs), ctypes.addressof(rq) if rq is not None else None,
+                                                              chain_id, current_num_batch, verdict.ctypes.data, ctypes.addressof(sig_ptrs) if outputs else None))
+        else:
+            self.L._check(self.L.c.hz_ledger_verify_l2(self.h, m, ctypes.addressof(arr), ctypes.addressof(sigs), chain_id, current_num_batch, verdict.ctypes.data,
+                                                       ctypes.addressof(sig_ptrs) if outputs else None))
         return (verdict[:m], sig_out) if outputs else verdict[:m]
 
     def sig_outputs_dev(self):
@@ -1149,6 +1214,26 @@ class Ledger(_Resident):
         account last_idx + 1 for each, in row order, and every later row may name it. Returns apply_batch_exits' dictionary plus
         aux_from_idx, is_old0_1, old_key1, old_value1, out_idx_after ([rows, 32]) and new_last_idx ([1, 32]). from_bjj: the keys as a
         prebuilt [n_l1, 32] array (from_bjj_array) to go with a prebuilt hz_l1tx array."""
+        return self._apply_batch_creates(l1_txs, txs, fee_plan_tokens, fee_idxs, chain_id, current_num_batch, n_sib, verify, aux_to_idx, outputs, into, sigs, from_bjj)
+
+    def apply_batch_atomic(self, l1_txs, txs, fee_plan_tokens, fee_idxs, chain_id, current_num_batch, n_sib=None, verify=False, aux_to_idx=None, outputs=True,
+                           into=None, sigs=None, from_bjj=None, rq=None):
+        """apply_batch_creates over L2 transactions that may carry atomic links: rqOffset (0 .. 7) names a row of the batch, and
+        rqTxCompressedDataV2, rqToEthAddr, rqToBjjAy -- explicit, what the signer committed to -- must equal that row's txCompressedDataV2
+        and signed destination, or be zero where the offset is 0 or names an L1 row, a NOP or a place outside the batch. A mismatch refuses
+        the batch with reason 13, verified or not; sig_l2_hash is the message with the rq fields. rq: a prebuilt hz_l2rq array
+        (l2rq_array), False: none at all. Returns apply_batch_creates' dictionary."""
+        if rq is None and not isinstance(txs, ctypes.Array):
+            rq = l2rq_array(txs)
+        return self._apply_batch_creates(l1_txs, txs, fee_plan_tokens, fee_idxs, chain_id, current_num_batch, n_sib, verify, aux_to_idx, outputs, into, sigs, from_bjj,
+                                         atomic=True, rq=rq if rq is not False else None)
+
+    def rq_ms(self):
+        """device time of the link kernel of the last apply_batch_atomic / verify_l2_atomic (0.0 when none ran)"""
+        return self.L.c.hz_ledger_rq_ms(self.h)
+
+    def _apply_batch_creates(self, l1_txs, txs, fee_plan_tokens, fee_idxs, chain_id, current_num_batch, n_sib, verify, aux_to_idx, outputs, into, sigs, from_bjj,
+                             atomic=False, rq=None):
         import numpy as np
         n_sib = self.k if n_sib is None else n_sib
         prebuilt = isinstance(l1_txs, ctypes.Array)
@@ -1179,13 +1264,16 @@ class Ledger(_Resident):
                 exit_ptrs[i] = more[name].ctypes.data
             for i, name in enumerate(LEDGER_CREATE_ARRAYS):
                 create_ptrs[i] = more[name].ctypes.data
-        self.L._check(self.L.c.hz_ledger_apply_batch_creates(self.h, n_l1, ctypes.addressof(l1), bjj.ctypes.data if bjj is not None else None, m, ctypes.addressof(arr),
-                                                             ctypes.addressof(sigs) if sigs is not False else None, LEDGER_VERIFY_SIGS if verify else 0,
-                                                             aux.ctypes.data if aux is not None else None, chain_id, current_num_batch, F, plan.ctypes.data,
-                                                             idxs.ctypes.data, n_sib, ctypes.addressof(ptrs) if outputs else None,
-                                                             ctypes.addressof(sig_ptrs) if outputs and verify else None, aux_out.ctypes.data if outputs and R else None,
-                                                             flags.ctypes.data if outputs and n_l1 else None, ctypes.addressof(exit_ptrs) if outputs else None,
-                                                             ctypes.addressof(create_ptrs) if outputs else None))
+        head = [self.h, n_l1, ctypes.addressof(l1), bjj.ctypes.data if bjj is not None else None, m, ctypes.addressof(arr),
+                ctypes.addressof(sigs) if sigs is not False else None]
+        tail = [LEDGER_VERIFY_SIGS if verify else 0, aux.ctypes.data if aux is not None else None, chain_id, current_num_batch, F, plan.ctypes.data, idxs.ctypes.data,
+                n_sib, ctypes.addressof(ptrs) if outputs else None, ctypes.addressof(sig_ptrs) if outputs and verify else None,
+                aux_out.ctypes.data if outputs and R else None, flags.ctypes.data if outputs and n_l1 else None, ctypes.addressof(exit_ptrs) if outputs else None,
+                ctypes.addressof(create_ptrs) if outputs else None]
+        if atomic:   # hz_ledger_apply_batch_creates' argument list with rq behind sigs
+            self.L._check(self.L.c.hz_ledger_apply_batch_atomic(*head, ctypes.addressof(rq) if rq is not None else None, *tail))
+        else:
+            self.L._check(self.L.c.hz_ledger_apply_batch_creates(*head, *tail))
         out.update(sig_out)
         out.update(more)
         return out

@@ -41,6 +41,11 @@
 //   k_ledger_create        a lane per create row, before everything else of the call: the new account's static fields into its plane
 //                          slot beyond `live`. From there the pipeline above sees a deposit on auxFromIdx; the tree's planner makes it an insert
 //   k_ledger_create_pack   a lane per row, behind the tree update: auxFromIdx, isOld0_1, oldKey1, oldValue1, the last idx after the row
+// hz_ledger_apply_batch_atomic takes the atomic link of every L2 transaction, hz_l2rq (ledger_rq.h): the message kernel
+// hashes the transaction's own rq fields, and
+//   k_ledger_rq            a lane per L2 transaction, behind the message kernel and before the one synchronise: the rq fields against the
+//                          link fields of the row rqOffset names; a mismatch lowers the failure word with reason 13
+// runs whether or not signatures are verified; without HZ_LEDGER_VERIFY_SIGS k_ledger_sig_v2 (ledger_sig.hip) writes the V2 rows it reads.
 // Values are plain 256-bit integers in eight 32-bit limbs (the Fc container of fr.h, nothing is reduced modulo r); deltas are
 // two's complement: every true prefix is below 2^220 in magnitude, so a set top bit means "negative"; the arithmetic is u256.h's, shared
 // with ledger_sig.h. Buffers and block offsets are hostutil.h's, the event holder resident.h's; the stream is the tree's (state_stream).
@@ -62,6 +67,7 @@
 #include "ledger_l1.h"
 #include "ledger_exit.h"
 #include "ledger_create.h"
+#include "ledger_rq.h"
 #include "smt_internal.h"
 #include "smt_plan.h"
 
@@ -69,7 +75,7 @@
 #define HZ_LEDGER_MAX_TX (1u << 20)
 #define HZ_LEDGER_MAX_F 64u
 #define HZ_LEDGER_CHUNK 64u   // transactions per lane of the fee scan
-#define HZ_LEDGER_REASONS 13u   // refusal reasons 1 .. 12; 0 is none
+#define HZ_LEDGER_REASONS 14u   // refusal reasons 1 .. 13; 0 is none
 
 namespace hz {
 
@@ -306,20 +312,58 @@ __global__ __launch_bounds__(64) void k_ledger_resolve_pick(const int32_t* __res
     out[i] = a != HZ_RESOLVE_NONE ? first_idx + a : 0ull;
 }
 
+// a lane per L2 transaction, row n_l1 + i of n_l1 + m: its rq fields against its target's link fields (ledger_rq.h). v2: the message
+// kernel's (or k_ledger_sig_v2's) rows of this call, written by an earlier kernel of the same stream; a NOP target's row is zero there
+// already, its toEthAddr / toBjjAy are masked here
+__global__ __launch_bounds__(64) void k_ledger_rq(const hz_l2tx* __restrict__ txs, const hz_l2sig* __restrict__ sigs, const uint8_t* __restrict__ rq,
+                                                  const uint8_t* __restrict__ v2, uint32_t* __restrict__ fail_word, uint8_t* __restrict__ verdict, uint32_t m,
+                                                  uint32_t n_l1, uint32_t unit_base) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    if (txs[i].from_idx == 0) return;   // a NOP's entry is not looked at
+    const uint8_t* off = rq + (size_t)3 * m * 32;
+    const int64_t row = rq_target_row((uint64_t)n_l1 + i, off[i], n_l1, (uint64_t)n_l1 + m);
+    Fc t_v2 = fc_zero(), t_eth = fc_zero(), t_ay = fc_zero();
+    if (row >= 0) {
+        const uint32_t j = (uint32_t)(row - (int64_t)n_l1);   // n_l1 <= row < n_l1 + m
+        if (txs[j].from_idx != 0) {
+            t_v2 = load_fr(v2 + (size_t)j * 32);
+            t_eth = resolve_load32(sigs[j].to_eth_addr);
+            t_ay = resolve_load32(sigs[j].to_bjj_ay);
+        }
+    }
+    const bool ok = rq_fields_match(load_fr(rq + (size_t)i * 32), load_fr(rq + ((size_t)m + i) * 32), load_fr(rq + ((size_t)2 * m + i) * 32), t_v2, t_eth, t_ay);
+    if (!ok) {
+        if (verdict && verdict[i] == 0u) verdict[i] = (uint8_t)HZ_RQ_REASON;   // 7 and 8 stay
+        if (fail_word) atomicMin(fail_word, ((unit_base + i) << 8) | HZ_RQ_REASON);
+    }
+}
+
 static const char* const LEDGER_REASON[HZ_LEDGER_REASONS] = {"", "the sender's token is not the transaction's", "the nonce is not the sender's current nonce",
                                              "the sender's balance is below amount + fee", "the receiver's token is not the transaction's",
                                              "a new balance reaches 2^192", "the fee account's token is not the slot's plan token",
                                              "the signature is rejected", "max_num_batch has expired",
                                               "no account holds the signed destination with the transaction's token",
                                               "the receiver's ethAddr is not the signed to_eth_addr", "the receiver's key is not the signed to_bjj_ay / to_bjj_sign",
-                                              "the sender's nonce is 2^40 - 1: the next nonce is not a leaf field"};
+                                              "the sender's nonce is 2^40 - 1: the next nonce is not a leaf field",
+                                              "the rq fields are not the link fields of the row rq_offset names"};
 
 // ledger_sig.hip
 hipError_t launch_ledger_sig(const hz_l2tx* d_txs, const hz_l2sig* d_sigs, uint32_t chain_id, uint32_t current_num_batch, uint8_t* d_tcd, uint8_t* d_v2, uint8_t* d_hash,
                              const uint8_t* planes, const void* b8_table, uint32_t N, uint64_t first_idx, uint32_t* d_fail_word, uint8_t* d_verdict, uint32_t m,
-                             hipStream_t s, uint32_t unit_base = 0);
+                             hipStream_t s, uint32_t unit_base = 0, const uint8_t* d_rq = nullptr);
+hipError_t launch_ledger_sig_v2(const hz_l2tx* d_txs, const hz_l2sig* d_sigs, uint8_t* d_v2, uint32_t m, hipStream_t s);
+void ledger_sig_link_fields_host(const hz_l2tx& tx, const hz_l2sig& sig, Fc* v2, Fc* eth, Fc* ay);
 void ledger_sig_b8_table_host(void* out);
 size_t ledger_sig_b8_table_bytes();
+
+// the link check over the m L2 rows behind n_l1 L1 rows; d_v2 as an earlier kernel of stream s left it
+static hipError_t launch_ledger_rq(const hz_l2tx* d_txs, const hz_l2sig* d_sigs, const uint8_t* d_rq, const uint8_t* d_v2, uint32_t* d_fail_word, uint8_t* d_verdict, uint32_t m,
+                            uint32_t n_l1, hipStream_t s, uint32_t unit_base) {
+    if (m == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_ledger_rq, dim3((m + 63) / 64), dim3(64), 0, s, d_txs, d_sigs, d_rq, d_v2, d_fail_word, d_verdict, m, n_l1, unit_base);
+    return hipGetLastError();
+}
 
 }  // namespace hz
 
@@ -377,6 +421,11 @@ struct hz_ledger {
     bool have_create_outputs = false;
     DevEvent ec0, ec1, ec2, ec3;   // around k_ledger_create, around k_ledger_create_pack
     double create_ms = 0.0;
+    // atomic links (hz_ledger_apply_batch_atomic / _verify_l2_atomic): the rq fields plane-major, [3][m][32], then the m offsets
+    DevBuf rq_in;
+    PinnedBuf h_rq;
+    DevEvent eq0, eq1;   // around k_ledger_rq
+    double rq_ms = 0.0;
     ~hz_ledger() {
         if (exit) hz_smt_destroy(exit);
         if (smt) hz_smt_destroy(smt);
@@ -392,6 +441,16 @@ static void ledger_exit_reset(hz_ledger* l) {
     l->exit_keys.clear();
     l->exit_ms = 0.0;
 }
+
+// the rq entries are copied to the device from a pinned buffer the ledger reuses: a call that returns before its synchronise waits for
+// the stream here, so the next call does not fill the buffer under a copy still in flight
+struct LedgerDrain {
+    hipStream_t s = nullptr;
+    bool armed = false;
+    ~LedgerDrain() {
+        if (armed) (void)hipStreamSynchronize(s);
+    }
+};
 
 // a prepared update of the exit tree -- or of a growing ledger's state tree -- that does not reach smt_apply_finish did not happen
 struct LedgerExitGuard {
@@ -485,6 +544,8 @@ struct LedgerL1Run {
     const hz_ledger_create_out* create_out = nullptr;
     const uint64_t *aux_from = nullptr, *idx_after = nullptr;
     size_t n_creates = 0;
+    // hz_ledger_apply_batch_atomic: the links of the L2 rows, [m] or null (no transaction links: nothing to check)
+    const hz_l2rq* rq = nullptr;
 };
 
 // the argument checks of an L1 run that may create accounts; -> the events it makes, the rows as the pipeline takes them
@@ -599,7 +660,7 @@ static hz_status ledger_open(hz_ledger* l) {
     HZ_HIP(l->planes.alloc((size_t)4 * l->N * 32));
     HZ_HIP(l->h_fail.grow(64));
     for (DevEvent* e : {&l->e0, &l->e1, &l->e2, &l->es0, &l->es1, &l->er0, &l->er1, &l->el0, &l->el1, &l->ex0, &l->ex1, &l->ex2, &l->ex3, &l->ex_tree, &l->ec0,
-                        &l->ec1, &l->ec2, &l->ec3})
+                        &l->ec1, &l->ec2, &l->ec3, &l->eq0, &l->eq1})
         HZ_HIP(e->create());
     return HZ_OK;
 }
@@ -816,6 +877,37 @@ static hz_status ledger_sig_prepare(hz_ledger* l, size_t m, const hz_l2sig* sigs
     for (int a = 0; a < 3; a++) l->sig_dev[a] = at + (size_t)a * rows * 32;
     l->verdict_dev = at + rows * 96;
     if (m) HZ_HIP(hipMemcpyAsync(l->sig_in.p, sigs, m * sizeof(hz_l2sig), hipMemcpyHostToDevice, s));
+    return HZ_OK;
+}
+
+// the argument checks of the atomic links; a NOP's entry is not looked at
+static hz_status ledger_check_rq(const char* who, size_t m, const hz_l2tx* txs, const hz_l2rq* rq) {
+    if (!rq) return HZ_OK;
+    for (size_t i = 0; i < m; i++) {
+        if (txs[i].from_idx == 0) continue;
+        const hz_l2rq& q = rq[i];
+        if (q.rq_offset > HZ_RQ_MAX_OFFSET) return set_err(HZ_ERR_ARG, "%s: tx %zu: rq_offset = %u (0 .. 7)", who, i, (unsigned)q.rq_offset);
+        const uint8_t* f[3] = {q.rq_tx_compressed_data_v2, q.rq_to_eth_addr, q.rq_to_bjj_ay};
+        static const char* const name[3] = {"rq_tx_compressed_data_v2", "rq_to_eth_addr", "rq_to_bjj_ay"};
+        for (int a = 0; a < 3; a++)
+            if (!canon_lt_p(f[a])) return set_err(HZ_ERR_INPUT, "%s: tx %zu: %s is not below the field's modulus", who, i, name[a]);
+    }
+    return HZ_OK;
+}
+
+// the links on the device as the kernels read them: the three fields plane-major, [3][m][32], then the m offsets
+static hz_status ledger_rq_upload(hz_ledger* l, size_t m, const hz_l2rq* rq, hipStream_t s) {
+    const size_t bytes = m * 97;
+    HZ_HIP(l->h_rq.grow(bytes));
+    HZ_HIP(l->rq_in.grow(bytes));
+    uint8_t* h = (uint8_t*)l->h_rq.p;
+    for (size_t i = 0; i < m; i++) {
+        memcpy(h + i * 32, rq[i].rq_tx_compressed_data_v2, 32);
+        memcpy(h + (m + i) * 32, rq[i].rq_to_eth_addr, 32);
+        memcpy(h + (2 * m + i) * 32, rq[i].rq_to_bjj_ay, 32);
+        h[3 * m * 32 + i] = rq[i].rq_offset;
+    }
+    HZ_HIP(hipMemcpyAsync(l->rq_in.p, h, bytes, hipMemcpyHostToDevice, s));
     return HZ_OK;
 }
 
@@ -1041,6 +1133,13 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
         if (hz_status e = ledger_sig_prepare(l, m, sigs, s, with_sigs)) return e;
     const hz_l2sig* d_dest = by_addr ? (const hz_l2sig*)l->sig_in.p : nullptr;   // the signed destinations, for reasons 10 and 11 and the zero-amount rows
     if (by_addr) HZ_HIP(l->aux_rows.grow((R ? R : 1) * 32));
+    const bool links = run.rq != nullptr && m != 0;   // (an atomic call comes through ledger_apply_addr: sigs are uploaded, the three arrays have room)
+    LedgerDrain drain;
+    if (links) {
+        drain.s = s;
+        drain.armed = true;
+        if (hz_status e = ledger_rq_upload(l, m, run.rq, s)) return e;
+    }
     if (run.is_batch) HZ_HIP(l->l1_flags.grow(n_l1 ? n_l1 : 1));
 
     // ---- the semantic kernels
@@ -1079,12 +1178,24 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
     if (with_sigs) {   // they read the planes and the uploads only: any place before the failure-word read would do
         HZ_HIP(hipEventRecord(l->es0, s));
         HZ_HIP(launch_ledger_sig(d_txs + n_l1, (const hz_l2sig*)l->sig_in.p, chain_id, current_num_batch, l->sig_dev[0], l->sig_dev[1], l->sig_dev[2],
-                                 (const uint8_t*)l->planes.p, l->b8_table.p, N, l->first_idx, d_fail, nullptr, m32, s, L32));
+                                 (const uint8_t*)l->planes.p, l->b8_table.p, N, l->first_idx, d_fail, nullptr, m32, s, L32, links ? (const uint8_t*)l->rq_in.p : nullptr));
         HZ_HIP(hipEventRecord(l->es1, s));
+    }
+    if (links) {   // reason 13, verified or not: the V2 rows are the message kernel's, or those of its packing alone
+        if (!with_sigs) HZ_HIP(launch_ledger_sig_v2(d_txs + n_l1, (const hz_l2sig*)l->sig_in.p, l->sig_dev[1], m32, s));
+        HZ_HIP(hipEventRecord(l->eq0, s));
+        HZ_HIP(launch_ledger_rq(d_txs + n_l1, (const hz_l2sig*)l->sig_in.p, (const uint8_t*)l->rq_in.p, (const uint8_t*)l->sig_dev[1], d_fail, nullptr, m32, L32, s, L32));
+        HZ_HIP(hipEventRecord(l->eq1, s));
     }
     HZ_HIP(hipEventRecord(l->e1, s));
     HZ_HIP(hipMemcpyAsync(l->h_fail.p, d_fail, 4, hipMemcpyDeviceToHost, s));
     HZ_HIP(hipStreamSynchronize(s));   // the one round trip: nothing resident has been written yet
+    drain.armed = false;
+    if (links) {
+        float rq_ms = 0;
+        HZ_HIP(hipEventElapsedTime(&rq_ms, l->eq0, l->eq1));
+        l->rq_ms = rq_ms;
+    }
     const uint32_t word = *(const uint32_t*)l->h_fail.p;
     if (word != 0xFFFFFFFFu) {
         const uint32_t unit = word >> 8, reason = word & 0xFFu;
@@ -1252,32 +1363,57 @@ extern "C" hz_status hz_ledger_apply_l2_signed(hz_ledger* l, size_t m, const hz_
     return ledger_apply(l, "hz_ledger_apply_l2_signed", m, txs, sigs, true, chain_id, current_num_batch, F, fee_plan_tokens, fee_idxs, n_sib, out, sig_out);
 }
 
-extern "C" hz_status hz_ledger_verify_l2(hz_ledger* l, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, uint32_t chain_id, uint32_t current_num_batch,
-                                         uint8_t* verdict_out, const hz_ledger_sig_out* sig_out) {
-    const char* who = "hz_ledger_verify_l2";
+// hz_ledger_verify_l2, and hz_ledger_verify_l2_atomic with the links of the m transactions (rows 0 .. m - 1 of a batch without L1 rows)
+static hz_status ledger_verify(hz_ledger* l, const char* who, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, const hz_l2rq* rq, uint32_t chain_id,
+                               uint32_t current_num_batch, uint8_t* verdict_out, const hz_ledger_sig_out* sig_out) {
     if (hz_status e = ledger_ready(l, who)) return e;
     if (m && (!txs || !verdict_out)) return set_err(HZ_ERR_ARG, "%s: null argument", who);
     if (m > HZ_LEDGER_MAX_TX) return set_err(HZ_ERR_ARG, "%s: %zu transactions in one call (at most %u)", who, m, HZ_LEDGER_MAX_TX);
     if (hz_status e = ledger_check_txs(who, m, txs, l->first_idx, l->live)) return e;
     if (hz_status e = ledger_check_sigs(who, m, txs, sigs, chain_id)) return e;
+    if (hz_status e = ledger_check_rq(who, m, txs, rq)) return e;
+    const bool links = rq != nullptr && m != 0;
     ledger_forget(l);
     HZ_HIP(hipSetDevice(l->device));
     hipStream_t s = ledger_stream(l);
+    LedgerDrain drain;
+    if (links) {
+        drain.s = s;
+        drain.armed = true;
+        if (hz_status e = ledger_rq_upload(l, m, rq, s)) return e;
+    }
     HZ_HIP(l->ints.grow((m ? m : 1) * sizeof(hz_l2tx)));
     if (m) HZ_HIP(hipMemcpyAsync(l->ints.p, txs, m * sizeof(hz_l2tx), hipMemcpyHostToDevice, s));
     if (hz_status e = ledger_sig_prepare(l, m, sigs, s)) return e;
     HZ_HIP(hipEventRecord(l->es0, s));
     HZ_HIP(launch_ledger_sig((const hz_l2tx*)l->ints.p, (const hz_l2sig*)l->sig_in.p, chain_id, current_num_batch, l->sig_dev[0], l->sig_dev[1], l->sig_dev[2],
-                             (const uint8_t*)l->planes.p, l->b8_table.p, l->N, l->first_idx, nullptr, l->verdict_dev, (uint32_t)m, s));
+                             (const uint8_t*)l->planes.p, l->b8_table.p, l->N, l->first_idx, nullptr, l->verdict_dev, (uint32_t)m, s, 0,
+                             links ? (const uint8_t*)l->rq_in.p : nullptr));
     HZ_HIP(hipEventRecord(l->es1, s));
+    if (links) {   // behind both signature kernels: 13 goes where the verdict is still 0
+        HZ_HIP(hipEventRecord(l->eq0, s));
+        HZ_HIP(launch_ledger_rq((const hz_l2tx*)l->ints.p, (const hz_l2sig*)l->sig_in.p, (const uint8_t*)l->rq_in.p, (const uint8_t*)l->sig_dev[1], nullptr, l->verdict_dev,
+                                (uint32_t)m, 0, s, 0));
+        HZ_HIP(hipEventRecord(l->eq1, s));
+    }
     if (m) HZ_HIP(hipMemcpyAsync(verdict_out, l->verdict_dev, m, hipMemcpyDeviceToHost, s));
     if (hz_status e = ledger_sig_copy_out(l, m, sig_out, s)) return e;
     HZ_HIP(hipStreamSynchronize(s));
+    drain.armed = false;
     float ms = 0;
     HZ_HIP(hipEventElapsedTime(&ms, l->es0, l->es1));
     l->sig_ms = ms;
+    if (links) {
+        HZ_HIP(hipEventElapsedTime(&ms, l->eq0, l->eq1));
+        l->rq_ms = ms;
+    }
     l->have_sig_outputs = true;
     return HZ_OK;
+}
+
+extern "C" hz_status hz_ledger_verify_l2(hz_ledger* l, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, uint32_t chain_id, uint32_t current_num_batch,
+                                         uint8_t* verdict_out, const hz_ledger_sig_out* sig_out) {
+    return ledger_verify(l, "hz_ledger_verify_l2", m, txs, sigs, nullptr, chain_id, current_num_batch, verdict_out, sig_out);
 }
 
 extern "C" hz_status hz_ledger_sig_outputs_dev(hz_ledger* l, hz_ledger_sig_out* dev) {
@@ -1411,6 +1547,7 @@ static hz_status ledger_apply_addr(hz_ledger* l, const char* who, LedgerL1Run ru
         sigs = no_sigs.data();
     }
     if (hz_status e = ledger_check_sigs(who, m, txs, sigs, chain_id, verify)) return e;
+    if (hz_status e = ledger_check_rq(who, m, txs, run.rq)) return e;
     if (run.n_creates)   // before everything else of the call, the lookup included: the new accounts' static fields into their plane slots
         if (hz_status e = ledger_create_launch(l, run)) return e;
     std::vector<hz_l2tx> eff(m ? m : 1);   // (never empty: its address tells ledger_apply which call this is)
@@ -1667,5 +1804,60 @@ extern "C" hz_status hz_ledger_plan_creates(size_t n_l1, const hz_l1tx* l1, cons
         if (out_idx_after_out) out_idx_after_out[i] = i < n_l1 ? idx_after[i] : last;
     }
     if (n_creates_out) *n_creates_out = n_creates;
+    return HZ_OK;
+}
+
+// ---- atomic transactions: the rqOffset links ----------------------------------------------------------------------------
+extern "C" hz_status hz_ledger_apply_batch_atomic(hz_ledger* l, size_t n_l1, const hz_l1tx* l1, const uint8_t* from_bjj, size_t m, const hz_l2tx* txs,
+                                                  const hz_l2sig* sigs, const hz_l2rq* rq, uint32_t flags, const uint64_t* aux_to_idx, uint32_t chain_id,
+                                                  uint32_t current_num_batch, size_t F, const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs, size_t n_sib,
+                                                  const hz_ledger_out* out, const hz_ledger_sig_out* sig_out, uint8_t* aux_to_idx_out, uint8_t* l1_flags_out,
+                                                  const hz_ledger_exit_out* exit_out, const hz_ledger_create_out* create_out) {
+    static_assert(sizeof(hz_l2rq) == 97, "hz_l2rq is three elements and a byte");
+    const char* who = "hz_ledger_apply_batch_atomic";
+    if (l) l->rq_ms = 0.0;   // the time of THIS call. (sigs == NULL is hz_ledger_apply_batch's: zero entries stand in, so the link fields
+                             // of such rows are V2 and two zeros)
+    LedgerL1Run run;
+    run.n = n_l1;
+    run.tx = l1;
+    run.flags_out = l1_flags_out;
+    run.is_batch = true;
+    run.exits = true;
+    run.exit_out = exit_out;
+    run.creates = true;
+    run.from_bjj = from_bjj;
+    run.create_out = create_out;
+    run.rq = rq;
+    return ledger_apply_addr(l, who, run, m, txs, sigs, flags, aux_to_idx, chain_id, current_num_batch, F, fee_plan_tokens, fee_idxs, n_sib, out, sig_out, aux_to_idx_out);
+}
+
+extern "C" hz_status hz_ledger_verify_l2_atomic(hz_ledger* l, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, const hz_l2rq* rq, uint32_t chain_id,
+                                                uint32_t current_num_batch, uint8_t* verdict_out, const hz_ledger_sig_out* sig_out) {
+    if (l) l->rq_ms = 0.0;
+    return ledger_verify(l, "hz_ledger_verify_l2_atomic", m, txs, sigs, rq, chain_id, current_num_batch, verdict_out, sig_out);
+}
+
+extern "C" double hz_ledger_rq_ms(const hz_ledger* l) { return l ? l->rq_ms : 0.0; }
+
+extern "C" hz_status hz_ledger_plan_atomic(size_t n_l1, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, const hz_l2rq* rq, int64_t* target_row_out,
+                                           uint8_t* verdict_out) {
+    const char* who = "hz_ledger_plan_atomic";
+    if (m && (!txs || !sigs)) return set_err(HZ_ERR_ARG, "%s: null argument", who);
+    if (n_l1 > HZ_LEDGER_MAX_L1) return set_err(HZ_ERR_ARG, "%s: n_l1 = %zu L1 transactions (at most %d)", who, n_l1, HZ_LEDGER_MAX_L1);
+    if (m > HZ_LEDGER_MAX_TX) return set_err(HZ_ERR_ARG, "%s: %zu transactions in one call (at most %u)", who, m, HZ_LEDGER_MAX_TX);
+    if (hz_status e = ledger_check_rq(who, m, txs, rq)) return e;
+    for (size_t i = 0; i < m; i++) {
+        int64_t row = -1;
+        bool ok = true;
+        if (rq && txs[i].from_idx != 0) {
+            row = rq_target_row(n_l1 + i, rq[i].rq_offset, n_l1, n_l1 + m);
+            if (row >= 0 && txs[row - n_l1].from_idx == 0) row = -1;   // a NOP: zeros
+            Fc v2 = fc_zero(), eth = fc_zero(), ay = fc_zero();
+            if (row >= 0) ledger_sig_link_fields_host(txs[row - n_l1], sigs[row - n_l1], &v2, &eth, &ay);
+            ok = rq_fields_match(resolve_load32(rq[i].rq_tx_compressed_data_v2), resolve_load32(rq[i].rq_to_eth_addr), resolve_load32(rq[i].rq_to_bjj_ay), v2, eth, ay);
+        }
+        if (target_row_out) target_row_out[i] = row;
+        if (verdict_out) verdict_out[i] = ok ? 0u : (uint8_t)HZ_RQ_REASON;
+    }
     return HZ_OK;
 }

@@ -9,6 +9,7 @@
 // hm Q8 is a binary ladder with a dedicated doubling (4M + 4S) and a 9-product addition; S B8 takes no doubling at all: 64 mixed
 // additions from a table of d * 16^w * B8 (d < 16, w < 64) that the host builds once with these same routines (sig_b8_table).
 #pragma once
+#include "../../include/hermez_witness.h"
 #include "babyjub.h"
 #include "poseidon.h"
 #include "u256.h"
@@ -66,6 +67,31 @@ struct SigTx {
     uint32_t token_id, user_fee, to_bjj_sign, max_num_batch;
     Fc to_eth_addr, to_bjj_ay;
 };
+// 32 bytes of a hz_l2sig member (the struct is 4-byte aligned, not 16), or zero. (Masking the limbs of a SigTx member in a loop of
+// their own, inside an inlined routine, keeps the struct in private memory on the device: 40 bytes of scratch a lane.)
+HZ_HD Fc sig_load32_if(const uint8_t* p, bool active) {
+    const uint32_t* q = (const uint32_t*)p;
+    Fc r;
+#pragma unroll
+    for (int i = 0; i < 8; i++) r.v[i] = active ? q[i] : 0u;
+    return r;
+}
+// the fields of a transaction as uploaded, zero for a NOP: the one place that says what the message and the V2 row are made of, for the
+// kernels of ledger_sig.hip and for the host's hz_ledger_plan_atomic
+HZ_HD SigTx sig_load_tx(const hz_l2tx& x, const hz_l2sig& g, bool active) {
+    SigTx t;
+    t.from_idx = active ? x.from_idx : 0;
+    t.to_idx = active ? x.to_idx : 0;
+    t.amount_f = active ? x.amount_f : 0;
+    t.nonce = active ? x.nonce : 0;
+    t.token_id = active ? x.token_id : 0u;
+    t.user_fee = active ? x.user_fee : 0u;
+    t.to_bjj_sign = active ? g.to_bjj_sign : 0u;
+    t.max_num_batch = active ? g.max_num_batch : 0u;
+    t.to_eth_addr = sig_load32_if(g.to_eth_addr, active);
+    t.to_bjj_ay = sig_load32_if(g.to_bjj_ay, active);
+    return t;
+}
 HZ_HD Fc sig_tx_compressed_data(const SigTx& t, uint32_t chain_id) {
     Fc r = fc_zero();
     u256_or_shl(r, HZ_SIG_CONST, 0);
@@ -95,18 +121,21 @@ HZ_HD Fc sig_e1(const SigTx& t) {   // toEthAddr | amountF << 160 | maxNumBatch 
     u256_or_shl(r, t.max_num_batch, 200);
     return r;
 }
-// M = Poseidon(6)(txCompressedData, e1, toBjjAy, 0, 0, 0): the rq* fields are zero. K7: the digest-only constant block of t = 7
-HZ_HD Fc sig_message(const Fc& tcd, const SigTx& t, const Fr* K7) {
+// M = Poseidon(6)(txCompressedData, e1, toBjjAy, rqTxCompressedDataV2, rqToEthAddr, rqToBjjAy): the transaction's own rq fields, canonical
+// (DESIGN.md 8i). K7: the digest-only constant block of t = 7
+HZ_HD Fc sig_message(const Fc& tcd, const SigTx& t, const Fc& rq_v2, const Fc& rq_eth, const Fc& rq_ay, const Fr* K7) {
     Fr in[6];
     in[0] = fr_from_canon(tcd);
     in[1] = fr_from_canon(sig_e1(t));
     in[2] = fr_from_canon(t.to_bjj_ay);
-    in[3] = fr_zero();
-    in[4] = fr_zero();
-    in[5] = fr_zero();
+    in[3] = fr_from_canon(rq_v2);
+    in[4] = fr_from_canon(rq_eth);
+    in[5] = fr_from_canon(rq_ay);
     NoSink sink;
     return fr_to_canon(poseidon_hash<7>(in, K7, sink));
 }
+// the message of a transaction that links to nothing: the rq fields are zero
+HZ_HD Fc sig_message(const Fc& tcd, const SigTx& t, const Fr* K7) { return sig_message(tcd, t, fc_zero(), fc_zero(), fc_zero(), K7); }
 // src/decode-tx.circom:360-368
 HZ_HD bool sig_batch_expired(uint32_t max_num_batch, uint32_t current_num_batch) { return max_num_batch != 0 && max_num_batch < current_num_batch; }
 

@@ -6,6 +6,10 @@
 // A failure lowers the failure word of the semantic kernels ((unit << 8) | reason, atomicMin) or, for hz_ledger_verify_l2, is written
 // to the transaction's verdict byte; the verify kernel runs after the message kernel on the same stream, so 7 replaces 8 there as the
 // minimum does in the word. The arithmetic is ledger_sig.h's, shared with the host build.
+// The atomic calls hand the message kernel the transactions' own rq fields; k_ledger_rq (ledger.hip) reads the V2 rows
+// behind it on the same stream. For a call that does not verify,
+//   k_ledger_sig_v2      the V2 rows alone: the packing of the message kernel without its Poseidon
+// The rq fields lie plane-major, [3][m][32] (V2, toEthAddr, toBjjAy), then the m offset bytes: the host lays hz_l2rq out so.
 #define HZ_FR_INLINE 1
 #include <hip/hip_runtime.h>
 #include "../../include/hermez_witness.h"
@@ -23,35 +27,35 @@ __device__ __forceinline__ Fc sig_load32(const uint8_t* p) {
     return r;
 }
 
-__global__ __launch_bounds__(64) void k_ledger_sig_msg(const hz_l2tx* __restrict__ txs, const hz_l2sig* __restrict__ sigs, uint32_t chain_id, uint32_t current_num_batch,
-                                                       uint8_t* __restrict__ out_tcd, uint8_t* __restrict__ out_v2, uint8_t* __restrict__ out_hash,
+// rq field f of transaction i, zero without an rq array and for a NOP
+__device__ __forceinline__ Fc sig_load_rq(const uint8_t* __restrict__ rq, uint32_t f, uint32_t i, uint32_t m, bool active) {
+    Fc r = fc_zero();
+    if (rq && active) r = load_fr(rq + ((size_t)f * m + i) * 32);
+    return r;
+}
+
+__global__ __launch_bounds__(64) void k_ledger_sig_msg(const hz_l2tx* __restrict__ txs, const hz_l2sig* __restrict__ sigs, const uint8_t* __restrict__ rq, uint32_t chain_id,
+                                                       uint32_t current_num_batch, uint8_t* __restrict__ out_tcd, uint8_t* __restrict__ out_v2, uint8_t* __restrict__ out_hash,
                                                        uint32_t* __restrict__ fail_word, uint8_t* __restrict__ verdict, uint32_t m, uint32_t unit_base) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= m) return;
     const bool active = txs[i].from_idx != 0;
-    SigTx t;
-    t.from_idx = active ? txs[i].from_idx : 0;
-    t.to_idx = active ? txs[i].to_idx : 0;
-    t.amount_f = active ? txs[i].amount_f : 0;
-    t.nonce = active ? txs[i].nonce : 0;
-    t.token_id = active ? txs[i].token_id : 0u;
-    t.user_fee = active ? txs[i].user_fee : 0u;
-    t.to_bjj_sign = active ? sigs[i].to_bjj_sign : 0u;
-    t.max_num_batch = active ? sigs[i].max_num_batch : 0u;
-    t.to_eth_addr = sig_load32(sigs[i].to_eth_addr);
-    t.to_bjj_ay = sig_load32(sigs[i].to_bjj_ay);
-#pragma unroll
-    for (int q = 0; q < 8; q++) {
-        t.to_eth_addr.v[q] = active ? t.to_eth_addr.v[q] : 0u;
-        t.to_bjj_ay.v[q] = active ? t.to_bjj_ay.v[q] : 0u;
-    }
+    const SigTx t = sig_load_tx(txs[i], sigs[i], active);
     const Fc tcd = sig_tx_compressed_data(t, chain_id);
     store_fr(out_tcd + (size_t)i * 32, tcd);
     store_fr(out_v2 + (size_t)i * 32, sig_tx_compressed_data_v2(t));
-    store_fr(out_hash + (size_t)i * 32, sig_message(tcd, t, poseidon_consts<7>()));
+    store_fr(out_hash + (size_t)i * 32,
+             sig_message(tcd, t, sig_load_rq(rq, 0, i, m, active), sig_load_rq(rq, 1, i, m, active), sig_load_rq(rq, 2, i, m, active), poseidon_consts<7>()));
     const bool expired = active && sig_batch_expired(t.max_num_batch, current_num_batch);
     if (verdict) verdict[i] = expired ? 8u : 0u;
     if (expired && fail_word) atomicMin(fail_word, ((unit_base + i) << 8) | 8u);
+}
+
+// the V2 rows alone: what k_ledger_rq reads when the call verifies no signature
+__global__ __launch_bounds__(64) void k_ledger_sig_v2(const hz_l2tx* __restrict__ txs, const hz_l2sig* __restrict__ sigs, uint8_t* __restrict__ out_v2, uint32_t m) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    store_fr(out_v2 + (size_t)i * 32, sig_tx_compressed_data_v2(sig_load_tx(txs[i], sigs[i], txs[i].from_idx != 0)));
 }
 
 __global__ __launch_bounds__(64) void k_ledger_sig_verify(const hz_l2tx* __restrict__ txs, const hz_l2sig* __restrict__ sigs, const uint8_t* __restrict__ msg_hash,
@@ -75,13 +79,28 @@ __global__ __launch_bounds__(64) void k_ledger_sig_verify(const hz_l2tx* __restr
 
 hipError_t launch_ledger_sig(const hz_l2tx* d_txs, const hz_l2sig* d_sigs, uint32_t chain_id, uint32_t current_num_batch, uint8_t* d_tcd, uint8_t* d_v2, uint8_t* d_hash,
                              const uint8_t* planes, const void* b8_table, uint32_t N, uint64_t first_idx, uint32_t* d_fail_word, uint8_t* d_verdict, uint32_t m,
-                             hipStream_t s, uint32_t unit_base) {
+                             hipStream_t s, uint32_t unit_base, const uint8_t* d_rq) {
     if (m == 0) return hipSuccess;
     const dim3 grid((m + 63) / 64), block(64);
-    hipLaunchKernelGGL(k_ledger_sig_msg, grid, block, 0, s, d_txs, d_sigs, chain_id, current_num_batch, d_tcd, d_v2, d_hash, d_fail_word, d_verdict, m, unit_base);
+    hipLaunchKernelGGL(k_ledger_sig_msg, grid, block, 0, s, d_txs, d_sigs, d_rq, chain_id, current_num_batch, d_tcd, d_v2, d_hash, d_fail_word, d_verdict, m, unit_base);
     if (hipError_t e = hipGetLastError()) return e;
     hipLaunchKernelGGL(k_ledger_sig_verify, grid, block, 0, s, d_txs, d_sigs, (const uint8_t*)d_hash, planes, (const Fr*)b8_table, N, first_idx, d_fail_word, d_verdict, m, unit_base);
     return hipGetLastError();
+}
+
+// the V2 rows of a call that verifies nothing, for the link check
+hipError_t launch_ledger_sig_v2(const hz_l2tx* d_txs, const hz_l2sig* d_sigs, uint8_t* d_v2, uint32_t m, hipStream_t s) {
+    if (m == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_ledger_sig_v2, dim3((m + 63) / 64), dim3(64), 0, s, d_txs, d_sigs, d_v2, m);
+    return hipGetLastError();
+}
+
+// the link fields of an L2 row on the host, through the packing the kernels use (hz_ledger_plan_atomic); zero for a NOP
+void ledger_sig_link_fields_host(const hz_l2tx& tx, const hz_l2sig& sig, Fc* v2, Fc* eth, Fc* ay) {
+    const SigTx t = sig_load_tx(tx, sig, tx.from_idx != 0);
+    *v2 = sig_tx_compressed_data_v2(t);
+    *eth = t.to_eth_addr;
+    *ay = t.to_bjj_ay;
 }
 
 // the fixed-base table, built on the host with the routines the kernel uses

@@ -602,9 +602,34 @@ hz_status hz_smt_plan(size_t m, const uint64_t* key, size_t n_sib, uint32_t* dep
  *   hz_ledger_create_ms device time of the two create kernels of the last hz_ledger_apply_batch_creates
  *   hz_ledger_plan_creates  DIAGNOSTIC, no device: aux_from_idx_out / out_idx_after_out [n_l1 + m], *n_creates_out, and the argument errors
  *                       above but the depth, for a ledger of `capacity` that holds `size` accounts (growing == 0: a dense one)
+ * ATOMIC. An L2 transaction may commit to a partner: its signer puts the partner's txCompressedDataV2, signed toEthAddr and
+ * signed toBjjAy -- the partner's LINK FIELDS -- into the message, M = Poseidon(6)(txCompressedData, e1, toBjjAy, rqTxCompressedDataV2,
+ * rqToEthAddr, rqToBjjAy), and the coordinator names with rqOffset where in the batch the partner stands. RollupMain accepts the batch only
+ * if the three rq fields of every row equal, as full field elements, the link fields of its target (src/rq-tx-verifier.circom:91-93):
+ *   rq_offset 0: nothing, the comparison is against (0, 0, 0)    1 .. 3: row r + k    4 .. 7: row r - (8 - k) (7 the previous row, 4 four back)
+ * over the batch's n_l1 + m rows, L1 first (L2 transaction i is row r = n_l1 + i). An L1 row, an L2 NOP and a position before row 0 or past
+ * the last row have link fields (0, 0, 0): a link there, and offset 0, hold iff the three rq fields are zero. An rq_to_eth_addr >= 2^160 never
+ * matches. The link fields of an active L2 row are those of its signed values: to_idx as signed (0 and 1 included) and to_bjj_sign in V2,
+ * to_eth_addr and to_bjj_ay of its hz_l2sig. The rq fields are always explicit -- what the signer committed to -- and a NOP's hz_l2rq is
+ * ignored. The seven apply / verify / resolve calls above know no link: their message keeps three zeros, and they know no reason 13.
+ *   hz_ledger_apply_batch_atomic  hz_ledger_apply_batch_creates with rq[m] (entry i belongs to txs[i]; NULL: no transaction links; where
+ *                       sigs may be NULL there it may be here, and the link fields of every row are then V2 and two zeros), on a
+ *                       dense or a growing ledger. sig_l2_hash is the M above. Refusal reason
+ *                         13 the rq fields of the row are not its target's link fields
+ *                       ranks with 1 - 8 and 12 (lowest row, then lowest reason; reason 9 keeps its precedence) and is checked with or
+ *                       without HZ_LEDGER_VERIFY_SIGS: the circuit enforces it whoever verified a signature. A signature over other rq
+ *                       fields than the submitted ones is reason 7 under the flag. With rq == NULL, or every entry zero, every output
+ *                       equals hz_ledger_apply_batch_creates' byte for byte. HZ_ERR_ARG beyond that call's: rq_offset > 7.
+ *                       HZ_ERR_INPUT: an rq field >= r
+ *   hz_ledger_verify_l2_atomic  hz_ledger_verify_l2 with rq[m]: the rows are the m transactions alone (n_l1 = 0). Verdicts 0, 7, 8 or 13, the
+ *                       lowest where several hold. A rejection is not carried over to the partner of the rejected transaction
+ *   hz_ledger_plan_atomic  DIAGNOSTIC, no device: target_row_out[m], the row a transaction is compared with, or -1 for zeros (offset 0, a
+ *                       position outside the batch, an L1 row, a NOP); verdict_out[m], 0 or 13, computed on the host with the routines the
+ *                       kernel uses; the argument errors above. Both outputs may be NULL
+ *   hz_ledger_rq_ms     device time of the link kernel of the last such call (0: none ran)
  * OUT OF SCOPE: L1 transactions that create accounts or exit through a call other than hz_ledger_apply_batch_exits (creates:
  * hz_ledger_apply_batch_creates on a growing ledger), an L1 amount with
- * to_idx == 0 (no receiver), exit trees of earlier batches kept resident, atomic (rqOffset) fields, a resident address index kept across
+ * to_idx == 0 (no receiver), exit trees of earlier batches kept resident, a resident address index kept across
  * calls, batch (random linear combination) verification of signatures, more than one device per ledger. One thread at a time. */
 typedef struct hz_ledger hz_ledger;
 typedef struct {
@@ -723,6 +748,21 @@ double hz_ledger_create_ms(const hz_ledger* l);
 hz_status hz_ledger_plan_creates(size_t n_l1, const hz_l1tx* l1, const uint8_t* from_bjj, size_t m, const hz_l2tx* txs, size_t F,
                                  const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs, int32_t growing, uint64_t capacity, uint64_t first_idx,
                                  uint64_t size, uint64_t* aux_from_idx_out, uint64_t* out_idx_after_out, size_t* n_creates_out);
+typedef struct {
+    uint8_t rq_tx_compressed_data_v2[32], rq_to_eth_addr[32], rq_to_bjj_ay[32]; /* canonical little-endian */
+    uint8_t rq_offset;                                                           /* 0 .. 7 */
+} hz_l2rq;
+hz_status hz_ledger_apply_batch_atomic(hz_ledger* l, size_t n_l1, const hz_l1tx* l1, const uint8_t* from_bjj /* [n_l1][32] or NULL */, size_t m,
+                                       const hz_l2tx* txs, const hz_l2sig* sigs, const hz_l2rq* rq /* [m] or NULL */, uint32_t flags,
+                                       const uint64_t* aux_to_idx /* [m] or NULL */, uint32_t chain_id, uint32_t current_num_batch, size_t F,
+                                       const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs, size_t n_sib, const hz_ledger_out* out,
+                                       const hz_ledger_sig_out* sig_out, uint8_t* aux_to_idx_out, uint8_t* l1_flags_out,
+                                       const hz_ledger_exit_out* exit_out /* or NULL */, const hz_ledger_create_out* create_out /* or NULL */);
+hz_status hz_ledger_verify_l2_atomic(hz_ledger* l, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, const hz_l2rq* rq /* [m] or NULL */, uint32_t chain_id,
+                                     uint32_t current_num_batch, uint8_t* verdict_out /* [m]: 0, 7, 8 or 13 */, const hz_ledger_sig_out* sig_out);
+hz_status hz_ledger_plan_atomic(size_t n_l1, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, const hz_l2rq* rq /* [m] or NULL */,
+                                int64_t* target_row_out /* [m]: the row, -1: zeros */, uint8_t* verdict_out /* [m]: 0 or 13 */);
+double hz_ledger_rq_ms(const hz_ledger* l);
 
 /* Poseidon batch: n independent permutations of width t = n_inputs + 1 (2..7). ----------------
  * `in`  : [n][t-1] canonical elements; `out`: [n] digests (state[0] after the last round).
