@@ -1075,6 +1075,23 @@ def ledger_atomic_batch_inputs(ledger, db_like, l1_txs, l2_txs, n_tx, n_levels, 
     return _ledger_batch_inputs(ledger, db_like, l1_txs, l2_txs, n_tx, n_levels, max_l1, max_fee, fee_tokens, fee_idxs, chain_id, host_outputs, verify, True, True, True)
 
 
+def ledger_select_batch_inputs(ledger, db_like, l1_txs, pool, n_tx, n_levels, max_l1, max_fee, fee_tokens, fee_idxs, chain_id, host_outputs=True, verify=False):
+    """A batch chosen from a POOL and its RollupMain inputs: capi.Ledger.select_batch over the mandatory L1 rows and the pool (transaction
+    dictionaries in order of preference, signed, the rq fields explicit, `partner` the pool index a transaction requires) with the room
+    n_tx - len(l1_txs) leaves, the kept transactions compacted with the rqOffset the selection gives them, then
+    ledger_atomic_batch_inputs on those rows. -> (ledger_atomic_batch_inputs' result, the selection)"""
+    from .capi import select_compact
+    if len(l1_txs) > max_l1:
+        raise ValueError("too many L1 txs")
+    l1_txs, pool = [dict(t) for t in l1_txs], [dict(t) for t in pool]
+    for t in l1_txs + pool:
+        if "amountF" not in t or "amount" in t:
+            t["amountF"] = fix2float(t.get("amount", 0))
+    sel = ledger.select_batch(l1_txs, pool, chain_id, db_like.num_batch + 1, max_keep=n_tx - len(l1_txs), verify=verify)
+    rows = [{k: v for k, v in t.items() if k != "partner"} for t in select_compact(pool, sel)]
+    return ledger_atomic_batch_inputs(ledger, db_like, l1_txs, rows, n_tx, n_levels, max_l1, max_fee, fee_tokens, fee_idxs, chain_id, host_outputs, verify), sel
+
+
 RQ_SIGNALS = ("rqOffset", "rqTxCompressedDataV2", "rqToEthAddr", "rqToBjjAy")
 
 

@@ -78,6 +78,7 @@ EXPORTS = [
     "hz_ledger_create_growing", "hz_ledger_load_accounts", "hz_ledger_size", "hz_ledger_last_idx", "hz_ledger_state_smt", "hz_ledger_apply_batch_creates",
     "hz_ledger_create_outputs_dev", "hz_ledger_create_ms", "hz_ledger_plan_creates",
     "hz_ledger_apply_batch_atomic", "hz_ledger_verify_l2_atomic", "hz_ledger_plan_atomic", "hz_ledger_rq_ms",
+    "hz_ledger_select_batch", "hz_ledger_plan_select", "hz_ledger_select_ms",
 ]
 
 
@@ -124,6 +125,28 @@ class hz_l2rq(ctypes.Structure):
 
 
 LEDGER_RQ_REASON = 13   # the rq fields of a row are not its target's link fields
+SELECT_MAX_POOL, SELECT_MAX_SLOTS = 4096, 4096   # HZ_SELECT_MAX_POOL, HZ_SELECT_MAX_SLOTS
+SELECT_PARTNER, SELECT_FULL = 14, 15             # verdicts of hz_ledger_select_batch that are no refusal reasons
+
+
+class hz_ledger_select_out(ctypes.Structure):
+    _fields_ = [("verdict", ctypes.c_void_p), ("kept", ctypes.c_void_p), ("n_kept", ctypes.c_void_p), ("rq_offset", ctypes.c_void_p), ("aux_to_idx", ctypes.c_void_p),
+                ("rounds", ctypes.c_void_p)]
+
+
+def partner_array(txs):
+    """the `partner` key of every transaction dictionary (a POOL index, missing or None: -1) as an int32 array, or None when no
+    transaction has a partner"""
+    import numpy as np
+    vals = [t.get("partner") for t in txs]
+    if all(v is None or v < 0 for v in vals):
+        return None
+    return np.array([-1 if v is None else v for v in vals], dtype=np.int32)
+
+
+def select_compact(txs, result):
+    """the kept transactions of a Ledger.select_batch result, in order, as copies that carry the rqOffset of the compacted batch"""
+    return [dict(txs[i], rqOffset=result["rq_offset"][i]) for i in result["kept"]]
 
 
 def l2rq_array(txs):
@@ -370,8 +393,10 @@ class Lib:
         c.hz_ledger_apply_batch_atomic.argtypes = [vp, sz, vp, vp, sz, vp, vp, vp, u32, vp, u32, u32, sz, vp, vp, sz, vp, vp, vp, vp, vp, vp]
         c.hz_ledger_verify_l2_atomic.argtypes = [vp, sz, vp, vp, vp, u32, u32, vp, vp]
         c.hz_ledger_plan_atomic.argtypes = [sz, sz, vp, vp, vp, vp, vp]
+        c.hz_ledger_select_batch.argtypes = [vp, sz, vp, vp, sz, vp, vp, vp, vp, u32, u32, u32, sz, vp]
+        c.hz_ledger_plan_select.argtypes = [sz, vp, sz, vp, vp, vp, vp, vp, vp, ctypes.POINTER(sz), vp, vp, vp]
         for f in ("hz_ledger_device_ms", "hz_ledger_semantic_ms", "hz_ledger_sig_ms", "hz_ledger_resolve_ms", "hz_ledger_l1_ms", "hz_ledger_exit_ms", "hz_ledger_create_ms",
-                  "hz_ledger_rq_ms"):
+                  "hz_ledger_rq_ms", "hz_ledger_select_ms"):
             getattr(c, f).argtypes = [vp]
             getattr(c, f).restype = ctypes.c_double
 
@@ -500,6 +525,33 @@ class Lib:
         self._check(self.c.hz_ledger_plan_atomic(n_l1, m, ctypes.addressof(arr), ctypes.addressof(sigs), ctypes.addressof(rq) if rq is not None else None,
                                                  target.ctypes.data, verdict.ctypes.data))
         return {"target_row": target[:m].tolist(), "verdict": verdict[:m].tolist()}
+
+    def ledger_plan_select(self, l1_txs, txs, aux_to_idx=None, partner=None, kept=None):
+        """hz_ledger_plan_select, a diagnostic: the local slots of a select_batch call -- the distinct accounts its L1 rows (a create row
+        with its auxFromIdx as fromIdx) and its pool touch, by first appearance -- its argument errors, and, given kept (a flag per pool
+        transaction), the closure step alone; no device needed. partner: [m] pool indices, default the dictionaries' `partner` keys.
+        -> {"slot_sender", "slot_receiver": [n_l1 + m] (-1: none), "slot_account": [slots]} plus "forced", "rq_offset": [m] with kept"""
+        import numpy as np
+        l1, arr = l1tx_array(l1_txs), txs if isinstance(txs, ctypes.Array) else l2tx_array(txs)
+        n_l1, m = len(l1_txs), len(txs)
+        if partner is None and not isinstance(txs, ctypes.Array):
+            partner = partner_array(txs)
+        par = np.ascontiguousarray(partner, dtype=np.int32) if partner is not None else None
+        aux = np.ascontiguousarray(aux_to_idx, dtype=np.uint64) if aux_to_idx is not None else None
+        kin = np.ascontiguousarray(kept, dtype=np.uint8) if kept is not None else None
+        for a in (par, aux, kin):
+            if a is not None and a.size != m:
+                raise ValueError("one entry per pool transaction")
+        R = max(n_l1 + m, 1)
+        ss, sr, acct = np.zeros(R, dtype=np.int32), np.zeros(R, dtype=np.int32), np.zeros(2 * R, dtype=np.uint64)
+        forced, off, n = np.zeros(max(m, 1), dtype=np.uint8), np.zeros(max(m, 1), dtype=np.uint8), ctypes.c_size_t(0)
+        ptr = lambda a: a.ctypes.data if a is not None else None   # noqa: E731
+        self._check(self.c.hz_ledger_plan_select(n_l1, ctypes.addressof(l1), m, ctypes.addressof(arr), ptr(aux), ptr(par), ptr(kin), ss.ctypes.data, sr.ctypes.data,
+                                                 ctypes.byref(n), acct.ctypes.data, forced.ctypes.data, off.ctypes.data))
+        out = {"slot_sender": ss[:n_l1 + m].tolist(), "slot_receiver": sr[:n_l1 + m].tolist(), "slot_account": acct[:n.value].tolist()}
+        if kin is not None:
+            out.update(forced=forced[:m].tolist(), rq_offset=off[:m].tolist())
+        return out
 
     def ledger_plan_l2(self, txs, fee_plan_tokens, fee_idxs, k, first_idx=256):
         """hz_ledger_plan_l2, a diagnostic: the host planner alone (integers only, no device needed). txs: transaction dictionaries or an
@@ -1231,6 +1283,42 @@ class Ledger(_Resident):
     def rq_ms(self):
         """device time of the link kernel of the last apply_batch_atomic / verify_l2_atomic (0.0 when none ran)"""
         return self.L.c.hz_ledger_rq_ms(self.h)
+
+    def select_batch(self, l1_txs, txs, chain_id, current_num_batch, max_keep=None, verify=False, partner=None, sigs=None, from_bjj=None, rq=None):
+        """hz_ledger_select_batch: a batch chosen from the POOL txs, in order, behind the mandatory L1 rows (as apply_batch_atomic takes
+        them): what is applicable after everything kept before it is kept, the rest dropped with a reason; nothing resident changes.
+        partner: [m] pool indices (-1: none), default the dictionaries' `partner` keys; the rqOffset of a dictionary is not read, its rq
+        fields are. max_keep: the room in the batch, default the pool's length. sigs: a prebuilt hz_l2sig array, False: none at all.
+        -> {"verdict": [m] (0 kept or a NOP, a refusal reason, SELECT_PARTNER, SELECT_FULL), "kept": pool indices in order,
+        "rq_offset": [m], "aux_to_idx": [m], "rounds": int}; select_compact(txs, result) are the rows to apply"""
+        import numpy as np
+        prebuilt = isinstance(l1_txs, ctypes.Array)
+        l1 = l1_txs if prebuilt else l1tx_array(l1_txs)
+        bjj = from_bjj if from_bjj is not None or prebuilt else from_bjj_array(l1_txs)
+        arr = txs if isinstance(txs, ctypes.Array) else l2tx_array(txs)
+        n_l1, m = len(l1_txs), len(txs)
+        if not isinstance(txs, ctypes.Array):
+            sigs = l2sig_array(txs) if sigs is None else sigs
+            rq = l2rq_array(txs) if rq is None else rq
+            partner = partner_array(txs) if partner is None else partner
+        par = np.ascontiguousarray(partner, dtype=np.int32) if partner is not None else None
+        if par is not None and par.size != m:
+            raise ValueError("partner: one entry per pool transaction")
+        n = max(m, 1)
+        verdict, kept, off, aux = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint64)
+        n_kept, rounds = ctypes.c_size_t(0), ctypes.c_uint32(0)
+        out = hz_ledger_select_out(verdict.ctypes.data, kept.ctypes.data, ctypes.addressof(n_kept), off.ctypes.data, aux.ctypes.data, ctypes.addressof(rounds))
+        self.L._check(self.L.c.hz_ledger_select_batch(self.h, n_l1, ctypes.addressof(l1), bjj.ctypes.data if bjj is not None else None, m, ctypes.addressof(arr),
+                                                      ctypes.addressof(sigs) if sigs not in (None, False) else None,
+                                                      ctypes.addressof(rq) if rq not in (None, False) else None, par.ctypes.data if par is not None else None,
+                                                      LEDGER_VERIFY_SIGS if verify else 0, chain_id, current_num_batch, m if max_keep is None else max_keep,
+                                                      ctypes.addressof(out)))
+        return {"verdict": verdict[:m].tolist(), "kept": kept[:n_kept.value].tolist(), "rq_offset": off[:m].tolist(), "aux_to_idx": aux[:m].tolist(),
+                "rounds": rounds.value}
+
+    def select_ms(self):
+        """device time of k_ledger_select in the last select_batch"""
+        return self.L.c.hz_ledger_select_ms(self.h)
 
     def _apply_batch_creates(self, l1_txs, txs, fee_plan_tokens, fee_idxs, chain_id, current_num_batch, n_sib, verify, aux_to_idx, outputs, into, sigs, from_bjj,
                              atomic=False, rq=None):

@@ -68,6 +68,7 @@
 #include "ledger_exit.h"
 #include "ledger_create.h"
 #include "ledger_rq.h"
+#include "ledger_select.h"
 #include "smt_internal.h"
 #include "smt_plan.h"
 
@@ -426,6 +427,10 @@ struct hz_ledger {
     PinnedBuf h_rq;
     DevEvent eq0, eq1;   // around k_ledger_rq
     double rq_ms = 0.0;
+    // a batch selected from a pool (hz_ledger_select_batch): what k_ledger_select left, back on the host
+    PinnedBuf h_sel;
+    DevEvent esel0, esel1;   // around k_ledger_select
+    double select_ms = 0.0;
     ~hz_ledger() {
         if (exit) hz_smt_destroy(exit);
         if (smt) hz_smt_destroy(smt);
@@ -660,7 +665,7 @@ static hz_status ledger_open(hz_ledger* l) {
     HZ_HIP(l->planes.alloc((size_t)4 * l->N * 32));
     HZ_HIP(l->h_fail.grow(64));
     for (DevEvent* e : {&l->e0, &l->e1, &l->e2, &l->es0, &l->es1, &l->er0, &l->er1, &l->el0, &l->el1, &l->ex0, &l->ex1, &l->ex2, &l->ex3, &l->ex_tree, &l->ec0,
-                        &l->ec1, &l->ec2, &l->ec3, &l->eq0, &l->eq1})
+                        &l->ec1, &l->ec2, &l->ec3, &l->eq0, &l->eq1, &l->esel0, &l->esel1})
         HZ_HIP(e->create());
     return HZ_OK;
 }
@@ -1859,5 +1864,274 @@ extern "C" hz_status hz_ledger_plan_atomic(size_t n_l1, size_t m, const hz_l2tx*
         if (target_row_out) target_row_out[i] = row;
         if (verdict_out) verdict_out[i] = ok ? 0u : (uint8_t)HZ_RQ_REASON;
     }
+    return HZ_OK;
+}
+
+// ---- a batch selected from a pool ----------------------------------------------------------------------------------------
+// the local slots of hz_ledger_select_batch: the distinct accounts the L1 rows and the pool touch, numbered by first appearance -- the
+// groups ledger_plan_rows makes, L1's first. Per row (L1 rows, then the pool): the sender's and the receiver's slot, -1: none
+struct SelectPlan {
+    std::vector<int32_t> slot_s, slot_r;
+    std::vector<uint64_t> slot_account;
+};
+
+// partner[i] names another transaction of the pool or none; a NOP's entry is not looked at
+static hz_status select_check_partner(const char* who, size_t m, const hz_l2tx* txs, const int32_t* partner) {
+    if (!partner) return HZ_OK;
+    for (size_t i = 0; i < m; i++) {
+        if (txs[i].from_idx == 0) continue;
+        if (partner[i] < -1 || (partner[i] >= 0 && (size_t)partner[i] >= m))
+            return set_err(HZ_ERR_ARG, "%s: tx %zu: partner = %d is outside the pool (-1 .. %zu)", who, i, partner[i], m ? m - 1 : 0);
+        if (partner[i] >= 0 && (size_t)partner[i] == i) return set_err(HZ_ERR_ARG, "%s: tx %zu: partner = %d is the transaction itself", who, i, partner[i]);
+    }
+    return HZ_OK;
+}
+
+// eff: the pool with the effective receivers; a row whose to_idx is still 0 has none (an unresolved destination, or none asked for).
+// More candidates or slots than k_ledger_select's LDS holds is an argument error that names the first pool index that does not fit
+static hz_status select_plan(const char* who, size_t n_l1, const hz_l1tx* l1, size_t m, const hz_l2tx* eff, LedgerPlan& p, SelectPlan& sp) {
+    if (m > HZ_SELECT_MAX_POOL)
+        return set_err(HZ_ERR_ARG, "%s: tx %d does not fit: a pool holds at most %d candidates (HZ_SELECT_MAX_POOL)", who, HZ_SELECT_MAX_POOL, HZ_SELECT_MAX_POOL);
+    std::vector<hz_l2tx> rows(eff, eff + m);
+    for (size_t i = 0; i < m; i++)
+        if (rows[i].from_idx != 0 && rows[i].to_idx == 0) rows[i].amount_f = 0;   // no receiver event
+    ledger_plan_rows(n_l1, l1, m, rows.data(), 0, nullptr, nullptr, true, p);
+    const size_t R = n_l1 + m, G = p.seg_start.size() - 1;
+    std::vector<uint32_t> group_of(p.account.size());
+    for (size_t g = 0; g < G; g++)
+        for (uint32_t q = p.seg_start[g]; q < p.seg_start[g + 1]; q++) group_of[p.perm[q]] = (uint32_t)g;
+    sp.slot_s.assign(R, -1);
+    sp.slot_r.assign(R, -1);
+    for (size_t r = 0; r < R; r++) {
+        if (p.ev_sender[r] >= 0) sp.slot_s[r] = (int32_t)group_of[p.ev_sender[r]];
+        if (p.ev_receiver[r] >= 0) sp.slot_r[r] = (int32_t)group_of[p.ev_receiver[r]];
+        if (sp.slot_s[r] >= (int32_t)HZ_SELECT_MAX_SLOTS || sp.slot_r[r] >= (int32_t)HZ_SELECT_MAX_SLOTS)   // (an L1 run alone has at most 1024)
+            return set_err(HZ_ERR_ARG, "%s: tx %zu does not fit: the L1 rows and the pool touch more than %d distinct accounts (HZ_SELECT_MAX_SLOTS)", who, r - n_l1,
+                           HZ_SELECT_MAX_SLOTS);
+    }
+    sp.slot_account.resize(G);
+    for (size_t g = 0; g < G; g++) sp.slot_account[g] = p.account[p.perm[p.seg_start[g]]];
+    return HZ_OK;
+}
+
+extern "C" hz_status hz_ledger_plan_select(size_t n_l1, const hz_l1tx* l1, size_t m, const hz_l2tx* txs, const uint64_t* aux_to_idx, const int32_t* partner,
+                                           const uint8_t* kept_in, int32_t* slot_sender_out, int32_t* slot_receiver_out, size_t* n_slots_out,
+                                           uint64_t* slot_account_out, uint8_t* forced_out, uint8_t* rq_offset_out) {
+    const char* who = "hz_ledger_plan_select";
+    if ((n_l1 && !l1) || (m && !txs)) return set_err(HZ_ERR_ARG, "%s: null argument", who);
+    if (n_l1 > HZ_LEDGER_MAX_L1) return set_err(HZ_ERR_ARG, "%s: n_l1 = %zu L1 transactions (at most %d)", who, n_l1, HZ_LEDGER_MAX_L1);
+    for (size_t i = 0; i < n_l1; i++) {
+        if (l1[i].from_idx == 0) return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: from_idx = 0: the planner takes a create row with its auxFromIdx in from_idx's place", who, i);
+        if (hz_status e = ledger_check_l1_fields(who, i, l1[i])) return e;
+    }
+    if (m > HZ_SELECT_MAX_POOL)
+        return set_err(HZ_ERR_ARG, "%s: tx %d does not fit: a pool holds at most %d candidates (HZ_SELECT_MAX_POOL)", who, HZ_SELECT_MAX_POOL, HZ_SELECT_MAX_POOL);
+    if (hz_status e = select_check_partner(who, m, txs, partner)) return e;
+    std::vector<hz_l2tx> eff(txs, txs + m);
+    for (size_t i = 0; i < m; i++)
+        if (eff[i].from_idx != 0 && eff[i].to_idx == 0 && aux_to_idx && ledger_mantissa(eff[i].amount_f) != 0) eff[i].to_idx = aux_to_idx[i];
+    LedgerPlan p;
+    SelectPlan sp;
+    if (hz_status e = select_plan(who, n_l1, l1, m, eff.data(), p, sp)) return e;
+    for (size_t r = 0; r < n_l1 + m; r++) {
+        if (slot_sender_out) slot_sender_out[r] = sp.slot_s[r];
+        if (slot_receiver_out) slot_receiver_out[r] = sp.slot_r[r];
+    }
+    if (n_slots_out) *n_slots_out = sp.slot_account.size();
+    for (size_t g = 0; g < sp.slot_account.size(); g++)
+        if (slot_account_out) slot_account_out[g] = sp.slot_account[g];
+    if (kept_in) {   // the closure step alone, on the rows the kept transactions would have
+        std::vector<uint32_t> row(m, HZ_SELECT_NO_ROW);
+        uint32_t n_kept = 0;
+        for (size_t i = 0; i < m; i++)
+            if (kept_in[i] && txs[i].from_idx != 0) row[i] = n_kept++;
+        for (size_t i = 0; i < m; i++) {
+            uint32_t off = 0;
+            bool forced = false;
+            const int32_t q = partner && txs[i].from_idx != 0 ? partner[i] : -1;
+            if (q >= 0 && row[i] != HZ_SELECT_NO_ROW) {
+                off = select_link(row[q] != HZ_SELECT_NO_ROW, row[i], row[q]);
+                forced = off == 0;
+            }
+            if (forced_out) forced_out[i] = forced;
+            if (rq_offset_out) rq_offset_out[i] = (uint8_t)off;
+        }
+    }
+    return HZ_OK;
+}
+
+extern "C" double hz_ledger_select_ms(const hz_ledger* l) { return l ? l->select_ms : 0.0; }
+
+extern "C" hz_status hz_ledger_select_batch(hz_ledger* l, size_t n_l1, const hz_l1tx* l1, const uint8_t* from_bjj, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs,
+                                            const hz_l2rq* rq, const int32_t* partner, uint32_t flags, uint32_t chain_id, uint32_t current_num_batch, size_t max_keep,
+                                            const hz_ledger_select_out* out) {
+    const char* who = "hz_ledger_select_batch";
+    if (hz_status e = ledger_ready(l, who)) return e;
+    l->select_ms = 0.0;
+    if (!out || (m && !txs)) return set_err(HZ_ERR_ARG, "%s: null argument", who);
+    const bool verify = (flags & HZ_LEDGER_VERIFY_SIGS) != 0;
+    if (flags & ~HZ_LEDGER_VERIFY_SIGS) return set_err(HZ_ERR_ARG, "%s: flags = %#x", who, flags);
+    // the L1 rows as hz_ledger_apply_batch_atomic takes them
+    LedgerL1Run run;
+    run.n = n_l1;
+    run.is_batch = run.exits = run.creates = true;
+    run.from_bjj = from_bjj;
+    size_t l1_events = 0;
+    std::vector<hz_l1tx> eff_l1;
+    std::vector<uint64_t> aux_from, idx_after;
+    if (hz_status e = ledger_check_creates(who, l->smt != nullptr, l->N, l->first_idx, l->live, n_l1, l1, from_bjj, &l1_events, eff_l1, aux_from, idx_after, &run.n_creates))
+        return e;
+    run.tx = eff_l1.data();
+    run.aux_from = aux_from.data();
+    run.idx_after = idx_after.data();
+    const uint64_t count = l->live + run.n_creates;
+    if (m > HZ_SELECT_MAX_POOL)
+        return set_err(HZ_ERR_ARG, "%s: tx %d does not fit: a pool holds at most %d candidates (HZ_SELECT_MAX_POOL)", who, HZ_SELECT_MAX_POOL, HZ_SELECT_MAX_POOL);
+    if (hz_status e = ledger_check_txs(who, m, txs, l->first_idx, count, true, true)) return e;
+    if (hz_status e = select_check_partner(who, m, txs, partner)) return e;
+    std::vector<hz_l2sig> no_sigs;
+    if (!sigs && m && !verify) {   // no destination is signed: zero entries stand in, as in hz_ledger_apply_batch
+        for (size_t i = 0; i < m; i++)
+            if (txs[i].from_idx != 0 && txs[i].to_idx == 0) return set_err(HZ_ERR_ARG, "%s: null sigs with tx %zu to an address", who, i);
+        no_sigs.assign(m, hz_l2sig{});
+        sigs = no_sigs.data();
+    }
+    if (hz_status e = ledger_check_sigs(who, m, txs, sigs, chain_id, verify)) return e;
+    const bool links = (rq != nullptr || partner != nullptr) && m != 0;
+    std::vector<hz_l2rq> rq_eff;
+    if (links) {   // the offsets are not read: positions do not survive a drop
+        rq_eff.assign(m, hz_l2rq{});
+        for (size_t i = 0; rq && i < m; i++) {
+            rq_eff[i] = rq[i];
+            rq_eff[i].rq_offset = 0;
+        }
+        if (hz_status e = ledger_check_rq(who, m, txs, rq_eff.data())) return e;
+    }
+    ledger_forget(l);
+    HZ_HIP(hipSetDevice(l->device));
+    hipStream_t s = ledger_stream(l);
+    if (run.n_creates)   // before the lookup: the new accounts' static fields into their plane slots, beyond the ledger's size
+        if (hz_status e = ledger_create_launch(l, run)) return e;
+    std::vector<uint64_t> found(m ? m : 1);
+    if (hz_status e = ledger_resolve(l, m, txs, sigs, true, found.data(), count)) return e;
+    std::vector<hz_l2tx> eff(txs, txs + m);
+    auto wants_receiver = [&](size_t i) { return txs[i].from_idx != 0 && txs[i].to_idx == 0 && ledger_mantissa(txs[i].amount_f) != 0; };
+    for (size_t i = 0; i < m; i++)
+        if (wants_receiver(i)) eff[i].to_idx = found[i];   // 0: reason 9
+    LedgerPlan& p = l->plan;
+    SelectPlan sp;
+    if (hz_status e = select_plan(who, n_l1, eff_l1.data(), m, eff.data(), p, sp)) return e;
+    const size_t R = n_l1 + m;
+    const uint32_t m32 = (uint32_t)m, L32 = (uint32_t)n_l1, n_slots = (uint32_t)sp.slot_account.size();
+
+    // ---- integer tables, one pinned block
+    Carve c;
+    const size_t o_tx = c.take((m ? m : 1) * sizeof(hz_l2tx)), o_sel = c.take(m * sizeof(SelectTxDev)), o_l1 = c.take(n_l1 * sizeof(LedgerL1Dev)),
+                 o_slot_acct = c.take((size_t)n_slots * 4), o_partner = c.take(partner ? m * 4 : 0);
+    const size_t ints_bytes = c.end;
+    HZ_HIP(l->h_ints.grow(ints_bytes));
+    uint8_t* hb = (uint8_t*)l->h_ints.p;
+    if (m) memcpy(hb + o_tx, txs, m * sizeof(hz_l2tx));
+    for (size_t i = 0; i < m; i++) {
+        SelectTxDev d{};
+        const hz_l2tx& t = txs[i];
+        if (t.from_idx != 0) {
+            const bool has_amount = ledger_mantissa(t.amount_f) != 0, exit = t.to_idx == HZ_LEDGER_EXIT_IDX, unresolved = wants_receiver(i) && found[i] == 0;
+            d.amount_f = t.amount_f;
+            d.nonce = t.nonce;
+            d.token_id = t.token_id;
+            d.user_fee = t.user_fee;
+            d.acct_s = (uint32_t)(t.from_idx - l->first_idx);
+            d.slot_s = (uint16_t)sp.slot_s[n_l1 + i];
+            d.slot_r = HZ_L1_NO_SLOT;
+            d.flags = (uint8_t)(SELECT_ACTIVE | (exit ? SELECT_EXIT : 0u) | (unresolved ? SELECT_UNRESOLVED : 0u));
+            if (has_amount && !exit && !unresolved) {
+                d.flags |= SELECT_RECEIVER;
+                d.acct_r = (uint32_t)(eff[i].to_idx - l->first_idx);
+                d.slot_r = (uint16_t)sp.slot_r[n_l1 + i];
+            }
+        }
+        ((SelectTxDev*)(hb + o_sel))[i] = d;
+        if (partner) ((int32_t*)(hb + o_partner))[i] = t.from_idx != 0 ? partner[i] : -1;
+    }
+    for (size_t i = 0; i < n_l1; i++) {
+        const hz_l1tx& t = eff_l1[i];
+        LedgerL1Dev d{};
+        d.amount_f = t.amount_f;
+        d.load_amount_f = t.load_amount_f;
+        d.token_id = t.token_id;
+        d.acct_s = (uint32_t)(t.from_idx - l->first_idx);
+        d.slot_s = (uint16_t)sp.slot_s[i];
+        d.slot_r = HZ_L1_NO_SLOT;
+        d.pos_s = d.pos_r = -1;
+        d.pos_x = t.to_idx == HZ_LEDGER_EXIT_IDX && ledger_mantissa(t.amount_f) != 0 ? 0 : -1;   // a forceExit with an amount: the exit leaf's token is the sender's
+        if (sp.slot_r[i] >= 0) {
+            d.acct_r = (uint32_t)(t.to_idx - l->first_idx);
+            d.slot_r = (uint16_t)sp.slot_r[i];
+        }
+        memcpy(d.from_eth, t.from_eth_addr, 20);
+        ((LedgerL1Dev*)(hb + o_l1))[i] = d;
+    }
+    for (uint32_t q = 0; q < n_slots; q++) ((uint32_t*)(hb + o_slot_acct))[q] = (uint32_t)(sp.slot_account[q] - l->first_idx);
+
+    // ---- device buffers: work = ops[R][14] words | header | kept[m] | verdict[m] | rq_offset[m]
+    Carve w;
+    const size_t w_ops = w.take((R ? R : 1) * HZ_SELECT_OP_WORDS * 4), w_hdr = w.take(16), w_kept = w.take(m * 4), w_verdict = w.take(m), w_off = w.take(m);
+    const size_t back_bytes = w.end - w_hdr;
+    HZ_HIP(l->ints.grow(ints_bytes));
+    HZ_HIP(l->work.grow(w.end));
+    HZ_HIP(l->h_sel.grow(back_bytes));
+    uint8_t* db = (uint8_t*)l->ints.p;
+    uint8_t* wb = (uint8_t*)l->work.p;
+    const hz_l2tx* d_txs = (const hz_l2tx*)(db + o_tx);
+    LedgerDrain drain;
+    drain.s = s;
+    drain.armed = true;
+    HZ_HIP(hipMemcpyAsync(l->ints.p, l->h_ints.p, ints_bytes, hipMemcpyHostToDevice, s));
+    const uint8_t* d_sig_verdict = nullptr;
+    if (verify || links) {
+        if (hz_status e = ledger_sig_prepare(l, m, sigs, s, verify)) return e;
+        if (links)
+            if (hz_status e = ledger_rq_upload(l, m, rq_eff.data(), s)) return e;
+        if (verify) {
+            HZ_HIP(hipEventRecord(l->es0, s));
+            HZ_HIP(launch_ledger_sig(d_txs, (const hz_l2sig*)l->sig_in.p, chain_id, current_num_batch, l->sig_dev[0], l->sig_dev[1], l->sig_dev[2], (const uint8_t*)l->planes.p,
+                                     l->b8_table.p, l->N, l->first_idx, nullptr, l->verdict_dev, m32, s, 0, links ? (const uint8_t*)l->rq_in.p : nullptr));
+            HZ_HIP(hipEventRecord(l->es1, s));
+        } else if (m) {   // the V2 rows alone, for the link compare; no verdict yet
+            HZ_HIP(hipMemsetAsync(l->verdict_dev, 0, m, s));
+            HZ_HIP(launch_ledger_sig_v2(d_txs, (const hz_l2sig*)l->sig_in.p, l->sig_dev[1], m32, s));
+        }
+        if (links) {
+            hipLaunchKernelGGL(k_ledger_select_rq, dim3((m32 + 63) / 64), dim3(64), 0, s, d_txs, (const hz_l2sig*)l->sig_in.p, (const uint8_t*)l->rq_in.p,
+                               (const uint8_t*)l->sig_dev[1], partner ? (const int32_t*)(db + o_partner) : (const int32_t*)nullptr, l->verdict_dev, m32);
+            HZ_HIP(hipGetLastError());
+        }
+        if (m) d_sig_verdict = l->verdict_dev;
+    }
+    const uint32_t cap = (uint32_t)std::min<size_t>(max_keep, HZ_SELECT_MAX_POOL);
+    HZ_HIP(hipEventRecord(l->esel0, s));
+    hipLaunchKernelGGL(k_ledger_select, dim3(1), dim3(256), 0, s, (const LedgerL1Dev*)(db + o_l1), (const SelectTxDev*)(db + o_sel), (const uint32_t*)(db + o_slot_acct),
+                       partner ? (const int32_t*)(db + o_partner) : (const int32_t*)nullptr, d_sig_verdict, (const uint8_t*)l->planes.p, (uint32_t*)(wb + w_ops),
+                       (uint32_t*)(wb + w_hdr), (uint32_t*)(wb + w_kept), wb + w_verdict, wb + w_off, l->N, L32, m32, n_slots, cap);
+    HZ_HIP(hipGetLastError());   // (a workgroup with more LDS than the device grants is refused here, not faulted)
+    HZ_HIP(hipEventRecord(l->esel1, s));
+    HZ_HIP(hipMemcpyAsync(l->h_sel.p, wb + w_hdr, back_bytes, hipMemcpyDeviceToHost, s));
+    HZ_HIP(hipStreamSynchronize(s));
+    drain.armed = false;
+    float ms = 0;
+    HZ_HIP(hipEventElapsedTime(&ms, l->esel0, l->esel1));
+    l->select_ms = ms;
+    const uint8_t* back = (const uint8_t*)l->h_sel.p;
+    const uint32_t* hdr = (const uint32_t*)back;
+    if (hdr[2] != 0xFFFFFFFFu)
+        return set_err(HZ_ERR_INPUT, "%s: refused at index %u (L1 transaction %u), reason 5: %s", who, hdr[2], hdr[2], LEDGER_REASON[5]);
+    const size_t n_kept = hdr[0];
+    if (out->n_kept) *out->n_kept = n_kept;
+    if (out->rounds) *out->rounds = hdr[1];
+    if (out->kept && n_kept) memcpy(out->kept, back + (w_kept - w_hdr), n_kept * 4);
+    if (out->verdict && m) memcpy(out->verdict, back + (w_verdict - w_hdr), m);
+    if (out->rq_offset && m) memcpy(out->rq_offset, back + (w_off - w_hdr), m);
+    for (size_t i = 0; out->aux_to_idx && i < m; i++) out->aux_to_idx[i] = wants_receiver(i) ? found[i] : 0;
     return HZ_OK;
 }

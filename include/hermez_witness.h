@@ -627,6 +627,47 @@ hz_status hz_smt_plan(size_t m, const uint64_t* key, size_t n_sib, uint32_t* dep
  *                       position outside the batch, an L1 row, a NOP); verdict_out[m], 0 or 13, computed on the host with the routines the
  *                       kernel uses; the argument errors above. Both outputs may be NULL
  *   hz_ledger_rq_ms     device time of the link kernel of the last such call (0: none ran)
+ * SELECT. The calls above take a batch somebody has chosen; hz_ledger_select_batch chooses one from a POOL of m candidate L2
+ * transactions in the caller's order of preference, over the resident state and behind the same mandatory L1 rows: it keeps what is
+ * applicable after everything kept before it and DROPS the rest with a reason, where the calls above refuse. L1 rows run first and are
+ * nullified as in 8f, never dropped. partner[i] (or NULL: none) is the POOL index of the transaction that transaction i requires, -1 for
+ * none; rq[i].rq_offset is ignored (positions do not survive a drop), the three rq fields stay what the signer committed to.
+ *   STATIC verdicts, from the planes as they are before the batch plus the slots of created accounts: 1 the sender's token differs; 4 the
+ *   receiver's token differs and the amount is not zero; 7 / 8 from the signature kernels under HZ_LEDGER_VERIFY_SIGS; 9 to_idx == 0 with an
+ *   amount and no account among live plus created holds the signed destination; 13 partner[i] >= 0 and the rq fields are not that
+ *   transaction's link fields, or partner[i] < 0 and an rq field is not zero.
+ *   THE WALK goes in pool order over the balances and nonces the L1 run left. A transaction is kept when it has no static verdict, is not
+ *   forced out, fewer than max_keep are kept so far, its nonce is the sender's current nonce (else 2), that nonce is not 2^40 - 1 (else
+ *   12), balance >= amount + fee (else 3) and the receiver's new balance stays below 2^192 (else 5). A kept transaction debits its sender
+ *   by amount + fee -- whether or not a fee slot would take the fee -- raises its nonce, and credits the receiver when the amount is not
+ *   zero and the row is not an exit (a self-transfer sees the sender's new balance). A dropped transaction leaves no trace.
+ *   THE VERDICT byte: 0 kept; else the reason hz_ledger_apply_batch_atomic names when that transaction is the one it refuses -- 9 where 9
+ *   holds, otherwise the lowest reason that holds, static or not, on the state the walk has reached; HZ_SELECT_PARTNER (14) forced out by
+ *   the closure below (it ranks before a reason: the transaction was valid when a walk reached it); HZ_SELECT_FULL (15) nothing holds
+ *   but max_keep are kept. A pool NOP (from_idx == 0) gets 0, is not kept and not counted; its partner entry is not read.
+ *   CLOSURE over links. After a walk a kept transaction is forced out when its partner is not kept, or when the partner's distance d in
+ *   the compacted batch (row of the partner minus its own, kept transactions only) is no offset: d = 1 .. 3 is offset d, d = -4 .. -1
+ *   offset 8 + d. If anything was forced out the walk runs again from the L1 run's balances with the forced set added; the set only
+ *   grows, so there are at most (linked transactions + 1) walks, and *rounds is their number. The result is defined by this procedure
+ *   and nothing else. Links are one-directional: a dropped requirer does not drop a partner that does not require it.
+ *   hz_ledger_select_batch  out's members are nullable host pointers: verdict[m]; kept[m], pool indices in order, *n_kept of them valid;
+ *                       rq_offset[m], for a kept transaction its offset in the compacted batch (0 without a partner); aux_to_idx[m], the
+ *                       receiver the lookup found (0: none asked for or none found); *rounds. sigs may be NULL where
+ *                       hz_ledger_apply_batch_atomic allows it. HZ_ERR_ARG beyond that call's: partner[i] == i or outside -1 .. m - 1; m >
+ *                       HZ_SELECT_MAX_POOL or more than HZ_SELECT_MAX_SLOTS distinct accounts among the L1 rows and the pool, naming the
+ *                       first pool index that does not fit. HZ_ERR_INPUT: an L1 row that refuses the batch (reason 5), named as apply does
+ *                       CONTRACT. The call changes nothing resident: root, planes below size, size. It may write plane slots beyond size,
+ *                       as a refused hz_ledger_apply_batch_creates does. It does not touch the exit tree. It invalidates the *_dev
+ *                       outputs of earlier calls, as hz_ledger_verify_l2 does. A later hz_ledger_apply_batch_atomic over the same L1
+ *                       rows and the kept transactions, compacted and carrying rq_offset, with the same flags, is not refused for
+ *                       reasons 1 - 5, 7 - 9, 12 or 13 at an L2 row. Still possible, and not this call's business: reason 6 and reason
+ *                       5 at a fee slot (both depend on a fee plan the call never sees) and the tree planners' depth errors
+ *   hz_ledger_plan_select  DIAGNOSTIC, no device: the local slot of every L1 row's and pool transaction's sender and receiver (-1: none;
+ *                       aux_to_idx[m] or NULL stands for the lookup: a to_idx == 0 row takes its receiver from there, 0 or NULL: none),
+ *                       the accounts of the slots, the argument errors above (the state is not known here: an L1 row that creates an
+ *                       account is given with its auxFromIdx in from_idx's place, from_idx == 0 is HZ_ERR_ARG); and, given kept_in[m], the closure step alone --
+ *                       forced_out[m] and rq_offset_out[m] -- by the routine the kernel runs. Every output may be NULL
+ *   hz_ledger_select_ms device time of k_ledger_select in the last hz_ledger_select_batch
  * OUT OF SCOPE: L1 transactions that create accounts or exit through a call other than hz_ledger_apply_batch_exits (creates:
  * hz_ledger_apply_batch_creates on a growing ledger), an L1 amount with
  * to_idx == 0 (no receiver), exit trees of earlier batches kept resident, a resident address index kept across
@@ -763,6 +804,26 @@ hz_status hz_ledger_verify_l2_atomic(hz_ledger* l, size_t m, const hz_l2tx* txs,
 hz_status hz_ledger_plan_atomic(size_t n_l1, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, const hz_l2rq* rq /* [m] or NULL */,
                                 int64_t* target_row_out /* [m]: the row, -1: zeros */, uint8_t* verdict_out /* [m]: 0 or 13 */);
 double hz_ledger_rq_ms(const hz_ledger* l);
+#define HZ_SELECT_MAX_POOL 4096  /* candidates in one hz_ledger_select_batch */
+#define HZ_SELECT_MAX_SLOTS 4096 /* distinct accounts its L1 rows and pool may touch */
+#define HZ_SELECT_PARTNER 14     /* verdicts of hz_ledger_select_batch that are no refusal reasons */
+#define HZ_SELECT_FULL 15
+typedef struct {
+    uint8_t* verdict;     /* [m] */
+    uint32_t* kept;       /* [m], *n_kept valid */
+    size_t* n_kept;
+    uint8_t* rq_offset;   /* [m] */
+    uint64_t* aux_to_idx; /* [m] */
+    uint32_t* rounds;
+} hz_ledger_select_out;
+hz_status hz_ledger_select_batch(hz_ledger* l, size_t n_l1, const hz_l1tx* l1, const uint8_t* from_bjj /* [n_l1][32] or NULL */, size_t m,
+                                 const hz_l2tx* txs, const hz_l2sig* sigs, const hz_l2rq* rq /* [m] or NULL */, const int32_t* partner /* [m] or NULL */,
+                                 uint32_t flags, uint32_t chain_id, uint32_t current_num_batch, size_t max_keep, const hz_ledger_select_out* out);
+hz_status hz_ledger_plan_select(size_t n_l1, const hz_l1tx* l1, size_t m, const hz_l2tx* txs, const uint64_t* aux_to_idx /* [m] or NULL */,
+                                const int32_t* partner /* [m] or NULL */, const uint8_t* kept_in /* [m] or NULL */, int32_t* slot_sender_out /* [n_l1 + m] */,
+                                int32_t* slot_receiver_out /* [n_l1 + m] */, size_t* n_slots_out, uint64_t* slot_account_out /* [n_slots] */,
+                                uint8_t* forced_out /* [m] */, uint8_t* rq_offset_out /* [m] */);
+double hz_ledger_select_ms(const hz_ledger* l);
 
 /* Poseidon batch: n independent permutations of width t = n_inputs + 1 (2..7). ----------------
  * `in`  : [n][t-1] canonical elements; `out`: [n] digests (state[0] after the last round).
