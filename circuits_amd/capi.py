@@ -127,6 +127,7 @@ class hz_l2rq(ctypes.Structure):
 LEDGER_RQ_REASON = 13   # the rq fields of a row are not its target's link fields
 SELECT_MAX_POOL, SELECT_MAX_SLOTS = 4096, 4096   # HZ_SELECT_MAX_POOL, HZ_SELECT_MAX_SLOTS
 SELECT_PARTNER, SELECT_FULL = 14, 15             # verdicts of hz_ledger_select_batch that are no refusal reasons
+LEDGER_FEE_OVERFLOW = 16                         # HZ_LEDGER_FEE_OVERFLOW: the refusal reason of a fee of 2^128 or more
 
 
 class hz_ledger_select_out(ctypes.Structure):

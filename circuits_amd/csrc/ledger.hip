@@ -3,7 +3,7 @@
 // The split is the library's: the host does integer work on indices only (ledger_plan.h: events, their grouping by account, fee slots),
 // the device everything that touches a 256-bit value. One call is
 //   k_ledger_tx        a lane per transaction: float40 -> amount, fee = amount x table[selector] (>> 60 below 192), the signed deltas
-//                      of its sender and receiver events
+//                      of its sender and receiver events; a fee of 2^128 or more lowers the failure word with reason 16
 //   k_ledger_fee_sum / k_ledger_fee_scan   the accumulated fees after every transaction, per slot: chunk sums, then a lane per
 //                      (chunk, slot) walks its chunk; the last row is the delta of the fee events
 //   k_ledger_scan      balances and nonces with sequential semantics: the events of an account lie behind each other (grouped order)
@@ -76,7 +76,7 @@
 #define HZ_LEDGER_MAX_TX (1u << 20)
 #define HZ_LEDGER_MAX_F 64u
 #define HZ_LEDGER_CHUNK 64u   // transactions per lane of the fee scan
-#define HZ_LEDGER_REASONS 14u   // refusal reasons 1 .. 13; 0 is none
+#define HZ_LEDGER_REASONS 17u   // refusal reasons 1 .. 13 and 16; 0 is none, 14 and 15 are verdicts of hz_ledger_select_batch
 
 namespace hz {
 
@@ -93,10 +93,13 @@ struct LedgerPos {
 };
 
 // ---- kernels ----------------------------------------------------------------------------------------------------------------------------
-// amount = mantissa x 10^exponent (src/lib/decode-float.circom), fee (src/compute-fee.circom); deltas at the events' grouped positions
+__device__ __forceinline__ void ledger_fail(uint32_t* word, uint32_t unit, uint32_t reason) { atomicMin(word, (unit << 8) | reason); }
+
+// amount = mantissa x 10^exponent (src/lib/decode-float.circom), fee (src/compute-fee.circom); deltas at the events' grouped positions.
+// A fee of 2^128 or more lowers the failure word with reason 16 at the row: only where the circuit applies the fee, an L2 row that is no NOP
 __global__ __launch_bounds__(64) void k_ledger_tx(const hz_l2tx* __restrict__ txs, const int32_t* __restrict__ pos_s, const int32_t* __restrict__ pos_r,
                                                   uint8_t* __restrict__ fee_out, uint8_t* __restrict__ delta, const int32_t* __restrict__ pos_x,
-                                                  uint8_t* __restrict__ exit_amt, uint32_t m, uint32_t n_l1) {
+                                                  uint8_t* __restrict__ exit_amt, uint32_t* __restrict__ fail_word, uint32_t m, uint32_t n_l1) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= m) return;
     Fc fee = fc_zero();
@@ -104,6 +107,7 @@ __global__ __launch_bounds__(64) void k_ledger_tx(const hz_l2tx* __restrict__ tx
         const Fc amount = l1_float40(txs[i].amount_f);
         const uint32_t sel = txs[i].user_fee;
         fee = ledger_fee(amount, sel);
+        if (ledger_fee_overflows(fee)) ledger_fail(fail_word, i, HZ_LEDGER_FEE_OVERFLOW);
         store_fr(delta + (size_t)pos_s[i] * 32, u256_neg(u256_add(amount, fee)));
         if (pos_r[i] >= 0) store_fr(delta + (size_t)pos_r[i] * 32, amount);
         if (pos_x && pos_x[i] >= 0) store_fr(exit_amt + (size_t)pos_x[i] * 32, amount);   // an exit: no receiver delta (pos_x == NULL: the call takes none)
@@ -141,8 +145,6 @@ __global__ __launch_bounds__(64) void k_ledger_fee_scan(const uint8_t* __restric
         if (pos_fee[j] >= 0) store_fr(delta + (size_t)pos_fee[j] * 32, acc);
     }
 }
-
-__device__ __forceinline__ void ledger_fail(uint32_t* word, uint32_t unit, uint32_t reason) { atomicMin(word, (unit << 8) | reason); }
 
 // a lane per account group: the leaf before and after every event of the account, in order
 __global__ __launch_bounds__(64) void k_ledger_scan(const LedgerPos* __restrict__ pos, const uint32_t* __restrict__ seg_start, const hz_l2tx* __restrict__ txs,
@@ -347,7 +349,9 @@ static const char* const LEDGER_REASON[HZ_LEDGER_REASONS] = {"", "the sender's t
                                               "no account holds the signed destination with the transaction's token",
                                               "the receiver's ethAddr is not the signed to_eth_addr", "the receiver's key is not the signed to_bjj_ay / to_bjj_sign",
                                               "the sender's nonce is 2^40 - 1: the next nonce is not a leaf field",
-                                              "the rq fields are not the link fields of the row rq_offset names"};
+                                              "the rq fields are not the link fields of the row rq_offset names", "", "",
+                                             "amount x fee factor does not fit 128 bits (src/compute-fee.circom:89-91)"};
+static_assert(HZ_LEDGER_FEE_OVERFLOW == 16 && HZ_LEDGER_FEE_OVERFLOW > HZ_SELECT_FULL, "the reason behind the select verdicts");
 
 // ledger_sig.hip
 hipError_t launch_ledger_sig(const hz_l2tx* d_txs, const hz_l2sig* d_sigs, uint32_t chain_id, uint32_t current_num_batch, uint8_t* d_tcd, uint8_t* d_v2, uint8_t* d_hash,
@@ -1151,7 +1155,7 @@ static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_
     HZ_HIP(hipEventRecord(l->e0, s));
     if (R32) {
         hipLaunchKernelGGL(k_ledger_tx, dim3((R32 + 63) / 64), dim3(64), 0, s, d_txs, (const int32_t*)(db + o_pos_s), (const int32_t*)(db + o_pos_r), wb + w_fee,
-                           wb + w_delta, X ? (const int32_t*)(db + o_pos_x) : (const int32_t*)nullptr, wb + w_xamt, R32, L32);
+                           wb + w_delta, X ? (const int32_t*)(db + o_pos_x) : (const int32_t*)nullptr, wb + w_xamt, d_fail, R32, L32);
         HZ_HIP(hipGetLastError());
     }
     if (L32) {   // the deltas of the L1 events, beside those k_ledger_tx wrote: one workgroup, no synchronise of its own

@@ -5,7 +5,7 @@
 // in LDS, in one workgroup, a parallel phase on each side:
 //   1 parallel   a lane per local slot: the resident balance into LDS. A lane per L1 row: l1_static. A lane per pool transaction: amount,
 //                fee, debit = amount + fee; the static verdict (the sender's token 1, the receiver's token 4, the verdict bytes of the
-//                signature and link kernels 7 / 8 / 13, an unresolved destination 9); want = tx.nonce - resident nonce as a small
+//                signature and link kernels 7 / 8 / 13, an unresolved destination 9, a fee of 2^128 or more 16); want = tx.nonce - resident nonce as a small
 //                integer. The operands of every row go to a per-call buffer, 14 words a row
 //   2 serial     rows are staged 64 at a time into an LDS tile by the first wavefront; one lane walks the tile: l1_step on an L1 row,
 //                select_step / select_credit on a pool row, with the forced-out mask and the max_keep cap. LDS and registers only
@@ -75,11 +75,13 @@ HZ_HD bool select_credit(Fc& to, const Fc& amount) {
 // the lower of two verdicts of which 0 means none
 HZ_HD uint32_t select_lower(uint32_t a, uint32_t b) { return a == 0u ? b : b == 0u ? a : a < b ? a : b; }
 
-// the static verdict: 9 where it holds, else the lowest of 1, 4 and the verdict byte of the signature and link kernels (0, 7, 8 or 13)
-HZ_HD uint32_t select_static(uint32_t flags, uint32_t token_id, uint32_t tok_s, uint32_t tok_r, uint32_t sig_verdict) {
+// the static verdict: 9 where it holds, else the lowest of 1, 4, the verdict byte of the signature and link kernels (0, 7, 8 or 13) and
+// 16 for a fee of 2^128 or more (fee_over: ledger_fee_overflows, amount and selector alone; a caller that knows no fee leaves it out)
+HZ_HD uint32_t select_static(uint32_t flags, uint32_t token_id, uint32_t tok_s, uint32_t tok_r, uint32_t sig_verdict, bool fee_over = false) {
     if (flags & SELECT_UNRESOLVED) return 9u;
     if (token_id != tok_s) return 1u;
-    return select_lower((flags & SELECT_RECEIVER) && token_id != tok_r ? 4u : 0u, sig_verdict);
+    const uint32_t v = select_lower((flags & SELECT_RECEIVER) && token_id != tok_r ? 4u : 0u, sig_verdict);
+    return select_lower(v, fee_over ? (uint32_t)HZ_LEDGER_FEE_OVERFLOW : 0u);
 }
 
 // the rqOffset that names a row d rows away, 0: none does
@@ -176,10 +178,11 @@ __global__ __launch_bounds__(256) void k_ledger_select(const LedgerL1Dev* __rest
             const Fc e0_s = load_fr(planes + (size_t)t.acct_s * 32);
             uint32_t tok_r = 0u;
             if (t.flags & SELECT_RECEIVER) tok_r = load_fr(planes + (size_t)t.acct_r * 32).v[0];
-            const uint32_t st = select_static(t.flags, t.token_id, e0_s.v[0], tok_r, sig_verdict ? sig_verdict[i] : 0u);
             const uint64_t resident = (uint64_t)e0_s.v[1] | ((uint64_t)(e0_s.v[2] & 0xFFu) << 32);
             amount = l1_float40(t.amount_f);
-            debit = u256_add(amount, ledger_fee(amount, t.user_fee));
+            const Fc fee = ledger_fee(amount, t.user_fee);
+            const uint32_t st = select_static(t.flags, t.token_id, e0_s.v[0], tok_r, sig_verdict ? sig_verdict[i] : 0u, ledger_fee_overflows(fee));
+            debit = u256_add(amount, fee);
             word = select_want(t.nonce, resident) << 8 | st;
         }
         lds.forced[i] = 0u;

@@ -436,7 +436,12 @@ hz_status hz_smt_plan(size_t m, const uint64_t* key, size_t n_sib, uint32_t* dep
  *   12 the sender's nonce is 2^40 - 1: the next nonce is not a leaf field. The circuit does not wrap (src/rollup-tx.circom:519 feeds
  *      nonce + 1 into the state hash), so neither does the ledger. It ranks like 1 - 8 (lowest index, then lowest reason) in every call
  *      that applies L2 transactions. A transaction nonce of 2^40 or more never equals a resident nonce: that is reason 2
- * builder.py raises for 1, 3 and 6 and builds inputs the circuit rejects for 2 and 4; the ledger refuses those two as well. A refused
+ *   16 (HZ_LEDGER_FEE_OVERFLOW) amount x fee factor does not fit 128 bits (src/compute-fee.circom:89-91): the fee, amount * table[user_fee]
+ *      after the shift, is 2^128 or more. Selectors 31 to 255 can reach it with a float40 amount, selectors 0 to 30 cannot. Checked only
+ *      where the circuit applies the fee: an L2 row that is not a NOP, exits included; an L1 row and a NOP are never refused for it. It
+ *      ranks with 1 - 8, 12 and 13 (lowest row, then lowest reason; reason 9 keeps its precedence) in all seven apply calls
+ * builder.py raises for 1, 3 and 6 and builds inputs the circuit rejects for 2 and 4; the ledger refuses those two as well.
+ * builder.py also builds inputs the circuit rejects for 16, as upstream's BatchBuilder does; the ledger refuses them. A refused
  * call changes nothing (fields, tree, root), writes none of its outputs and leaves no work in flight; the one exception is hz_smt_apply's:
  * a HIP failure reported after the write-back was queued. HZ_ERR_ARG: null arguments, an index outside the state, to_idx 0 or 1 (transfer
  * to an address, exit: not supported yet), amount_f >= 2^40, too many updates, n_sib outside k .. 64, F > 64, apply before load.
@@ -451,7 +456,8 @@ hz_status hz_smt_plan(size_t m, const uint64_t* key, size_t n_sib, uint32_t* dep
  *                       pointers): txCompressedData, txCompressedDataV2 and M of every transaction, [m] each; a NOP's rows are those of
  *                       the empty transaction
  *   hz_ledger_verify_l2 the mempool filter: the same kernels, one verdict per transaction (0 accepted or NOP, 7, 8; 7 beside 8 is 7) in
- *                       verdict_out[m]. Changes nothing resident and refuses nothing; the transactions need not be applicable in order
+ *                       verdict_out[m]. Changes nothing resident and refuses nothing; the transactions need not be applicable in order.
+ *                       It and hz_ledger_verify_l2_atomic are signature and link filters (0, 7, 8, 13): neither knows reason 16
  *   hz_ledger_sig_outputs_dev  sig_out's arrays as DEVICE pointers of the last successful hz_ledger_apply_l2_signed / _verify_l2, valid
  *                       until the ledger's next call; fit for hz_set_input_dev
  *   hz_ledger_sig_ms    device time of the two signature kernels of the last such call
@@ -635,7 +641,7 @@ hz_status hz_smt_plan(size_t m, const uint64_t* key, size_t n_sib, uint32_t* dep
  *   STATIC verdicts, from the planes as they are before the batch plus the slots of created accounts: 1 the sender's token differs; 4 the
  *   receiver's token differs and the amount is not zero; 7 / 8 from the signature kernels under HZ_LEDGER_VERIFY_SIGS; 9 to_idx == 0 with an
  *   amount and no account among live plus created holds the signed destination; 13 partner[i] >= 0 and the rq fields are not that
- *   transaction's link fields, or partner[i] < 0 and an rq field is not zero.
+ *   transaction's link fields, or partner[i] < 0 and an rq field is not zero; 16 the fee is 2^128 or more (amount and selector alone).
  *   THE WALK goes in pool order over the balances and nonces the L1 run left. A transaction is kept when it has no static verdict, is not
  *   forced out, fewer than max_keep are kept so far, its nonce is the sender's current nonce (else 2), that nonce is not 2^40 - 1 (else
  *   12), balance >= amount + fee (else 3) and the receiver's new balance stays below 2^192 (else 5). A kept transaction debits its sender
@@ -660,7 +666,7 @@ hz_status hz_smt_plan(size_t m, const uint64_t* key, size_t n_sib, uint32_t* dep
  *                       as a refused hz_ledger_apply_batch_creates does. It does not touch the exit tree. It invalidates the *_dev
  *                       outputs of earlier calls, as hz_ledger_verify_l2 does. A later hz_ledger_apply_batch_atomic over the same L1
  *                       rows and the kept transactions, compacted and carrying rq_offset, with the same flags, is not refused for
- *                       reasons 1 - 5, 7 - 9, 12 or 13 at an L2 row. Still possible, and not this call's business: reason 6 and reason
+ *                       reasons 1 - 5, 7 - 9, 12, 13 or 16 at an L2 row. Still possible, and not this call's business: reason 6 and reason
  *                       5 at a fee slot (both depend on a fee plan the call never sees) and the tree planners' depth errors
  *   hz_ledger_plan_select  DIAGNOSTIC, no device: the local slot of every L1 row's and pool transaction's sender and receiver (-1: none;
  *                       aux_to_idx[m] or NULL stands for the lookup: a to_idx == 0 row takes its receiver from there, 0 or NULL: none),
@@ -808,6 +814,7 @@ double hz_ledger_rq_ms(const hz_ledger* l);
 #define HZ_SELECT_MAX_SLOTS 4096 /* distinct accounts its L1 rows and pool may touch */
 #define HZ_SELECT_PARTNER 14     /* verdicts of hz_ledger_select_batch that are no refusal reasons */
 #define HZ_SELECT_FULL 15
+#define HZ_LEDGER_FEE_OVERFLOW 16 /* refusal reason: amount x fee factor does not fit 128 bits (src/compute-fee.circom:89-91) */
 typedef struct {
     uint8_t* verdict;     /* [m] */
     uint32_t* kept;       /* [m], *n_kept valid */

@@ -116,11 +116,13 @@ def scheme_model(leaf_of, txs, plan_tokens, fee_idxs):
     m, F = len(txs), len(plan_tokens)
     p = plan_model(txs, plan_tokens, fee_idxs)
     M = len(p["account"])
-    delta, acc, rows = [0] * M, [0] * F, []
+    delta, acc, rows, over = [0] * M, [0] * F, [], []
     for i, t in enumerate(txs):
         if t.get("fromIdx", 0):
             amount = B.float2fix(t.get("amountF", 0))
             fee = B.compute_fee(amount, t.get("userFee", 0))
+            if fee >> 128:   # reason 16: the circuit rejects such a fee (src/compute-fee.circom:89-91); only a charged row has one
+                over.append((i, 16))
             delta[p["ev_sender"][i]] = -(amount + fee)
             if p["ev_receiver"][i] >= 0:
                 delta[p["ev_receiver"][i]] = amount
@@ -133,7 +135,7 @@ def scheme_model(leaf_of, txs, plan_tokens, fee_idxs):
     groups = {}
     for e, a in enumerate(p["account"]):
         groups.setdefault(a, []).append(e)
-    fail = None
+    fail = min(over) if over else None
     before = [None] * M
     for a in sorted(groups, reverse=True):   # any order of the groups must give the same answer
         leaf = dict(leaf_of(a))

@@ -172,13 +172,15 @@ def scheme_model(leaf_of, l1_txs, l2_txs, plan_tokens, fee_idxs):
     p = plan_model(l1_txs, l2_txs, plan_tokens, fee_idxs)
     M, X = len(p["account"]), len(p["exit_row"])
     l1_delta, flags, eff3s = l1_run(leaf_of, l1_txs, p)
-    delta, acc, rows, amounts = [0] * M, [0] * F, [], [0] * X
+    delta, acc, rows, amounts, over = [0] * M, [0] * F, [], [0] * X, []
     for e, v in l1_delta.items():
         delta[e] = v
     for i, t in enumerate(rows_tx):
         if i >= n_l1 and t.get("fromIdx", 0):
             amount = L1.amount_of(t)
             fee = B.compute_fee(amount, t.get("userFee", 0))
+            if fee >> 128:   # reason 16: the circuit rejects such a fee (src/compute-fee.circom:89-91); only a charged row has one
+                over.append((i, 16))
             delta[p["ev_sender"][i]] = -(amount + fee)
             if p["ev_receiver"][i] >= 0:
                 delta[p["ev_receiver"][i]] = amount
@@ -193,7 +195,7 @@ def scheme_model(leaf_of, l1_txs, l2_txs, plan_tokens, fee_idxs):
     groups = {}
     for e, a in enumerate(p["account"]):
         groups.setdefault(a, []).append(e)
-    fail, before, after = None, [None] * M, {}
+    fail, before, after = min(over) if over else None, [None] * M, {}
     for a in sorted(groups, reverse=True):
         leaf = dict(leaf_of(a))
         for e in groups[a]:

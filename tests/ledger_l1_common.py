@@ -122,13 +122,15 @@ def scheme_model(leaf_of, l1_txs, l2_txs, plan_tokens, fee_idxs):
     p = plan_model(l1_txs, l2_txs, plan_tokens, fee_idxs)
     M = len(p["account"])
     l1_delta, flags, _, slot_bal = l1_run(leaf_of, l1_txs, p)
-    delta, acc, rows = [0] * M, [0] * F, []
+    delta, acc, rows, over = [0] * M, [0] * F, [], []
     for e, v in l1_delta.items():
         delta[e] = v
     for i, t in enumerate(rows_tx):
         if i >= n_l1 and t.get("fromIdx", 0):
             amount = amount_of(t)
             fee = B.compute_fee(amount, t.get("userFee", 0))
+            if fee >> 128:   # reason 16: the circuit rejects such a fee (src/compute-fee.circom:89-91); only a charged row has one
+                over.append((i, 16))
             delta[p["ev_sender"][i]] = -(amount + fee)
             if p["ev_receiver"][i] >= 0:
                 delta[p["ev_receiver"][i]] = amount
@@ -141,7 +143,7 @@ def scheme_model(leaf_of, l1_txs, l2_txs, plan_tokens, fee_idxs):
     groups = {}
     for e, a in enumerate(p["account"]):
         groups.setdefault(a, []).append(e)
-    fail, before, after = None, [None] * M, {}
+    fail, before, after = min(over) if over else None, [None] * M, {}
     for a in sorted(groups, reverse=True):
         leaf = dict(leaf_of(a))
         for e in groups[a]:

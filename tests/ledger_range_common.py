@@ -6,6 +6,7 @@ import functools
 
 import numpy as np
 
+import fee_bound_common as FB
 import ledger_addr_common as A
 import ledger_common as C
 import ledger_l1_common as L1
@@ -40,7 +41,9 @@ def set_balance(cols, j, balance):
 
 
 # ---- the wide state ----------------------------------------------------------------------------------------------------------------------
-EXACT_F, EXACT_SEL = TOP, 191                                      # the transfer that empties its sender exactly
+EXACT_F, EXACT_SEL = TOP, 30                                       # the transfer that empties its sender exactly: the highest selector that the
+assert FB.float40_table()[30][2] is None and FB.float40_table()[31][2] is not None   # largest amount can carry (a fee of 2^128 or more is reason 16)
+FEE_255, FEE_191 = FB.float40_table()[255][1], FB.float40_table()[191][1]   # the largest amounts those two selectors can carry
 EXACT = V + B.compute_fee(V, EXACT_SEL)
 
 
@@ -87,18 +90,41 @@ def wide_state():
 WIDE_FEE = 40   # offset of token 1's fee account
 
 
-def all_selectors(st):
-    """256 transfers, transaction i with selector i, mantissa MANTISSAS[i % 5] and exponent i % 32 lowered until amount + fee is below
-    1/256 of a 2^191 balance -> (txs, plan, idxs)"""
-    f0, txs, nonce = st.first_idx, [], {}
+def all_selectors_rows():
+    """[(selector, float40, overflowing float40 or None)]: row i has selector i, mantissa MANTISSAS[i % 5] and exponent i % 32 lowered until amount + fee is below
+    1/256 of a 2^191 balance. The circuit
+    rejects a fee of 2^128 or more (src/compute-fee.circom:89-91) and so does the ledger (reason 16): where that mantissa gives such a fee
+    (32 rows, fees of 129 to 183 bits) the row takes the largest mantissa of its exponent whose fee stays below 2^128 -- 0, a zero amount,
+    where a mantissa of 1 is already above it -- and the original goes to the refusal tests"""
+    rows = []
     for i in range(256):
         mant, expo = MANTISSAS[i % 5], i % 32
-        while B.float2fix(f40(mant, expo)) + B.compute_fee(B.float2fix(f40(mant, expo)), i) >= RICH >> 8:
+        while B.float2fix(f40(mant, expo)) + B.compute_fee(B.float2fix(f40(mant, expo)), i) >= RICH >> 8:   # below 1/256 of a 2^191 balance
             expo -= 1
+        f = f40(mant, expo)
+        if B.compute_fee(B.float2fix(f), i) >> 128:
+            rows.append((i, f40(FB._search(i, expo), expo), f))
+        else:
+            rows.append((i, f, None))
+    return rows
+
+
+def all_selectors(st):
+    """256 transfers, transaction i with selector i, all_selectors_rows' amounts (every exponent, every fee below 2^128) ->
+    (txs, plan, idxs)"""
+    f0, txs, nonce = st.first_idx, [], {}
+    for i, f, _ in all_selectors_rows():
+        assert B.float2fix(f) + B.compute_fee(B.float2fix(f), i) < RICH >> 8
         frm = f0 + 1 + i % 4
-        txs.append(txf(frm, f0 + 48 + i % 16, f40(mant, expo), i, nonce=nonce.get(frm, 0)))
+        txs.append(txf(frm, f0 + 48 + i % 16, f, i, nonce=nonce.get(frm, 0)))
         nonce[frm] = nonce.get(frm, 0) + 1
     return txs, [1], [f0 + WIDE_FEE]
+
+
+def overflowing_selectors(st):
+    """the 32 rows all_selectors no longer holds, as single transfers from an account that could pay them: [(txs, plan, idxs)]"""
+    f0 = st.first_idx
+    return [([txf(f0 + 1 + i % 4, f0 + 48 + i % 16, over, i, nonce=0)], [1], [f0 + WIDE_FEE]) for i, _, over in all_selectors_rows() if over is not None]
 
 
 def nonce_carry(st):
@@ -202,7 +228,7 @@ def l1_high_limbs(st):
     l1_txs = [top_l1(st, f0 + 41, f0 + 42, amount=True, load=True), top_l1(st, f0 + 43, f0 + 44, amount=True), top_l1(st, f0 + 1, f0 + 47, amount=True, load=True),
               top_l1(st, f0 + 45, 0, load=True), top_l1(st, f0 + 41, 0, load=True)]
     spend = B.floor_fix2float(st.state(f0 + 42)["balance"] + V // 2)   # more than 42 held before the run
-    l2_txs = [txf(f0 + 42, f0 + 9, spend, 176, nonce=0), txf(f0 + 1, f0 + 48, TOP, 191, nonce=0)]
+    l2_txs = [txf(f0 + 42, f0 + 9, spend, EXACT_SEL, nonce=0), txf(f0 + 1, f0 + 48, TOP, EXACT_SEL, nonce=0)]
     counted = B.floor_fix2float(st.state(f0 + 44)["balance"] + V // 2)
     refused = [(([top_l1(st, f0 + 43, f0 + 44, amount=True)], [txf(f0 + 8, f0 + 9, f40(5, 0), 0, nonce=0), txf(f0 + 44, f0 + 9, counted, 0, nonce=0)], plan, idxs), 2, 3),
                (([top_l1(st, f0 + 41, 0, load=True), top_l1(st, f0 + 46, 0, load=True)], [], plan, idxs), 1, 5)]
@@ -232,10 +258,11 @@ def signed_state():
 
 def signed_extremes(st, by_addr=False):
     """four signed transfers: nonce 2^40 - 2, token 2^32 - 1, maxNumBatch 2^32 - 1 in all; userFee 255 on amount 0 (exponent 31, mantissa
-    0), on 10^31, the largest amount at selector 191, and one to the "any" address with a key of sign 1 (by_addr: with toIdx = 0)"""
+    0), on the largest amount selector 255 can carry, the largest at selector 191, and one to the "any" address with a key of sign 1
+    (by_addr: with toIdx = 0 and that amount of selector 255)"""
     f0, leaf = st.first_idx, st.state(st.any)
     assert leaf["sign"] == 1 and leaf["ethAddr"] == A.ANY
-    rows = [(f0 + 6, f40(0, 31), 255), (f0 + 7, f40(1, 31), 255), (f0 + 8, TOP, 191), (st.any, f40(0, 31) if not by_addr else f40(3, 31), 255)]
+    rows = [(f0 + 6, f40(0, 31), 255), (f0 + 7, FEE_255, 255), (f0 + 8, FEE_191, 191), (st.any, f40(0, 31) if not by_addr else FEE_255, 255)]
     txs = []
     for i, (to, amount_f, sel) in enumerate(rows):
         t = dict(txf(f0 + 2 + i, to, amount_f, sel, token=TOK_MAX, nonce=NONCE_MAX - 1), maxNumBatch=(1 << 32) - 1)
@@ -259,6 +286,8 @@ def check_lines():
     for sel in range(256):
         for f in amounts:
             lines.append("g %x %x %x" % (f, sel, B.compute_fee(B.float2fix(f), sel)))
+    for sel, below, above in FB.float40_table():   # the bound of 2^128 from both sides, for every selector
+        lines += ["v %x %x %x" % (f, sel, FB.fee_of(f, sel) >> 128 != 0) for f in (below, above) if f is not None]
     for i in range(1, 8):   # a carry and a borrow across every limb boundary
         lo, one = (1 << 32 * i) - 1, 1
         lines.append("a %x %x %x" % (lo, one, lo + one))

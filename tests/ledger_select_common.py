@@ -14,7 +14,7 @@ import ledger_l1_common as L1
 import ledger_sig_common as S
 from circuits_amd import builder as B
 
-PARTNER, FULL = 14, 15
+PARTNER, FULL, FEE_OVERFLOW = 14, 15, 16
 NONCE_MAX = (1 << 40) - 1
 LIMIT = 1 << 192
 Refused = CR.Refused
@@ -91,6 +91,8 @@ def model(acc, l1_txs, pool, current_num_batch=1, max_keep=None, verify=False, c
         want = Q.link_fields(pool[partner[i]]) if partner[i] >= 0 else (0, 0, 0)
         if tuple(t.get(f, 0) for f in Q.RQ_FIELDS) != want:
             bad.add(13)
+        if B.compute_fee(L1.amount_of(t), t.get("userFee", 0)) >> 128:   # amount and selector alone: the highest-numbered reason
+            bad.add(FEE_OVERFLOW)
         static.append(bad - {0})
     active = [bool(t.get("fromIdx", 0)) for t in pool]
     forced, rounds = set(), 0
@@ -259,5 +261,19 @@ def check_lines():
         lines.append("l %x %x %x %x" % (kept_p, row, prow, offset_of(prow - row) if kept_p else 0))
     for flags, token, tok_s, tok_r, sig, exp in ((1, 1, 1, 0, 0, 0), (1, 1, 2, 0, 0, 1), (9, 1, 1, 2, 0, 4), (1, 1, 1, 2, 0, 0), (9, 1, 1, 1, 7, 7), (9, 1, 1, 2, 7, 4),
                                                  (9, 1, 1, 2, 13, 4), (1, 1, 1, 0, 13, 13), (1, 1, 1, 0, 8, 8), (5, 1, 2, 0, 7, 9), (5, 1, 1, 0, 0, 9), (9, 2, 1, 1, 7, 1)):
-        lines.append("t %x %x %x %x %x %x" % (flags, token, tok_s, tok_r, sig, exp))
+        lines.append("t %x %x %x %x %x 0 %x" % (flags, token, tok_s, tok_r, sig, exp))
+        lines.append("t %x %x %x %x %x 1 %x" % (flags, token, tok_s, tok_r, sig, exp or FEE_OVERFLOW))   # every other reason is lower
+    return "\n".join(lines) + "\n" + fee_lines()
+
+
+def fee_lines():
+    """g float40 selector fee over: ledger_fee and ledger_fee_overflows on l1_float40's amount, over the whole float40 table of
+    fee_bound_common (both check programs read this record)"""
+    import fee_bound_common as FB
+    lines = []
+    for sel, below, above in FB.float40_table():
+        for f in (below, above):
+            if f is not None:
+                fee = FB.fee_of(f, sel)
+                lines.append("g %x %x %x %x" % (f, sel, fee, fee >> 128 != 0))
     return "\n".join(lines) + "\n"

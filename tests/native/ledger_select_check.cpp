@@ -3,7 +3,8 @@
 //   c to amount ok new                             select_credit: whether the new balance stays below 2^192, the balance it leaves
 //   o d expect                                     select_offset of the distance d (32 bits, two's complement)
 //   l partner_kept row partner_row expect          select_link: the offset, 0 for forced out
-//   t flags token tok_s tok_r sig expect           select_static
+//   t flags token tok_s tok_r sig fee_over expect  select_static
+//   g float40 selector fee over                    ledger_fee on l1_float40's amount (up to 201 bits), then ledger_fee_overflows
 // -- and prints "cases=N mismatches=K".
 #include <stdint.h>
 #include <stdio.h>
@@ -50,8 +51,11 @@ int main() {
             ok = select_offset((int64_t)(int32_t)(uint32_t)u(1)) == u(2);
         } else if (op == 'l' && f.size() == 5) {
             ok = select_link(u(1) != 0, (uint32_t)u(2), (uint32_t)u(3)) == u(4);
-        } else if (op == 't' && f.size() == 7) {
-            ok = select_static((uint32_t)u(1), (uint32_t)u(2), (uint32_t)u(3), (uint32_t)u(4), (uint32_t)u(5)) == u(6);
+        } else if (op == 't' && f.size() == 8) {
+            ok = select_static((uint32_t)u(1), (uint32_t)u(2), (uint32_t)u(3), (uint32_t)u(4), (uint32_t)u(5), u(6) != 0) == u(7);
+        } else if (op == 'g' && f.size() == 5) {
+            const Fc fee = ledger_fee(l1_float40(u(1)), (uint32_t)u(2));
+            ok = same(fee, parse_fc(f[3].c_str())) && ledger_fee_overflows(fee) == (u(4) != 0);
         } else {
             fprintf(stderr, "bad line: %s with %zu fields\n", f[0].c_str(), f.size());
             return 2;

@@ -2,6 +2,7 @@
 // one per line, every field in hex, the expectation last --
 //   f float40 amount                    l1_float40
 //   g float40 selector fee              ledger_fee on l1_float40's amount
+//   v float40 selector over             ledger_fee_overflows on that fee (0 or 1)
 //   a x y sum                           u256_add (modulo 2^256)
 //   n x neg                             u256_neg
 //   s x shifted                         u256_shr60
@@ -41,8 +42,8 @@ int main() {
         if (f.empty()) continue;
         auto u = [&](size_t i) { return strtoull(f[i].c_str(), nullptr, 16); };
         const char op = f[0][0];
-        const size_t want = op == 'o' ? 5 : (op == 'g' || op == 'a' || op == 'l') ? 4 : 3;
-        if (!strchr("fgansol", op) || f.size() != want) {
+        const size_t want = op == 'o' ? 5 : (op == 'g' || op == 'v' || op == 'a' || op == 'l') ? 4 : 3;
+        if (!strchr("fgvansol", op) || f.size() != want) {
             fprintf(stderr, "bad line: %s with %zu fields\n", f[0].c_str(), f.size());
             return 2;
         }
@@ -53,6 +54,8 @@ int main() {
             ok = same(l1_float40(u(1)), expect);
         } else if (op == 'g') {
             ok = same(ledger_fee(l1_float40(u(1)), (uint32_t)u(2)), expect);
+        } else if (op == 'v') {
+            ok = ledger_fee_overflows(ledger_fee(l1_float40(u(1)), (uint32_t)u(2))) == (u(3) != 0);
         } else if (op == 'a') {
             ok = same(u256_add(parse_fc(f[1]), parse_fc(f[2])), expect);
         } else if (op == 'n') {

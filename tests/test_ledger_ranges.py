@@ -2,7 +2,7 @@
 same state with host hashing: all 256 fee selectors on amounts of every exponent, nonces that carry into and fill the byte beside the
 sign bit, balances up to 2^192 - 1, token ids with bit 31 set, 64 fee slots on either side of the scan's chunk, L1 amounts with bits in
 limb 4, signed transfers whose fields are at their maxima, the refusal of a nonce that would leave its field (reason 12), of planes that
-are not leaves, and the circuit itself. Every comparison is on bytes, bit-exact; tests/test_ledger_ranges_cpu.py proves the fixtures."""
+are not leaves, and the circuit itself, which takes no fee of 2^128 or more (neither does the ledger: reason 16). Every comparison is on bytes, bit-exact; tests/test_ledger_ranges_cpu.py proves the fixtures."""
 import types
 
 import numpy as np
@@ -47,7 +47,7 @@ def test_apply_l2_parity_with_the_builder(hz, name):
         f0 = st.first_idx
         assert D.to_int(lg.accounts([f0 + 5])[0][1]) == (1 << 192) - 1 and D.to_int(lg.accounts([f0 + 6])[0][1]) == 0
     if name == "all_selectors":
-        assert max(D.to_int(r) for r in got["final_acc_fee"]).bit_length() > 183
+        assert max(D.to_int(r) for r in got["final_acc_fee"]).bit_length() > 131   # single fees stop at 128 bits (reason 16), their sum does not
     TL._final_tree_matches(lg, st, db)
     lg.close()
 
@@ -254,24 +254,25 @@ def test_load_refuses_planes_that_are_not_leaves(hz):
 
 
 def test_the_circuit_accepts_the_edges(hz):
-    """rollup-main at (8, 16, 2, 4) on nonce_carry plus two all_selectors rows: l2_batch_inputs == BatchBuilder's dictionary key by key;
-    the HIP context and the oracle accept it; hashGlobalInputs is the builder's.
-    The two rows were meant to be of exponent 31. The circuit, however, rejects a fee of 2^128 or more (src/compute-fee.circom:89-91,
-    "checks overflow of 128 bits"), which neither BatchBuilder nor the ledger does: of the eight all_selectors rows of exponent 31 only
-    one (mantissa 1, selector 95, a fee of 99 bits) stays below it; the others have fees of 129 to 166 bits. So the batch takes that
-    row and the row of the highest exponent and fee among the rest that stay below 2^128, and the oracle is asserted to reject the
-    inputs the ledger makes of two rows of exponent 31 above the bound (NOTES.md: an open divergence)"""
+    """rollup-main at (8, 16, 2, 4) on nonce_carry plus two all_selectors rows of exponent 31 (fees of 128 bits, the largest the circuit
+    takes: src/compute-fee.circom:89-91): l2_batch_inputs == BatchBuilder's dictionary key by key; the HIP context and the oracle accept
+    it; hashGlobalInputs is the builder's.
+    The two rows those replaced in the fixture (the same selectors and exponent, fees of 129 bits or more) make a batch the builder
+    still builds inputs for: the oracle and the HIP context reject them at the first of the two rows with the overflow constraint, and
+    the ledger refuses the same row with reason 16"""
     from oracle_binding import OracleCtx
+    import fee_bound_common as FB
     shape = (8, 16, 2, 4)
     st = R.wide_state()
     carry, fee_tokens, fee_idxs = R.nonce_carry(st)
-    rows = R.all_selectors(st)[0]
+    rows, table = R.all_selectors(st)[0], R.all_selectors_rows()
     fee = lambda t: B.compute_fee(B.float2fix(t["amountF"]), t["userFee"])   # noqa: E731
     e31 = [t for t in rows if t["amountF"] >> 35 == 31]
-    fit = [t for t in e31 if not fee(t) >> 128]
-    assert len(e31) == 8 and [t["userFee"] for t in fit] == [95]
-    second = max((t for t in rows if not fee(t) >> 128 and t is not fit[0]), key=lambda t: (t["amountF"] >> 35, fee(t)))
-    assert second["amountF"] >> 35 >= 29 and fee(second).bit_length() > 120
+    assert len(e31) == 8 and all(not fee(t) >> 128 for t in e31)
+    two = sorted(e31, key=fee)[-2:]
+    assert all(fee(t).bit_length() == 128 for t in two)
+    above = [dict(t, amountF=table[t["userFee"]][2]) for t in two]
+    assert all(t["amountF"] >> 35 == 31 and fee(t) >> 128 for t in above)
 
     def batch(two):
         out, seen = [dict(t) for t in carry], {}
@@ -281,14 +282,28 @@ def test_the_circuit_accepts_the_edges(hz):
         for t in out:
             t["signer"] = S.signer(st, t["fromIdx"])
         return out
-    over = st.to_ledger(hz)   # the ledger applies fees of 129 bits; the circuit does not take them
-    like = types.SimpleNamespace(last_idx=st.first_idx + st.N - 1, num_batch=0)
-    inp, _ = B.l2_batch_inputs(over, like, batch(e31[:2]), *shape, fee_tokens, fee_idxs, 1)
+    g = hz.ctx("rollup-main", nTx=shape[0], nLevels=shape[1], maxL1Tx=shape[2], maxFeeTx=shape[3])
+    # above the bound: the builder's inputs, since the ledger makes none
+    txs = batch(above)
+    _, bb = C.builder_batch(st, txs, fee_tokens + [0] * 2, fee_idxs + [0] * 2, shape[1], max_l1=shape[2])
     o = OracleCtx("rollup-main", *shape)
-    o.set_inputs(inp)
-    assert o.run() is not None
+    o.set_inputs(bb.get_input())
+    ref = o.run()
+    name = FB.OVF_SHIFTED if above[0]["userFee"] < 192 else FB.OVF_NOTSHIFTED
+    assert ref is not None and ref[1] == len(carry) and ref[2] == FB.constraint_ids()[name], ref
+    g.set_inputs(bb.get_input())
+    with pytest.raises(HzError) as e:
+        g.run()
+    assert (e.value.unit, e.value.constraint_id, e.value.lhs, e.value.rhs) == (ref[1], ref[2], ref[4], ref[5]), str(e.value)
+    over = st.to_ledger(hz)
+    like = types.SimpleNamespace(last_idx=st.first_idx + st.N - 1, num_batch=0)
+    with pytest.raises(HzError) as e:
+        B.l2_batch_inputs(over, like, txs, *shape, fee_tokens, fee_idxs, 1)
+    _refused(e, len(carry), 16)
+    assert over.root() == st.root
     over.close()
-    txs = batch([fit[0], second])
+    # below it
+    txs = batch(two)
     assert len(txs) == shape[0]
     db, bb = C.builder_batch(st, txs, fee_tokens + [0] * 2, fee_idxs + [0] * 2, shape[1], max_l1=shape[2])
     exp = bb.get_input()
@@ -299,7 +314,6 @@ def test_the_circuit_accepts_the_edges(hz):
     for name in exp:
         assert inp[name] == exp[name], name
     assert inp["nonce1"][2] == 1 << 32 and inp["nonce1"][4] == (1 << 40) - 2 and inp["tokenID1"][5] == R.TOK_MAX
-    g = hz.ctx("rollup-main", nTx=shape[0], nLevels=shape[1], maxL1Tx=shape[2], maxFeeTx=shape[3])
     g.set_inputs(inp)
     g.run()
     assert g.get("main.hashGlobalInputs") == bb.get_hash_inputs()

@@ -1,6 +1,6 @@
 """The ledger at the edges of its value ranges without a device (tests/ledger_range_common.py): the scheme models against BatchBuilder
 field by field on every batch meant to be valid -- which proves the fixtures valid, no batch may be skipped or caught --, every expected
-refusal by its lowest index and reason, the distribution the fixtures promise (all 32 exponents, fees above 180 bits, both signs beside
+refusal by its lowest index and reason, the distribution the fixtures promise (all 32 exponents, fees up to the circuit's bound of 128 bits, both signs beside
 a full nonce byte, all 64 slots), and the 256-bit routines of csrc/u256.h, ledger_fee.h and l1_float40 built for the host under the
 address and undefined-behaviour sanitizers against Python integers."""
 import os
@@ -55,11 +55,12 @@ def test_all_selectors_against_the_builder():
     txs, plan, idxs = R.all_selectors(st)
     assert [t["userFee"] for t in txs] == list(range(256))
     assert {t["amountF"] >> 35 for t in txs} == set(range(32))
-    assert {t["amountF"] & R.MANT for t in txs} == set(R.MANTISSAS)
+    assert {t["amountF"] & R.MANT for t in txs} >= set(R.MANTISSAS)
     fees = [B.compute_fee(B.float2fix(t["amountF"]), t["userFee"]) for t in txs]
-    assert max(fees).bit_length() > 180 and max(B.float2fix(t["amountF"]) for t in txs) >> 128
+    # the circuit takes no fee of 2^128 or more and neither does the ledger (reason 16): the fixture goes up to the bound, in 16 rows or more
+    assert max(fees).bit_length() == 128 and sum(f.bit_length() == 128 for f in fees) >= 16 and max(B.float2fix(t["amountF"]) for t in txs) >> 128
     bb, res = _model_vs_builder(st, txs, plan, idxs)
-    assert res[3] == [sum(fees)] and sum(fees).bit_length() > 183
+    assert res[3] == [sum(fees)] and sum(fees).bit_length() > 131   # the accumulated fee does carry into limb 4
 
 
 def test_nonce_carry_and_the_brim_against_the_builder():
@@ -159,6 +160,7 @@ def test_host_build_of_the_256_bit_routines_agrees_with_python(tmp_path):
     text = R.check_lines()
     n = len(text.splitlines())
     assert sum(ln.startswith("f ") for ln in text.splitlines()) == 160 and sum(ln.startswith("g ") for ln in text.splitlines()) == 256 * 160
+    assert sum(ln.startswith("v ") for ln in text.splitlines()) == 256 + 225 and sum(ln.startswith("v ") and ln.endswith(" 1") for ln in text.splitlines()) == 225
     src = os.path.join(os.path.dirname(__file__), "native", "u256_check.cpp")
     exe = str(tmp_path / "u256_check")
     subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wno-unknown-pragmas", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", src, "-o", exe])
@@ -166,7 +168,7 @@ def test_host_build_of_the_256_bit_routines_agrees_with_python(tmp_path):
     assert r.returncode == 0 and "cases=%d mismatches=0" % n in r.stdout, r.stdout + r.stderr[-2000:]
     # the program does judge: one expectation changed per kind of record is one mismatch each
     lines = text.splitlines()
-    kinds = "fgansol"
+    kinds = "fgvansol"
     for kind in kinds:
         at = next(i for i, ln in enumerate(lines) if ln.startswith(kind + " "))
         last = lines[at].split()[-1]

@@ -52,7 +52,7 @@ def test_the_header_states_the_contract():
     assert header.index(" * ATOMIC (DESIGN.md 8i).") < at < scope
     para = header[at:scope]
     for word in NEW_SYMBOLS + ["rq_offset is ignored", "changes nothing resident", "beyond size", "does not touch the exit tree", "invalidates the *_dev",
-                               "reasons 1 - 5, 7 - 9, 12 or 13", "reason 6", "HZ_SELECT_PARTNER (14)", "HZ_SELECT_FULL (15)", "(linked transactions + 1)",
+                               "reasons 1 - 5, 7 - 9, 12, 13 or 16", "reason 6", "HZ_SELECT_PARTNER (14)", "HZ_SELECT_FULL (15)", "(linked transactions + 1)",
                                "one-directional"]:
         assert word in para, word
 
