@@ -695,3 +695,463 @@ def lane_units(n, per_lane):
     [[unit of slot 0, ...] per lane], padding slots left out."""
     nl = (n + per_lane - 1) // per_lane
     return [[li + g * nl for g in range(per_lane) if li + g * nl < n] for li in range(nl)]
+
+
+# ---- the twelve other mains: the gadget templates, AySign2Ax, HashState, DecodeTx, FeeTx as `component main` ----------------------
+# Inputs outside the ranges the enclosing RollupTx feeds them (tests/test_standalone_fuzz*.py). Every list is built by _assemble: the
+# named edges first, one per instance, then seeded draws; compute-fee and balance-updater lay whole wavefronts out as well (WAVE = the
+# workgroup of k_gadget<..>, one wavefront).
+WAVE = 64
+HALF = (P - 1) // 2
+SEL_PALETTE = (0, 1, 2, P - 1)   # what a selector or "bit" is set to, beside a random field element
+FEE_SEL_EDGES = (0, 191, 192, 207, 208, 255, 256, 256 + 7, 256 + 192, P - 1)
+AMOUNT_EDGES = (0, (1 << 128) - 1, 1 << 128, (1 << 192) - 1, 1 << 192, P - 1)
+BALANCE_EDGES = (0, (1 << 192) - 1, 1 << 192, P - 1)
+
+
+def is_bit(v):
+    return v % P in (0, 1)
+
+
+def _sel(rng):
+    """a selector input: one of SEL_PALETTE or a random field element"""
+    k = rng.randrange(len(SEL_PALETTE) + 1)
+    return SEL_PALETTE[k] if k < len(SEL_PALETTE) else rng.randrange(2, P)
+
+
+def _assemble(n, edges, draw):
+    """n cases: the named edges in order (all of them where n >= len(edges)), then draw() until the list is full"""
+    out = [{k: _copy(v) for k, v in e.items()} for e in edges[:n]]
+    while len(out) < n:
+        out.append(draw())
+    return out
+
+
+def _gadget_bases(template):
+    """the valid inputs tests/test_gadget_mains.py holds for one gadget main (the reference's literal vectors)"""
+    import test_gadget_mains as G
+    return [it[0] for c in G.all_cases() if c.template == template for it in c.items if not isinstance(it[1], str)]
+
+
+def decode_float_cases(n, seed):
+    """`in` = mantissa | exponent << 35 at exponent 0 / 31 and mantissa 0 / 2^35 - 1, 2^40 - 1, 2^40, 2^40 + 1, P - 1; then 40-bit
+    values, half of them through `garbage` (mostly above 40 bits: Num2Bits(40) fails, the decoder reads the low bits)"""
+    rng = random.Random(seed)
+    m35 = (1 << 35) - 1
+    edges = [{"in": m | (e << 35)} for e in (0, 31) for m in (0, m35, 1, 0x400000000)]
+    edges += [{"in": v} for v in ((1 << 40) - 1, 1 << 40, (1 << 40) + 1, P - 1, P - 2, (1 << 41) - 1, (1 << 253) + 5, HALF, HALF + 1)]
+
+    def draw():
+        v = rng.getrandbits(40)
+        return {"in": garbage(rng, v) if rng.random() < 0.5 else v}
+    return _assemble(n, edges, draw)
+
+
+def _fee_triplet(rng, i):
+    """(feeSel, amount) walking the named edges in coprime strides, so that every value and many pairs of them occur in 64 lanes"""
+    fs = FEE_SEL_EDGES + (rng.randrange(192), rng.randrange(256), rng.randrange(P))
+    am = AMOUNT_EDGES + (rng.getrandbits(100), 10 ** 18, rng.randrange(P), rng.getrandbits(60))
+    return fs[i % len(fs)], am[i % len(am)]
+
+
+def apply_fee_of(template, d):
+    """the selector ComputeFee sees: its input, or BalanceUpdater's (1 - onChain) * (1 - nop)"""
+    return d["applyFee"] % P if template == "compute-fee" else (1 - d["onChain"]) * (1 - d["nop"]) % P
+
+
+def compute_fee_cases(n, seed):
+    """ComputeFee with garbage selectors. Wavefront by wavefront (64 instances, the kernel's fast path is chosen per wavefront):
+      0   the named edges: feeSel in FEE_SEL_EDGES, amount in AMOUNT_EDGES, applyFee in {0, 1, 2, P - 1, random}, mixed
+      1   applyFee a bit on every lane, feeSel and amount garbage (the product-free path with out-of-range selectors)
+      2-4 exactly one non-bit applyFee, at lane 0, 17, 63 (the general path running over bit lanes)
+      5   no applyFee a bit
+      6.. inputs in range (feeSel < 192, amount < 2^100: accepted), one in four of them through `garbage`, applyFee a bit on most lanes"""
+    rng = random.Random(seed)
+    out = []
+    for i in range(n):
+        w, lane = divmod(i, WAVE)
+        sel, amount = _fee_triplet(rng, i + 3 * w)
+        if w == 0:
+            ap = (0, 1, 2, P - 1, rng.randrange(2, P))[lane % 5]
+        elif w == 1:
+            ap = rng.getrandbits(1)
+        elif w in (2, 3, 4):
+            ap = rng.getrandbits(1)
+            if lane == (0, 17, 63)[w - 2]:
+                ap = (2, P - 1, rng.randrange(2, P))[w - 2]
+        elif w == 5:
+            ap = (2, P - 1, rng.randrange(2, P), 7)[lane % 4]
+        else:
+            ap = rng.getrandbits(1) if rng.random() < 0.9 else _sel(rng)
+        if w >= 6 or (w >= 1 and lane % 3 == 0):   # a share of every wavefront stays in range: accepted instances beside rejected ones
+            sel, amount = rng.randrange(192), rng.getrandbits(100)
+            if w >= 6 and rng.random() < 0.25:
+                sel, amount = garbage(rng, sel), garbage(rng, amount)
+        out.append({"feeSel": sel, "amount": amount, "applyFee": ap})
+    return out
+
+
+def balance_updater_cases(n, seed):
+    """BalanceUpdater with garbage everywhere; the wavefronts of compute_fee_cases by the EFFECTIVE selector (1 - onChain) * (1 - nop)
+    (onChain = nop = 2 gives 1: a bit made of two non-bits), balances and loads at BALANCE_EDGES so that the 193-bit sum
+    2^192 + balance + load - amount - fee wraps mod P, the two nullifiers in {0, 1, 2, P - 1, random}"""
+    rng = random.Random(seed)
+    nonbit_pairs = ((2, 0), (0, 2), (P - 1, 0), (0, P - 1), (2, P - 1))
+    out = []
+    for i in range(n):
+        w, lane = divmod(i, WAVE)
+        sel, amount = _fee_triplet(rng, i + 3 * w)
+        on, nop = rng.getrandbits(1), rng.getrandbits(1)
+        be = BALANCE_EDGES + (rng.getrandbits(120), (1 << 100) + rng.getrandbits(100), rng.randrange(P))
+        d = {"oldStBalanceSender": be[i % len(be)], "oldStBalanceReceiver": be[(i // 2) % len(be)], "amount": amount,
+             "loadAmount": be[(i // 3) % len(be)], "feeSelector": sel, "onChain": on, "nop": nop,
+             "nullifyLoadAmount": (0, 1, 2, P - 1, rng.randrange(P))[i % 5], "nullifyAmount": (0, 1, 2, P - 1, rng.randrange(P))[(i // 5) % 5]}
+        if w == 0:
+            d["onChain"], d["nop"] = (0, 1, 2, P - 1, rng.randrange(2, P))[lane % 5], (0, 1, 2, P - 1, rng.randrange(2, P))[(lane // 5) % 5]
+        elif w == 1 and lane % 16 == 5:
+            d["onChain"] = d["nop"] = 2
+        elif w in (2, 3, 4) and lane == (0, 17, 63)[w - 2]:
+            d["onChain"], d["nop"] = nonbit_pairs[w - 2]
+        elif w == 5:
+            d["onChain"], d["nop"] = nonbit_pairs[lane % len(nonbit_pairs)] if lane % 3 else (rng.randrange(3, P - 1), 0)
+        elif w >= 6 and rng.random() < 0.1:
+            d["onChain"], d["nop"] = _sel(rng), _sel(rng)
+        if w >= 6 or (w >= 1 and lane % 3 == 0):   # in range: what RollupTx feeds (accepted), a quarter of the late ones through `garbage`
+            d.update(oldStBalanceSender=(1 << 100) + rng.getrandbits(100), oldStBalanceReceiver=rng.getrandbits(120), amount=rng.getrandbits(90),
+                     loadAmount=rng.getrandbits(90) if is_bit(d["onChain"]) and d["onChain"] else 0, feeSelector=rng.randrange(192),
+                     nullifyLoadAmount=rng.getrandbits(1), nullifyAmount=rng.getrandbits(1))
+            if w >= 6 and rng.random() < 0.25:
+                f = rng.choice(("oldStBalanceSender", "oldStBalanceReceiver", "amount", "loadAmount", "feeSelector", "nullifyLoadAmount", "nullifyAmount"))
+                d[f] = garbage(rng, d[f])
+        out.append(d)
+    return out
+
+
+def fee_accumulator_cases(n, max_fee, seed):
+    """FeeAccumulator(max_fee): the token in no slot, in slot 0, in the last slot, in every slot; tokenID and plan entries that differ
+    by P - 1 (unequal: IsEqual works in the field, x and x + P - 1 = x - 1 are different elements); fee2Charge and accumulators at
+    P - 1 (the sum wraps); then random plans with field-sized values. No constraint of this main can fail."""
+    rng = random.Random(seed)
+    F = max_fee
+    acc = [1000 + j for j in range(F)]
+    plan = [100 + j for j in range(F)]
+    edges = [{"tokenID": 999, "fee2Charge": 7, "feePlanTokenID": plan, "accFeeIn": acc},
+             {"tokenID": 100, "fee2Charge": 7, "feePlanTokenID": plan, "accFeeIn": acc},
+             {"tokenID": 100 + F - 1, "fee2Charge": 7, "feePlanTokenID": plan, "accFeeIn": acc},
+             {"tokenID": 5, "fee2Charge": 7, "feePlanTokenID": [5] * F, "accFeeIn": acc},
+             {"tokenID": 5, "fee2Charge": 7, "feePlanTokenID": [(5 + P - 1) % P] * F, "accFeeIn": acc},
+             {"tokenID": 0, "fee2Charge": 7, "feePlanTokenID": [P - 1] * (F - 1) + [0], "accFeeIn": acc},
+             {"tokenID": P - 1, "fee2Charge": 1, "feePlanTokenID": [0] * (F - 1) + [P - 1], "accFeeIn": acc},
+             {"tokenID": 100, "fee2Charge": P - 1, "feePlanTokenID": plan, "accFeeIn": [P - 1] * F},
+             {"tokenID": 100 + F - 1, "fee2Charge": P - 1, "feePlanTokenID": plan, "accFeeIn": [P - 1] * F},
+             {"tokenID": 101 % P, "fee2Charge": 1, "feePlanTokenID": plan, "accFeeIn": [P - 1] * F},
+             {"tokenID": 0, "fee2Charge": 0, "feePlanTokenID": [0] * F, "accFeeIn": [0] * F}]
+
+    def draw():
+        toks = [rng.choice((rng.randrange(24), rng.randrange(P), P - 1 - rng.randrange(4))) for _ in range(F)]
+        r = rng.random()
+        token = rng.choice(toks) if r < 0.6 else (rng.choice(toks) + P - 1) % P if r < 0.75 else rng.randrange(P)
+        big = rng.random() < 0.6
+        return {"tokenID": token, "fee2Charge": rng.choice((P - 1, rng.randrange(P), 1 << 192)) if big else rng.getrandbits(100), "feePlanTokenID": toks,
+                "accFeeIn": [rng.choice((P - 1, rng.randrange(P), (1 << 192) - 1, 1 << 192)) if big and rng.random() < 0.5 else rng.getrandbits(120) for _ in range(F)]}
+    return _assemble(n, edges, draw)
+
+
+STATES_BITS = ("newExit", "newAccount", "onChain")
+STATES_FIELDS = ("fromIdx", "toIdx", "toEthAddr", "auxFromIdx", "auxToIdx", "amount", "newExit", "loadAmount", "newAccount", "onChain", "fromEthAddr",
+                 "ethAddr1", "tokenID", "tokenID1", "tokenID2")
+
+
+def rollup_tx_states_cases(n, seed):
+    """RollupTxStates: every bit input non-boolean in turn; toIdx in {0, 1, 2, 255, 256}; toEthAddr = 2^160 - 1 and +- 1; the three
+    token ids and the two addresses equal or unequal in every combination; fromIdx = auxFromIdx = 0; L2 rows with a load amount AND
+    newAccount (both L2 checks violated at once: the first in the template's order is the one reported); then the reference's
+    vectors mutated"""
+    rng = random.Random(seed)
+    bases = _gadget_bases("rollup-tx-states")
+    l1 = next(b for b in bases if b["onChain"] == 1 and not b["newAccount"] and b["fromIdx"])
+    l2 = next(b for b in bases if b["onChain"] == 0 and b["fromIdx"])
+    edges = []
+    for f in STATES_BITS:
+        for v in (2, P - 1, rng.randrange(2, P)):
+            for b in (l1, l2):
+                edges.append(dict(b, **{f: v}))
+    for v in (0, 1, 2, 255, 256):
+        edges += [dict(l1, toIdx=v), dict(l2, toIdx=v)]
+    for v in ((1 << 160) - 2, (1 << 160) - 1, 1 << 160):
+        edges += [dict(l2, toIdx=0, toEthAddr=v), dict(l1, toEthAddr=v)]
+    for t1 in (0, 1):
+        for t2 in (0, 1):
+            for e in (0, 1):
+                for amt in (0, 7):
+                    edges.append(dict(l1, tokenID=3, tokenID1=3 + t1, tokenID2=3 + t2, fromEthAddr=0x1234, ethAddr1=0x1234 + e, amount=amt, loadAmount=5))
+    edges += [dict(l1, fromIdx=0, auxFromIdx=0), dict(l2, fromIdx=0, auxFromIdx=0), dict(l1, fromIdx=0, auxFromIdx=0, newAccount=1)]
+    # both L2 checks at once, and each alone
+    edges += [dict(l2, loadAmount=v, newAccount=a) for v, a in ((5, 1), (P - 1, 1), (5, 2), (1 << 200, P - 1), (5, 0), (0, 1))]
+    edges += [dict(l2, loadAmount=5, newAccount=1, onChain=v) for v in (2, P - 1)]
+
+    def draw():
+        b = rng.choice(bases)
+        r = rng.random()
+        if r < 0.12:   # an L2 row that violates both of its checks
+            return dict(b, onChain=rng.choice((0, 0, 2, P - 1)), loadAmount=rng.choice((1, rng.randrange(1, P))), newAccount=rng.choice((1, 1, 2, rng.randrange(1, P))))
+        return mutate(rng, b, key_fields=("fromIdx", "toIdx", "auxFromIdx", "auxToIdx"), key_bits=20, bit_fields=STATES_BITS)
+    return _assemble(n, edges, draw)
+
+
+RQ_KINDS = ("TxCompressedDataV2", "ToEthAddr", "ToBjjAy")
+
+
+def _rq_selected(d, kind, off3):
+    return ([0] + list(d["future" + kind]) + list(d["past" + kind])[::-1])[off3]
+
+
+def rq_tx_verifier_cases(n, seed):
+    """RqTxVerifier: rqTxOffset 0..7, 8, 9, 8 + k, P - 1 (Num2Bits(3) fails, the multiplexers take the low three bits); for each, the
+    requested values right in the selected slot, wrong there and right in another slot, and one, two or all three of the comparisons
+    wrong at once"""
+    rng = random.Random(seed)
+
+    def fresh(off):
+        d = {"rqTxOffset": off}
+        for k in RQ_KINDS:
+            d["future" + k] = [rng.randrange(1, P) for _ in range(3)]
+            d["past" + k] = [rng.randrange(1, P) for _ in range(4)]
+        for k in RQ_KINDS:
+            d["rq" + k] = _rq_selected(d, k, off % P & 7)
+        return d
+
+    def spoil(d, kinds, how):
+        for k in kinds:
+            off3 = d["rqTxOffset"] % P & 7
+            if how == 0:
+                d["rq" + k] = _rq_selected(d, k, (off3 + 1 + rng.randrange(7)) & 7)   # the value of a slot that is not selected
+            elif how == 1:
+                d["rq" + k] = (d["rq" + k] + rng.choice((1, P - 1))) % P
+            else:
+                d["rq" + k] = rng.randrange(P)
+        return d
+    offsets = list(range(8)) + [8, 9, 8 + 5, 8 + 7, 16 + 3, (1 << 3) + (1 << 100), P - 1, P - 8]
+    edges = [fresh(off) for off in offsets]
+    for j, off in enumerate(offsets):
+        edges.append(spoil(fresh(off), [RQ_KINDS[j % 3]], j % 3))
+    for off in (1, 3, 4, 7, 9, P - 1):
+        for kinds in ((0, 1), (0, 2), (1, 2), (0, 1, 2)):
+            edges.append(spoil(fresh(off), [RQ_KINDS[k] for k in kinds], rng.randrange(3)))
+    edges.append({k: (0 if not isinstance(v, list) else [0] * len(v)) for k, v in fresh(0).items()})
+
+    def draw():
+        r = rng.random()
+        off = rng.randrange(8) if r < 0.7 else rng.choice((8, 9, 8 + rng.randrange(8), P - 1, rng.randrange(P), 1 << rng.randrange(3, 253)))
+        d = fresh(off)
+        r = rng.random()
+        if r < 0.45:
+            return d
+        return spoil(d, rng.sample(RQ_KINDS, rng.choice((1, 1, 2, 2, 3))), rng.randrange(3))
+    return _assemble(n, edges, draw)
+
+
+def mux256_cases(n, seed):
+    """Mux256: each of the eight selectors in {0, 1, 2, P - 1, random} in turn over a base selection, all eight of them garbage,
+    field-sized inputs. No constraint of this main can fail."""
+    rng = random.Random(seed)
+    big = [rng.randrange(P) for _ in range(256)]
+    small = list(range(256))
+    edges = []
+    for pos in range(8):
+        for v in (0, 1, 2, P - 1, rng.randrange(2, P)):
+            base = rng.randrange(256)
+            s = [(base >> b) & 1 for b in range(8)]
+            s[pos] = v
+            edges.append({"s": s, "in": big if (pos + v) % 2 else small})
+    edges += [{"s": [v] * 8, "in": big} for v in (0, 1, 2, P - 1)]
+    edges.append({"s": [1] * 8, "in": [P - 1] * 256})
+
+    def draw():
+        r = rng.random()
+        s = [rng.getrandbits(1) for _ in range(8)]
+        if r < 0.7:
+            for pos in rng.sample(range(8), rng.randrange(1, 9)):
+                s[pos] = _sel(rng)
+        ins = [rng.randrange(P) for _ in range(256)] if rng.random() < 0.5 else rng.choice((big, small))
+        return {"s": s, "in": ins}
+    return _assemble(n, edges, draw)
+
+
+def bits_compressed_cases(n, seed):
+    """BitsCompressed2AySign: "bits" that are 2, P - 1 or random at single positions (0, 1, 127, 253, 254, 255) and everywhere; all
+    ones (ay = 2^254 - 1 >= P before the reduction); bit 255 (the sign) non-boolean. No constraint of this main can fail."""
+    rng = random.Random(seed)
+    from circuits_amd import builder as B
+    comp = B.BASE8[1] | (1 << 255)
+    base = [(comp >> i) & 1 for i in range(256)]
+    edges = [{"bjjCompressed": list(base)}, {"bjjCompressed": [1] * 256}, {"bjjCompressed": [1] * 254 + [0, 0]}, {"bjjCompressed": [0] * 256}]
+    for pos in (0, 1, 127, 253, 254, 255):
+        for v in (2, P - 1, rng.randrange(2, P)):
+            b = list(base)
+            b[pos] = v
+            edges.append({"bjjCompressed": b})
+    edges += [{"bjjCompressed": [v] * 256} for v in (2, P - 1)]
+    edges.append({"bjjCompressed": [rng.randrange(P) for _ in range(256)]})
+
+    def draw():
+        v = rng.getrandbits(256)
+        b = [(v >> i) & 1 for i in range(256)]
+        if rng.random() < 0.75:
+            for pos in rng.sample(range(256), rng.choice((1, 2, 8, 256))):
+                b[pos] = _sel(rng)
+        return {"bjjCompressed": b}
+    return _assemble(n, edges, draw)
+
+
+def ay_sign_2_ax_ays(seed):
+    """(with, without): the `ay` of the named edges that have a point on the curve, and those that have none (bjj_x_of)"""
+    from circuits_amd import builder as B
+    rng = random.Random(seed)
+    named = [0, 1, P - 1, 2, P - 2, B.BASE8[1], bjj_order8_point()[1], 1 << 253, (1 << 253) - 1, (1 << 253) + 1, HALF, HALF + 1]
+    named += [B.Account(200 + i).ay for i in range(4)]
+    have = [y for y in named if bjj_x_of(y) is not None]
+    none = [y for y in named if bjj_x_of(y) is None]
+    while len(have) < 10 or len(none) < 10:
+        y = rng.randrange(P)
+        (have if bjj_x_of(y) is not None else none).append(y)
+    return have, none
+
+
+def ay_sign_2_ax_cases(n, seed):
+    """AySign2Ax: ay in {0, 1, P - 1, 2, P - 2} (for +-1 the root is x = 0), Base8's ay, an order-8 point's, 2^253 and 2^253 +- 1,
+    (P +- 1) / 2, at least eight ay with a point and eight without -- each with sign in {0, 1, 2, P - 1}; then random ay (half of
+    them have a point) with the sign of one of the two roots, the other root's, or garbage"""
+    rng = random.Random(seed)
+    have, none = ay_sign_2_ax_ays(seed)
+    edges = [{"ay": y, "sign": s} for y in have + none for s in (0, 1, 2, P - 1)]
+
+    def draw():
+        y = rng.randrange(P) if rng.random() < 0.8 else garbage(rng, rng.choice(have))
+        x = bjj_x_of(y)
+        r = rng.random()
+        if x is not None and r < 0.7:   # the sign of the smaller root (0) or of the larger one (1): both are accepted
+            return {"ay": y, "sign": rng.getrandbits(1)}
+        return {"ay": y, "sign": _sel(rng) if r < 0.85 else rng.getrandbits(1)}
+    return _assemble(n, edges, draw)
+
+
+HASH_STATE_WIDTH = {"tokenID": 32, "nonce": 40, "sign": 1, "balance": 192, "ay": 253, "ethAddr": 160}
+
+
+def hash_state_cases(n, seed):
+    """HashState: every input at 0, 1, P - 1 and at 2^k - 1, 2^k, 2^k + 1 around its own width (sign and nonce out of range among
+    them), all of them at once, then `garbage`. No constraint of this main can fail: the template packs and hashes."""
+    rng = random.Random(seed)
+    base = {"tokenID": 1, "nonce": 49, "sign": 1, "balance": 12343256, "ay": 0x144e7e10fd47e0c67a733643b760e80ed399f70e78ae97620dbb719579cd645d,
+            "ethAddr": 0x7e5f4552091a69125d5dfcb7b8c2659029395bdf}
+    edges = [dict(base)]
+    for f, w in HASH_STATE_WIDTH.items():
+        for v in (0, 1, 2, P - 1, (1 << w) - 1, 1 << w, (1 << w) + 1, 1 << 192, 1 << 253):
+            edges.append(dict(base, **{f: v % P}))
+    edges += [{f: v for f in base} for v in (0, 1, P - 1, 1 << 192)]
+
+    def draw():
+        d = dict(base)
+        for f in rng.sample(list(base), rng.randrange(1, 7)):
+            d[f] = garbage(rng, d[f]) if rng.random() < 0.7 else rng.randrange(1 << 192, P)
+        return d
+    return _assemble(n, edges, draw)
+
+
+DECODE_TX_BITS = ("onChain", "newAccount", "previousOnChain")
+DECODE_TX_WIDTH = {"maxNumBatch": 32, "amountF": 40, "loadAmountF": 40, "toEthAddr": 160, "fromEthAddr": 160, "txCompressedData": 225}
+
+
+def decode_tx_bases(n_levels):
+    """valid DecodeTx inputs: every transaction of two synthetic batches, cut out the way src/rollup-main.circom wires them"""
+    from circuits_amd import builder as B
+    out = []
+    for seed, n_acc in ((31, 6), (32, 9)):
+        bb = B.synthetic_batch(10, n_levels, 4, 2, n_accounts=n_acc, exits=1, seed=seed)
+        inp = bb.get_input()
+        for i in range(bb.nTx):
+            d = {k: _copy(inp[k][i]) for k in ("txCompressedData", "maxNumBatch", "amountF", "toEthAddr", "toBjjAy", "rqTxCompressedDataV2", "rqToEthAddr", "rqToBjjAy",
+                                               "fromEthAddr", "fromBjjCompressed", "loadAmountF", "onChain", "newAccount", "auxFromIdx", "auxToIdx")}
+            d.update(previousOnChain=inp["onChain"][i - 1] if i else 1, globalChainID=inp["globalChainID"], currentNumBatch=inp["currentNumBatch"],
+                     inIdx=inp["imOutIdx"][i - 1] if i else inp["oldLastIdx"])
+            out.append(d)
+    return out
+
+
+def decode_tx_cases(n, n_levels, seed):
+    """DecodeTx(n_levels): the bit inputs non-boolean; each decomposed input one bit above its width (32, 40, 48, 160, 225 bits) and at
+    its last value inside; fromBjjCompressed with non-bits; inIdx at 2^nLevels - 1 and 2^48 - 1; several of these at once; then every
+    scalar through `mutate` / `garbage`"""
+    rng = random.Random(seed)
+    bases = decode_tx_bases(n_levels)
+    l1 = [b for b in bases if b["onChain"]]
+    l2 = [b for b in bases if not b["onChain"]]
+    create = [b for b in l1 if b["newAccount"]]
+    assert l1 and l2 and create
+    edges = []
+    for f in DECODE_TX_BITS:
+        for v in (2, P - 1, rng.randrange(2, P)):
+            edges.append(dict(rng.choice(l1 if f != "previousOnChain" else bases), **{f: v}))
+    for f, w in DECODE_TX_WIDTH.items():
+        for b in (l1[0], l2[0]):
+            edges.append(dict(b, **{f: b[f] | (1 << w)}))
+            edges.append(dict(b, **{f: (1 << w) - 1}))
+    for f in ("auxFromIdx", "auxToIdx", "inIdx"):   # indexes: 48 bits in the data, nLevels in the tree
+        for v in ((1 << n_levels) - 1, 1 << n_levels, (1 << 48) - 1, 1 << 48):
+            edges.append(dict(rng.choice(create if f != "auxToIdx" else l2), **{f: v}))
+    for pos, v in ((0, 2), (100, P - 1), (253, 2), (254, rng.randrange(2, P)), (255, 2), (255, P - 1)):
+        b = rng.choice(create)
+        bits = list(b["fromBjjCompressed"])
+        bits[pos] = v
+        edges.append(dict(b, fromBjjCompressed=bits))
+    edges.append(dict(create[0], fromBjjCompressed=[1] * 256))
+    edges.append(dict(l2[0], fromBjjCompressed=[2] * 256))
+    scalars = [k for k in bases[0] if k != "fromBjjCompressed"]
+
+    def draw():
+        b = rng.choice(bases)
+        r = rng.random()
+        if r < 0.2:    # two or three range failures at once
+            d = dict(b)
+            for f in rng.sample(list(DECODE_TX_WIDTH), rng.randrange(2, 4)):
+                d[f] = (d[f] + (1 << rng.randrange(DECODE_TX_WIDTH[f], 253))) % P
+            return d
+        if r < 0.3:    # every scalar garbage
+            return dict(b, **{f: garbage(rng, b[f]) for f in scalars})
+        if r < 0.4:
+            return dict(b, **{f: garbage(rng, b[f], key_bits=n_levels) for f in rng.sample(scalars, 2)})
+        return mutate(rng, b, key_fields=("auxFromIdx", "auxToIdx", "inIdx"), key_bits=n_levels,
+                      bit_fields=DECODE_TX_BITS + tuple(("fromBjjCompressed", (rng.randrange(256),)) for _ in range(2)))
+    return _assemble(n, edges, draw)
+
+
+def fee_tx_cases(n, n_levels, seed):
+    """FeeTx(n_levels): the fee slots of a built batch and the reference's two literal cases (scenarios.fee_tx_cases); feeIdx 0, the
+    same index in several instances, 2^nLevels and above; a plan token that is not the leaf's; balance and accFee at 2^192 - 1 and
+    P - 1; then `mutate` with the sibling and key patterns rollup_tx_cases uses"""
+    import scenarios
+    rng = random.Random(seed)
+    bases = [c for c, _ in scenarios.fee_tx_cases(n_levels)]
+    slots = [b for b in bases if b["feeIdx"] and b["feeIdx"] < (1 << n_levels)]
+    assert slots
+    s0 = slots[0]
+    edges = [dict(s0), dict(s0), dict(s0, feeIdx=0), dict(slots[-1], feeIdx=0, accFee=P - 1)]
+    # two checks violated at once (the plan token and the proof): which one is reported is the template's order
+    edges += [dict(s0, feePlanToken=(s0["feePlanToken"] + 1) % P, oldStateRoot=(s0["oldStateRoot"] + 1) % P),
+              dict(s0, feePlanToken=(s0["feePlanToken"] + 1) % P, siblings=[0] * (n_levels + 1)),
+              dict(s0, feePlanToken=(s0["feePlanToken"] + 1) % P, siblings=list(s0["siblings"][:-1]) + [5])]
+    edges += [dict(s0, feeIdx=v) for v in (1 << n_levels, s0["feeIdx"] + (1 << n_levels), (1 << 48) - 1, P - 1, s0["feeIdx"] ^ 1)]
+    edges += [dict(s0, feePlanToken=v) for v in ((s0["feePlanToken"] + 1) % P, (s0["feePlanToken"] + P - 1) % P, rng.randrange(P))]
+    edges += [dict(s0, tokenID=(s0["tokenID"] + 1) % P), dict(s0, tokenID=(s0["tokenID"] + 1) % P, feePlanToken=(s0["feePlanToken"] + 1) % P)]
+    for v in ((1 << 192) - 1, 1 << 192, P - 1):
+        edges += [dict(s0, balance=v), dict(s0, accFee=v), dict(s0, balance=v, accFee=v)]
+    edges += [dict(s0, sign=2, nonce=P - 1), dict(s0, siblings=list(s0["siblings"][:-1]) + [5])]
+
+    def draw():
+        b = rng.choice(slots if rng.random() < 0.8 else bases)
+        if rng.random() < 0.15:   # the plan token AND the proof wrong
+            return dict(b, feePlanToken=garbage(rng, b["feePlanToken"]), **{rng.choice(("balance", "oldStateRoot", "ay", "nonce")): rng.randrange(P)})
+        return mutate(rng, b, sibling_fields=("siblings",), key_fields=("feeIdx",), key_bits=n_levels, bit_fields=("sign",))
+    return _assemble(n, edges, draw)
+
