@@ -1258,6 +1258,42 @@ class LedgerExits:
         self.exit_tree, self.exit_leaves = DeviceSMT(ledger.exit_tree()), self._Leaves(ledger)
 
 
+class ArchivedExits:
+    """The exit tree and exit leaves of a batch a capi.Ledger has kept (exit_keep), as withdraw_input reads them off a built BatchBuilder:
+    exit_tree has root and find, exit_leaves[idx] the leaf's fields, both served from the ledger's withdraw_rows. Valid while the batch is kept."""
+
+    class _Tree:
+        def __init__(self, ledger, batch_num):
+            self.ledger, self.batch_num = ledger, batch_num
+
+        @property
+        def root(self):
+            return self.ledger.exit_root_of(self.batch_num)
+
+        def find(self, key):
+            r = self.ledger.withdraw_rows([self.batch_num], [key], 63)   # 64 siblings: no leaf is too deep
+            sib = [int.from_bytes(x.tobytes(), "little") for x in r["siblings_state"][0]]
+            while sib and sib[-1] == 0:
+                sib.pop()
+            return {"found": int(r["status"][0]) == 0, "siblings": sib}
+
+    class _Leaves:
+        def __init__(self, ledger, batch_num):
+            self.ledger, self.batch_num = ledger, batch_num
+
+        def __getitem__(self, idx):
+            r = self.ledger.withdraw_rows([self.batch_num], [idx], 63)
+            if int(r["status"][0]) != 0:
+                raise KeyError(idx)
+            v = {name: int.from_bytes(r[name][0].tobytes(), "little") for name in ("token_id", "sign", "balance", "ay", "eth_addr")}
+            return {"tokenID": v["token_id"], "nonce": 0, "sign": v["sign"], "balance": v["balance"], "ay": v["ay"], "ethAddr": v["eth_addr"]}
+
+    def __init__(self, ledger, batch_num):
+        if batch_num not in ledger.exit_kept():
+            raise KeyError("batch %d is not kept" % batch_num)
+        self.exit_tree, self.exit_leaves = self._Tree(ledger, batch_num), self._Leaves(ledger, batch_num)
+
+
 class ExitTreeFixture:
     """An exit tree built directly (what a batch of `n_leaves` exits leaves behind; reference test/withdraw.test.js:39-157 reaches it
     through four exit transactions): exit_tree / exit_leaves as withdraw_input() reads them. device=N hashes the tree on GPU N.

@@ -79,6 +79,8 @@ EXPORTS = [
     "hz_ledger_create_outputs_dev", "hz_ledger_create_ms", "hz_ledger_plan_creates",
     "hz_ledger_apply_batch_atomic", "hz_ledger_verify_l2_atomic", "hz_ledger_plan_atomic", "hz_ledger_rq_ms",
     "hz_ledger_select_batch", "hz_ledger_plan_select", "hz_ledger_select_ms",
+    "hz_ledger_exit_keep", "hz_ledger_exit_forget", "hz_ledger_exit_kept", "hz_ledger_exit_archive_stats", "hz_ledger_exit_root_of", "hz_ledger_withdraw_rows",
+    "hz_ledger_withdraw_rows_dev", "hz_ledger_withdraw_ms", "hz_ledger_exit_keep_ms",
 ]
 
 
@@ -188,6 +190,11 @@ LEDGER_EXIT_ARRAYS = ("new_exit", "is_old0_2", "old_key2", "old_value2", "exit_r
 
 
 # hz_ledger_create_out's arrays in order: [rows, 32] each, the last [1, 32]
+# hz_withdraw_rows_out's members in order: Withdraw's input signals, and the status bytes
+WITHDRAW_ARRAYS = ("root_exit", "eth_addr", "token_id", "balance", "idx", "sign", "ay", "siblings_state", "status")
+WITHDRAW_SIGNALS = {"root_exit": "rootExit", "eth_addr": "ethAddr", "token_id": "tokenID", "balance": "balance", "idx": "idx", "sign": "sign", "ay": "ay",
+                    "siblings_state": "siblingsState"}
+WITHDRAW_MAX_ROWS = 1 << 20
 LEDGER_CREATE_ARRAYS = ("aux_from_idx", "is_old0_1", "old_key1", "old_value1", "out_idx_after", "new_last_idx")
 
 
@@ -396,8 +403,15 @@ class Lib:
         c.hz_ledger_plan_atomic.argtypes = [sz, sz, vp, vp, vp, vp, vp]
         c.hz_ledger_select_batch.argtypes = [vp, sz, vp, vp, sz, vp, vp, vp, vp, u32, u32, u32, sz, vp]
         c.hz_ledger_plan_select.argtypes = [sz, vp, sz, vp, vp, vp, vp, vp, vp, ctypes.POINTER(sz), vp, vp, vp]
+        c.hz_ledger_exit_keep.argtypes = [vp, u32]
+        c.hz_ledger_exit_forget.argtypes = [vp, u32]
+        c.hz_ledger_exit_kept.argtypes = [vp, vp, sz, ctypes.POINTER(sz)]
+        c.hz_ledger_exit_archive_stats.argtypes = [vp] + [ctypes.POINTER(sz)] * 4
+        c.hz_ledger_exit_root_of.argtypes = [vp, u32, vp]
+        c.hz_ledger_withdraw_rows.argtypes = [vp, sz, vp, vp, ctypes.c_int32, vp]
+        c.hz_ledger_withdraw_rows_dev.argtypes = [vp, vp]
         for f in ("hz_ledger_device_ms", "hz_ledger_semantic_ms", "hz_ledger_sig_ms", "hz_ledger_resolve_ms", "hz_ledger_l1_ms", "hz_ledger_exit_ms", "hz_ledger_create_ms",
-                  "hz_ledger_rq_ms", "hz_ledger_select_ms"):
+                  "hz_ledger_rq_ms", "hz_ledger_select_ms", "hz_ledger_withdraw_ms", "hz_ledger_exit_keep_ms"):
             getattr(c, f).argtypes = [vp]
             getattr(c, f).restype = ctypes.c_double
 
@@ -1406,6 +1420,71 @@ class Ledger(_Resident):
     def exit_ms(self):
         """device time of the exit kernels plus the exit tree's update of the last apply_batch_exits (0.0 without an exit operation)"""
         return self.L.c.hz_ledger_exit_ms(self.h)
+
+    def exit_keep(self, batch_num):
+        """freezes the exit tree as it stands under batch_num (above every kept number); the live tree and the *_dev outputs stay"""
+        self.L._check(self.L.c.hz_ledger_exit_keep(self.h, batch_num))
+
+    def exit_forget(self, below_batch):
+        """drops every kept batch with a number below below_batch"""
+        self.L._check(self.L.c.hz_ledger_exit_forget(self.h, below_batch))
+
+    def exit_kept(self):
+        """the kept batch numbers, ascending"""
+        import numpy as np
+        n = ctypes.c_size_t()
+        self.L._check(self.L.c.hz_ledger_exit_kept(self.h, None, 0, ctypes.byref(n)))
+        out = np.zeros(max(n.value, 1), dtype=np.uint32)
+        self.L._check(self.L.c.hz_ledger_exit_kept(self.h, out.ctypes.data, n.value, ctypes.byref(n)))
+        return out[:n.value].tolist()
+
+    def exit_archive_stats(self):
+        """{snapshots, slabs, bytes_used, bytes_reserved} of the archive of kept exit trees"""
+        v = [ctypes.c_size_t() for _ in range(4)]
+        self.L._check(self.L.c.hz_ledger_exit_archive_stats(self.h, *[ctypes.byref(x) for x in v]))
+        return dict(zip(("snapshots", "slabs", "bytes_used", "bytes_reserved"), (x.value for x in v)))
+
+    def exit_root_of(self, batch_num):
+        """the exit root of a kept batch as an int; a batch that is not kept raises"""
+        out = (ctypes.c_uint8 * 32)()
+        self.L._check(self.L.c.hz_ledger_exit_root_of(self.h, batch_num, ctypes.addressof(out)))
+        return int.from_bytes(bytes(out), "little")
+
+    def withdraw_rows(self, batch_nums, idxs, n_levels, outputs=True, into=None):
+        """Withdraw(n_levels)'s inputs for the queries (batch_nums[i], idxs[i]) over the kept exit trees -> {name: array} by WITHDRAW_ARRAYS:
+        seven [n, 32] arrays, siblings_state [n, n_levels + 1, 32] and status [n] (0 found, 1 batch not kept, 2 idx not in that tree, 3 the
+        leaf needs n_levels + 1 or more siblings; the rows of such a query are zero). outputs=False: nothing is copied to the host
+        (withdraw_rows_dev has the arrays); into: arrays to write into by name, the others are not copied"""
+        import numpy as np
+        b = np.ascontiguousarray(batch_nums, dtype=np.uint32)
+        k = np.ascontiguousarray(idxs, dtype=np.uint64)
+        if b.shape != k.shape or b.ndim != 1:
+            raise ValueError("withdraw_rows: batch_nums and idxs are two lists of one length")
+        n = b.size
+        got = {}
+        if into is not None:
+            got = dict(into)
+        elif outputs:
+            got = {name: np.zeros((n, 32), dtype=np.uint8) for name in WITHDRAW_ARRAYS[:7]}
+            got["siblings_state"] = np.zeros((n, max(n_levels + 1, 0), 32), dtype=np.uint8)
+            got["status"] = np.zeros(n, dtype=np.uint8)
+        ptrs = (ctypes.c_void_p * len(WITHDRAW_ARRAYS))(*[got[name].ctypes.data if name in got else None for name in WITHDRAW_ARRAYS])
+        self.L._check(self.L.c.hz_ledger_withdraw_rows(self.h, n, b.ctypes.data, k.ctypes.data, n_levels, ctypes.addressof(ptrs) if got else None))
+        return got
+
+    def withdraw_rows_dev(self):
+        """device pointers of the nine arrays of the last withdraw_rows, by name; valid until the ledger's next call"""
+        ptrs = (ctypes.c_void_p * len(WITHDRAW_ARRAYS))()
+        self.L._check(self.L.c.hz_ledger_withdraw_rows_dev(self.h, ctypes.addressof(ptrs)))
+        return {name: ptrs[i] for i, name in enumerate(WITHDRAW_ARRAYS)}
+
+    def withdraw_ms(self):
+        """device time of the two kernels of the last withdraw_rows"""
+        return self.L.c.hz_ledger_withdraw_ms(self.h)
+
+    def exit_keep_ms(self):
+        """device time of the copies of the last exit_keep"""
+        return self.L.c.hz_ledger_exit_keep_ms(self.h)
 
     def l1_flags_dev(self):
         """device pointer of the [n_l1] flag bytes of the last successful apply_batch; valid until the ledger's next call"""

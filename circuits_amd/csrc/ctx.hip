@@ -484,6 +484,21 @@ static hz_status set_input_common(hz_ctx* c, int32_t instance, const char* name,
         }
     } else {
         if (!stream) stream = c->s_main;   // never the legacy default stream (hermez_witness.h "streams")
+        if (instance < 0 && B > 1 && outer == s.upi) {
+            // every instance at once, and the signal covers every unit of an instance: the units of all instances lie behind each other on
+            // both sides, so the whole input is ONE [B * outer][inner] -> [inner][B * outer] transpose (one copy when inner == 1)
+            // instead of a copy or a launch per instance (hz_ledger_withdraw_rows_dev feeds 2^16 instances of Withdraw this way)
+            const size_t units = (size_t)B * outer;
+            if (d->inner == 1) {
+                HZ_HIP(hipMemcpyAsync(dst0, dev, units * 32, hipMemcpyDeviceToDevice, stream));
+            } else {
+                const size_t n = units * d->inner;
+                const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 2048);
+                hipLaunchKernelGGL(k_transpose32, dim3(blocks), dim3(256), 0, stream, (const uint4*)dev, (uint4*)dst0, (uint32_t)units, d->inner, s.n_units);
+                HZ_HIP(hipGetLastError());
+            }
+            b1 = b0;   // nothing is left for the loop
+        }
         for (uint32_t b = b0; b < b1; b++) {
             const uint8_t* src = (const uint8_t*)dev + (size_t)(b - b0) * per * 32;
             uint8_t* dst = dst0 + (size_t)b * s.upi * 32;

@@ -46,6 +46,11 @@
 //   k_ledger_rq            a lane per L2 transaction, behind the message kernel and before the one synchronise: the rq fields against the
 //                          link fields of the row rqOffset names; a mismatch lowers the failure word with reason 13
 // runs whether or not signatures are verified; without HZ_LEDGER_VERIFY_SIGS k_ledger_sig_v2 (ledger_sig.hip) writes the V2 rows it reads.
+// hz_ledger_exit_keep freezes the exit tree a batch left behind into the ledger's archive before the next apply call empties
+// it -- copies of the shape's integers, the tree's two digest pools and the final exit leaves into a slab, no kernel --, and
+// hz_ledger_withdraw_rows answers (batch, idx) queries over the kept trees with Withdraw's input rows (ledger_archive.h):
+//   k_withdraw_walk        a lane per query: SmtShape::find over the snapshot's integers; status, depth, leaf and a source per depth
+//   k_withdraw_fill        a lane per 16 bytes: the siblings and the seven single rows, zeros where the status is not 0
 // Values are plain 256-bit integers in eight 32-bit limbs (the Fc container of fr.h, nothing is reduced modulo r); deltas are
 // two's complement: every true prefix is below 2^220 in magnitude, so a set top bit means "negative"; the arithmetic is u256.h's, shared
 // with ledger_sig.h. Buffers and block offsets are hostutil.h's, the event holder resident.h's; the stream is the tree's (state_stream).
@@ -69,6 +74,7 @@
 #include "ledger_create.h"
 #include "ledger_rq.h"
 #include "ledger_select.h"
+#include "ledger_archive.h"
 #include "smt_internal.h"
 #include "smt_plan.h"
 
@@ -76,6 +82,7 @@
 #define HZ_LEDGER_MAX_TX (1u << 20)
 #define HZ_LEDGER_MAX_F 64u
 #define HZ_LEDGER_CHUNK 64u   // transactions per lane of the fee scan
+#define HZ_ARCHIVE_SLAB_BYTES ((size_t)1 << 20)   // a slab of the exit archive; a snapshot larger than this gets a slab of its own size
 #define HZ_LEDGER_REASONS 17u   // refusal reasons 1 .. 13 and 16; 0 is none, 14 and 15 are verdicts of hz_ledger_select_batch
 
 namespace hz {
@@ -374,6 +381,30 @@ static hipError_t launch_ledger_rq(const hz_l2tx* d_txs, const hz_l2sig* d_sigs,
 
 using namespace hz;
 
+// the archive of exit trees (ledger_archive.h): snapshots in ascending batch order, each inside one slab; a slab is
+// allocated when the last one has no room for the next snapshot and freed when every snapshot in it is forgotten. Made by the first
+// hz_ledger_exit_keep / hz_ledger_withdraw_rows: a ledger that keeps nothing owns none of this
+struct ArchiveSlab {
+    DevBuf buf;
+    size_t used = 0;
+    uint32_t live = 0;   // snapshots in it
+};
+struct ArchiveSnap {
+    uint32_t batch_num = 0;
+    ArchiveSlab* slab = nullptr;   // nullptr: the empty tree, no bytes
+    size_t bytes = 0;
+    ArchiveDesc desc{};
+};
+struct LedgerArchive {
+    std::vector<ArchiveSnap> snaps;
+    std::vector<std::unique_ptr<ArchiveSlab>> slabs;   // in allocation order: the last one is the current one
+    DevBuf table;                                      // ArchiveDesc[snaps.size()], room for table.bytes / 64
+    DevEvent ek0, ek1, ew0, ew1;                       // around a keep's copies, around the two kernels of hz_ledger_withdraw_rows
+    double keep_ms = 0.0, withdraw_ms = 0.0;
+    uint8_t* rows_dev[HZ_WITHDRAW_ARRAYS] = {};
+    bool have_rows = false;
+};
+
 struct hz_ledger {
     int32_t device = 0;
     uint32_t k = 0, N = 0;
@@ -435,7 +466,10 @@ struct hz_ledger {
     PinnedBuf h_sel;
     DevEvent esel0, esel1;   // around k_ledger_select
     double select_ms = 0.0;
+    // exit trees of earlier batches (hz_ledger_exit_keep)
+    std::unique_ptr<LedgerArchive> archive;
     ~hz_ledger() {
+        archive.reset();
         if (exit) hz_smt_destroy(exit);
         if (smt) hz_smt_destroy(smt);
         if (tree) hz_state_destroy(tree);
@@ -474,6 +508,14 @@ static void ledger_forget(hz_ledger* l) {
     l->have_outputs = l->have_sig_outputs = l->have_aux = l->have_l1 = l->have_exit_outputs = l->have_create_outputs = false;
     l->l1_ms = 0.0;
     l->create_ms = 0.0;
+    if (l->archive) l->archive->have_rows = false;
+}
+
+// a reload starts a new history: no exit tree of the old one is kept
+static void ledger_archive_clear(hz_ledger* l) {
+    if (!l->archive) return;
+    l->archive->snaps.clear();
+    l->archive->slabs.clear();
 }
 
 static hz_status ledger_ready(const hz_ledger* l, const char* who) {
@@ -743,6 +785,7 @@ extern "C" hz_status hz_ledger_load(hz_ledger* l, const uint8_t* e0, const uint8
     // a leaf's ranges, which every kernel assumes: before the tree or the planes are touched, so a refused load leaves a loaded ledger as it was
     if (hz_status e = ledger_check_leaves("hz_ledger_load", l->first_idx, l->N, e0, balance, eth_addr)) return e;
     ledger_forget(l);
+    ledger_archive_clear(l);
     if (hz_status e = hz_state_load(l->tree, e0, balance, ay, eth_addr)) return e;   // checks every field < r
     const uint8_t* src[4] = {e0, balance, ay, eth_addr};
     hipStream_t s = ledger_stream(l);
@@ -777,6 +820,7 @@ extern "C" hz_status hz_ledger_load_accounts(hz_ledger* l, uint64_t n, const uin
     }
     ledger_forget(l);
     ledger_exit_reset(l);
+    ledger_archive_clear(l);
     HZ_HIP(hipSetDevice(l->device));
     if (hz_status e = hz_smt_reset(l->smt)) return e;   // synchronises the stream
     l->live = 0;
@@ -1716,6 +1760,262 @@ extern "C" hz_status hz_ledger_exit_accounts(hz_ledger* l, size_t n, const uint6
     HZ_HIP(hipStreamSynchronize(s));
     return HZ_OK;
 }
+
+// ---- exit trees of earlier batches kept, Withdraw's inputs in bulk (ledger_archive.h) ------------------------------------------
+static hz_status ledger_archive(hz_ledger* l, LedgerArchive** out) {
+    if (!l->archive) {
+        std::unique_ptr<LedgerArchive> a(new LedgerArchive);
+        HZ_HIP(hipSetDevice(l->device));
+        for (DevEvent* e : {&a->ek0, &a->ek1, &a->ew0, &a->ew1}) HZ_HIP(e->create());
+        l->archive = std::move(a);
+    }
+    *out = l->archive.get();
+    return HZ_OK;
+}
+
+// the snapshot of batch_num, or -1
+static int64_t archive_find(const LedgerArchive* a, uint32_t batch_num) {
+    if (!a) return -1;
+    const auto it = std::lower_bound(a->snaps.begin(), a->snaps.end(), batch_num, [](const ArchiveSnap& s, uint32_t b) { return s.batch_num < b; });
+    return it != a->snaps.end() && it->batch_num == batch_num ? (int64_t)(it - a->snaps.begin()) : -1;
+}
+
+// the descriptors of `snaps` into a table with room for them; the caller synchronises
+static hipError_t archive_upload_table(const std::vector<ArchiveSnap>& snaps, void* table, std::vector<ArchiveDesc>& host, hipStream_t s) {
+    host.resize(snaps.size());
+    for (size_t i = 0; i < snaps.size(); i++) host[i] = snaps[i].desc;
+    return snaps.empty() ? hipSuccess : hipMemcpyAsync(table, host.data(), snaps.size() * sizeof(ArchiveDesc), hipMemcpyHostToDevice, s);
+}
+
+extern "C" hz_status hz_ledger_exit_keep(hz_ledger* l, uint32_t batch_num) {
+    const char* who = "hz_ledger_exit_keep";
+    if (hz_status e = ledger_ready(l, who)) return e;
+    if (l->archive && !l->archive->snaps.empty() && batch_num <= l->archive->snaps.back().batch_num)
+        return set_err(HZ_ERR_ARG, "%s: batch_num = %u is not above the last kept batch, %u", who, batch_num, l->archive->snaps.back().batch_num);
+    if (smt_poisoned(l->exit)) return set_err(HZ_ERR_HIP, "%s: the exit tree's last update failed on the device", who);
+    LedgerArchive* a = nullptr;
+    if (hz_status e = ledger_archive(l, &a)) return e;
+    const SmtView v = smt_view(l->exit);
+    const size_t G = v.leaves;
+    if (G != l->exit_keys.size()) return set_err(HZ_ERR_HIP, "%s: the exit tree holds %zu leaves, the ledger %zu exit leaves", who, G, l->exit_keys.size());
+    const ArchiveLayout lay = archive_layout(v.nodes, G);
+    // leaf number -> place among the final exit leaves
+    std::vector<uint32_t> place(G);
+    for (size_t i = 0; i < G; i++) {
+        const auto it = std::lower_bound(l->exit_keys.begin(), l->exit_keys.end(), std::make_pair(v.leaf_key[i], 0u));
+        if (it == l->exit_keys.end() || it->first != v.leaf_key[i]) return set_err(HZ_ERR_HIP, "%s: leaf %zu of the exit tree has no exit leaf", who, i);
+        place[i] = it->second;
+    }
+    HZ_HIP(hipSetDevice(l->device));
+    // every allocation comes first: where one fails nothing of the archive has changed
+    std::unique_ptr<ArchiveSlab> fresh;
+    ArchiveSlab* slab = nullptr;
+    if (lay.bytes) {
+        slab = a->slabs.empty() ? nullptr : a->slabs.back().get();
+        if (!slab || slab->used + lay.bytes > slab->buf.bytes) {
+            fresh.reset(new ArchiveSlab);
+            HZ_HIP(fresh->buf.alloc(std::max(HZ_ARCHIVE_SLAB_BYTES, lay.bytes)));
+            slab = fresh.get();
+        }
+    }
+    DevBuf grown;
+    const size_t want = (a->snaps.size() + 1) * sizeof(ArchiveDesc);
+    if (want > a->table.bytes) HZ_HIP(grown.alloc(std::max((size_t)64 * sizeof(ArchiveDesc), 2 * a->table.bytes)));
+    void* table = grown.p ? grown.p : a->table.p;
+    ArchiveSnap snap;
+    snap.batch_num = batch_num;
+    snap.slab = slab;
+    snap.bytes = lay.bytes;
+    uint8_t* base = slab ? (uint8_t*)slab->buf.p + slab->used : nullptr;
+    snap.desc.root = v.root;
+    snap.desc.leaves = (uint32_t)G;
+    snap.desc.nodes = (uint32_t)v.nodes;
+    snap.desc.batch_num = batch_num;
+    if (base) {   // (the empty tree: root 0, no address is ever read)
+        snap.desc.child = (const int32_t*)(base + lay.child);
+        snap.desc.leaf_key = (const uint64_t*)(base + lay.leaf_key);
+        snap.desc.leaf_place = (const uint32_t*)(base + lay.leaf_place);
+        snap.desc.node = base + lay.node;
+        snap.desc.leaf = base + lay.leaf;
+        snap.desc.fields = base + lay.fields;
+    }
+    std::vector<ArchiveSnap> next = a->snaps;
+    next.push_back(snap);
+    std::vector<ArchiveDesc> host_table;
+    hipStream_t s = ledger_stream(l);
+    // the tree's pools and the final exit leaves are at rest: every apply call ends behind its synchronise
+    const hz_status st = [&]() -> hz_status {
+        HZ_HIP(hipEventRecord(a->ek0, s));
+        if (v.nodes) {
+            HZ_HIP(hipMemcpyAsync(base + lay.child, v.child, v.nodes * 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            HZ_HIP(hipMemcpyAsync(base + lay.node, v.node_digest, v.nodes * 32, hipMemcpyDeviceToDevice, s));
+        }
+        if (G) {
+            HZ_HIP(hipMemcpyAsync(base + lay.leaf_key, v.leaf_key, G * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+            HZ_HIP(hipMemcpyAsync(base + lay.leaf_place, place.data(), G * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+            HZ_HIP(hipMemcpyAsync(base + lay.leaf, v.leaf_hash, G * 32, hipMemcpyDeviceToDevice, s));
+            HZ_HIP(hipMemcpyAsync(base + lay.fields, l->exit_final.p, G * 4 * 32, hipMemcpyDeviceToDevice, s));
+        }
+        HZ_HIP(archive_upload_table(next, table, host_table, s));
+        HZ_HIP(hipEventRecord(a->ek1, s));
+        HZ_HIP(hipStreamSynchronize(s));
+        float ms = 0;
+        HZ_HIP(hipEventElapsedTime(&ms, a->ek0, a->ek1));
+        a->keep_ms = ms;
+        return HZ_OK;
+    }();
+    if (st) {
+        (void)hipStreamSynchronize(s);   // nothing stays in flight over the host arrays; the old table's entries were rewritten with their own values
+        return st;
+    }
+    if (grown.p) std::swap(a->table.p, grown.p), std::swap(a->table.bytes, grown.bytes);
+    if (fresh) a->slabs.push_back(std::move(fresh));
+    if (slab) {
+        slab->used += lay.bytes;
+        slab->live++;
+    }
+    a->snaps.swap(next);
+    return HZ_OK;
+}
+
+extern "C" hz_status hz_ledger_exit_forget(hz_ledger* l, uint32_t below_batch) {
+    const char* who = "hz_ledger_exit_forget";
+    if (!l) return set_err(HZ_ERR_ARG, "%s: null ledger", who);
+    LedgerArchive* a = l->archive.get();
+    if (!a) return HZ_OK;
+    size_t drop = 0;
+    while (drop < a->snaps.size() && a->snaps[drop].batch_num < below_batch) drop++;
+    if (drop == 0) return HZ_OK;
+    HZ_HIP(hipSetDevice(l->device));
+    for (size_t i = 0; i < drop; i++)
+        if (ArchiveSlab* slab = a->snaps[i].slab) slab->live--;
+    a->snaps.erase(a->snaps.begin(), a->snaps.begin() + (ptrdiff_t)drop);
+    for (size_t i = a->slabs.size(); i-- > 0;)
+        if (a->slabs[i]->live == 0) a->slabs.erase(a->slabs.begin() + (ptrdiff_t)i);   // (no call is in flight: every one ends behind a synchronise)
+    std::vector<ArchiveDesc> host_table;
+    hipStream_t s = ledger_stream(l);
+    HZ_HIP(archive_upload_table(a->snaps, a->table.p, host_table, s));
+    HZ_HIP(hipStreamSynchronize(s));
+    return HZ_OK;
+}
+
+extern "C" hz_status hz_ledger_exit_kept(const hz_ledger* l, uint32_t* batch_out, size_t cap, size_t* n) {
+    if (!l || !n || (cap && !batch_out)) return set_err(HZ_ERR_ARG, "hz_ledger_exit_kept: null argument");
+    const size_t count = l->archive ? l->archive->snaps.size() : 0;
+    for (size_t i = 0; i < count && i < cap; i++) batch_out[i] = l->archive->snaps[i].batch_num;
+    *n = count;
+    return HZ_OK;
+}
+
+extern "C" hz_status hz_ledger_exit_archive_stats(const hz_ledger* l, size_t* snapshots, size_t* slabs, size_t* bytes_used, size_t* bytes_reserved) {
+    if (!l) return set_err(HZ_ERR_ARG, "hz_ledger_exit_archive_stats: null ledger");
+    size_t used = 0, reserved = 0;
+    const LedgerArchive* a = l->archive.get();
+    if (a) {
+        for (const ArchiveSnap& s : a->snaps) used += s.bytes;
+        for (const auto& s : a->slabs) reserved += s->buf.bytes;
+        reserved += a->table.bytes;
+    }
+    if (snapshots) *snapshots = a ? a->snaps.size() : 0;
+    if (slabs) *slabs = a ? a->slabs.size() : 0;
+    if (bytes_used) *bytes_used = used;
+    if (bytes_reserved) *bytes_reserved = reserved;
+    return HZ_OK;
+}
+
+extern "C" hz_status hz_ledger_exit_root_of(hz_ledger* l, uint32_t batch_num, uint8_t* out32) {
+    const char* who = "hz_ledger_exit_root_of";
+    if (!l || !out32) return set_err(HZ_ERR_ARG, "%s: null argument", who);
+    const int64_t at = archive_find(l->archive.get(), batch_num);
+    if (at < 0) return set_err(HZ_ERR_ARG, "%s: batch %u is not kept", who, batch_num);
+    const ArchiveDesc& d = l->archive->snaps[(size_t)at].desc;
+    memset(out32, 0, 32);
+    if (d.root == 0) return HZ_OK;
+    const uint32_t src = arc_src(d.root);
+    HZ_HIP(hipSetDevice(l->device));
+    hipStream_t s = ledger_stream(l);
+    HZ_HIP(hipMemcpyAsync(out32, (src >> 30 == ARC_NODE ? d.node : d.leaf) + (size_t)(src & 0x3FFFFFFFu) * 32, 32, hipMemcpyDeviceToHost, s));
+    HZ_HIP(hipStreamSynchronize(s));
+    return HZ_OK;
+}
+
+extern "C" hz_status hz_ledger_withdraw_rows(hz_ledger* l, size_t n, const uint32_t* batch_num, const uint64_t* idx, int32_t n_levels, const hz_withdraw_rows_out* out) {
+    static_assert(sizeof(hz_withdraw_rows_out) == HZ_WITHDRAW_ARRAYS * sizeof(uint8_t*), "hz_withdraw_rows_out is an array of pointers");
+    const char* who = "hz_ledger_withdraw_rows";
+    if (n_levels < 0 || n_levels + 1 > (int32_t)HZ_ARCHIVE_MAX_DEPTH) return set_err(HZ_ERR_ARG, "%s: n_levels + 1 = %d siblings (1 .. 64)", who, n_levels + 1);
+    if (n > HZ_WITHDRAW_MAX_ROWS) return set_err(HZ_ERR_ARG, "%s: %zu queries in one call (at most 2^20)", who, n);
+    if (n && (!batch_num || !idx)) return set_err(HZ_ERR_ARG, "%s: null argument", who);
+    if (!l) return set_err(HZ_ERR_ARG, "%s: null ledger", who);
+    if (hz_status e = ledger_ready(l, who)) return e;
+    LedgerArchive* a = nullptr;
+    if (hz_status e = ledger_archive(l, &a)) return e;
+    ledger_forget(l);   // the call's buffers are reused
+    a->withdraw_ms = 0.0;
+    if (n == 0) return HZ_OK;
+    const uint32_t S = (uint32_t)n_levels + 1, N = (uint32_t)n;
+    HZ_HIP(hipSetDevice(l->device));
+    hipStream_t s = ledger_stream(l);
+    // the integers: snapshot [n] | idx [n] | meta [n] | sources [n][S]; the first two are the host's
+    Carve c;
+    const size_t o_snap = c.take(n * 4), o_idx = c.take(n * 8), host_bytes = c.end, o_meta = c.take(n * sizeof(WithdrawMeta)), o_src = c.take(n * S * 4);
+    // the rows: the seven single arrays [7][n][32] | siblings [n][S][32] | status [n]
+    const size_t o_sib = (size_t)WR_ROWS * n * 32, o_status = o_sib + n * S * 32, out_bytes = o_status + n;
+    HZ_HIP(l->h_ints.grow(host_bytes));
+    HZ_HIP(l->ints.grow(c.end));
+    HZ_HIP(l->outs.grow(out_bytes));
+    uint8_t* hb = (uint8_t*)l->h_ints.p;
+    uint32_t last_batch = 0;
+    int64_t last_at = -2;
+    for (size_t i = 0; i < n; i++) {   // (queries on one batch mostly come in runs)
+        if (last_at == -2 || batch_num[i] != last_batch) last_batch = batch_num[i], last_at = archive_find(a, last_batch);
+        ((int32_t*)(hb + o_snap))[i] = (int32_t)last_at;
+        ((uint64_t*)(hb + o_idx))[i] = idx[i];
+    }
+    LedgerDrain drain;
+    drain.s = s;
+    drain.armed = true;   // the pinned block is the ledger's: no copy from it, or into the caller's arrays, outlives the call
+    uint8_t* db = (uint8_t*)l->ints.p;
+    uint8_t* ob = (uint8_t*)l->outs.p;
+    HZ_HIP(hipMemcpyAsync(db, hb, host_bytes, hipMemcpyHostToDevice, s));
+    HZ_HIP(hipEventRecord(a->ew0, s));
+    hipLaunchKernelGGL(k_withdraw_walk, dim3((N + 63) / 64), dim3(64), 0, s, (const ArchiveDesc*)a->table.p, (const int32_t*)(db + o_snap), (const uint64_t*)(db + o_idx),
+                       (WithdrawMeta*)(db + o_meta), (uint32_t*)(db + o_src), ob + o_status, S, N);
+    HZ_HIP(hipGetLastError());
+    const size_t lanes = n * (S + WR_ROWS) * 2;
+    hipLaunchKernelGGL(k_withdraw_fill, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, (const ArchiveDesc*)a->table.p, (const int32_t*)(db + o_snap),
+                       (const uint64_t*)(db + o_idx), (const WithdrawMeta*)(db + o_meta), (const uint32_t*)(db + o_src), ob, ob + o_sib, S, N);
+    HZ_HIP(hipGetLastError());
+    HZ_HIP(hipEventRecord(a->ew1, s));
+    uint8_t* dev[HZ_WITHDRAW_ARRAYS];
+    for (uint32_t r = 0; r < WR_ROWS; r++) dev[r] = ob + (size_t)r * n * 32;
+    dev[WR_ROWS] = ob + o_sib;
+    dev[WR_ROWS + 1] = ob + o_status;
+    if (out) {
+        uint8_t* const* h = (uint8_t* const*)out;
+        for (uint32_t r = 0; r < HZ_WITHDRAW_ARRAYS; r++)
+            if (h[r]) HZ_HIP(hipMemcpyAsync(h[r], dev[r], r < WR_ROWS ? n * 32 : r == WR_ROWS ? n * S * 32 : n, hipMemcpyDeviceToHost, s));
+    }
+    HZ_HIP(hipStreamSynchronize(s));
+    drain.armed = false;
+    float ms = 0;
+    HZ_HIP(hipEventElapsedTime(&ms, a->ew0, a->ew1));
+    a->withdraw_ms = ms;
+    for (uint32_t r = 0; r < HZ_WITHDRAW_ARRAYS; r++) a->rows_dev[r] = dev[r];
+    a->have_rows = true;
+    return HZ_OK;
+}
+
+extern "C" hz_status hz_ledger_withdraw_rows_dev(hz_ledger* l, hz_withdraw_rows_out* dev) {
+    if (!l || !dev) return set_err(HZ_ERR_ARG, "hz_ledger_withdraw_rows_dev: null argument");
+    if (!l->archive || !l->archive->have_rows)
+        return set_err(HZ_ERR_ARG, "hz_ledger_withdraw_rows_dev: no successful hz_ledger_withdraw_rows (of at least one query) since the ledger's last other call");
+    uint8_t** d = (uint8_t**)dev;
+    for (int r = 0; r < HZ_WITHDRAW_ARRAYS; r++) d[r] = l->archive->rows_dev[r];
+    return HZ_OK;
+}
+
+extern "C" double hz_ledger_withdraw_ms(const hz_ledger* l) { return l && l->archive ? l->archive->withdraw_ms : 0.0; }
+extern "C" double hz_ledger_exit_keep_ms(const hz_ledger* l) { return l && l->archive ? l->archive->keep_ms : 0.0; }
 
 extern "C" hz_status hz_ledger_plan_exits(size_t n_l1, const hz_l1tx* l1, size_t m, const hz_l2tx* txs, size_t F, const uint32_t* fee_plan_tokens,
                                           const uint64_t* fee_idxs, int32_t k, uint64_t first_idx, size_t n_sib, int32_t* ev_sender_out, int32_t* ev_receiver_out,

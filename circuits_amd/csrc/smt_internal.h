@@ -32,6 +32,17 @@ void smt_apply_abort(hz_smt* t);
 // the empty tree again without a synchronise: for an owner whose every call on the tree ended in finish or abort
 void smt_clear(hz_smt* t);
 hipStream_t smt_stream(const hz_smt* t);
+// the tree as it stands, read-only, for an owner that freezes it (ledger_archive.h): the shape's integers on the host, the digest pools
+// on the device. Valid until the tree's next call; nothing may be in flight on the tree's stream
+struct SmtView {
+    int32_t root;                // 0 empty, n + 1 node n, -(l + 1) leaf l
+    size_t nodes, leaves;
+    const int32_t* child;        // host, [2 * nodes]
+    const uint64_t* leaf_key;    // host, [leaves]
+    const uint8_t* node_digest;  // device, [nodes][32]
+    const uint8_t* leaf_hash;    // device, [leaves][32]
+};
+SmtView smt_view(const hz_smt* t);
 // a call failed on the device behind its queued write-back: every public call answers HZ_ERR_HIP until hz_smt_reset
 bool smt_poisoned(const hz_smt* t);
 

@@ -315,6 +315,10 @@ void hz::smt_clear(hz_smt* t) {
 }
 
 hipStream_t hz::smt_stream(const hz_smt* t) { return t->r.s; }
+SmtView hz::smt_view(const hz_smt* t) {
+    const SmtShape& sh = t->shape;
+    return SmtView{sh.root, sh.nodes(), sh.leaves(), sh.child.data(), sh.leaf_key.data(), (const uint8_t*)t->node.p, (const uint8_t*)t->leaf.p};
+}
 bool hz::smt_poisoned(const hz_smt* t) { return t->poisoned; }
 
 extern "C" hz_status hz_smt_apply(hz_smt* t, size_t m, const uint64_t* key, const uint8_t* fields, size_t n_sib, uint8_t* siblings_out, uint64_t* old_key_out,

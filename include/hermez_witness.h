@@ -572,6 +572,35 @@ hz_status hz_smt_plan(size_t m, const uint64_t* key, size_t n_sib, uint32_t* dep
  * LIFETIME. The exit tree and the exit leaves are those of the last successful call that applied a batch: every apply call (all six)
  * starts by emptying them, so after a refused call, and after a call of the other five, the tree is empty. A refused call leaves root,
  * planes and state tree untouched, as above.
+ * EXIT TREES KEPT. A withdrawal is made against the exit tree of an EARLIER batch: the contract keeps one exit root per batch
+ * number. hz_ledger_exit_keep freezes the exit tree as it stands under a batch number before the next apply call empties it; the frozen
+ * trees -- the ARCHIVE -- lie in device memory the ledger owns, and the inputs of Withdraw(nLevels) come out of them in bulk:
+ *   hz_ledger_exit_keep the exit tree and the exit leaves as they stand, kept under batch_num: after a successful
+ *                       hz_ledger_apply_batch_exits / _creates / _atomic the batch's, after any other apply call or a refused one the
+ *                       empty tree (a legitimate entry: exit root 0, no leaf). batch_num must be above every kept number (HZ_ERR_ARG). The
+ *                       live exit tree, root, planes and the *_dev outputs of earlier calls stay as they are. A device allocation that
+ *                       fails is HZ_ERR_HIP and the keep did not happen: the archive is unchanged. A ledger that never calls this
+ *                       allocates nothing for the archive
+ *   hz_ledger_exit_forget  drops every kept batch with a number below below_batch; its memory is free for later keeps once every
+ *                       batch that shares its slab of device memory is forgotten too
+ *   hz_ledger_exit_kept the kept batch numbers, ascending: the first cap of them into batch_out, *n the number kept
+ *   hz_ledger_exit_archive_stats  kept snapshots, device slabs, the bytes the snapshots fill and the bytes reserved (slabs plus the
+ *                       descriptor table). Every output may be NULL
+ *   hz_ledger_exit_root_of  the exit root of a kept batch (HZ_ERR_ARG: not kept)
+ *   hz_ledger_withdraw_rows  n <= 2^20 queries (batch_num[i], idx[i]) in any order, over any mix of kept batches, for Withdraw(n_levels):
+ *                       out (may be NULL; nullable host pointers) takes the circuit's input signals row-major, as hz_set_input(...,
+ *                       instance = -1, ...) wants them for a context of n instances: root_exit, eth_addr, token_id, balance, idx, sign, ay
+ *                       [n][32], siblings_state [n][n_levels + 1][32] zero-padded, and status [n] bytes:
+ *                         0 found        1 batch_num is not kept        2 idx is not in that tree (the walk met nothing or another leaf,
+ *                         or idx >= 2^48)        3 the leaf needs n_levels + 1 or more siblings (hz_smt_proofs' depth rule)
+ *                       Every row of a query whose status is not 0 is zero. tokenID and sign are unpacked from the leaf's e0 on the
+ *                       device. Like hz_ledger_verify_l2 the call refuses nothing but arguments -- HZ_ERR_ARG: a null argument, n above
+ *                       2^20, n_levels + 1 outside 1 .. 64 -- changes nothing resident and invalidates the *_dev outputs of earlier calls
+ *   hz_ledger_withdraw_rows_dev  the same nine arrays as DEVICE pointers of the last hz_ledger_withdraw_rows, valid until the ledger's
+ *                       next call; fit for hz_set_input_dev
+ *   hz_ledger_withdraw_ms / hz_ledger_exit_keep_ms  device time of the two kernels of the last hz_ledger_withdraw_rows; of the copies of
+ *                       the last hz_ledger_exit_keep
+ * The archive lives as long as the loaded state: hz_ledger_load / hz_ledger_load_accounts empty it. It works on dense and growing ledgers.
  * CREATES. An L1 row with from_idx == 0 creates an account: createAccount, createAccountDeposit,
  * createAccountDepositTransfer, and the coordinator's L1 transactions. The state tree's shape changes, so only a GROWING ledger takes one:
  *   hz_ledger_create_growing  a ledger of up to `capacity` accounts (1 .. 2^24; first_idx >= 2) whose state tree is an hz_smt of n_sib_max siblings it
@@ -676,7 +705,7 @@ hz_status hz_smt_plan(size_t m, const uint64_t* key, size_t n_sib, uint32_t* dep
  *   hz_ledger_select_ms device time of k_ledger_select in the last hz_ledger_select_batch
  * OUT OF SCOPE: L1 transactions that create accounts or exit through a call other than hz_ledger_apply_batch_exits (creates:
  * hz_ledger_apply_batch_creates on a growing ledger), an L1 amount with
- * to_idx == 0 (no receiver), exit trees of earlier batches kept resident, a resident address index kept across
+ * to_idx == 0 (no receiver), persisting, or carrying across a reload, the exit trees of earlier batches kept resident, a resident address index kept across
  * calls, batch (random linear combination) verification of signatures, more than one device per ledger. One thread at a time. */
 typedef struct hz_ledger hz_ledger;
 typedef struct {
@@ -773,6 +802,23 @@ hz_status hz_ledger_plan_exits(size_t n_l1, const hz_l1tx* l1, size_t m, const h
                                size_t* n_exits_out, uint32_t* exit_row_out, uint64_t* exit_key_out, int32_t* exit_prev_out, uint32_t* exit_perm_out,
                                uint8_t* exit_insert_out, uint8_t* exit_is_old0_out, uint64_t* exit_old_key_out);
 double hz_ledger_exit_ms(const hz_ledger* l);
+#define HZ_WITHDRAW_ARRAYS 9
+#define HZ_WITHDRAW_MAX_ROWS ((size_t)1 << 20)
+typedef struct {
+    uint8_t *root_exit, *eth_addr, *token_id, *balance, *idx, *sign, *ay; /* [n]: Withdraw's inputs (src/withdraw.circom:26-33) */
+    uint8_t* siblings_state;                                              /* [n][n_levels + 1] */
+    uint8_t* status;                                                      /* [n] BYTES: 0 found, 1 not kept, 2 absent, 3 too deep */
+} hz_withdraw_rows_out;
+hz_status hz_ledger_exit_keep(hz_ledger* l, uint32_t batch_num);
+hz_status hz_ledger_exit_forget(hz_ledger* l, uint32_t below_batch);
+hz_status hz_ledger_exit_kept(const hz_ledger* l, uint32_t* batch_out /* [cap] */, size_t cap, size_t* n);
+hz_status hz_ledger_exit_archive_stats(const hz_ledger* l, size_t* snapshots, size_t* slabs, size_t* bytes_used, size_t* bytes_reserved);
+hz_status hz_ledger_exit_root_of(hz_ledger* l, uint32_t batch_num, uint8_t* out32);
+hz_status hz_ledger_withdraw_rows(hz_ledger* l, size_t n, const uint32_t* batch_num, const uint64_t* idx, int32_t n_levels,
+                                  const hz_withdraw_rows_out* out /* or NULL */);
+hz_status hz_ledger_withdraw_rows_dev(hz_ledger* l, hz_withdraw_rows_out* dev);
+double hz_ledger_withdraw_ms(const hz_ledger* l);
+double hz_ledger_exit_keep_ms(const hz_ledger* l);
 hz_status hz_ledger_create_growing(int32_t device, uint64_t capacity, uint64_t first_idx, int32_t n_sib_max, hz_ledger** out);
 hz_status hz_ledger_load_accounts(hz_ledger* l, uint64_t n, const uint8_t* e0, const uint8_t* balance, const uint8_t* ay, const uint8_t* eth_addr);
 uint64_t hz_ledger_size(const hz_ledger* l);
