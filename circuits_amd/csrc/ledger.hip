@@ -1,59 +1,45 @@
-// hz_ledger: an hz_state plus the resident leaf fields, and L2 transfers computed and applied on the device.
+// hz_ledger: an hz_state -- or, on a growing ledger, an hz_smt -- plus the resident leaf fields, and batches computed and applied on the
+// device (DESIGN.md 8c .. 8k).
 //
-// The split is the library's: the host does integer work on indices only (ledger_plan.h: events, their grouping by account, fee slots),
-// the device everything that touches a 256-bit value. One call is
-//   k_ledger_tx        a lane per transaction: float40 -> amount, fee = amount x table[selector] (>> 60 below 192), the signed deltas
-//                      of its sender and receiver events; a fee of 2^128 or more lowers the failure word with reason 16
-//   k_ledger_fee_sum / k_ledger_fee_scan   the accumulated fees after every transaction, per slot: chunk sums, then a lane per
-//                      (chunk, slot) walks its chunk; the last row is the delta of the fee events
-//   k_ledger_scan      balances and nonces with sequential semantics: the events of an account lie behind each other (grouped order)
-//                      and one lane carries balance and e0 through them, checks token, nonce, underflow and overflow, lowers the failure
-//                      word with atomicMin, and writes every event's leaf before and after
-//   -- one synchronise: the failure word. A refused batch ends here; nothing resident has been written --
-//   k_ledger_pack      the before-fields of every transaction and fee slot into the output arrays
-//   the tree update    state_apply_launch (state.hip): the body of hz_state_apply on the records k_ledger_scan wrote
-//   k_ledger_gather    events back to transactions: siblings1/2/3, the root after each transaction and fee slot
-//   k_ledger_writeback the last leaf of every touched account into the resident planes
-// hz_ledger_apply_l2_signed adds the two signature kernels of ledger_sig.hip after k_ledger_scan, on the same stream and
-// before the one synchronise: they lower the same failure word with reasons 7 and 8. hz_ledger_verify_l2 runs those two alone.
-// hz_ledger_apply_l2_addr accepts to_idx == 0, a receiver named by address or key. Before the plan can be made
-//   k_ledger_resolve       a lane per account: the account's key (ledger_resolve.h) probed in the table of the batch's distinct queries,
-//                          the slot's result lowered to the lowest matching account with atomicMin
-//   k_ledger_resolve_pick  a lane per transaction: its slot's result as an index, or 0
-//   -- a second synchronise, before the first: the planner needs the receivers --
-// and the pipeline above then runs on the effective receivers, while the uploaded transactions keep the signed to_idx = 0;
-// k_ledger_scan checks the receiver against the signed destination (reasons 10 and 11), k_ledger_pack writes the auxToIdx rows and the
-// leaf-2 rows of a zero-amount transfer to an address.
-// hz_ledger_apply_batch puts a run of L1 transactions in front: the batch has n_l1 + m rows, "transaction" above reads
-// "row", and
-//   k_ledger_l1            (ledger_l1.h) one workgroup: the nullifiers and the ordered recurrence of the L1 run over balances in LDS; it
-//                          leaves the L1 events' deltas where k_ledger_tx leaves those of the L2 rows, and the flag bytes
-// runs before k_ledger_scan, on the same stream and without a synchronise of its own. The scan carries balances through L1 events as
-// through any other, without the token and nonce checks (an invalid L1 transaction is nullified, not refused).
-// hz_ledger_apply_batch_exits accepts to_idx == 1, an L2 exit or an L1 forceExit: the row keeps its sender event, has no
-// receiver event, and its amount goes into the batch's exit tree, an hz_smt the ledger owns (ledger_exit.h, smt_internal.h):
-//   k_ledger_exit_scan     a lane per exit key, before the one synchronise: the exit leaf before and after each of its operations
-//   the exit tree's update smt_apply_launch on that tree's own stream behind an event, beside the state tree's update
-//   k_ledger_exit_pack / _gather   the leaf-2 rows, newExit, isOld0_2, oldKey2, oldValue2, siblings2 and the exit root after every row
-// hz_ledger_create_growing makes a ledger whose state tree is an hz_smt and whose planes are [capacity][32]: N below is
-// then the plane stride and `live` the number of accounts, the tree update is smt_apply_prepare / _launch / _finish on the same record
-// buffer, and hz_ledger_apply_batch_creates accepts from_idx == 0 in L1 rows (ledger_create.h):
-//   k_ledger_create        a lane per create row, before everything else of the call: the new account's static fields into its plane
-//                          slot beyond `live`. From there the pipeline above sees a deposit on auxFromIdx; the tree's planner makes it an insert
-//   k_ledger_create_pack   a lane per row, behind the tree update: auxFromIdx, isOld0_1, oldKey1, oldValue1, the last idx after the row
-// hz_ledger_apply_batch_atomic takes the atomic link of every L2 transaction, hz_l2rq (ledger_rq.h): the message kernel
-// hashes the transaction's own rq fields, and
-//   k_ledger_rq            a lane per L2 transaction, behind the message kernel and before the one synchronise: the rq fields against the
-//                          link fields of the row rqOffset names; a mismatch lowers the failure word with reason 13
-// runs whether or not signatures are verified; without HZ_LEDGER_VERIFY_SIGS k_ledger_sig_v2 (ledger_sig.hip) writes the V2 rows it reads.
-// hz_ledger_exit_keep freezes the exit tree a batch left behind into the ledger's archive before the next apply call empties
-// it -- copies of the shape's integers, the tree's two digest pools and the final exit leaves into a slab, no kernel --, and
-// hz_ledger_withdraw_rows answers (batch, idx) queries over the kept trees with Withdraw's input rows (ledger_archive.h):
-//   k_withdraw_walk        a lane per query: SmtShape::find over the snapshot's integers; status, depth, leaf and a source per depth
-//   k_withdraw_fill        a lane per 16 bytes: the siblings and the seven single rows, zeros where the status is not 0
-// Values are plain 256-bit integers in eight 32-bit limbs (the Fc container of fr.h, nothing is reduced modulo r); deltas are
-// two's complement: every true prefix is below 2^220 in magnitude, so a set top bit means "negative"; the arithmetic is u256.h's, shared
-// with ledger_sig.h. Buffers and block offsets are hostutil.h's, the event holder resident.h's; the stream is the tree's (state_stream).
+// The split is the library's: the host does integer work on indices only (ledger_plan.h: events, their grouping by account, fee slots;
+// ledger_tables.h: the typed tables of one call), the device everything that touches a 256-bit value. Every exported apply call states
+// itself as a LedgerCall -- the request, the host destinations, and what it accepts: by_addr (to_idx == 0, a receiver named by address or
+// key, 8e), is_batch (an L1 run in front: the batch has n_l1 + m rows and "transaction" below reads "row", 8f), exits (to_idx == 1 into
+// the batch's exit tree, an hz_smt the ledger owns, 8g), creates (from_idx == 0 in L1 rows of a growing ledger, 8h), rq != NULL (atomic
+// links, 8i) -- and ledger_apply runs it in stages over one LedgerApply on the stack:
+//   1 plan      the argument checks in the order their errors win. A by_addr call first makes the rows the plan is made of
+//               (ledger_prepare): the L1 rows with auxFromIdx in from_idx's place; k_ledger_create, a lane per create row, the new account's
+//               static fields into its plane slot beyond `live`; the receivers -- k_ledger_resolve, a lane per account probing the table of
+//               the batch's distinct queries, k_ledger_resolve_pick, a lane per transaction, and the lookup's synchronise: the planner needs
+//               them, and a destination nobody holds is reason 9 here. Then the plan, and the exit tree's own (smt_apply_prepare)
+//   2 buffers   the layouts (LedgerTables, LedgerWork) and the room: no allocation after this stage but the signatures' and the links'
+//   3 tables    LedgerTables::fill into the pinned block, the state tree's plan (state_apply_prepare / smt_apply_prepare on the same record
+//               buffer), then the create rows, which read it
+//   4 launch    one upload, then on the tree's stream
+//                 k_ledger_tx        a lane per row: float40 -> amount, fee = amount x table[selector], the signed deltas of its events; a
+//                                    fee of 2^128 or more is reason 16
+//                 k_ledger_l1        (ledger_l1.h) one workgroup: the nullifiers and the ordered recurrence of the L1 run over balances in
+//                                    LDS; the L1 events' deltas beside k_ledger_tx's, and the flag bytes
+//                 k_ledger_fee_sum / _fee_scan   the accumulated fees after every row, per slot; the last row is the fee events' delta
+//                 k_ledger_scan      a lane per account: balance and e0 carried through its events in order, token, nonce, underflow and
+//                                    overflow checked (not on L1 events: an invalid L1 transaction is nullified, not refused), the receiver
+//                                    against the signed destination (10, 11), every event's leaf before and after
+//                 k_ledger_exit_scan a lane per exit key: the exit leaf before and after each of its operations
+//                 the signature kernels of ledger_sig.hip (7, 8) where the call verifies; k_ledger_rq, a lane per L2 row: its rq fields
+//                                    against the link fields of the row rqOffset names (13), on V2 rows k_ledger_sig_v2 writes otherwise
+//               all lowering one failure word with atomicMin -- and the one synchronise
+//   5 verdict   a refused batch ends here; nothing resident has been written
+//   6 commit    k_ledger_pack (the before-fields, auxToIdx, the leaf-2 rows of a zero-amount transfer to an address), the tree update
+//               (state_apply_launch / smt_apply_launch), k_ledger_create_pack, k_ledger_gather (siblings, the root after each row and fee
+//               slot), k_ledger_writeback (the last leaf of every touched account into the planes); the exit tree's update on its own
+//               stream behind an event, then k_ledger_exit_pack / _gather
+//   7 copy out  to the host arrays the caller gave    8 finish   the trees' updates finished, the times, what the getters hand out
+// hz_ledger_verify_l2 runs the signature kernels alone. hz_ledger_select_batch (8j) shares ledger_prepare's pieces and runs
+// k_ledger_select over a pool. hz_ledger_exit_keep (8k) freezes the exit tree a batch left into the ledger's archive -- copies, no kernel --
+// and hz_ledger_withdraw_rows answers (batch, idx) queries over the kept trees (ledger_archive.h: k_withdraw_walk, k_withdraw_fill).
+// Values are plain 256-bit integers in eight 32-bit limbs (the Fc container of fr.h, nothing is reduced modulo r); deltas are two's
+// complement: every true prefix is below 2^220 in magnitude, so a set top bit means "negative"; the arithmetic is u256.h's, shared with
+// ledger_sig.h. Buffers are hostutil.h's, events and time spans resident.h's; the stream is the tree's (state_stream / smt_stream).
 #define HZ_FR_INLINE 1
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -75,13 +61,13 @@
 #include "ledger_rq.h"
 #include "ledger_select.h"
 #include "ledger_archive.h"
+#include "ledger_tables.h"
 #include "smt_internal.h"
 #include "smt_plan.h"
 
 #define HZ_LEDGER_MAX_EVENTS 65536u
 #define HZ_LEDGER_MAX_TX (1u << 20)
 #define HZ_LEDGER_MAX_F 64u
-#define HZ_LEDGER_CHUNK 64u   // transactions per lane of the fee scan
 #define HZ_ARCHIVE_SLAB_BYTES ((size_t)1 << 20)   // a slab of the exit archive; a snapshot larger than this gets a slab of its own size
 #define HZ_LEDGER_REASONS 17u   // refusal reasons 1 .. 13 and 16; 0 is none, 14 and 15 are verdicts of hz_ledger_select_batch
 
@@ -93,11 +79,6 @@ struct LedgerOutDev {
 };
 enum { LO_TX1 = 0, LO_SIB1 = 6, LO_TX2 = 7, LO_SIB2 = 13, LO_ROOT_AFTER = 14, LO_ACC_FEE = 15, LO_TX3 = 16, LO_SIB3 = 22, LO_ROOT_FEE = 23,
        LO_FINAL_FEE = 24, LO_OLD_ROOT = 25, LO_NEW_ROOT = 26 };
-
-// one event in grouped order
-struct LedgerPos {
-    uint32_t ev, unit, kind, acct;
-};
 
 // ---- kernels ----------------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void ledger_fail(uint32_t* word, uint32_t unit, uint32_t reason) { atomicMin(word, (unit << 8) | reason); }
@@ -399,7 +380,7 @@ struct LedgerArchive {
     std::vector<ArchiveSnap> snaps;
     std::vector<std::unique_ptr<ArchiveSlab>> slabs;   // in allocation order: the last one is the current one
     DevBuf table;                                      // ArchiveDesc[snaps.size()], room for table.bytes / 64
-    DevEvent ek0, ek1, ew0, ew1;                       // around a keep's copies, around the two kernels of hz_ledger_withdraw_rows
+    DevSpan t_keep, t_withdraw;                        // around a keep's copies, around the two kernels of hz_ledger_withdraw_rows
     double keep_ms = 0.0, withdraw_ms = 0.0;
     uint8_t* rows_dev[HZ_WITHDRAW_ARRAYS] = {};
     bool have_rows = false;
@@ -416,25 +397,26 @@ struct hz_ledger {
     LedgerPlan plan;
     LedgerOutDev out_dev{};
     bool have_outputs = false;
-    DevEvent e0, e1, e2;       // on the tree's stream (state_stream): before the semantic kernels, after them, after the write-back
+    DevSpan t_semantic;        // on the tree's stream (state_stream): around the semantic kernels;
+    DevEvent e_done;           // after the write-back
     double device_ms = 0.0, semantic_ms = 0.0;
     // signatures: the uploaded hz_l2sig, the three per-transaction arrays and the verdict bytes, the fixed-base table (once per ledger)
     DevBuf sig_in, sig_outs, b8_table;
     uint8_t* sig_dev[3] = {nullptr, nullptr, nullptr};
     uint8_t* verdict_dev = nullptr;
     bool have_sig_outputs = false;
-    DevEvent es0, es1;
+    DevSpan t_sig;
     double sig_ms = 0.0;
     // receivers by address (hz_ledger_apply_l2_addr / _resolve_l2): the query table and the per-transaction results, the auxToIdx rows
     DevBuf res, aux_rows;
     PinnedBuf h_res;
     bool have_aux = false;
-    DevEvent er0, er1;
+    DevSpan t_resolve;
     double resolve_ms = 0.0;
     // the L1 run (hz_ledger_apply_batch): the flag bytes
     DevBuf l1_flags;
     bool have_l1 = false;
-    DevEvent el0, el1;
+    DevSpan t_l1;
     double l1_ms = 0.0;
     // exits (hz_ledger_apply_batch_exits): the batch's exit tree, the six exit arrays, the leaf every exit key ends with (plane-major,
     // [4][exit_keys.size()]) and which key lies where
@@ -443,7 +425,8 @@ struct hz_ledger {
     uint8_t* exit_dev[HZ_LEDGER_EXIT_ARRAYS] = {};
     std::vector<std::pair<uint64_t, uint32_t>> exit_keys;   // (key, its place in exit_final), ascending
     bool have_exit_outputs = false;
-    DevEvent ex0, ex1, ex2, ex3, ex_tree;   // around the scan, around pack and gather (the tree's stream); after the exit tree's update (its own)
+    DevSpan t_exit_scan, t_exit_rows;   // around the scan, around pack and gather (the tree's stream)
+    DevEvent e_exit_tree;               // after the exit tree's update (its own stream)
     double exit_ms = 0.0;
     // a growing ledger (hz_ledger_create_growing): the state tree is an hz_smt, tree == nullptr, N is the capacity -- the
     // plane stride -- and live the number of accounts; a dense ledger has live == N for good
@@ -455,16 +438,16 @@ struct hz_ledger {
     PinnedBuf h_create;
     uint8_t* create_dev[HZ_LEDGER_CREATE_ARRAYS] = {};
     bool have_create_outputs = false;
-    DevEvent ec0, ec1, ec2, ec3;   // around k_ledger_create, around k_ledger_create_pack
+    DevSpan t_create, t_create_pack;   // around k_ledger_create, around k_ledger_create_pack
     double create_ms = 0.0;
     // atomic links (hz_ledger_apply_batch_atomic / _verify_l2_atomic): the rq fields plane-major, [3][m][32], then the m offsets
     DevBuf rq_in;
     PinnedBuf h_rq;
-    DevEvent eq0, eq1;   // around k_ledger_rq
+    DevSpan t_rq;   // around k_ledger_rq
     double rq_ms = 0.0;
     // a batch selected from a pool (hz_ledger_select_batch): what k_ledger_select left, back on the host
     PinnedBuf h_sel;
-    DevEvent esel0, esel1;   // around k_ledger_select
+    DevSpan t_select;   // around k_ledger_select
     double select_ms = 0.0;
     // exit trees of earlier batches (hz_ledger_exit_keep)
     std::unique_ptr<LedgerArchive> archive;
@@ -577,26 +560,42 @@ static hz_status ledger_check_l1_fields(const char* who, size_t i, const hz_l1tx
     return HZ_OK;
 }
 
-// the L1 run of hz_ledger_apply_batch: its transactions, where the flag bytes go on the host (may be null); is_batch tells the call
-// from hz_ledger_apply_l2_addr, which has none
-struct LedgerL1Run {
-    size_t n = 0;
-    const hz_l1tx* tx = nullptr;
-    uint8_t* flags_out = nullptr;
-    bool is_batch = false;
-    // hz_ledger_apply_batch_exits: to_idx == 1 is taken in L1 and L2 rows; where the exit arrays go on the host (may be null)
-    bool exits = false;
-    const hz_ledger_exit_out* exit_out = nullptr;
-    // hz_ledger_apply_batch_creates: from_idx == 0 is taken in L1 rows; the compressed keys of those rows; where the create arrays go on
-    // the host (may be null). Once the rows are checked: tx are the rows with auxFromIdx in from_idx's place, aux_from / idx_after [n]
-    // the running index, n_creates the accounts the call makes
-    bool creates = false;
+// one apply call, as its exported function states it
+struct LedgerCall {
+    const char* who = "";
+    // the request: the L1 run with the compressed keys of its create rows, the m L2 rows with their signatures and links (rq == null: no
+    // transaction links, nothing to check), the fee plan; aux_to_idx: the receivers by address as the caller found them, or null
+    size_t n_l1 = 0, m = 0, F = 0, n_sib = 0;
+    const hz_l1tx* l1 = nullptr;
     const uint8_t* from_bjj = nullptr;
-    const hz_ledger_create_out* create_out = nullptr;
-    const uint64_t *aux_from = nullptr, *idx_after = nullptr;
-    size_t n_creates = 0;
-    // hz_ledger_apply_batch_atomic: the links of the L2 rows, [m] or null (no transaction links: nothing to check)
+    const hz_l2tx* txs = nullptr;
+    const hz_l2sig* sigs = nullptr;
     const hz_l2rq* rq = nullptr;
+    uint32_t flags = 0, chain_id = 0, current_num_batch = 0;
+    bool verify = false;   // flags & HZ_LEDGER_VERIFY_SIGS, or hz_ledger_apply_l2_signed
+    const uint32_t* plan_tokens = nullptr;
+    const uint64_t *fee_idxs = nullptr, *aux_to_idx = nullptr;
+    // where the outputs go on the host; each may be null
+    const hz_ledger_out* out = nullptr;
+    const hz_ledger_sig_out* sig_out = nullptr;
+    uint8_t *aux_to_idx_out = nullptr, *flags_out = nullptr;
+    const hz_ledger_exit_out* exit_out = nullptr;
+    const hz_ledger_create_out* create_out = nullptr;
+    // what the call accepts: to_idx == 0 in L2 rows (and sigs uploaded for their destination fields whether or not they are verified), an
+    // L1 run, to_idx == 1 in L1 and L2 rows, from_idx == 0 in L1 rows
+    bool by_addr = false, is_batch = false, exits = false, creates = false;
+};
+
+// what the checks of a by_addr call (ledger_prepare) leave: the rows as the pipeline takes them
+struct LedgerRows {
+    std::vector<hz_l1tx> eff_l1;   // a create row is a deposit on auxFromIdx, in from_idx's place
+    std::vector<uint64_t> aux_from, idx_after;   // [n_l1] the running index; aux_from 0: the row creates nothing
+    const hz_l1tx* l1 = nullptr;   // eff_l1's, or the caller's where the call creates nothing
+    size_t n_creates = 0, l1_events = 0;
+    std::vector<hz_l2sig> no_sigs;
+    const hz_l2sig* sigs = nullptr;   // the caller's, or zero entries where no destination is signed
+    std::vector<hz_l2tx> eff;      // the L2 rows with the effective receivers: what the plan is made of
+    uint64_t count = 0;            // the accounts an L2 row or a fee slot may name: live plus created
 };
 
 // the argument checks of an L1 run that may create accounts; -> the events it makes, the rows as the pipeline takes them
@@ -710,9 +709,10 @@ static hz_status ledger_open(hz_ledger* l) {
     HZ_HIP(hipSetDevice(l->device));
     HZ_HIP(l->planes.alloc((size_t)4 * l->N * 32));
     HZ_HIP(l->h_fail.grow(64));
-    for (DevEvent* e : {&l->e0, &l->e1, &l->e2, &l->es0, &l->es1, &l->er0, &l->er1, &l->el0, &l->el1, &l->ex0, &l->ex1, &l->ex2, &l->ex3, &l->ex_tree, &l->ec0,
-                        &l->ec1, &l->ec2, &l->ec3, &l->eq0, &l->eq1, &l->esel0, &l->esel1})
-        HZ_HIP(e->create());
+    for (DevSpan* t : {&l->t_semantic, &l->t_sig, &l->t_resolve, &l->t_l1, &l->t_exit_scan, &l->t_exit_rows, &l->t_create, &l->t_create_pack, &l->t_rq, &l->t_select})
+        HZ_HIP(t->create());
+    HZ_HIP(l->e_done.create());
+    HZ_HIP(l->e_exit_tree.create());
     return HZ_OK;
 }
 
@@ -887,12 +887,17 @@ extern "C" hz_status hz_ledger_accounts(hz_ledger* l, size_t n, const uint64_t* 
     return HZ_OK;
 }
 
-extern "C" hz_status hz_ledger_outputs_dev(hz_ledger* l, hz_ledger_out* dev) {
-    if (!l || !dev) return set_err(HZ_ERR_ARG, "hz_ledger_outputs_dev: null argument");
-    if (!l->have_outputs) return set_err(HZ_ERR_ARG, "hz_ledger_outputs_dev: no successful hz_ledger_apply_l2 since the ledger's last other call");
-    uint8_t** d = (uint8_t**)dev;
-    for (int a = 0; a < HZ_LEDGER_ARRAYS; a++) d[a] = l->out_dev.a[a];
+// the *_dev getters: the n device pointers of the last successful `call` into dev, a struct of n pointers; have == nullptr: the ledger
+// holds none of them
+static hz_status ledger_hand_out(const char* who, const hz_ledger* l, void* dev, const bool* have, const char* call, uint8_t* const* src, int n) {
+    if (!l || !dev) return set_err(HZ_ERR_ARG, "%s: null argument", who);
+    if (!have || !*have) return set_err(HZ_ERR_ARG, "%s: no successful %s since the ledger's last other call", who, call);
+    for (int a = 0; a < n; a++) ((uint8_t**)dev)[a] = src[a];
     return HZ_OK;
+}
+
+extern "C" hz_status hz_ledger_outputs_dev(hz_ledger* l, hz_ledger_out* dev) {
+    return ledger_hand_out("hz_ledger_outputs_dev", l, dev, l ? &l->have_outputs : nullptr, "hz_ledger_apply_l2", l ? l->out_dev.a : nullptr, HZ_LEDGER_ARRAYS);
 }
 
 // the argument checks of the signed calls beyond those of the transactions; a NOP's entry is not looked at. verify == false
@@ -972,450 +977,6 @@ static hz_status ledger_sig_copy_out(hz_ledger* l, size_t m, const hz_ledger_sig
     return HZ_OK;
 }
 
-// hz_ledger_apply_l2 (sigs == nullptr), hz_ledger_apply_l2_signed and, with eff_txs, hz_ledger_apply_l2_addr: the caller has checked the
-// arguments; eff_txs are the transactions with the effective receivers, which the plan is made of, while txs -- the signed ones, to_idx
-// == 0 where the receiver is named by address -- are what the kernels see; sigs are uploaded for their destination fields whether or
-// not they are verified. With an L1 run in front (hz_ledger_apply_batch; the caller has checked it too) the batch has R = n_l1 + m rows:
-// every per-transaction table, kernel and output below is per row, while sigs, sig_out and the signature kernels keep to the m L2 rows
-static hz_status ledger_apply(hz_ledger* l, const char* who, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, bool with_sigs, uint32_t chain_id,
-                              uint32_t current_num_batch, size_t F, const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs, size_t n_sib, const hz_ledger_out* out,
-                              const hz_ledger_sig_out* sig_out, const hz_l2tx* eff_txs = nullptr, uint8_t* aux_to_idx_out = nullptr, const LedgerL1Run& run = LedgerL1Run()) {
-    const size_t n_l1 = run.n;
-    const hz_l1tx* l1 = run.tx;
-    static_assert(sizeof(hz_ledger_out) == HZ_LEDGER_ARRAYS * sizeof(uint8_t*), "hz_ledger_out is an array of pointers");
-    if (hz_status e = ledger_ready(l, who)) return e;
-    ledger_exit_reset(l);
-    const bool growing = l->smt != nullptr;
-    if (hz_status e = ledger_n_sib(l, who, n_sib)) return e;
-    // N is the plane stride; a growing ledger's tree hands out siblings zero-padded to n_sib, so the gather reads all of them
-    const uint32_t N = l->N, k = growing ? (uint32_t)n_sib : l->k;
-    LedgerPlan& p = l->plan;
-    const bool by_addr = eff_txs != nullptr;
-    if (by_addr) {
-        ledger_plan_rows(n_l1, l1, m, eff_txs, F, fee_plan_tokens, fee_idxs, run.exits, p);
-    } else {
-        if (hz_status e = ledger_check_plan(who, m, txs, F, fee_plan_tokens, fee_idxs, l->live, l->first_idx, p)) return e;
-        if (with_sigs)
-            if (hz_status e = ledger_check_sigs(who, m, txs, sigs, chain_id)) return e;
-    }
-    ledger_forget(l);
-    const size_t R = n_l1 + m;
-    const uint32_t m32 = (uint32_t)m, R32 = (uint32_t)R, L32 = (uint32_t)n_l1, F32 = (uint32_t)F, S = (uint32_t)n_sib;
-    const uint32_t M = (uint32_t)p.account.size(), G = (uint32_t)p.seg_start.size() - 1, n_slots = (uint32_t)p.slot_account.size();
-    const uint32_t n_chunks = R32 ? (R32 + HZ_LEDGER_CHUNK - 1) / HZ_LEDGER_CHUNK : 1u;
-    const uint32_t X = (uint32_t)p.exit_row.size(), GX = (uint32_t)p.exit_seg_start.size() - 1;   // exit operations, exit keys
-    HZ_HIP(hipSetDevice(l->device));
-    hipStream_t s = ledger_stream(l);
-    // the exit tree's plan comes first: a leaf it cannot hold refuses the call before anything is launched, and the pack kernel's
-    // integers are the planner's
-    SmtCallBufs xb{};
-    LedgerExitGuard exit_guard;
-    if (X) {
-        if (hz_status e = smt_apply_prepare(l->exit, who, HZ_ERR_ARG, X, p.exit_key.data(), (uint32_t)n_sib, true, &xb)) return e;
-        exit_guard.t = l->exit;
-    }
-
-    // ---- integer tables, one pinned block
-    Carve c;
-    const size_t o_tx = c.take(R * sizeof(hz_l2tx)), o_pos_s = c.take(R * 4), o_pos_r = c.take(R * 4), o_ev_s = c.take(R * 4), o_ev_r = c.take(R * 4),
-                 o_slot = c.take(R * 4), o_last = c.take((R + F) * 4), o_ev_fee = c.take(F * 4), o_pos_fee = c.take(F * 4), o_plan = c.take(F * 4),
-                 o_acct = c.take((size_t)M * 4), o_pos = c.take((size_t)M * sizeof(LedgerPos)), o_seg = c.take(((size_t)G + 1) * 4),
-                 o_l1 = c.take(n_l1 * sizeof(LedgerL1Dev)), o_slot_acct = c.take((size_t)n_slots * 4), o_ev_x = c.take(X ? R * 4 : 0),
-                 o_pos_x = c.take(X ? R * 4 : 0), o_last_x = c.take(X ? R * 4 : 0), o_xpos = c.take((size_t)X * sizeof(LedgerExitPos)),
-                 o_xseg = c.take(X ? ((size_t)GX + 1) * 4 : 0), o_xop = c.take((size_t)X * sizeof(LedgerExitOp)),
-                 o_crow = c.take(run.creates ? R * sizeof(LedgerCreateRow) : 0);
-    const size_t ints_bytes = c.end;   // (G + 1 >= 1: never empty)
-    HZ_HIP(l->h_ints.grow(ints_bytes));
-    uint8_t* hb = (uint8_t*)l->h_ints.p;
-    std::vector<uint32_t> pos_of(M);
-    for (uint32_t q = 0; q < M; q++) pos_of[p.perm[q]] = q;
-    std::vector<uint32_t> xpos_of(X);
-    for (uint32_t q = 0; q < X; q++) xpos_of[p.exit_perm[q]] = q;
-    for (size_t i = 0; i < n_l1; i++) {   // an L1 row as the per-row kernels read it (token_id, to_idx), and as k_ledger_l1 does
-        hz_l2tx row{};
-        row.from_idx = l1[i].from_idx;
-        row.to_idx = l1[i].to_idx;
-        row.amount_f = l1[i].amount_f;
-        row.token_id = l1[i].token_id;
-        ((hz_l2tx*)(hb + o_tx))[i] = row;
-        LedgerL1Dev d{};
-        d.amount_f = l1[i].amount_f;
-        d.load_amount_f = l1[i].load_amount_f;
-        d.token_id = l1[i].token_id;
-        d.acct_s = (uint32_t)(l1[i].from_idx - l->first_idx);
-        d.slot_s = (uint16_t)p.l1_slot_sender[i];
-        d.pos_s = (int32_t)pos_of[p.ev_sender[i]];
-        d.pos_r = -1;
-        d.slot_r = HZ_L1_NO_SLOT;
-        d.pos_x = p.ev_exit[i] >= 0 ? (int32_t)xpos_of[p.ev_exit[i]] : -1;
-        if (p.ev_receiver[i] >= 0) {
-            d.acct_r = (uint32_t)(l1[i].to_idx - l->first_idx);
-            d.slot_r = (uint16_t)p.l1_slot_receiver[i];
-            d.pos_r = (int32_t)pos_of[p.ev_receiver[i]];
-        }
-        memcpy(d.from_eth, l1[i].from_eth_addr, 20);
-        ((LedgerL1Dev*)(hb + o_l1))[i] = d;
-    }
-    for (uint32_t q = 0; q < n_slots; q++) ((uint32_t*)(hb + o_slot_acct))[q] = (uint32_t)(p.slot_account[q] - l->first_idx);
-    if (m) memcpy(hb + o_tx + n_l1 * sizeof(hz_l2tx), txs, m * sizeof(hz_l2tx));
-    for (size_t i = 0; i < R; i++) {
-        ((int32_t*)(hb + o_pos_s))[i] = p.ev_sender[i] >= 0 ? (int32_t)pos_of[p.ev_sender[i]] : -1;
-        ((int32_t*)(hb + o_pos_r))[i] = p.ev_receiver[i] >= 0 ? (int32_t)pos_of[p.ev_receiver[i]] : -1;
-        ((int32_t*)(hb + o_ev_s))[i] = p.ev_sender[i];
-        ((int32_t*)(hb + o_ev_r))[i] = p.ev_receiver[i];
-        ((int32_t*)(hb + o_slot))[i] = p.fee_slot[i];
-        ((int32_t*)(hb + o_last))[i] = p.last_event[i];
-    }
-    for (size_t j = 0; j < F; j++) {
-        ((int32_t*)(hb + o_last))[R + j] = p.last_event_fee[j];
-        ((int32_t*)(hb + o_ev_fee))[j] = p.ev_fee[j];
-        ((int32_t*)(hb + o_pos_fee))[j] = p.ev_fee[j] >= 0 ? (int32_t)pos_of[p.ev_fee[j]] : -1;
-        ((uint32_t*)(hb + o_plan))[j] = fee_plan_tokens[j];
-    }
-    for (uint32_t e = 0; e < M; e++) ((uint32_t*)(hb + o_acct))[e] = (uint32_t)(p.account[e] - l->first_idx);
-    for (uint32_t q = 0; q < M; q++) {
-        const uint32_t e = p.perm[q];
-        ((LedgerPos*)(hb + o_pos))[q] = LedgerPos{e, p.unit[e], p.kind[e], (uint32_t)(p.account[e] - l->first_idx)};
-    }
-    for (uint32_t g = 0; g <= G; g++) ((uint32_t*)(hb + o_seg))[g] = p.seg_start[g];
-    if (X) {
-        for (size_t i = 0; i < R; i++) {
-            ((int32_t*)(hb + o_ev_x))[i] = p.ev_exit[i];
-            ((int32_t*)(hb + o_pos_x))[i] = p.ev_exit[i] >= 0 ? (int32_t)xpos_of[p.ev_exit[i]] : -1;
-            ((int32_t*)(hb + o_last_x))[i] = p.last_exit[i];
-        }
-        for (uint32_t q = 0; q < X; q++) {
-            const uint32_t x = p.exit_perm[q];
-            ((LedgerExitPos*)(hb + o_xpos))[q] = LedgerExitPos{x, p.exit_row[x], (uint32_t)(p.exit_key[x] - l->first_idx)};
-        }
-        for (uint32_t x = 0; x < X; x++)
-            ((LedgerExitOp*)(hb + o_xop))[x] = LedgerExitOp{xb.old_key[x], (uint32_t)(p.exit_key[x] - l->first_idx),
-                                                            (xb.fnc[x] ? EXIT_OP_INSERT : 0u) | (xb.is_old0[x] ? EXIT_OP_IS_OLD0 : 0u)};
-        for (uint32_t g = 0; g <= GX; g++) ((uint32_t*)(hb + o_xseg))[g] = p.exit_seg_start[g];
-    }
-
-    // ---- device buffers: work = fee[m] | chunk sums | delta[M] | before[M][2] | failure word | exit amounts[X] | exit before[X][2];
-    // outs = the 27 arrays; exit_outs = the six exit arrays
-    size_t w = 0;
-    const size_t w_fee = w;
-    w += (size_t)(R32 ? R32 : 1) * 32;
-    const size_t w_chunk = w;
-    w += (size_t)n_chunks * (F32 ? F32 : 1) * 32;
-    const size_t w_delta = w;
-    w += (size_t)(M ? M : 1) * 32;
-    const size_t w_before = w;
-    w += (size_t)(M ? M : 1) * 64;
-    const size_t w_fail = w;
-    w += 64;
-    const size_t w_xamt = w;
-    w += (size_t)X * 32;
-    const size_t w_xbefore = w;
-    w += (size_t)X * 64;
-    size_t elems[HZ_LEDGER_ARRAYS];
-    for (int a = 0; a < HZ_LEDGER_ARRAYS; a++) elems[a] = a < LO_TX3 ? R : F;
-    elems[LO_SIB1] = elems[LO_SIB2] = R * n_sib;
-    elems[LO_ACC_FEE] = R * F;
-    elems[LO_SIB3] = F * n_sib;
-    elems[LO_OLD_ROOT] = elems[LO_NEW_ROOT] = 1;
-    size_t out_bytes = 0;
-    for (int a = 0; a < HZ_LEDGER_ARRAYS; a++) out_bytes += elems[a] * 32;
-    HZ_HIP(l->ints.grow(ints_bytes));
-    HZ_HIP(l->work.grow(w));
-    HZ_HIP(l->outs.grow(out_bytes));
-    const size_t exit_out_bytes = ((size_t)(HZ_LEDGER_EXIT_ARRAYS - 1) * R + 1) * 32;   // five arrays per row, the new exit root
-    uint8_t* xd[HZ_LEDGER_EXIT_ARRAYS] = {};
-    const size_t create_out_bytes = ((size_t)(HZ_LEDGER_CREATE_ARRAYS - 1) * R + 1) * 32;   // five arrays per row, the new last idx
-    LedgerCreateOutDev cd{};
-    if (run.creates) {
-        HZ_HIP(l->create_outs.grow(create_out_bytes));
-        for (int a = 0; a < HZ_LEDGER_CREATE_ARRAYS; a++) cd.a[a] = (uint8_t*)l->create_outs.p + (size_t)a * R * 32;
-    }
-    if (run.exits) {
-        HZ_HIP(l->exit_outs.grow(exit_out_bytes));
-        HZ_HIP(l->exit_final.grow((size_t)4 * (GX ? GX : 1) * 32));
-        for (int a = 0; a < HZ_LEDGER_EXIT_ARRAYS; a++) xd[a] = (uint8_t*)l->exit_outs.p + (size_t)a * R * 32;
-    }
-    LedgerOutDev od;
-    {
-        uint8_t* at = (uint8_t*)l->outs.p;
-        for (int a = 0; a < HZ_LEDGER_ARRAYS; a++) {
-            od.a[a] = at;
-            at += elems[a] * 32;
-        }
-    }
-    uint8_t* db = (uint8_t*)l->ints.p;
-    uint8_t* wb = (uint8_t*)l->work.p;
-    const hz_l2tx* d_txs = (const hz_l2tx*)(db + o_tx);
-    const LedgerPos* d_pos = (const LedgerPos*)(db + o_pos);
-    const uint32_t* d_seg = (const uint32_t*)(db + o_seg);
-    uint32_t* d_fail = (uint32_t*)(wb + w_fail);
-
-    // the state tree's update: hz_state's on a dense ledger; on a growing one hz_smt's, whose planner turns the first event of a key the
-    // tree does not hold -- a create row's sender event -- into an INSERT and refuses a leaf at depth >= n_sib before anything of the
-    // update is launched
-    StateCallBufs tb{};
-    SmtCallBufs sb{};
-    LedgerExitGuard tree_guard;
-    if (M && growing) {
-        if (hz_status e = smt_apply_prepare(l->smt, who, HZ_ERR_ARG, M, p.account.data(), S, true, &sb)) return e;
-        tree_guard.t = l->smt;
-        tb.fields = sb.fields;
-        tb.siblings = sb.siblings;
-        tb.old_value = sb.old_value;
-        tb.old_root = sb.roots;
-        tb.new_root = sb.roots + 32;
-    } else if (M) {
-        if (hz_status e = state_apply_prepare(l->tree, M, p.account.data(), S, &tb)) return e;
-    }
-    const uint64_t new_last = l->first_idx + l->live + run.n_creates - 1;
-    if (run.creates)
-        for (size_t i = 0; i < R; i++) {   // the create arrays' integers: the running index, and what the tree's planner says of the insert
-            LedgerCreateRow row{};
-            row.idx_after = i < n_l1 ? run.idx_after[i] : new_last;
-            row.ev = p.ev_sender[i];
-            if (i < n_l1 && run.aux_from[i]) {
-                row.aux_from = run.aux_from[i];
-                row.old_key = sb.old_key[row.ev];
-                row.flags = CREATE_ROW | (sb.is_old0[row.ev] ? CREATE_IS_OLD0 : 0u);
-            }
-            ((LedgerCreateRow*)(hb + o_crow))[i] = row;
-        }
-    HZ_HIP(hipMemcpyAsync(l->ints.p, l->h_ints.p, ints_bytes, hipMemcpyHostToDevice, s));
-    HZ_HIP(hipMemsetAsync(d_fail, 0xFF, 4, s));
-    if (with_sigs || by_addr)
-        if (hz_status e = ledger_sig_prepare(l, m, sigs, s, with_sigs)) return e;
-    const hz_l2sig* d_dest = by_addr ? (const hz_l2sig*)l->sig_in.p : nullptr;   // the signed destinations, for reasons 10 and 11 and the zero-amount rows
-    if (by_addr) HZ_HIP(l->aux_rows.grow((R ? R : 1) * 32));
-    const bool links = run.rq != nullptr && m != 0;   // (an atomic call comes through ledger_apply_addr: sigs are uploaded, the three arrays have room)
-    LedgerDrain drain;
-    if (links) {
-        drain.s = s;
-        drain.armed = true;
-        if (hz_status e = ledger_rq_upload(l, m, run.rq, s)) return e;
-    }
-    if (run.is_batch) HZ_HIP(l->l1_flags.grow(n_l1 ? n_l1 : 1));
-
-    // ---- the semantic kernels
-    HZ_HIP(hipEventRecord(l->e0, s));
-    if (R32) {
-        hipLaunchKernelGGL(k_ledger_tx, dim3((R32 + 63) / 64), dim3(64), 0, s, d_txs, (const int32_t*)(db + o_pos_s), (const int32_t*)(db + o_pos_r), wb + w_fee,
-                           wb + w_delta, X ? (const int32_t*)(db + o_pos_x) : (const int32_t*)nullptr, wb + w_xamt, d_fail, R32, L32);
-        HZ_HIP(hipGetLastError());
-    }
-    if (L32) {   // the deltas of the L1 events, beside those k_ledger_tx wrote: one workgroup, no synchronise of its own
-        HZ_HIP(hipEventRecord(l->el0, s));
-        hipLaunchKernelGGL(k_ledger_l1, dim3(1), dim3(256), 0, s, (const LedgerL1Dev*)(db + o_l1), (const uint32_t*)(db + o_slot_acct), (const uint8_t*)l->planes.p,
-                           wb + w_delta, wb + w_xamt, (uint8_t*)l->l1_flags.p, N, L32, n_slots);
-        HZ_HIP(hipGetLastError());
-        HZ_HIP(hipEventRecord(l->el1, s));
-    }
-    if (F32) {
-        hipLaunchKernelGGL(k_ledger_fee_sum, dim3(n_chunks), dim3(64), 0, s, (const uint8_t*)(wb + w_fee), (const int32_t*)(db + o_slot), wb + w_chunk, R32, F32);
-        HZ_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_ledger_fee_scan, dim3(n_chunks), dim3(64), 0, s, (const uint8_t*)(wb + w_fee), (const int32_t*)(db + o_slot),
-                           (const uint8_t*)(wb + w_chunk), (const int32_t*)(db + o_pos_fee), od.a[LO_ACC_FEE], od.a[LO_FINAL_FEE], wb + w_delta, R32, F32, n_chunks);
-        HZ_HIP(hipGetLastError());
-    }
-    if (G) {
-        hipLaunchKernelGGL(k_ledger_scan, dim3((G + 63) / 64), dim3(64), 0, s, d_pos, d_seg, d_txs, d_dest, (const uint32_t*)(db + o_plan), (const uint8_t*)(wb + w_delta),
-                           (const uint8_t*)l->planes.p, wb + w_before, tb.fields, d_fail, N, G, R32, L32);
-        HZ_HIP(hipGetLastError());
-    }
-    if (X) {   // the exit leaves: it reads the amounts k_ledger_tx and k_ledger_l1 left and the planes, and writes per-call buffers only
-        HZ_HIP(hipEventRecord(l->ex0, s));
-        hipLaunchKernelGGL(k_ledger_exit_scan, dim3((GX + 63) / 64), dim3(64), 0, s, (const LedgerExitPos*)(db + o_xpos), (const uint32_t*)(db + o_xseg),
-                           (const uint8_t*)(wb + w_xamt), (const uint8_t*)l->planes.p, wb + w_xbefore, xb.fields, (uint8_t*)l->exit_final.p, d_fail, N, GX);
-        HZ_HIP(hipGetLastError());
-        HZ_HIP(hipEventRecord(l->ex1, s));
-    }
-    if (with_sigs) {   // they read the planes and the uploads only: any place before the failure-word read would do
-        HZ_HIP(hipEventRecord(l->es0, s));
-        HZ_HIP(launch_ledger_sig(d_txs + n_l1, (const hz_l2sig*)l->sig_in.p, chain_id, current_num_batch, l->sig_dev[0], l->sig_dev[1], l->sig_dev[2],
-                                 (const uint8_t*)l->planes.p, l->b8_table.p, N, l->first_idx, d_fail, nullptr, m32, s, L32, links ? (const uint8_t*)l->rq_in.p : nullptr));
-        HZ_HIP(hipEventRecord(l->es1, s));
-    }
-    if (links) {   // reason 13, verified or not: the V2 rows are the message kernel's, or those of its packing alone
-        if (!with_sigs) HZ_HIP(launch_ledger_sig_v2(d_txs + n_l1, (const hz_l2sig*)l->sig_in.p, l->sig_dev[1], m32, s));
-        HZ_HIP(hipEventRecord(l->eq0, s));
-        HZ_HIP(launch_ledger_rq(d_txs + n_l1, (const hz_l2sig*)l->sig_in.p, (const uint8_t*)l->rq_in.p, (const uint8_t*)l->sig_dev[1], d_fail, nullptr, m32, L32, s, L32));
-        HZ_HIP(hipEventRecord(l->eq1, s));
-    }
-    HZ_HIP(hipEventRecord(l->e1, s));
-    HZ_HIP(hipMemcpyAsync(l->h_fail.p, d_fail, 4, hipMemcpyDeviceToHost, s));
-    HZ_HIP(hipStreamSynchronize(s));   // the one round trip: nothing resident has been written yet
-    drain.armed = false;
-    if (links) {
-        float rq_ms = 0;
-        HZ_HIP(hipEventElapsedTime(&rq_ms, l->eq0, l->eq1));
-        l->rq_ms = rq_ms;
-    }
-    const uint32_t word = *(const uint32_t*)l->h_fail.p;
-    if (word != 0xFFFFFFFFu) {
-        const uint32_t unit = word >> 8, reason = word & 0xFFu;
-        if (unit >= R32)
-            return set_err(HZ_ERR_INPUT, "%s: refused at index %u (fee slot %u), reason %u: %s", who, unit, unit - R32, reason, LEDGER_REASON[reason < HZ_LEDGER_REASONS ? reason : 0]);
-        if (L32)
-            return set_err(HZ_ERR_INPUT, "%s: refused at index %u (%s transaction %u), reason %u: %s", who, unit, unit < L32 ? "L1" : "L2", unit < L32 ? unit : unit - L32,
-                           reason, LEDGER_REASON[reason < HZ_LEDGER_REASONS ? reason : 0]);
-        return set_err(HZ_ERR_INPUT, "%s: refused at index %u (transaction %u), reason %u: %s", who, unit, unit, reason, LEDGER_REASON[reason < HZ_LEDGER_REASONS ? reason : 0]);
-    }
-
-    // ---- outputs, tree, resident planes
-    if (X) {   // the exit tree's update depends on the scan alone: on its own stream, beside everything below
-        HZ_HIP(hipStreamWaitEvent(smt_stream(l->exit), l->ex1, 0));
-        if (hz_status e = smt_apply_launch(l->exit, X, S, true)) return e;
-        HZ_HIP(hipEventRecord(l->ex_tree, smt_stream(l->exit)));
-    }
-    if (run.exits) HZ_HIP(hipMemsetAsync(l->exit_outs.p, 0, exit_out_bytes, s));
-    if (R32 + F32) {
-        hipLaunchKernelGGL(k_ledger_pack, dim3((R32 + F32 + 63) / 64), dim3(64), 0, s, od, d_txs, d_dest, (uint8_t*)l->aux_rows.p, l->first_idx, (const int32_t*)(db + o_ev_s),
-                           (const int32_t*)(db + o_ev_r), (const int32_t*)(db + o_ev_fee), (const uint32_t*)(db + o_acct), (const uint8_t*)(wb + w_before), (const uint8_t*)l->planes.p, N, R32, F32, L32);
-        HZ_HIP(hipGetLastError());
-    }
-    const uint8_t* root0 = nullptr;
-    if (M) {
-        if (hz_status e = growing ? smt_apply_launch(l->smt, M, S, true) : state_apply_launch(l->tree, M, S, false)) return e;
-        root0 = tb.old_root;
-    } else if (growing) {   // no update at all: the root as it stands, through the host
-        uint8_t r32[32];
-        if (hz_status e = hz_smt_root(l->smt, r32)) return e;
-        HZ_HIP(hipMemcpy(l->root_buf.p, r32, 32, hipMemcpyHostToDevice));
-        root0 = (const uint8_t*)l->root_buf.p;
-    } else {
-        root0 = state_root_dev(l->tree);
-    }
-    if (run.creates) {   // behind the tree's update: oldValue1 is its old-value buffer's
-        HZ_HIP(hipEventRecord(l->ec2, s));
-        hipLaunchKernelGGL(k_ledger_create_pack, dim3((R32 + 64) / 64), dim3(64), 0, s, cd, (const LedgerCreateRow*)(db + o_crow), (const uint8_t*)tb.old_value, new_last, R32);
-        HZ_HIP(hipGetLastError());
-        HZ_HIP(hipEventRecord(l->ec3, s));
-    }
-    HZ_HIP(hipMemcpyAsync(od.a[LO_OLD_ROOT], root0, 32, hipMemcpyDeviceToDevice, s));
-    HZ_HIP(hipMemcpyAsync(od.a[LO_NEW_ROOT], M ? tb.new_root + (size_t)(M - 1) * 32 : root0, 32, hipMemcpyDeviceToDevice, s));
-    if (R32 + F32) {
-        const size_t threads = (size_t)(R32 + F32) * (S + 1);
-        hipLaunchKernelGGL(k_ledger_gather, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, od, (const int32_t*)(db + o_ev_s), (const int32_t*)(db + o_ev_r),
-                           (const int32_t*)(db + o_ev_fee), (const int32_t*)(db + o_last), (const uint8_t*)tb.siblings, (const uint8_t*)tb.new_root, root0, k, S, R32,
-                           F32);
-        HZ_HIP(hipGetLastError());
-    }
-    if (G) {
-        hipLaunchKernelGGL(k_ledger_writeback, dim3((G + 63) / 64), dim3(64), 0, s, d_pos, d_seg, (const uint8_t*)tb.fields, (uint8_t*)l->planes.p, N, G);
-        HZ_HIP(hipGetLastError());
-    }
-    if (X) {   // the exit rows, once the exit tree's update is through: leaf-2 rows and siblings2 over what k_ledger_pack / _gather left there
-        LedgerExitOutDev xo;
-        for (int q = 0; q < 6; q++) xo.tx2[q] = od.a[LO_TX2 + q];
-        xo.sib2 = od.a[LO_SIB2];
-        for (int a = 0; a < HZ_LEDGER_EXIT_ARRAYS; a++) xo.x[a] = xd[a];
-        HZ_HIP(hipStreamWaitEvent(s, l->ex_tree, 0));
-        HZ_HIP(hipEventRecord(l->ex2, s));
-        hipLaunchKernelGGL(k_ledger_exit_pack, dim3((R32 + 63) / 64), dim3(64), 0, s, xo, (const int32_t*)(db + o_ev_x), (const LedgerExitOp*)(db + o_xop),
-                           (const uint8_t*)(wb + w_xbefore), (const uint8_t*)xb.old_value, (const uint8_t*)l->planes.p, N, R32);
-        HZ_HIP(hipGetLastError());
-        const size_t threads = (size_t)R32 * (S + 1);
-        hipLaunchKernelGGL(k_ledger_exit_gather, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, xo, (const int32_t*)(db + o_ev_x),
-                           (const int32_t*)(db + o_last_x), (const uint8_t*)xb.siblings, (const uint8_t*)xb.roots, S, R32);
-        HZ_HIP(hipGetLastError());
-        HZ_HIP(hipMemcpyAsync(xd[XO_NEW_ROOT], xb.roots + (size_t)X * 32, 32, hipMemcpyDeviceToDevice, s));
-        HZ_HIP(hipEventRecord(l->ex3, s));
-    }
-    HZ_HIP(hipEventRecord(l->e2, s));
-    if (run.create_out) {
-        uint8_t* const* h = (uint8_t* const*)run.create_out;
-        for (int a = 0; a < HZ_LEDGER_CREATE_ARRAYS; a++) {
-            const size_t rows = a == CO_NEW_LAST ? 1 : R;
-            if (h[a] && rows) HZ_HIP(hipMemcpyAsync(h[a], cd.a[a], rows * 32, hipMemcpyDeviceToHost, s));
-        }
-    }
-    if (run.exit_out) {
-        uint8_t* const* h = (uint8_t* const*)run.exit_out;
-        for (int a = 0; a < HZ_LEDGER_EXIT_ARRAYS; a++) {
-            const size_t rows = a == XO_NEW_ROOT ? 1 : R;
-            if (h[a] && rows) HZ_HIP(hipMemcpyAsync(h[a], xd[a], rows * 32, hipMemcpyDeviceToHost, s));
-        }
-    }
-    if (out) {
-        uint8_t* const* h = (uint8_t* const*)out;
-        for (int a = 0; a < HZ_LEDGER_ARRAYS; a++)
-            if (h[a] && elems[a]) HZ_HIP(hipMemcpyAsync(h[a], od.a[a], elems[a] * 32, hipMemcpyDeviceToHost, s));
-    }
-    if (with_sigs)
-        if (hz_status e = ledger_sig_copy_out(l, m, sig_out, s)) return e;
-    if (by_addr && aux_to_idx_out && R) HZ_HIP(hipMemcpyAsync(aux_to_idx_out, l->aux_rows.p, R * 32, hipMemcpyDeviceToHost, s));
-    if (run.flags_out && n_l1) HZ_HIP(hipMemcpyAsync(run.flags_out, l->l1_flags.p, n_l1, hipMemcpyDeviceToHost, s));
-    if (M && growing) {
-        tree_guard.t = nullptr;
-        if (hz_status e = smt_apply_finish(l->smt)) {
-            smt_apply_abort(l->smt);
-            return e;
-        }
-        l->live += run.n_creates;   // the tree holds them: from here the created accounts exist
-    } else if (M) {
-        if (hz_status e = state_apply_finish(l->tree)) return e;
-    } else {
-        HZ_HIP(hipStreamSynchronize(s));
-    }
-    float ms = 0;
-    if (X) {
-        exit_guard.t = nullptr;
-        if (hz_status e = smt_apply_finish(l->exit)) {
-            smt_apply_abort(l->exit);
-            return e;
-        }
-        l->exit_ms = hz_smt_device_ms(l->exit);
-        HZ_HIP(hipEventElapsedTime(&ms, l->ex0, l->ex1));
-        l->exit_ms += ms;
-        HZ_HIP(hipEventElapsedTime(&ms, l->ex2, l->ex3));
-        l->exit_ms += ms;
-        for (uint32_t g = 0; g < GX; g++) l->exit_keys.push_back({p.exit_key[p.exit_perm[p.exit_seg_start[g]]], g});
-        std::sort(l->exit_keys.begin(), l->exit_keys.end());
-    }
-    if (run.exits) {
-        for (int a = 0; a < HZ_LEDGER_EXIT_ARRAYS; a++) l->exit_dev[a] = xd[a];
-        l->have_exit_outputs = true;
-    }
-    HZ_HIP(hipEventElapsedTime(&ms, l->e0, l->e1));
-    l->semantic_ms = ms;
-    HZ_HIP(hipEventElapsedTime(&ms, l->e0, l->e2));
-    l->device_ms = ms;
-    l->out_dev = od;
-    l->have_outputs = true;
-    l->have_aux = by_addr;
-    l->have_l1 = run.is_batch;
-    if (run.creates) {
-        for (int a = 0; a < HZ_LEDGER_CREATE_ARRAYS; a++) l->create_dev[a] = cd.a[a];
-        l->have_create_outputs = true;
-        HZ_HIP(hipEventElapsedTime(&ms, l->ec2, l->ec3));
-        l->create_ms = ms;
-        if (run.n_creates) {
-            HZ_HIP(hipEventElapsedTime(&ms, l->ec0, l->ec1));
-            l->create_ms += ms;
-        }
-    }
-    if (L32) {
-        HZ_HIP(hipEventElapsedTime(&ms, l->el0, l->el1));
-        l->l1_ms = ms;
-    }
-    if (with_sigs) {
-        HZ_HIP(hipEventElapsedTime(&ms, l->es0, l->es1));
-        l->sig_ms = ms;
-        l->have_sig_outputs = true;
-    }
-    return HZ_OK;
-}
-
-extern "C" hz_status hz_ledger_apply_l2(hz_ledger* l, size_t m, const hz_l2tx* txs, size_t F, const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs,
-                                        size_t n_sib, const hz_ledger_out* out) {
-    return ledger_apply(l, "hz_ledger_apply_l2", m, txs, nullptr, false, 0, 0, F, fee_plan_tokens, fee_idxs, n_sib, out, nullptr);
-}
-
-extern "C" hz_status hz_ledger_apply_l2_signed(hz_ledger* l, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, uint32_t chain_id, uint32_t current_num_batch,
-                                               size_t F, const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs, size_t n_sib, const hz_ledger_out* out,
-                                               const hz_ledger_sig_out* sig_out) {
-    return ledger_apply(l, "hz_ledger_apply_l2_signed", m, txs, sigs, true, chain_id, current_num_batch, F, fee_plan_tokens, fee_idxs, n_sib, out, sig_out);
-}
-
 // hz_ledger_verify_l2, and hz_ledger_verify_l2_atomic with the links of the m transactions (rows 0 .. m - 1 of a batch without L1 rows)
 static hz_status ledger_verify(hz_ledger* l, const char* who, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, const hz_l2rq* rq, uint32_t chain_id,
                                uint32_t current_num_batch, uint8_t* verdict_out, const hz_ledger_sig_out* sig_out) {
@@ -1438,28 +999,23 @@ static hz_status ledger_verify(hz_ledger* l, const char* who, size_t m, const hz
     HZ_HIP(l->ints.grow((m ? m : 1) * sizeof(hz_l2tx)));
     if (m) HZ_HIP(hipMemcpyAsync(l->ints.p, txs, m * sizeof(hz_l2tx), hipMemcpyHostToDevice, s));
     if (hz_status e = ledger_sig_prepare(l, m, sigs, s)) return e;
-    HZ_HIP(hipEventRecord(l->es0, s));
+    HZ_HIP(l->t_sig.begin(s));
     HZ_HIP(launch_ledger_sig((const hz_l2tx*)l->ints.p, (const hz_l2sig*)l->sig_in.p, chain_id, current_num_batch, l->sig_dev[0], l->sig_dev[1], l->sig_dev[2],
                              (const uint8_t*)l->planes.p, l->b8_table.p, l->N, l->first_idx, nullptr, l->verdict_dev, (uint32_t)m, s, 0,
                              links ? (const uint8_t*)l->rq_in.p : nullptr));
-    HZ_HIP(hipEventRecord(l->es1, s));
+    HZ_HIP(l->t_sig.end(s));
     if (links) {   // behind both signature kernels: 13 goes where the verdict is still 0
-        HZ_HIP(hipEventRecord(l->eq0, s));
+        HZ_HIP(l->t_rq.begin(s));
         HZ_HIP(launch_ledger_rq((const hz_l2tx*)l->ints.p, (const hz_l2sig*)l->sig_in.p, (const uint8_t*)l->rq_in.p, (const uint8_t*)l->sig_dev[1], nullptr, l->verdict_dev,
                                 (uint32_t)m, 0, s, 0));
-        HZ_HIP(hipEventRecord(l->eq1, s));
+        HZ_HIP(l->t_rq.end(s));
     }
     if (m) HZ_HIP(hipMemcpyAsync(verdict_out, l->verdict_dev, m, hipMemcpyDeviceToHost, s));
     if (hz_status e = ledger_sig_copy_out(l, m, sig_out, s)) return e;
     HZ_HIP(hipStreamSynchronize(s));
     drain.armed = false;
-    float ms = 0;
-    HZ_HIP(hipEventElapsedTime(&ms, l->es0, l->es1));
-    l->sig_ms = ms;
-    if (links) {
-        HZ_HIP(hipEventElapsedTime(&ms, l->eq0, l->eq1));
-        l->rq_ms = ms;
-    }
+    HZ_HIP(l->t_sig.read(l->sig_ms));
+    if (links) HZ_HIP(l->t_rq.read(l->rq_ms));
     l->have_sig_outputs = true;
     return HZ_OK;
 }
@@ -1470,13 +1026,9 @@ extern "C" hz_status hz_ledger_verify_l2(hz_ledger* l, size_t m, const hz_l2tx* 
 }
 
 extern "C" hz_status hz_ledger_sig_outputs_dev(hz_ledger* l, hz_ledger_sig_out* dev) {
-    if (!l || !dev) return set_err(HZ_ERR_ARG, "hz_ledger_sig_outputs_dev: null argument");
-    if (!l->have_sig_outputs)
-        return set_err(HZ_ERR_ARG, "hz_ledger_sig_outputs_dev: no successful hz_ledger_apply_l2_signed / hz_ledger_verify_l2 since the ledger's last other call");
-    dev->tx_compressed_data = l->sig_dev[0];
-    dev->tx_compressed_data_v2 = l->sig_dev[1];
-    dev->sig_l2_hash = l->sig_dev[2];
-    return HZ_OK;
+    static_assert(sizeof(hz_ledger_sig_out) == 3 * sizeof(uint8_t*), "hz_ledger_sig_out is an array of pointers");
+    return ledger_hand_out("hz_ledger_sig_outputs_dev", l, dev, l ? &l->have_sig_outputs : nullptr, "hz_ledger_apply_l2_signed / hz_ledger_verify_l2",
+                           l ? l->sig_dev : nullptr, 3);
 }
 
 extern "C" double hz_ledger_sig_ms(const hz_ledger* l) { return l ? l->sig_ms : 0.0; }
@@ -1490,43 +1042,30 @@ static hz_status ledger_resolve(hz_ledger* l, size_t m, const hz_l2tx* txs, cons
     size_t queries = 0;
     for (size_t i = 0; i < m; i++) {
         out[i] = 0;
-        queries += txs[i].from_idx != 0 && txs[i].to_idx == 0 && !(skip_zero && ledger_mantissa(txs[i].amount_f) == 0);
+        queries += ResolveTables::asks(txs[i], skip_zero);
     }
     if (!queries) return HZ_OK;
     const uint32_t slots = resolve_slots(queries), m32 = (uint32_t)m;
-    Carve c;
-    const size_t o_table = c.take((size_t)slots * sizeof(ResolveKey)), o_result = c.take((size_t)slots * 4), o_slot = c.take(m * 4), up_bytes = c.end,
-                 o_out = c.take(m * 8);
+    ResolveTables T;
+    T.layout(slots, m);
     HZ_HIP(hipSetDevice(l->device));
-    HZ_HIP(l->h_res.grow(c.end));
-    HZ_HIP(l->res.grow(c.end));
-    uint8_t* hb = (uint8_t*)l->h_res.p;
-    uint8_t* db = (uint8_t*)l->res.p;
-    memset(hb + o_table, 0, (size_t)slots * sizeof(ResolveKey));
-    memset(hb + o_result, 0xFF, (size_t)slots * 4);
-    for (size_t i = 0; i < m; i++) {
-        int32_t slot = -1;
-        if (txs[i].from_idx != 0 && txs[i].to_idx == 0 && !(skip_zero && ledger_mantissa(txs[i].amount_f) == 0))
-            slot = resolve_insert((ResolveKey*)(hb + o_table), slots,
-                                  resolve_key(txs[i].token_id, resolve_load32(sigs[i].to_eth_addr), resolve_load32(sigs[i].to_bjj_ay), sigs[i].to_bjj_sign));
-        ((int32_t*)(hb + o_slot))[i] = slot;
-    }
+    HZ_HIP(l->h_res.grow(T.end));
+    HZ_HIP(l->res.grow(T.end));
+    void *hb = l->h_res.p, *db = l->res.p;
+    T.fill(hb, txs, sigs, skip_zero);
     hipStream_t s = ledger_stream(l);
-    HZ_HIP(hipMemcpyAsync(db, hb, up_bytes, hipMemcpyHostToDevice, s));
-    HZ_HIP(hipEventRecord(l->er0, s));
-    hipLaunchKernelGGL(k_ledger_resolve, dim3(((uint32_t)count + 255) / 256), dim3(256), 0, s, (const uint8_t*)l->planes.p, (const ResolveKey*)(db + o_table),
-                       (uint32_t*)(db + o_result), slots, l->N, (uint32_t)count);
+    HZ_HIP(hipMemcpyAsync(db, hb, T.up, hipMemcpyHostToDevice, s));
+    HZ_HIP(l->t_resolve.begin(s));
+    hipLaunchKernelGGL(k_ledger_resolve, dim3(((uint32_t)count + 255) / 256), dim3(256), 0, s, (const uint8_t*)l->planes.p, T.table.dev(db), T.result.dev(db), slots, l->N,
+                       (uint32_t)count);
     HZ_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_ledger_resolve_pick, dim3((m32 + 63) / 64), dim3(64), 0, s, (const int32_t*)(db + o_slot), (const uint32_t*)(db + o_result),
-                       (uint64_t*)(db + o_out), l->first_idx, m32);
+    hipLaunchKernelGGL(k_ledger_resolve_pick, dim3((m32 + 63) / 64), dim3(64), 0, s, T.slot.dev(db), T.result.dev(db), T.out.dev(db), l->first_idx, m32);
     HZ_HIP(hipGetLastError());
-    HZ_HIP(hipEventRecord(l->er1, s));
-    HZ_HIP(hipMemcpyAsync(hb + o_out, db + o_out, m * 8, hipMemcpyDeviceToHost, s));
+    HZ_HIP(l->t_resolve.end(s));
+    HZ_HIP(hipMemcpyAsync(T.out.host(hb), T.out.dev(db), T.out.bytes(), hipMemcpyDeviceToHost, s));
     HZ_HIP(hipStreamSynchronize(s));   // the round trip of the lookup: the planner needs the receivers
-    memcpy(out, hb + o_out, m * 8);
-    float ms = 0;
-    HZ_HIP(hipEventElapsedTime(&ms, l->er0, l->er1));
-    l->resolve_ms = ms;
+    memcpy(out, T.out.host(hb), T.out.bytes());
+    HZ_HIP(l->t_resolve.read(l->resolve_ms));
     return HZ_OK;
 }
 
@@ -1538,103 +1077,535 @@ extern "C" hz_status hz_ledger_resolve_l2(hz_ledger* l, size_t m, const hz_l2tx*
     return ledger_resolve(l, m, txs, sigs, false, aux_to_idx_out, l->live);
 }
 
-// k_ledger_create on the ledger's stream: every slot lies at or beyond the ledger's size and below its capacity (ledger_check_creates)
-static hz_status ledger_create_launch(hz_ledger* l, const LedgerL1Run& run) {
-    const uint32_t n = (uint32_t)run.n_creates;
+// ---- what the by_addr apply calls and hz_ledger_select_batch share: the checks and preparations before a plan can be made -----------------
+static hz_status ledger_check_flags(const char* who, uint32_t flags) {
+    if (flags & ~HZ_LEDGER_VERIFY_SIGS) return set_err(HZ_ERR_ARG, "%s: flags = %#x", who, flags);
+    return HZ_OK;
+}
+
+// the one wording of a refusal: a fee slot (unit >= R), a row of a batch with an L1 run (L1 != 0), else a transaction
+static hz_status ledger_refused(const char* who, size_t unit, uint32_t reason, size_t R, size_t L1) {
+    char what[64];
+    if (unit >= R)
+        snprintf(what, sizeof what, "fee slot %zu", unit - R);
+    else if (L1)
+        snprintf(what, sizeof what, "%s transaction %zu", unit < L1 ? "L1" : "L2", unit < L1 ? unit : unit - L1);
+    else
+        snprintf(what, sizeof what, "transaction %zu", unit);
+    return set_err(HZ_ERR_INPUT, "%s: refused at index %zu (%s), reason %u: %s", who, unit, what, reason, LEDGER_REASON[reason < HZ_LEDGER_REASONS ? reason : 0]);
+}
+
+// the argument checks of the L1 run; -> r.l1, the rows as the pipeline takes them, the events they make, the accounts the call makes
+static hz_status ledger_effective_l1(const hz_ledger* l, const char* who, size_t n_l1, const hz_l1tx* l1, const uint8_t* from_bjj, bool creates, bool exits, LedgerRows& r) {
+    r.l1 = l1;
+    if (creates) {
+        if (hz_status e = ledger_check_creates(who, l->smt != nullptr, l->N, l->first_idx, l->live, n_l1, l1, from_bjj, &r.l1_events, r.eff_l1, r.aux_from, r.idx_after, &r.n_creates))
+            return e;
+        r.l1 = r.eff_l1.data();
+    } else if (hz_status e = ledger_check_l1(who, n_l1, l1, l->first_idx, l->live, &r.l1_events, exits)) {
+        return e;
+    }
+    r.count = l->live + r.n_creates;
+    return HZ_OK;
+}
+
+// sigs == NULL without verification: no destination is signed, zero entries stand in (the link fields of such rows are V2 and two zeros)
+static hz_status ledger_stand_in_sigs(const char* who, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, bool verify, LedgerRows& r) {
+    r.sigs = sigs;
+    if (sigs || !m || verify) return HZ_OK;
+    for (size_t i = 0; i < m; i++)
+        if (txs[i].from_idx != 0 && txs[i].to_idx == 0) return set_err(HZ_ERR_ARG, "%s: null sigs with tx %zu to an address", who, i);
+    r.no_sigs.assign(m, hz_l2sig{});
+    r.sigs = r.no_sigs.data();
+    return HZ_OK;
+}
+
+// k_ledger_create on the ledger's stream, before everything else of the call, the lookup included: the new accounts' static fields into
+// their plane slots. Every slot lies at or beyond the ledger's size and below its capacity (ledger_check_creates)
+static hz_status ledger_create_launch(hz_ledger* l, size_t n_l1, const hz_l1tx* l1, const uint8_t* from_bjj, const LedgerRows& r) {
+    const uint32_t n = (uint32_t)r.n_creates;
     HZ_HIP(hipSetDevice(l->device));
     HZ_HIP(l->h_create.grow((size_t)n * sizeof(LedgerCreateDev)));
     HZ_HIP(l->create_in.grow((size_t)n * sizeof(LedgerCreateDev)));
     LedgerCreateDev* h = (LedgerCreateDev*)l->h_create.p;
     uint32_t q = 0;
-    for (size_t i = 0; i < run.n; i++) {
-        if (!run.aux_from[i]) continue;
+    for (size_t i = 0; i < n_l1; i++) {
+        if (!r.aux_from[i]) continue;
         LedgerCreateDev c{};
-        c.acct = (uint32_t)(run.aux_from[i] - l->first_idx);
-        c.token_id = run.tx[i].token_id;
-        memcpy(c.bjj, run.from_bjj + i * 32, 32);
-        memcpy(c.from_eth, run.tx[i].from_eth_addr, 20);
+        c.acct = (uint32_t)(r.aux_from[i] - l->first_idx);
+        c.token_id = l1[i].token_id;
+        memcpy(c.bjj, from_bjj + i * 32, 32);
+        memcpy(c.from_eth, l1[i].from_eth_addr, 20);
         h[q++] = c;
     }
     hipStream_t s = ledger_stream(l);
     HZ_HIP(hipMemcpyAsync(l->create_in.p, h, (size_t)n * sizeof(LedgerCreateDev), hipMemcpyHostToDevice, s));
-    HZ_HIP(hipEventRecord(l->ec0, s));
+    HZ_HIP(l->t_create.begin(s));
     hipLaunchKernelGGL(k_ledger_create, dim3((n + 63) / 64), dim3(64), 0, s, (const LedgerCreateDev*)l->create_in.p, (uint8_t*)l->planes.p, l->N, n);
     HZ_HIP(hipGetLastError());
-    HZ_HIP(hipEventRecord(l->ec1, s));
+    HZ_HIP(l->t_create.end(s));
     return HZ_OK;
 }
 
-// hz_ledger_apply_l2_addr, and hz_ledger_apply_batch (is_batch) with its L1 run in front
-static hz_status ledger_apply_addr(hz_ledger* l, const char* who, LedgerL1Run run, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, uint32_t flags,
-                                   const uint64_t* aux_to_idx, uint32_t chain_id, uint32_t current_num_batch, size_t F, const uint32_t* fee_plan_tokens,
-                                   const uint64_t* fee_idxs, size_t n_sib, const hz_ledger_out* out, const hz_ledger_sig_out* sig_out, uint8_t* aux_to_idx_out) {
-    if (hz_status e = ledger_ready(l, who)) return e;
-    ledger_exit_reset(l);
-    const size_t n_l1 = run.n;
-    const hz_l1tx* l1 = run.tx;
-    if (run.is_batch) l->l1_ms = 0.0;   // the time of THIS call, whatever becomes of it
-    const bool verify = (flags & HZ_LEDGER_VERIFY_SIGS) != 0;
-    if (flags & ~HZ_LEDGER_VERIFY_SIGS) return set_err(HZ_ERR_ARG, "%s: flags = %#x", who, flags);
-    if (!verify && sig_out) return set_err(HZ_ERR_ARG, "%s: sig_out without HZ_LEDGER_VERIFY_SIGS", who);
-    if (hz_status e = ledger_n_sib(l, who, n_sib)) return e;
-    size_t l1_events = 0;
-    std::vector<hz_l1tx> eff_l1;
-    std::vector<uint64_t> aux_from, idx_after;
-    if (run.creates) {   // the rows as the pipeline takes them: a create row is a deposit on auxFromIdx
-        if (hz_status e = ledger_check_creates(who, l->smt != nullptr, l->N, l->first_idx, l->live, n_l1, l1, run.from_bjj, &l1_events, eff_l1, aux_from, idx_after,
-                                               &run.n_creates))
-            return e;
-        run.tx = eff_l1.data();
-        run.aux_from = aux_from.data();
-        run.idx_after = idx_after.data();
-    } else if (hz_status e = ledger_check_l1(who, n_l1, l1, l->first_idx, l->live, &l1_events, run.exits)) {
-        return e;
-    }
-    const uint64_t count = l->live + run.n_creates;   // the accounts an L2 row or a fee slot may name: live plus created
-    if (hz_status e = ledger_check_plan(who, m, txs, F, fee_plan_tokens, fee_idxs, count, l->first_idx, l->plan, true, l1_events, run.exits)) return e;
-    std::vector<hz_l2sig> no_sigs;
-    if (run.is_batch && !sigs && m && !verify) {   // no destination is signed: zero entries stand in, and the call is hz_ledger_apply_l2_addr's
-        for (size_t i = 0; i < m; i++)
-            if (txs[i].from_idx != 0 && txs[i].to_idx == 0) return set_err(HZ_ERR_ARG, "%s: null sigs with tx %zu to an address", who, i);
-        no_sigs.assign(m, hz_l2sig{});
-        sigs = no_sigs.data();
-    }
-    if (hz_status e = ledger_check_sigs(who, m, txs, sigs, chain_id, verify)) return e;
-    if (hz_status e = ledger_check_rq(who, m, txs, run.rq)) return e;
-    if (run.n_creates)   // before everything else of the call, the lookup included: the new accounts' static fields into their plane slots
-        if (hz_status e = ledger_create_launch(l, run)) return e;
-    std::vector<hz_l2tx> eff(m ? m : 1);   // (never empty: its address tells ledger_apply which call this is)
-    if (m) memcpy(eff.data(), txs, m * sizeof(hz_l2tx));
-    auto wants_receiver = [&](size_t i) { return txs[i].from_idx != 0 && txs[i].to_idx == 0 && ledger_mantissa(txs[i].amount_f) != 0; };
-    if (aux_to_idx) {
-        for (size_t i = 0; i < m; i++) {
-            if (!wants_receiver(i)) continue;
-            if (!ledger_has(l->first_idx, count, aux_to_idx[i]))
-                return set_err(HZ_ERR_ARG, "%s: tx %zu: aux_to_idx = %llu is outside the state (%llu .. %llu)", who, i, (unsigned long long)aux_to_idx[i],
-                               (unsigned long long)l->first_idx, (unsigned long long)(l->first_idx + count - 1));
-            eff[i].to_idx = aux_to_idx[i];
-        }
-        l->resolve_ms = 0.0;
-    } else {
-        std::vector<uint64_t> found(m ? m : 1);
+// r.eff: the L2 rows with the receivers of those that want one -- the caller's, checked, or the lookup's. A destination nobody holds
+// keeps to_idx == 0; where refuse, it is reason 9 at once, before the plan can exist: reported whatever else is wrong with the batch
+static hz_status ledger_effective_receivers(hz_ledger* l, const char* who, size_t n_l1, size_t m, const hz_l2tx* txs, const uint64_t* aux_to_idx, bool refuse, LedgerRows& r) {
+    r.eff.assign(txs, txs + m);
+    const bool given = aux_to_idx != nullptr;
+    std::vector<uint64_t> found(given ? 0 : m ? m : 1);
+    if (!given) {
         ledger_forget(l);
-        if (hz_status e = ledger_resolve(l, m, txs, sigs, true, found.data(), count)) return e;
-        for (size_t i = 0; i < m; i++) {
-            if (!wants_receiver(i)) continue;
-            if (found[i] == 0)   // before the plan can exist: reported whatever else is wrong with the batch
-                return set_err(HZ_ERR_INPUT, "%s: refused at index %zu (%stransaction %zu), reason 9: %s", who, n_l1 + i, n_l1 ? "L2 " : "", i, LEDGER_REASON[9]);
-            eff[i].to_idx = found[i];
+        if (hz_status e = ledger_resolve(l, m, txs, r.sigs, true, found.data(), r.count)) return e;
+    }
+    const uint64_t* to = given ? aux_to_idx : found.data();
+    for (size_t i = 0; i < m; i++) {
+        if (!ledger_wants_receiver(txs[i])) continue;
+        if (given && !ledger_has(l->first_idx, r.count, to[i]))
+            return set_err(HZ_ERR_ARG, "%s: tx %zu: aux_to_idx = %llu is outside the state (%llu .. %llu)", who, i, (unsigned long long)to[i],
+                           (unsigned long long)l->first_idx, (unsigned long long)(l->first_idx + r.count - 1));
+        if (!given && to[i] == 0 && refuse) return ledger_refused(who, n_l1 + i, 9, n_l1 + m, n_l1);
+        r.eff[i].to_idx = to[i];
+    }
+    if (given) l->resolve_ms = 0.0;
+    return HZ_OK;
+}
+
+// the checks of a by_addr apply call, in the order their errors win; -> the rows the plan is made of
+static hz_status ledger_prepare(hz_ledger* l, const LedgerCall& c, LedgerRows& r) {
+    if (hz_status e = ledger_ready(l, c.who)) return e;
+    ledger_exit_reset(l);
+    if (c.is_batch) l->l1_ms = 0.0;   // the time of THIS call, whatever becomes of it
+    if (hz_status e = ledger_check_flags(c.who, c.flags)) return e;
+    if (!c.verify && c.sig_out) return set_err(HZ_ERR_ARG, "%s: sig_out without HZ_LEDGER_VERIFY_SIGS", c.who);
+    if (hz_status e = ledger_n_sib(l, c.who, c.n_sib)) return e;
+    if (hz_status e = ledger_effective_l1(l, c.who, c.n_l1, c.l1, c.from_bjj, c.creates, c.exits, r)) return e;
+    if (hz_status e = ledger_check_plan(c.who, c.m, c.txs, c.F, c.plan_tokens, c.fee_idxs, r.count, l->first_idx, l->plan, true, r.l1_events, c.exits)) return e;
+    r.sigs = c.sigs;
+    if (c.is_batch)   // (without an L1 run the call is hz_ledger_apply_l2_addr's: null sigs is its error)
+        if (hz_status e = ledger_stand_in_sigs(c.who, c.m, c.txs, c.sigs, c.verify, r)) return e;
+    if (hz_status e = ledger_check_sigs(c.who, c.m, c.txs, r.sigs, c.chain_id, c.verify)) return e;
+    if (hz_status e = ledger_check_rq(c.who, c.m, c.txs, c.rq)) return e;
+    if (r.n_creates)
+        if (hz_status e = ledger_create_launch(l, c.n_l1, c.l1, c.from_bjj, r)) return e;
+    return ledger_effective_receivers(l, c.who, c.n_l1, c.m, c.txs, c.aux_to_idx, true, r);
+}
+
+// ---- one apply call, in stages (the header comment names them) ----------------------------------------------------------------------------
+// What the stages share. The batch has R = n_l1 + m rows: every per-transaction table, kernel and output is per row, while sigs, sig_out
+// and the signature kernels keep to the m L2 rows. The plan is made of the effective rows (rows.l1, rows.eff), while c.txs -- the signed
+// ones, to_idx == 0 where the receiver is named by address -- are what the kernels see. Every early return drains the stream under a
+// copy from the ledger's pinned rq buffer and aborts a prepared tree update (the members are destroyed in that order)
+struct LedgerApply {
+    hz_ledger* const l;
+    const LedgerCall& c;
+    LedgerRows rows;
+    hipStream_t s = nullptr;
+    bool growing = false, links = false;
+    size_t R = 0;
+    uint32_t m32 = 0, R32 = 0, L32 = 0, F32 = 0, S = 0, N = 0, k = 0, M = 0, G = 0, n_slots = 0, n_chunks = 0, X = 0, GX = 0;
+    LedgerTables T;
+    LedgerWork W;
+    void *db = nullptr, *wb = nullptr;   // the integer tables and the work buffer on the device
+    SmtCallBufs xb{}, sb{};              // the exit tree's update; a growing ledger's state tree's
+    StateCallBufs tb{};                  // the state tree's update, whichever tree it is
+    LedgerExitGuard exit_guard, tree_guard;
+    LedgerDrain drain;
+    size_t elems[HZ_LEDGER_ARRAYS] = {}, exit_out_bytes = 0;
+    LedgerOutDev od{};
+    uint8_t* xd[HZ_LEDGER_EXIT_ARRAYS] = {};
+    LedgerCreateOutDev cd{};
+    uint64_t new_last = 0;
+    const hz_l2sig* d_dest = nullptr;   // by_addr: the signed destinations, for reasons 10 and 11 and the zero-amount rows
+    LedgerApply(hz_ledger* l_, const LedgerCall& c_) : l(l_), c(c_) {}
+    const hz_l2tx* d_txs() const { return T.tx.dev(db); }
+    const uint8_t* planes() const { return (const uint8_t*)l->planes.p; }
+    uint32_t* d_fail() const { return (uint32_t*)W.fail.dev(wb); }
+};
+
+// stage 1: the argument checks, the plan, the exit tree's plan -- a leaf it cannot hold refuses the call before anything is launched,
+// and the pack kernel's integers are the planner's
+static hz_status ledger_apply_plan(LedgerApply& a) {
+    static_assert(sizeof(hz_ledger_out) == HZ_LEDGER_ARRAYS * sizeof(uint8_t*), "hz_ledger_out is an array of pointers");
+    hz_ledger* l = a.l;
+    const LedgerCall& c = a.c;
+    if (c.by_addr)
+        if (hz_status e = ledger_prepare(l, c, a.rows)) return e;
+    if (hz_status e = ledger_ready(l, c.who)) return e;
+    ledger_exit_reset(l);
+    a.growing = l->smt != nullptr;
+    if (hz_status e = ledger_n_sib(l, c.who, c.n_sib)) return e;
+    LedgerPlan& p = l->plan;
+    if (c.by_addr) {
+        ledger_plan_rows(c.n_l1, a.rows.l1, c.m, a.rows.eff.data(), c.F, c.plan_tokens, c.fee_idxs, c.exits, p);
+    } else {
+        if (hz_status e = ledger_check_plan(c.who, c.m, c.txs, c.F, c.plan_tokens, c.fee_idxs, l->live, l->first_idx, p)) return e;
+        if (c.verify)
+            if (hz_status e = ledger_check_sigs(c.who, c.m, c.txs, c.sigs, c.chain_id)) return e;
+        a.rows.sigs = c.sigs;
+    }
+    ledger_forget(l);
+    a.R = c.n_l1 + c.m;
+    a.m32 = (uint32_t)c.m, a.R32 = (uint32_t)a.R, a.L32 = (uint32_t)c.n_l1, a.F32 = (uint32_t)c.F, a.S = (uint32_t)c.n_sib;
+    // N is the plane stride; a growing ledger's tree hands out siblings zero-padded to n_sib, so the gather reads all of them
+    a.N = l->N, a.k = a.growing ? a.S : l->k;
+    a.M = (uint32_t)p.account.size(), a.G = (uint32_t)p.seg_start.size() - 1, a.n_slots = (uint32_t)p.slot_account.size();
+    a.n_chunks = a.R32 ? (a.R32 + HZ_LEDGER_CHUNK - 1) / HZ_LEDGER_CHUNK : 1u;
+    a.X = (uint32_t)p.exit_row.size(), a.GX = (uint32_t)p.exit_seg_start.size() - 1;   // exit operations, exit keys
+    a.links = c.rq != nullptr && c.m != 0;   // (an atomic call is by_addr: sigs are uploaded, the three arrays have room)
+    HZ_HIP(hipSetDevice(l->device));
+    a.s = ledger_stream(l);
+    if (a.X) {
+        if (hz_status e = smt_apply_prepare(l->exit, c.who, HZ_ERR_ARG, a.X, p.exit_key.data(), a.S, true, &a.xb)) return e;
+        a.exit_guard.t = l->exit;
+    }
+    return HZ_OK;
+}
+
+// stage 2: the layouts and the room. ints = the integer tables; work = LedgerWork; outs = the 27 arrays; exit_outs = the six exit
+// arrays (five per row, the new exit root), create_outs likewise (the new last idx)
+static hz_status ledger_apply_buffers(LedgerApply& a) {
+    hz_ledger* l = a.l;
+    const size_t R = a.R, F = a.c.F;
+    a.T.layout(R, F, a.M, a.G, a.X, a.GX, a.c.n_l1, a.n_slots, a.c.creates);
+    a.W.layout(R, F, a.M, a.X);
+    for (int q = 0; q < HZ_LEDGER_ARRAYS; q++) a.elems[q] = q < LO_TX3 ? R : F;
+    a.elems[LO_SIB1] = a.elems[LO_SIB2] = R * a.c.n_sib;
+    a.elems[LO_ACC_FEE] = R * F;
+    a.elems[LO_SIB3] = F * a.c.n_sib;
+    a.elems[LO_OLD_ROOT] = a.elems[LO_NEW_ROOT] = 1;
+    size_t out_bytes = 0;
+    for (int q = 0; q < HZ_LEDGER_ARRAYS; q++) out_bytes += a.elems[q] * 32;
+    HZ_HIP(l->h_ints.grow(a.T.end));
+    HZ_HIP(l->ints.grow(a.T.end));
+    HZ_HIP(l->work.grow(a.W.end));
+    HZ_HIP(l->outs.grow(out_bytes));
+    if (a.c.creates) {
+        HZ_HIP(l->create_outs.grow(((size_t)(HZ_LEDGER_CREATE_ARRAYS - 1) * R + 1) * 32));
+        for (int q = 0; q < HZ_LEDGER_CREATE_ARRAYS; q++) a.cd.a[q] = (uint8_t*)l->create_outs.p + (size_t)q * R * 32;
+    }
+    if (a.c.exits) {
+        a.exit_out_bytes = ((size_t)(HZ_LEDGER_EXIT_ARRAYS - 1) * R + 1) * 32;
+        HZ_HIP(l->exit_outs.grow(a.exit_out_bytes));
+        HZ_HIP(l->exit_final.grow((size_t)4 * (a.GX ? a.GX : 1) * 32));
+        for (int q = 0; q < HZ_LEDGER_EXIT_ARRAYS; q++) a.xd[q] = (uint8_t*)l->exit_outs.p + (size_t)q * R * 32;
+    }
+    uint8_t* at = (uint8_t*)l->outs.p;
+    for (int q = 0; q < HZ_LEDGER_ARRAYS; q++) {
+        a.od.a[q] = at;
+        at += a.elems[q] * 32;
+    }
+    a.db = l->ints.p;
+    a.wb = l->work.p;
+    return HZ_OK;
+}
+
+// stage 3: the tables, and the state tree's plan: hz_state's on a dense ledger; on a growing one hz_smt's, whose planner turns the first
+// event of a key the tree does not hold -- a create row's sender event -- into an INSERT and refuses a leaf at depth >= n_sib before
+// anything of the update is launched. The create rows read its integers, so they are written behind it
+static hz_status ledger_apply_tables(LedgerApply& a) {
+    hz_ledger* l = a.l;
+    const LedgerPlan& p = l->plan;
+    a.T.fill(l->h_ints.p, p, a.rows.l1, a.c.txs, a.c.plan_tokens, l->first_idx, a.xb.old_key, a.xb.fnc, a.xb.is_old0);
+    if (a.M && a.growing) {
+        if (hz_status e = smt_apply_prepare(l->smt, a.c.who, HZ_ERR_ARG, a.M, p.account.data(), a.S, true, &a.sb)) return e;
+        a.tree_guard.t = l->smt;
+        a.tb.fields = a.sb.fields;
+        a.tb.siblings = a.sb.siblings;
+        a.tb.old_value = a.sb.old_value;
+        a.tb.old_root = a.sb.roots;
+        a.tb.new_root = a.sb.roots + 32;
+    } else if (a.M) {
+        if (hz_status e = state_apply_prepare(l->tree, a.M, p.account.data(), a.S, &a.tb)) return e;
+    }
+    a.new_last = l->first_idx + l->live + a.rows.n_creates - 1;
+    if (a.c.creates) a.T.fill_creates(l->h_ints.p, p, a.rows.aux_from.data(), a.rows.idx_after.data(), a.new_last, a.sb.old_key, a.sb.is_old0);
+    return HZ_OK;
+}
+
+// stage 4: the uploads and the semantic kernels, up to the one synchronise: the failure word. Nothing resident has been written yet
+static hz_status ledger_apply_launch(LedgerApply& a) {
+    hz_ledger* l = a.l;
+    const LedgerCall& c = a.c;
+    const LedgerTables& T = a.T;
+    const LedgerWork& W = a.W;
+    void *db = a.db, *wb = a.wb;
+    hipStream_t s = a.s;
+    const uint32_t R32 = a.R32, L32 = a.L32, F32 = a.F32, G = a.G, X = a.X;
+    HZ_HIP(hipMemcpyAsync(l->ints.p, l->h_ints.p, T.end, hipMemcpyHostToDevice, s));
+    HZ_HIP(hipMemsetAsync(a.d_fail(), 0xFF, 4, s));
+    if (c.verify || c.by_addr)
+        if (hz_status e = ledger_sig_prepare(l, c.m, a.rows.sigs, s, c.verify)) return e;
+    const hz_l2sig* d_sigs = (const hz_l2sig*)l->sig_in.p;
+    a.d_dest = c.by_addr ? d_sigs : nullptr;
+    if (c.by_addr) HZ_HIP(l->aux_rows.grow((a.R ? a.R : 1) * 32));
+    if (a.links) {
+        a.drain.s = s;
+        a.drain.armed = true;
+        if (hz_status e = ledger_rq_upload(l, c.m, c.rq, s)) return e;
+    }
+    if (c.is_batch) HZ_HIP(l->l1_flags.grow(c.n_l1 ? c.n_l1 : 1));
+    HZ_HIP(l->t_semantic.begin(s));
+    if (R32) {   // (pos_x == NULL: the batch has no exit operation)
+        hipLaunchKernelGGL(k_ledger_tx, dim3((R32 + 63) / 64), dim3(64), 0, s, a.d_txs(), T.pos_s.dev(db), T.pos_r.dev(db), W.fee.dev(wb), W.delta.dev(wb),
+                           X ? T.pos_x.dev(db) : nullptr, W.xamt.dev(wb), a.d_fail(), R32, L32);
+        HZ_HIP(hipGetLastError());
+    }
+    if (L32) {   // the deltas of the L1 events, beside those k_ledger_tx wrote: one workgroup, no synchronise of its own
+        HZ_HIP(l->t_l1.begin(s));
+        hipLaunchKernelGGL(k_ledger_l1, dim3(1), dim3(256), 0, s, T.l1.dev(db), T.slot_acct.dev(db), a.planes(), W.delta.dev(wb), W.xamt.dev(wb), (uint8_t*)l->l1_flags.p,
+                           a.N, L32, a.n_slots);
+        HZ_HIP(hipGetLastError());
+        HZ_HIP(l->t_l1.end(s));
+    }
+    if (F32) {
+        hipLaunchKernelGGL(k_ledger_fee_sum, dim3(a.n_chunks), dim3(64), 0, s, W.fee.dev(wb), T.slot.dev(db), W.chunk.dev(wb), R32, F32);
+        HZ_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_ledger_fee_scan, dim3(a.n_chunks), dim3(64), 0, s, W.fee.dev(wb), T.slot.dev(db), W.chunk.dev(wb), T.pos_fee.dev(db), a.od.a[LO_ACC_FEE],
+                           a.od.a[LO_FINAL_FEE], W.delta.dev(wb), R32, F32, a.n_chunks);
+        HZ_HIP(hipGetLastError());
+    }
+    if (G) {
+        hipLaunchKernelGGL(k_ledger_scan, dim3((G + 63) / 64), dim3(64), 0, s, T.pos.dev(db), T.seg.dev(db), a.d_txs(), a.d_dest, T.plan_tok.dev(db), W.delta.dev(wb), a.planes(),
+                           W.before.dev(wb), a.tb.fields, a.d_fail(), a.N, G, R32, L32);
+        HZ_HIP(hipGetLastError());
+    }
+    if (X) {   // the exit leaves: it reads the amounts k_ledger_tx and k_ledger_l1 left and the planes, and writes per-call buffers only
+        HZ_HIP(l->t_exit_scan.begin(s));
+        hipLaunchKernelGGL(k_ledger_exit_scan, dim3((a.GX + 63) / 64), dim3(64), 0, s, T.xpos.dev(db), T.xseg.dev(db), W.xamt.dev(wb), a.planes(), W.xbefore.dev(wb),
+                           a.xb.fields, (uint8_t*)l->exit_final.p, a.d_fail(), a.N, a.GX);
+        HZ_HIP(hipGetLastError());
+        HZ_HIP(l->t_exit_scan.end(s));
+    }
+    if (c.verify) {   // they read the planes and the uploads only: any place before the failure-word read would do
+        HZ_HIP(l->t_sig.begin(s));
+        HZ_HIP(launch_ledger_sig(a.d_txs() + c.n_l1, d_sigs, c.chain_id, c.current_num_batch, l->sig_dev[0], l->sig_dev[1], l->sig_dev[2], a.planes(), l->b8_table.p, a.N,
+                                 l->first_idx, a.d_fail(), nullptr, a.m32, s, L32, a.links ? (const uint8_t*)l->rq_in.p : nullptr));
+        HZ_HIP(l->t_sig.end(s));
+    }
+    if (a.links) {   // reason 13, verified or not: the V2 rows are the message kernel's, or those of its packing alone
+        if (!c.verify) HZ_HIP(launch_ledger_sig_v2(a.d_txs() + c.n_l1, d_sigs, l->sig_dev[1], a.m32, s));
+        HZ_HIP(l->t_rq.begin(s));
+        HZ_HIP(launch_ledger_rq(a.d_txs() + c.n_l1, d_sigs, (const uint8_t*)l->rq_in.p, (const uint8_t*)l->sig_dev[1], a.d_fail(), nullptr, a.m32, L32, s, L32));
+        HZ_HIP(l->t_rq.end(s));
+    }
+    HZ_HIP(l->t_semantic.end(s));
+    HZ_HIP(hipMemcpyAsync(l->h_fail.p, a.d_fail(), 4, hipMemcpyDeviceToHost, s));
+    HZ_HIP(hipStreamSynchronize(s));   // the one round trip
+    a.drain.armed = false;
+    if (a.links) HZ_HIP(l->t_rq.read(l->rq_ms));
+    return HZ_OK;
+}
+
+// stage 5: the verdict. A refused batch ends here
+static hz_status ledger_apply_verdict(LedgerApply& a) {
+    const uint32_t word = *(const uint32_t*)a.l->h_fail.p;
+    return word == 0xFFFFFFFFu ? HZ_OK : ledger_refused(a.c.who, word >> 8, word & 0xFFu, a.R, a.c.n_l1);
+}
+
+// stage 6: outputs, tree, resident planes
+static hz_status ledger_apply_commit(LedgerApply& a) {
+    hz_ledger* l = a.l;
+    const LedgerTables& T = a.T;
+    void *db = a.db, *wb = a.wb;
+    hipStream_t s = a.s;
+    const uint32_t R32 = a.R32, F32 = a.F32, S = a.S, M = a.M, G = a.G, X = a.X;
+    if (X) {   // the exit tree's update depends on the scan alone: on its own stream, beside everything below
+        HZ_HIP(hipStreamWaitEvent(smt_stream(l->exit), l->t_exit_scan.e1, 0));
+        if (hz_status e = smt_apply_launch(l->exit, X, S, true)) return e;
+        HZ_HIP(hipEventRecord(l->e_exit_tree, smt_stream(l->exit)));
+    }
+    if (a.c.exits) HZ_HIP(hipMemsetAsync(l->exit_outs.p, 0, a.exit_out_bytes, s));
+    if (R32 + F32) {
+        hipLaunchKernelGGL(k_ledger_pack, dim3((R32 + F32 + 63) / 64), dim3(64), 0, s, a.od, a.d_txs(), a.d_dest, (uint8_t*)l->aux_rows.p, l->first_idx, T.ev_s.dev(db),
+                           T.ev_r.dev(db), T.ev_fee.dev(db), T.acct.dev(db), a.W.before.dev(wb), a.planes(), a.N, R32, F32, a.L32);
+        HZ_HIP(hipGetLastError());
+    }
+    const uint8_t* root0 = nullptr;
+    if (M) {
+        if (hz_status e = a.growing ? smt_apply_launch(l->smt, M, S, true) : state_apply_launch(l->tree, M, S, false)) return e;
+        root0 = a.tb.old_root;
+    } else if (a.growing) {   // no update at all: the root as it stands, through the host
+        uint8_t r32[32];
+        if (hz_status e = hz_smt_root(l->smt, r32)) return e;
+        HZ_HIP(hipMemcpy(l->root_buf.p, r32, 32, hipMemcpyHostToDevice));
+        root0 = (const uint8_t*)l->root_buf.p;
+    } else {
+        root0 = state_root_dev(l->tree);
+    }
+    if (a.c.creates) {   // behind the tree's update: oldValue1 is its old-value buffer's
+        HZ_HIP(l->t_create_pack.begin(s));
+        hipLaunchKernelGGL(k_ledger_create_pack, dim3((R32 + 64) / 64), dim3(64), 0, s, a.cd, T.crow.dev(db), a.tb.old_value, a.new_last, R32);
+        HZ_HIP(hipGetLastError());
+        HZ_HIP(l->t_create_pack.end(s));
+    }
+    HZ_HIP(hipMemcpyAsync(a.od.a[LO_OLD_ROOT], root0, 32, hipMemcpyDeviceToDevice, s));
+    HZ_HIP(hipMemcpyAsync(a.od.a[LO_NEW_ROOT], M ? a.tb.new_root + (size_t)(M - 1) * 32 : root0, 32, hipMemcpyDeviceToDevice, s));
+    if (R32 + F32) {
+        const size_t threads = (size_t)(R32 + F32) * (S + 1);
+        hipLaunchKernelGGL(k_ledger_gather, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, a.od, T.ev_s.dev(db), T.ev_r.dev(db), T.ev_fee.dev(db), T.last.dev(db),
+                           a.tb.siblings, a.tb.new_root, root0, a.k, S, R32, F32);
+        HZ_HIP(hipGetLastError());
+    }
+    if (G) {
+        hipLaunchKernelGGL(k_ledger_writeback, dim3((G + 63) / 64), dim3(64), 0, s, T.pos.dev(db), T.seg.dev(db), a.tb.fields, (uint8_t*)l->planes.p, a.N, G);
+        HZ_HIP(hipGetLastError());
+    }
+    if (X) {   // the exit rows, once the exit tree's update is through: leaf-2 rows and siblings2 over what k_ledger_pack / _gather left there
+        LedgerExitOutDev xo;
+        for (int q = 0; q < 6; q++) xo.tx2[q] = a.od.a[LO_TX2 + q];
+        xo.sib2 = a.od.a[LO_SIB2];
+        for (int q = 0; q < HZ_LEDGER_EXIT_ARRAYS; q++) xo.x[q] = a.xd[q];
+        HZ_HIP(hipStreamWaitEvent(s, l->e_exit_tree, 0));
+        HZ_HIP(l->t_exit_rows.begin(s));
+        hipLaunchKernelGGL(k_ledger_exit_pack, dim3((R32 + 63) / 64), dim3(64), 0, s, xo, T.ev_x.dev(db), T.xop.dev(db), a.W.xbefore.dev(wb), a.xb.old_value, a.planes(), a.N,
+                           R32);
+        HZ_HIP(hipGetLastError());
+        const size_t threads = (size_t)R32 * (S + 1);
+        hipLaunchKernelGGL(k_ledger_exit_gather, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, xo, T.ev_x.dev(db), T.last_x.dev(db), a.xb.siblings, a.xb.roots,
+                           S, R32);
+        HZ_HIP(hipGetLastError());
+        HZ_HIP(hipMemcpyAsync(a.xd[XO_NEW_ROOT], a.xb.roots + (size_t)X * 32, 32, hipMemcpyDeviceToDevice, s));
+        HZ_HIP(l->t_exit_rows.end(s));
+    }
+    HZ_HIP(hipEventRecord(l->e_done, s));
+    return HZ_OK;
+}
+
+// n arrays of `rows` elements each (the last one: a single element) to the host arrays of `out`, a struct of n nullable pointers
+static hz_status ledger_copy_rows(const void* out, uint8_t* const* dev, int n, size_t rows, hipStream_t s) {
+    uint8_t* const* h = (uint8_t* const*)out;
+    for (int q = 0; out && q < n; q++) {
+        const size_t count = q == n - 1 ? 1 : rows;
+        if (h[q] && count) HZ_HIP(hipMemcpyAsync(h[q], dev[q], count * 32, hipMemcpyDeviceToHost, s));
+    }
+    return HZ_OK;
+}
+
+// stage 7: the copies to the host arrays the caller gave
+static hz_status ledger_apply_copy_out(LedgerApply& a) {
+    static_assert(XO_NEW_ROOT == HZ_LEDGER_EXIT_ARRAYS - 1 && CO_NEW_LAST == HZ_LEDGER_CREATE_ARRAYS - 1, "the single element is the last array");
+    hz_ledger* l = a.l;
+    const LedgerCall& c = a.c;
+    if (hz_status e = ledger_copy_rows(c.create_out, a.cd.a, HZ_LEDGER_CREATE_ARRAYS, a.R, a.s)) return e;
+    if (hz_status e = ledger_copy_rows(c.exit_out, a.xd, HZ_LEDGER_EXIT_ARRAYS, a.R, a.s)) return e;
+    if (c.out) {
+        uint8_t* const* h = (uint8_t* const*)c.out;
+        for (int q = 0; q < HZ_LEDGER_ARRAYS; q++)
+            if (h[q] && a.elems[q]) HZ_HIP(hipMemcpyAsync(h[q], a.od.a[q], a.elems[q] * 32, hipMemcpyDeviceToHost, a.s));
+    }
+    if (c.verify)
+        if (hz_status e = ledger_sig_copy_out(l, c.m, c.sig_out, a.s)) return e;
+    if (c.by_addr && c.aux_to_idx_out && a.R) HZ_HIP(hipMemcpyAsync(c.aux_to_idx_out, l->aux_rows.p, a.R * 32, hipMemcpyDeviceToHost, a.s));
+    if (c.flags_out && c.n_l1) HZ_HIP(hipMemcpyAsync(c.flags_out, l->l1_flags.p, c.n_l1, hipMemcpyDeviceToHost, a.s));
+    return HZ_OK;
+}
+
+// stage 8: the trees' updates finished -- from there the created accounts exist --, the times, what the getters may hand out
+static hz_status ledger_apply_finish(LedgerApply& a) {
+    hz_ledger* l = a.l;
+    const LedgerCall& c = a.c;
+    const LedgerPlan& p = l->plan;
+    if (a.M && a.growing) {
+        a.tree_guard.t = nullptr;
+        if (hz_status e = smt_apply_finish(l->smt)) {
+            smt_apply_abort(l->smt);
+            return e;
+        }
+        l->live += a.rows.n_creates;
+    } else if (a.M) {
+        if (hz_status e = state_apply_finish(l->tree)) return e;
+    } else {
+        HZ_HIP(hipStreamSynchronize(a.s));
+    }
+    double ms = 0.0;
+    if (a.X) {
+        a.exit_guard.t = nullptr;
+        if (hz_status e = smt_apply_finish(l->exit)) {
+            smt_apply_abort(l->exit);
+            return e;
+        }
+        l->exit_ms = hz_smt_device_ms(l->exit);
+        for (const DevSpan* t : {&l->t_exit_scan, &l->t_exit_rows}) {
+            HZ_HIP(t->read(ms));
+            l->exit_ms += ms;
+        }
+        for (uint32_t g = 0; g < a.GX; g++) l->exit_keys.push_back({p.exit_key[p.exit_perm[p.exit_seg_start[g]]], g});
+        std::sort(l->exit_keys.begin(), l->exit_keys.end());
+    }
+    if (c.exits) {
+        for (int q = 0; q < HZ_LEDGER_EXIT_ARRAYS; q++) l->exit_dev[q] = a.xd[q];
+        l->have_exit_outputs = true;
+    }
+    HZ_HIP(l->t_semantic.read(l->semantic_ms));
+    HZ_HIP(elapsed_ms(l->t_semantic.e0, l->e_done, l->device_ms));
+    l->out_dev = a.od;
+    l->have_outputs = true;
+    l->have_aux = c.by_addr;
+    l->have_l1 = c.is_batch;
+    if (c.creates) {
+        for (int q = 0; q < HZ_LEDGER_CREATE_ARRAYS; q++) l->create_dev[q] = a.cd.a[q];
+        l->have_create_outputs = true;
+        HZ_HIP(l->t_create_pack.read(l->create_ms));
+        if (a.rows.n_creates) {
+            HZ_HIP(l->t_create.read(ms));
+            l->create_ms += ms;
         }
     }
-    return ledger_apply(l, who, m, txs, sigs, verify, chain_id, current_num_batch, F, fee_plan_tokens, fee_idxs, n_sib, out, sig_out, eff.data(), aux_to_idx_out,
-                        run);
+    if (a.L32) HZ_HIP(l->t_l1.read(l->l1_ms));
+    if (c.verify) {
+        HZ_HIP(l->t_sig.read(l->sig_ms));
+        l->have_sig_outputs = true;
+    }
+    return HZ_OK;
+}
+
+static hz_status ledger_apply(hz_ledger* l, const LedgerCall& c) {
+    LedgerApply a(l, c);
+    for (hz_status (*stage)(LedgerApply&) : {ledger_apply_plan, ledger_apply_buffers, ledger_apply_tables, ledger_apply_launch, ledger_apply_verdict, ledger_apply_commit,
+                                             ledger_apply_copy_out, ledger_apply_finish})
+        if (hz_status e = stage(a)) return e;
+    return HZ_OK;
+}
+
+// ---- the exported apply calls: each states its call, by family ---------------------------------------------------------------------------
+static LedgerCall ledger_call_l2(const char* who, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, uint32_t chain_id, uint32_t current_num_batch, size_t F,
+                                 const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs, size_t n_sib, const hz_ledger_out* out, const hz_ledger_sig_out* sig_out) {
+    LedgerCall c;
+    c.who = who, c.m = m, c.txs = txs, c.sigs = sigs, c.chain_id = chain_id, c.current_num_batch = current_num_batch;
+    c.F = F, c.plan_tokens = fee_plan_tokens, c.fee_idxs = fee_idxs, c.n_sib = n_sib, c.out = out, c.sig_out = sig_out;
+    return c;
+}
+
+// by_addr: flags and the receivers by address on top
+static LedgerCall ledger_call_addr(LedgerCall c, uint32_t flags, const uint64_t* aux_to_idx, uint8_t* aux_to_idx_out) {
+    c.by_addr = true, c.flags = flags, c.verify = (flags & HZ_LEDGER_VERIFY_SIGS) != 0, c.aux_to_idx = aux_to_idx, c.aux_to_idx_out = aux_to_idx_out;
+    return c;
+}
+
+// is_batch: an L1 run in front
+static LedgerCall ledger_call_batch(LedgerCall c, size_t n_l1, const hz_l1tx* l1, uint8_t* l1_flags_out) {
+    c.is_batch = true, c.n_l1 = n_l1, c.l1 = l1, c.flags_out = l1_flags_out;
+    return c;
+}
+
+extern "C" hz_status hz_ledger_apply_l2(hz_ledger* l, size_t m, const hz_l2tx* txs, size_t F, const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs,
+                                        size_t n_sib, const hz_ledger_out* out) {
+    return ledger_apply(l, ledger_call_l2("hz_ledger_apply_l2", m, txs, nullptr, 0, 0, F, fee_plan_tokens, fee_idxs, n_sib, out, nullptr));
+}
+
+extern "C" hz_status hz_ledger_apply_l2_signed(hz_ledger* l, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, uint32_t chain_id, uint32_t current_num_batch,
+                                               size_t F, const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs, size_t n_sib, const hz_ledger_out* out,
+                                               const hz_ledger_sig_out* sig_out) {
+    LedgerCall c = ledger_call_l2("hz_ledger_apply_l2_signed", m, txs, sigs, chain_id, current_num_batch, F, fee_plan_tokens, fee_idxs, n_sib, out, sig_out);
+    c.verify = true;
+    return ledger_apply(l, c);
 }
 
 extern "C" hz_status hz_ledger_apply_l2_addr(hz_ledger* l, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, uint32_t flags, const uint64_t* aux_to_idx,
                                              uint32_t chain_id, uint32_t current_num_batch, size_t F, const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs,
                                              size_t n_sib, const hz_ledger_out* out, const hz_ledger_sig_out* sig_out, uint8_t* aux_to_idx_out) {
-    return ledger_apply_addr(l, "hz_ledger_apply_l2_addr", LedgerL1Run(), m, txs, sigs, flags, aux_to_idx, chain_id, current_num_batch, F, fee_plan_tokens,
-                             fee_idxs, n_sib, out, sig_out, aux_to_idx_out);
+    return ledger_apply(l, ledger_call_addr(ledger_call_l2("hz_ledger_apply_l2_addr", m, txs, sigs, chain_id, current_num_batch, F, fee_plan_tokens, fee_idxs, n_sib, out, sig_out),
+                                            flags, aux_to_idx, aux_to_idx_out));
 }
 
 // ---- an L1 run in front of the L2 transactions ---------------------------------------------------------------------------
@@ -1642,13 +1613,8 @@ extern "C" hz_status hz_ledger_apply_batch(hz_ledger* l, size_t n_l1, const hz_l
                                            const uint64_t* aux_to_idx, uint32_t chain_id, uint32_t current_num_batch, size_t F, const uint32_t* fee_plan_tokens,
                                            const uint64_t* fee_idxs, size_t n_sib, const hz_ledger_out* out, const hz_ledger_sig_out* sig_out,
                                            uint8_t* aux_to_idx_out, uint8_t* l1_flags_out) {
-    LedgerL1Run run;
-    run.n = n_l1;
-    run.tx = l1;
-    run.flags_out = l1_flags_out;
-    run.is_batch = true;
-    return ledger_apply_addr(l, "hz_ledger_apply_batch", run, m, txs, sigs, flags, aux_to_idx, chain_id, current_num_batch, F, fee_plan_tokens, fee_idxs, n_sib, out,
-                             sig_out, aux_to_idx_out);
+    const LedgerCall l2 = ledger_call_l2("hz_ledger_apply_batch", m, txs, sigs, chain_id, current_num_batch, F, fee_plan_tokens, fee_idxs, n_sib, out, sig_out);
+    return ledger_apply(l, ledger_call_batch(ledger_call_addr(l2, flags, aux_to_idx, aux_to_idx_out), n_l1, l1, l1_flags_out));
 }
 
 extern "C" hz_status hz_ledger_plan_batch(size_t n_l1, const hz_l1tx* l1, size_t m, const hz_l2tx* txs, size_t F, const uint32_t* fee_plan_tokens,
@@ -1686,19 +1652,15 @@ extern "C" hz_status hz_ledger_plan_batch(size_t n_l1, const hz_l1tx* l1, size_t
 }
 
 extern "C" hz_status hz_ledger_l1_flags_dev(hz_ledger* l, uint8_t** dev) {
-    if (!l || !dev) return set_err(HZ_ERR_ARG, "hz_ledger_l1_flags_dev: null argument");
-    if (!l->have_l1) return set_err(HZ_ERR_ARG, "hz_ledger_l1_flags_dev: no successful hz_ledger_apply_batch since the ledger's last other call");
-    *dev = (uint8_t*)l->l1_flags.p;
-    return HZ_OK;
+    uint8_t* const p = l ? (uint8_t*)l->l1_flags.p : nullptr;
+    return ledger_hand_out("hz_ledger_l1_flags_dev", l, dev, l ? &l->have_l1 : nullptr, "hz_ledger_apply_batch", &p, 1);
 }
 
 extern "C" double hz_ledger_l1_ms(const hz_ledger* l) { return l ? l->l1_ms : 0.0; }
 
 extern "C" hz_status hz_ledger_aux_to_idx_dev(hz_ledger* l, uint8_t** dev) {
-    if (!l || !dev) return set_err(HZ_ERR_ARG, "hz_ledger_aux_to_idx_dev: null argument");
-    if (!l->have_aux) return set_err(HZ_ERR_ARG, "hz_ledger_aux_to_idx_dev: no successful hz_ledger_apply_l2_addr since the ledger's last other call");
-    *dev = (uint8_t*)l->aux_rows.p;
-    return HZ_OK;
+    uint8_t* const p = l ? (uint8_t*)l->aux_rows.p : nullptr;
+    return ledger_hand_out("hz_ledger_aux_to_idx_dev", l, dev, l ? &l->have_aux : nullptr, "hz_ledger_apply_l2_addr", &p, 1);
 }
 
 extern "C" double hz_ledger_resolve_ms(const hz_ledger* l) { return l ? l->resolve_ms : 0.0; }
@@ -1709,24 +1671,15 @@ extern "C" hz_status hz_ledger_apply_batch_exits(hz_ledger* l, size_t n_l1, cons
                                                  const uint64_t* fee_idxs, size_t n_sib, const hz_ledger_out* out, const hz_ledger_sig_out* sig_out,
                                                  uint8_t* aux_to_idx_out, uint8_t* l1_flags_out, const hz_ledger_exit_out* exit_out) {
     static_assert(sizeof(hz_ledger_exit_out) == HZ_LEDGER_EXIT_ARRAYS * sizeof(uint8_t*), "hz_ledger_exit_out is an array of pointers");
-    LedgerL1Run run;
-    run.n = n_l1;
-    run.tx = l1;
-    run.flags_out = l1_flags_out;
-    run.is_batch = true;
-    run.exits = true;
-    run.exit_out = exit_out;
-    return ledger_apply_addr(l, "hz_ledger_apply_batch_exits", run, m, txs, sigs, flags, aux_to_idx, chain_id, current_num_batch, F, fee_plan_tokens, fee_idxs, n_sib,
-                             out, sig_out, aux_to_idx_out);
+    const LedgerCall l2 = ledger_call_l2("hz_ledger_apply_batch_exits", m, txs, sigs, chain_id, current_num_batch, F, fee_plan_tokens, fee_idxs, n_sib, out, sig_out);
+    LedgerCall c = ledger_call_batch(ledger_call_addr(l2, flags, aux_to_idx, aux_to_idx_out), n_l1, l1, l1_flags_out);
+    c.exits = true, c.exit_out = exit_out;
+    return ledger_apply(l, c);
 }
 
 extern "C" hz_status hz_ledger_exit_outputs_dev(hz_ledger* l, hz_ledger_exit_out* dev) {
-    if (!l || !dev) return set_err(HZ_ERR_ARG, "hz_ledger_exit_outputs_dev: null argument");
-    if (!l->have_exit_outputs)
-        return set_err(HZ_ERR_ARG, "hz_ledger_exit_outputs_dev: no successful hz_ledger_apply_batch_exits since the ledger's last other call");
-    uint8_t** d = (uint8_t**)dev;
-    for (int a = 0; a < HZ_LEDGER_EXIT_ARRAYS; a++) d[a] = l->exit_dev[a];
-    return HZ_OK;
+    return ledger_hand_out("hz_ledger_exit_outputs_dev", l, dev, l ? &l->have_exit_outputs : nullptr, "hz_ledger_apply_batch_exits", l ? l->exit_dev : nullptr,
+                           HZ_LEDGER_EXIT_ARRAYS);
 }
 
 extern "C" hz_smt* hz_ledger_exit_tree(hz_ledger* l) { return l ? l->exit : nullptr; }
@@ -1766,7 +1719,7 @@ static hz_status ledger_archive(hz_ledger* l, LedgerArchive** out) {
     if (!l->archive) {
         std::unique_ptr<LedgerArchive> a(new LedgerArchive);
         HZ_HIP(hipSetDevice(l->device));
-        for (DevEvent* e : {&a->ek0, &a->ek1, &a->ew0, &a->ew1}) HZ_HIP(e->create());
+        for (DevSpan* t : {&a->t_keep, &a->t_withdraw}) HZ_HIP(t->create());
         l->archive = std::move(a);
     }
     *out = l->archive.get();
@@ -1845,7 +1798,7 @@ extern "C" hz_status hz_ledger_exit_keep(hz_ledger* l, uint32_t batch_num) {
     hipStream_t s = ledger_stream(l);
     // the tree's pools and the final exit leaves are at rest: every apply call ends behind its synchronise
     const hz_status st = [&]() -> hz_status {
-        HZ_HIP(hipEventRecord(a->ek0, s));
+        HZ_HIP(a->t_keep.begin(s));
         if (v.nodes) {
             HZ_HIP(hipMemcpyAsync(base + lay.child, v.child, v.nodes * 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
             HZ_HIP(hipMemcpyAsync(base + lay.node, v.node_digest, v.nodes * 32, hipMemcpyDeviceToDevice, s));
@@ -1857,11 +1810,9 @@ extern "C" hz_status hz_ledger_exit_keep(hz_ledger* l, uint32_t batch_num) {
             HZ_HIP(hipMemcpyAsync(base + lay.fields, l->exit_final.p, G * 4 * 32, hipMemcpyDeviceToDevice, s));
         }
         HZ_HIP(archive_upload_table(next, table, host_table, s));
-        HZ_HIP(hipEventRecord(a->ek1, s));
+        HZ_HIP(a->t_keep.end(s));
         HZ_HIP(hipStreamSynchronize(s));
-        float ms = 0;
-        HZ_HIP(hipEventElapsedTime(&ms, a->ek0, a->ek1));
-        a->keep_ms = ms;
+        HZ_HIP(a->t_keep.read(a->keep_ms));
         return HZ_OK;
     }();
     if (st) {
@@ -1955,37 +1906,29 @@ extern "C" hz_status hz_ledger_withdraw_rows(hz_ledger* l, size_t n, const uint3
     const uint32_t S = (uint32_t)n_levels + 1, N = (uint32_t)n;
     HZ_HIP(hipSetDevice(l->device));
     hipStream_t s = ledger_stream(l);
-    // the integers: snapshot [n] | idx [n] | meta [n] | sources [n][S]; the first two are the host's
-    Carve c;
-    const size_t o_snap = c.take(n * 4), o_idx = c.take(n * 8), host_bytes = c.end, o_meta = c.take(n * sizeof(WithdrawMeta)), o_src = c.take(n * S * 4);
+    WithdrawTables T;
+    T.layout(n, S);
     // the rows: the seven single arrays [7][n][32] | siblings [n][S][32] | status [n]
     const size_t o_sib = (size_t)WR_ROWS * n * 32, o_status = o_sib + n * S * 32, out_bytes = o_status + n;
-    HZ_HIP(l->h_ints.grow(host_bytes));
-    HZ_HIP(l->ints.grow(c.end));
+    HZ_HIP(l->h_ints.grow(T.up));
+    HZ_HIP(l->ints.grow(T.end));
     HZ_HIP(l->outs.grow(out_bytes));
-    uint8_t* hb = (uint8_t*)l->h_ints.p;
-    uint32_t last_batch = 0;
-    int64_t last_at = -2;
-    for (size_t i = 0; i < n; i++) {   // (queries on one batch mostly come in runs)
-        if (last_at == -2 || batch_num[i] != last_batch) last_batch = batch_num[i], last_at = archive_find(a, last_batch);
-        ((int32_t*)(hb + o_snap))[i] = (int32_t)last_at;
-        ((uint64_t*)(hb + o_idx))[i] = idx[i];
-    }
+    T.fill(l->h_ints.p, batch_num, idx, [&](uint32_t batch) { return archive_find(a, batch); });
     LedgerDrain drain;
     drain.s = s;
     drain.armed = true;   // the pinned block is the ledger's: no copy from it, or into the caller's arrays, outlives the call
-    uint8_t* db = (uint8_t*)l->ints.p;
+    void* db = l->ints.p;
     uint8_t* ob = (uint8_t*)l->outs.p;
-    HZ_HIP(hipMemcpyAsync(db, hb, host_bytes, hipMemcpyHostToDevice, s));
-    HZ_HIP(hipEventRecord(a->ew0, s));
-    hipLaunchKernelGGL(k_withdraw_walk, dim3((N + 63) / 64), dim3(64), 0, s, (const ArchiveDesc*)a->table.p, (const int32_t*)(db + o_snap), (const uint64_t*)(db + o_idx),
-                       (WithdrawMeta*)(db + o_meta), (uint32_t*)(db + o_src), ob + o_status, S, N);
+    HZ_HIP(hipMemcpyAsync(db, l->h_ints.p, T.up, hipMemcpyHostToDevice, s));
+    HZ_HIP(a->t_withdraw.begin(s));
+    hipLaunchKernelGGL(k_withdraw_walk, dim3((N + 63) / 64), dim3(64), 0, s, (const ArchiveDesc*)a->table.p, T.snap.dev(db), T.idx.dev(db), T.meta.dev(db), T.src.dev(db),
+                       ob + o_status, S, N);
     HZ_HIP(hipGetLastError());
     const size_t lanes = n * (S + WR_ROWS) * 2;
-    hipLaunchKernelGGL(k_withdraw_fill, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, (const ArchiveDesc*)a->table.p, (const int32_t*)(db + o_snap),
-                       (const uint64_t*)(db + o_idx), (const WithdrawMeta*)(db + o_meta), (const uint32_t*)(db + o_src), ob, ob + o_sib, S, N);
+    hipLaunchKernelGGL(k_withdraw_fill, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, (const ArchiveDesc*)a->table.p, T.snap.dev(db), T.idx.dev(db), T.meta.dev(db),
+                       T.src.dev(db), ob, ob + o_sib, S, N);
     HZ_HIP(hipGetLastError());
-    HZ_HIP(hipEventRecord(a->ew1, s));
+    HZ_HIP(a->t_withdraw.end(s));
     uint8_t* dev[HZ_WITHDRAW_ARRAYS];
     for (uint32_t r = 0; r < WR_ROWS; r++) dev[r] = ob + (size_t)r * n * 32;
     dev[WR_ROWS] = ob + o_sib;
@@ -1997,21 +1940,16 @@ extern "C" hz_status hz_ledger_withdraw_rows(hz_ledger* l, size_t n, const uint3
     }
     HZ_HIP(hipStreamSynchronize(s));
     drain.armed = false;
-    float ms = 0;
-    HZ_HIP(hipEventElapsedTime(&ms, a->ew0, a->ew1));
-    a->withdraw_ms = ms;
+    HZ_HIP(a->t_withdraw.read(a->withdraw_ms));
     for (uint32_t r = 0; r < HZ_WITHDRAW_ARRAYS; r++) a->rows_dev[r] = dev[r];
     a->have_rows = true;
     return HZ_OK;
 }
 
 extern "C" hz_status hz_ledger_withdraw_rows_dev(hz_ledger* l, hz_withdraw_rows_out* dev) {
-    if (!l || !dev) return set_err(HZ_ERR_ARG, "hz_ledger_withdraw_rows_dev: null argument");
-    if (!l->archive || !l->archive->have_rows)
-        return set_err(HZ_ERR_ARG, "hz_ledger_withdraw_rows_dev: no successful hz_ledger_withdraw_rows (of at least one query) since the ledger's last other call");
-    uint8_t** d = (uint8_t**)dev;
-    for (int r = 0; r < HZ_WITHDRAW_ARRAYS; r++) d[r] = l->archive->rows_dev[r];
-    return HZ_OK;
+    const LedgerArchive* a = l ? l->archive.get() : nullptr;
+    return ledger_hand_out("hz_ledger_withdraw_rows_dev", l, dev, a ? &a->have_rows : nullptr, "hz_ledger_withdraw_rows (of at least one query)",
+                           a ? a->rows_dev : nullptr, HZ_WITHDRAW_ARRAYS);
 }
 
 extern "C" double hz_ledger_withdraw_ms(const hz_ledger* l) { return l && l->archive ? l->archive->withdraw_ms : 0.0; }
@@ -2069,27 +2007,16 @@ extern "C" hz_status hz_ledger_apply_batch_creates(hz_ledger* l, size_t n_l1, co
                                                    const hz_ledger_sig_out* sig_out, uint8_t* aux_to_idx_out, uint8_t* l1_flags_out, const hz_ledger_exit_out* exit_out,
                                                    const hz_ledger_create_out* create_out) {
     static_assert(sizeof(hz_ledger_create_out) == HZ_LEDGER_CREATE_ARRAYS * sizeof(uint8_t*), "hz_ledger_create_out is an array of pointers");
-    LedgerL1Run run;
-    run.n = n_l1;
-    run.tx = l1;
-    run.flags_out = l1_flags_out;
-    run.is_batch = true;
-    run.exits = true;
-    run.exit_out = exit_out;
-    run.creates = true;
-    run.from_bjj = from_bjj;
-    run.create_out = create_out;
-    return ledger_apply_addr(l, "hz_ledger_apply_batch_creates", run, m, txs, sigs, flags, aux_to_idx, chain_id, current_num_batch, F, fee_plan_tokens, fee_idxs, n_sib,
-                             out, sig_out, aux_to_idx_out);
+    const LedgerCall l2 = ledger_call_l2("hz_ledger_apply_batch_creates", m, txs, sigs, chain_id, current_num_batch, F, fee_plan_tokens, fee_idxs, n_sib, out, sig_out);
+    LedgerCall c = ledger_call_batch(ledger_call_addr(l2, flags, aux_to_idx, aux_to_idx_out), n_l1, l1, l1_flags_out);
+    c.exits = true, c.exit_out = exit_out;
+    c.creates = true, c.from_bjj = from_bjj, c.create_out = create_out;
+    return ledger_apply(l, c);
 }
 
 extern "C" hz_status hz_ledger_create_outputs_dev(hz_ledger* l, hz_ledger_create_out* dev) {
-    if (!l || !dev) return set_err(HZ_ERR_ARG, "hz_ledger_create_outputs_dev: null argument");
-    if (!l->have_create_outputs)
-        return set_err(HZ_ERR_ARG, "hz_ledger_create_outputs_dev: no successful hz_ledger_apply_batch_creates since the ledger's last other call");
-    uint8_t** d = (uint8_t**)dev;
-    for (int a = 0; a < HZ_LEDGER_CREATE_ARRAYS; a++) d[a] = l->create_dev[a];
-    return HZ_OK;
+    return ledger_hand_out("hz_ledger_create_outputs_dev", l, dev, l ? &l->have_create_outputs : nullptr, "hz_ledger_apply_batch_creates",
+                           l ? l->create_dev : nullptr, HZ_LEDGER_CREATE_ARRAYS);
 }
 
 extern "C" double hz_ledger_create_ms(const hz_ledger* l) { return l ? l->create_ms : 0.0; }
@@ -2126,18 +2053,12 @@ extern "C" hz_status hz_ledger_apply_batch_atomic(hz_ledger* l, size_t n_l1, con
     const char* who = "hz_ledger_apply_batch_atomic";
     if (l) l->rq_ms = 0.0;   // the time of THIS call. (sigs == NULL is hz_ledger_apply_batch's: zero entries stand in, so the link fields
                              // of such rows are V2 and two zeros)
-    LedgerL1Run run;
-    run.n = n_l1;
-    run.tx = l1;
-    run.flags_out = l1_flags_out;
-    run.is_batch = true;
-    run.exits = true;
-    run.exit_out = exit_out;
-    run.creates = true;
-    run.from_bjj = from_bjj;
-    run.create_out = create_out;
-    run.rq = rq;
-    return ledger_apply_addr(l, who, run, m, txs, sigs, flags, aux_to_idx, chain_id, current_num_batch, F, fee_plan_tokens, fee_idxs, n_sib, out, sig_out, aux_to_idx_out);
+    const LedgerCall l2 = ledger_call_l2(who, m, txs, sigs, chain_id, current_num_batch, F, fee_plan_tokens, fee_idxs, n_sib, out, sig_out);
+    LedgerCall c = ledger_call_batch(ledger_call_addr(l2, flags, aux_to_idx, aux_to_idx_out), n_l1, l1, l1_flags_out);
+    c.exits = true, c.exit_out = exit_out;
+    c.creates = true, c.from_bjj = from_bjj, c.create_out = create_out;
+    c.rq = rq;
+    return ledger_apply(l, c);
 }
 
 extern "C" hz_status hz_ledger_verify_l2_atomic(hz_ledger* l, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, const hz_l2rq* rq, uint32_t chain_id,
@@ -2266,44 +2187,24 @@ extern "C" hz_status hz_ledger_plan_select(size_t n_l1, const hz_l1tx* l1, size_
 
 extern "C" double hz_ledger_select_ms(const hz_ledger* l) { return l ? l->select_ms : 0.0; }
 
-extern "C" hz_status hz_ledger_select_batch(hz_ledger* l, size_t n_l1, const hz_l1tx* l1, const uint8_t* from_bjj, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs,
-                                            const hz_l2rq* rq, const int32_t* partner, uint32_t flags, uint32_t chain_id, uint32_t current_num_batch, size_t max_keep,
-                                            const hz_ledger_select_out* out) {
-    const char* who = "hz_ledger_select_batch";
+// the argument checks of hz_ledger_select_batch, in the order their errors win; -> the rows (the L1 rows as hz_ledger_apply_batch_atomic
+// takes them), and where the call has links (rq or partner) the rq entries without their offsets: positions do not survive a drop
+static hz_status select_checks(hz_ledger* l, const char* who, size_t n_l1, const hz_l1tx* l1, const uint8_t* from_bjj, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs,
+                               const hz_l2rq* rq, const int32_t* partner, uint32_t flags, uint32_t chain_id, const hz_ledger_select_out* out, LedgerRows& r,
+                               std::vector<hz_l2rq>& rq_eff) {
     if (hz_status e = ledger_ready(l, who)) return e;
     l->select_ms = 0.0;
     if (!out || (m && !txs)) return set_err(HZ_ERR_ARG, "%s: null argument", who);
     const bool verify = (flags & HZ_LEDGER_VERIFY_SIGS) != 0;
-    if (flags & ~HZ_LEDGER_VERIFY_SIGS) return set_err(HZ_ERR_ARG, "%s: flags = %#x", who, flags);
-    // the L1 rows as hz_ledger_apply_batch_atomic takes them
-    LedgerL1Run run;
-    run.n = n_l1;
-    run.is_batch = run.exits = run.creates = true;
-    run.from_bjj = from_bjj;
-    size_t l1_events = 0;
-    std::vector<hz_l1tx> eff_l1;
-    std::vector<uint64_t> aux_from, idx_after;
-    if (hz_status e = ledger_check_creates(who, l->smt != nullptr, l->N, l->first_idx, l->live, n_l1, l1, from_bjj, &l1_events, eff_l1, aux_from, idx_after, &run.n_creates))
-        return e;
-    run.tx = eff_l1.data();
-    run.aux_from = aux_from.data();
-    run.idx_after = idx_after.data();
-    const uint64_t count = l->live + run.n_creates;
+    if (hz_status e = ledger_check_flags(who, flags)) return e;
+    if (hz_status e = ledger_effective_l1(l, who, n_l1, l1, from_bjj, true, true, r)) return e;
     if (m > HZ_SELECT_MAX_POOL)
         return set_err(HZ_ERR_ARG, "%s: tx %d does not fit: a pool holds at most %d candidates (HZ_SELECT_MAX_POOL)", who, HZ_SELECT_MAX_POOL, HZ_SELECT_MAX_POOL);
-    if (hz_status e = ledger_check_txs(who, m, txs, l->first_idx, count, true, true)) return e;
+    if (hz_status e = ledger_check_txs(who, m, txs, l->first_idx, r.count, true, true)) return e;
     if (hz_status e = select_check_partner(who, m, txs, partner)) return e;
-    std::vector<hz_l2sig> no_sigs;
-    if (!sigs && m && !verify) {   // no destination is signed: zero entries stand in, as in hz_ledger_apply_batch
-        for (size_t i = 0; i < m; i++)
-            if (txs[i].from_idx != 0 && txs[i].to_idx == 0) return set_err(HZ_ERR_ARG, "%s: null sigs with tx %zu to an address", who, i);
-        no_sigs.assign(m, hz_l2sig{});
-        sigs = no_sigs.data();
-    }
-    if (hz_status e = ledger_check_sigs(who, m, txs, sigs, chain_id, verify)) return e;
-    const bool links = (rq != nullptr || partner != nullptr) && m != 0;
-    std::vector<hz_l2rq> rq_eff;
-    if (links) {   // the offsets are not read: positions do not survive a drop
+    if (hz_status e = ledger_stand_in_sigs(who, m, txs, sigs, verify, r)) return e;
+    if (hz_status e = ledger_check_sigs(who, m, txs, r.sigs, chain_id, verify)) return e;
+    if ((rq != nullptr || partner != nullptr) && m != 0) {
         rq_eff.assign(m, hz_l2rq{});
         for (size_t i = 0; rq && i < m; i++) {
             rq_eff[i] = rq[i];
@@ -2311,131 +2212,83 @@ extern "C" hz_status hz_ledger_select_batch(hz_ledger* l, size_t n_l1, const hz_
         }
         if (hz_status e = ledger_check_rq(who, m, txs, rq_eff.data())) return e;
     }
+    return HZ_OK;
+}
+
+extern "C" hz_status hz_ledger_select_batch(hz_ledger* l, size_t n_l1, const hz_l1tx* l1, const uint8_t* from_bjj, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs,
+                                            const hz_l2rq* rq, const int32_t* partner, uint32_t flags, uint32_t chain_id, uint32_t current_num_batch, size_t max_keep,
+                                            const hz_ledger_select_out* out) {
+    const char* who = "hz_ledger_select_batch";
+    LedgerRows r;
+    std::vector<hz_l2rq> rq_eff;
+    if (hz_status e = select_checks(l, who, n_l1, l1, from_bjj, m, txs, sigs, rq, partner, flags, chain_id, out, r, rq_eff)) return e;
+    const bool verify = (flags & HZ_LEDGER_VERIFY_SIGS) != 0, links = !rq_eff.empty();
     ledger_forget(l);
     HZ_HIP(hipSetDevice(l->device));
     hipStream_t s = ledger_stream(l);
-    if (run.n_creates)   // before the lookup: the new accounts' static fields into their plane slots, beyond the ledger's size
-        if (hz_status e = ledger_create_launch(l, run)) return e;
-    std::vector<uint64_t> found(m ? m : 1);
-    if (hz_status e = ledger_resolve(l, m, txs, sigs, true, found.data(), count)) return e;
-    std::vector<hz_l2tx> eff(txs, txs + m);
-    auto wants_receiver = [&](size_t i) { return txs[i].from_idx != 0 && txs[i].to_idx == 0 && ledger_mantissa(txs[i].amount_f) != 0; };
-    for (size_t i = 0; i < m; i++)
-        if (wants_receiver(i)) eff[i].to_idx = found[i];   // 0: reason 9
-    LedgerPlan& p = l->plan;
+    if (r.n_creates)
+        if (hz_status e = ledger_create_launch(l, n_l1, l1, from_bjj, r)) return e;
+    if (hz_status e = ledger_effective_receivers(l, who, n_l1, m, txs, nullptr, false, r)) return e;   // to_idx == 0 stays: reason 9
     SelectPlan sp;
-    if (hz_status e = select_plan(who, n_l1, eff_l1.data(), m, eff.data(), p, sp)) return e;
-    const size_t R = n_l1 + m;
+    if (hz_status e = select_plan(who, n_l1, r.l1, m, r.eff.data(), l->plan, sp)) return e;
     const uint32_t m32 = (uint32_t)m, L32 = (uint32_t)n_l1, n_slots = (uint32_t)sp.slot_account.size();
-
-    // ---- integer tables, one pinned block
-    Carve c;
-    const size_t o_tx = c.take((m ? m : 1) * sizeof(hz_l2tx)), o_sel = c.take(m * sizeof(SelectTxDev)), o_l1 = c.take(n_l1 * sizeof(LedgerL1Dev)),
-                 o_slot_acct = c.take((size_t)n_slots * 4), o_partner = c.take(partner ? m * 4 : 0);
-    const size_t ints_bytes = c.end;
-    HZ_HIP(l->h_ints.grow(ints_bytes));
-    uint8_t* hb = (uint8_t*)l->h_ints.p;
-    if (m) memcpy(hb + o_tx, txs, m * sizeof(hz_l2tx));
-    for (size_t i = 0; i < m; i++) {
-        SelectTxDev d{};
-        const hz_l2tx& t = txs[i];
-        if (t.from_idx != 0) {
-            const bool has_amount = ledger_mantissa(t.amount_f) != 0, exit = t.to_idx == HZ_LEDGER_EXIT_IDX, unresolved = wants_receiver(i) && found[i] == 0;
-            d.amount_f = t.amount_f;
-            d.nonce = t.nonce;
-            d.token_id = t.token_id;
-            d.user_fee = t.user_fee;
-            d.acct_s = (uint32_t)(t.from_idx - l->first_idx);
-            d.slot_s = (uint16_t)sp.slot_s[n_l1 + i];
-            d.slot_r = HZ_L1_NO_SLOT;
-            d.flags = (uint8_t)(SELECT_ACTIVE | (exit ? SELECT_EXIT : 0u) | (unresolved ? SELECT_UNRESOLVED : 0u));
-            if (has_amount && !exit && !unresolved) {
-                d.flags |= SELECT_RECEIVER;
-                d.acct_r = (uint32_t)(eff[i].to_idx - l->first_idx);
-                d.slot_r = (uint16_t)sp.slot_r[n_l1 + i];
-            }
-        }
-        ((SelectTxDev*)(hb + o_sel))[i] = d;
-        if (partner) ((int32_t*)(hb + o_partner))[i] = t.from_idx != 0 ? partner[i] : -1;
-    }
-    for (size_t i = 0; i < n_l1; i++) {
-        const hz_l1tx& t = eff_l1[i];
-        LedgerL1Dev d{};
-        d.amount_f = t.amount_f;
-        d.load_amount_f = t.load_amount_f;
-        d.token_id = t.token_id;
-        d.acct_s = (uint32_t)(t.from_idx - l->first_idx);
-        d.slot_s = (uint16_t)sp.slot_s[i];
-        d.slot_r = HZ_L1_NO_SLOT;
-        d.pos_s = d.pos_r = -1;
-        d.pos_x = t.to_idx == HZ_LEDGER_EXIT_IDX && ledger_mantissa(t.amount_f) != 0 ? 0 : -1;   // a forceExit with an amount: the exit leaf's token is the sender's
-        if (sp.slot_r[i] >= 0) {
-            d.acct_r = (uint32_t)(t.to_idx - l->first_idx);
-            d.slot_r = (uint16_t)sp.slot_r[i];
-        }
-        memcpy(d.from_eth, t.from_eth_addr, 20);
-        ((LedgerL1Dev*)(hb + o_l1))[i] = d;
-    }
-    for (uint32_t q = 0; q < n_slots; q++) ((uint32_t*)(hb + o_slot_acct))[q] = (uint32_t)(sp.slot_account[q] - l->first_idx);
-
-    // ---- device buffers: work = ops[R][14] words | header | kept[m] | verdict[m] | rq_offset[m]
-    Carve w;
-    const size_t w_ops = w.take((R ? R : 1) * HZ_SELECT_OP_WORDS * 4), w_hdr = w.take(16), w_kept = w.take(m * 4), w_verdict = w.take(m), w_off = w.take(m);
-    const size_t back_bytes = w.end - w_hdr;
-    HZ_HIP(l->ints.grow(ints_bytes));
-    HZ_HIP(l->work.grow(w.end));
+    SelectTables T;
+    SelectWork W;
+    T.layout(n_l1, m, n_slots, partner != nullptr);
+    W.layout(n_l1 + m, m);
+    const size_t back_bytes = W.end - W.hdr.at;
+    HZ_HIP(l->h_ints.grow(T.end));
+    T.fill(l->h_ints.p, r.l1, txs, r.eff.data(), sp.slot_s.data(), sp.slot_r.data(), sp.slot_account.data(), partner, l->first_idx);
+    HZ_HIP(l->ints.grow(T.end));
+    HZ_HIP(l->work.grow(W.end));
     HZ_HIP(l->h_sel.grow(back_bytes));
-    uint8_t* db = (uint8_t*)l->ints.p;
-    uint8_t* wb = (uint8_t*)l->work.p;
-    const hz_l2tx* d_txs = (const hz_l2tx*)(db + o_tx);
+    void *db = l->ints.p, *wb = l->work.p;
+    const hz_l2tx* d_txs = T.tx.dev(db);
     LedgerDrain drain;
     drain.s = s;
     drain.armed = true;
-    HZ_HIP(hipMemcpyAsync(l->ints.p, l->h_ints.p, ints_bytes, hipMemcpyHostToDevice, s));
+    HZ_HIP(hipMemcpyAsync(l->ints.p, l->h_ints.p, T.end, hipMemcpyHostToDevice, s));
     const uint8_t* d_sig_verdict = nullptr;
     if (verify || links) {
-        if (hz_status e = ledger_sig_prepare(l, m, sigs, s, verify)) return e;
+        if (hz_status e = ledger_sig_prepare(l, m, r.sigs, s, verify)) return e;
+        const hz_l2sig* d_sigs = (const hz_l2sig*)l->sig_in.p;
         if (links)
             if (hz_status e = ledger_rq_upload(l, m, rq_eff.data(), s)) return e;
         if (verify) {
-            HZ_HIP(hipEventRecord(l->es0, s));
-            HZ_HIP(launch_ledger_sig(d_txs, (const hz_l2sig*)l->sig_in.p, chain_id, current_num_batch, l->sig_dev[0], l->sig_dev[1], l->sig_dev[2], (const uint8_t*)l->planes.p,
-                                     l->b8_table.p, l->N, l->first_idx, nullptr, l->verdict_dev, m32, s, 0, links ? (const uint8_t*)l->rq_in.p : nullptr));
-            HZ_HIP(hipEventRecord(l->es1, s));
+            HZ_HIP(l->t_sig.begin(s));
+            HZ_HIP(launch_ledger_sig(d_txs, d_sigs, chain_id, current_num_batch, l->sig_dev[0], l->sig_dev[1], l->sig_dev[2], (const uint8_t*)l->planes.p, l->b8_table.p, l->N,
+                                     l->first_idx, nullptr, l->verdict_dev, m32, s, 0, links ? (const uint8_t*)l->rq_in.p : nullptr));
+            HZ_HIP(l->t_sig.end(s));
         } else if (m) {   // the V2 rows alone, for the link compare; no verdict yet
             HZ_HIP(hipMemsetAsync(l->verdict_dev, 0, m, s));
-            HZ_HIP(launch_ledger_sig_v2(d_txs, (const hz_l2sig*)l->sig_in.p, l->sig_dev[1], m32, s));
+            HZ_HIP(launch_ledger_sig_v2(d_txs, d_sigs, l->sig_dev[1], m32, s));
         }
         if (links) {
-            hipLaunchKernelGGL(k_ledger_select_rq, dim3((m32 + 63) / 64), dim3(64), 0, s, d_txs, (const hz_l2sig*)l->sig_in.p, (const uint8_t*)l->rq_in.p,
-                               (const uint8_t*)l->sig_dev[1], partner ? (const int32_t*)(db + o_partner) : (const int32_t*)nullptr, l->verdict_dev, m32);
+            hipLaunchKernelGGL(k_ledger_select_rq, dim3((m32 + 63) / 64), dim3(64), 0, s, d_txs, d_sigs, (const uint8_t*)l->rq_in.p, (const uint8_t*)l->sig_dev[1],
+                               partner ? T.partner.dev(db) : nullptr, l->verdict_dev, m32);
             HZ_HIP(hipGetLastError());
         }
         if (m) d_sig_verdict = l->verdict_dev;
     }
     const uint32_t cap = (uint32_t)std::min<size_t>(max_keep, HZ_SELECT_MAX_POOL);
-    HZ_HIP(hipEventRecord(l->esel0, s));
-    hipLaunchKernelGGL(k_ledger_select, dim3(1), dim3(256), 0, s, (const LedgerL1Dev*)(db + o_l1), (const SelectTxDev*)(db + o_sel), (const uint32_t*)(db + o_slot_acct),
-                       partner ? (const int32_t*)(db + o_partner) : (const int32_t*)nullptr, d_sig_verdict, (const uint8_t*)l->planes.p, (uint32_t*)(wb + w_ops),
-                       (uint32_t*)(wb + w_hdr), (uint32_t*)(wb + w_kept), wb + w_verdict, wb + w_off, l->N, L32, m32, n_slots, cap);
+    HZ_HIP(l->t_select.begin(s));
+    hipLaunchKernelGGL(k_ledger_select, dim3(1), dim3(256), 0, s, T.l1.dev(db), T.sel.dev(db), T.slot_acct.dev(db), partner ? T.partner.dev(db) : nullptr, d_sig_verdict,
+                       (const uint8_t*)l->planes.p, W.ops.dev(wb), W.hdr.dev(wb), W.kept.dev(wb), W.verdict.dev(wb), W.off.dev(wb), l->N, L32, m32, n_slots, cap);
     HZ_HIP(hipGetLastError());   // (a workgroup with more LDS than the device grants is refused here, not faulted)
-    HZ_HIP(hipEventRecord(l->esel1, s));
-    HZ_HIP(hipMemcpyAsync(l->h_sel.p, wb + w_hdr, back_bytes, hipMemcpyDeviceToHost, s));
+    HZ_HIP(l->t_select.end(s));
+    HZ_HIP(hipMemcpyAsync(l->h_sel.p, W.hdr.dev(wb), back_bytes, hipMemcpyDeviceToHost, s));
     HZ_HIP(hipStreamSynchronize(s));
     drain.armed = false;
-    float ms = 0;
-    HZ_HIP(hipEventElapsedTime(&ms, l->esel0, l->esel1));
-    l->select_ms = ms;
-    const uint8_t* back = (const uint8_t*)l->h_sel.p;
+    HZ_HIP(l->t_select.read(l->select_ms));
+    const uint8_t* back = (const uint8_t*)l->h_sel.p;   // the work buffer from the header on
     const uint32_t* hdr = (const uint32_t*)back;
-    if (hdr[2] != 0xFFFFFFFFu)
-        return set_err(HZ_ERR_INPUT, "%s: refused at index %u (L1 transaction %u), reason 5: %s", who, hdr[2], hdr[2], LEDGER_REASON[5]);
+    if (hdr[2] != 0xFFFFFFFFu) return ledger_refused(who, hdr[2], 5, n_l1 + m, n_l1);   // an L1 row
     const size_t n_kept = hdr[0];
     if (out->n_kept) *out->n_kept = n_kept;
     if (out->rounds) *out->rounds = hdr[1];
-    if (out->kept && n_kept) memcpy(out->kept, back + (w_kept - w_hdr), n_kept * 4);
-    if (out->verdict && m) memcpy(out->verdict, back + (w_verdict - w_hdr), m);
-    if (out->rq_offset && m) memcpy(out->rq_offset, back + (w_off - w_hdr), m);
-    for (size_t i = 0; out->aux_to_idx && i < m; i++) out->aux_to_idx[i] = wants_receiver(i) ? found[i] : 0;
+    if (out->kept && n_kept) memcpy(out->kept, back + (W.kept.at - W.hdr.at), n_kept * 4);
+    if (out->verdict && m) memcpy(out->verdict, back + (W.verdict.at - W.hdr.at), m);
+    if (out->rq_offset && m) memcpy(out->rq_offset, back + (W.off.at - W.hdr.at), m);
+    for (size_t i = 0; out->aux_to_idx && i < m; i++) out->aux_to_idx[i] = ledger_wants_receiver(txs[i]) ? r.eff[i].to_idx : 0;
     return HZ_OK;
 }

@@ -16,11 +16,31 @@ struct DevEvent {
     operator hipEvent_t() const { return e; }
 };
 
+// the device time between two recorded events, once the stream has been synchronised behind the second
+inline hipError_t elapsed_ms(hipEvent_t a, hipEvent_t b, double& ms) {
+    float f = 0;
+    const hipError_t e = hipEventElapsedTime(&f, a, b);
+    if (e == hipSuccess) ms = f;
+    return e;
+}
+
+// a pair of events around a stretch of a stream
+struct DevSpan {
+    DevEvent e0, e1;
+    hipError_t create() {
+        const hipError_t e = e0.create();
+        return e != hipSuccess ? e : e1.create();
+    }
+    hipError_t begin(hipStream_t s) { return hipEventRecord(e0, s); }
+    hipError_t end(hipStream_t s) { return hipEventRecord(e1, s); }
+    hipError_t read(double& ms) const { return elapsed_ms(e0, e1, ms); }
+};
+
 // a structure's device, its non-blocking stream and the device time of its last call: begin() .. end() on the stream, read by finish()
 struct Resident {
     int32_t device = 0;
     hipStream_t s = nullptr;
-    DevEvent e0, e1;
+    DevSpan span;
     double device_ms = 0.0;
     Resident() = default;
     Resident(const Resident&) = delete;
@@ -33,17 +53,14 @@ struct Resident {
         HZ_HIP(hipSetDevice(dev));
         device = dev;
         HZ_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        HZ_HIP(e0.create());
-        HZ_HIP(e1.create());
+        HZ_HIP(span.create());
         return HZ_OK;
     }
-    hipError_t begin() { return hipEventRecord(e0, s); }
-    hipError_t end() { return hipEventRecord(e1, s); }
+    hipError_t begin() { return span.begin(s); }
+    hipError_t end() { return span.end(s); }
     hz_status finish() {
         HZ_HIP(hipStreamSynchronize(s));
-        float ms = 0;
-        HZ_HIP(hipEventElapsedTime(&ms, e0, e1));
-        device_ms = ms;
+        HZ_HIP(span.read(device_ms));
         return HZ_OK;
     }
 };
