@@ -150,7 +150,10 @@ uint64_t hz_constraint_estimate(const hz_ctx* ctx);
  * for instance `instance`. For templates evaluated over n_instances, `instance` = -1 sets all
  * instances at once (`vals` = [n_instances][flat_len]). Values >= r are rejected. */
 hz_status hz_set_input(hz_ctx* ctx, int32_t instance, const char* name, const uint8_t* vals, size_t count);
-/* same, but `vals` already lives in device memory of ctx's device */
+/* same layout and counts, but `dvals` already lives in device memory of ctx's device. NOTHING is range-checked on this route: the
+ * caller guarantees canonical elements (< r), as the library's own *_dev outputs are; a witness computed from anything else means
+ * nothing and no later call reports it. The CHECKED routes from device memory are hz_inputs_upload / hz_inputs_stage
+ * (`packed` may be a device pointer): an element >= r there makes the next hz_witness_check answer HZ_ERR_INPUT. */
 hz_status hz_set_input_dev(hz_ctx* ctx, int32_t instance, const char* name, const void* dvals, size_t count, void* stream);
 /* forget which inputs were set (values are kept; calculateWitness semantics need a fresh set) */
 /* Replicate all input signals of instance `src` onto instance `dst`, device to device, on `stream`.
