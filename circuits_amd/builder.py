@@ -1092,6 +1092,56 @@ def ledger_select_batch_inputs(ledger, db_like, l1_txs, pool, n_tx, n_levels, ma
     return ledger_atomic_batch_inputs(ledger, db_like, l1_txs, rows, n_tx, n_levels, max_l1, max_fee, fee_tokens, fee_idxs, chain_id, host_outputs, verify), sel
 
 
+def ledger_packed_batch(ledger, ctx, db_like, l1_txs, l2_txs, fee_tokens, fee_idxs, chain_id, verify=False, instance=0, stage=True):
+    """ledger_atomic_batch_inputs' batch without the dictionary: the batch is applied with every array left on the device
+    (capi.Ledger.apply_resident: apply_batch_atomic on a growing ledger or where a transaction links, apply_batch_exits on a dense one),
+    capi.Ledger.main_inputs writes the packed input buffer of the RollupMain context `ctx` there, and -- stage=True -- Ctx.stage hands it to
+    `instance` device to device. The rows are taken as ledger_atomic_batch_inputs takes them (the rq fields of a linked transaction from
+    its target unless explicit; verify=True signs, and the ledger verifies); db_like.num_batch and, on a growing ledger, db_like.last_idx
+    are advanced. -> (the packed buffer's address, isAmountNullified per row, the new exit root, the new last idx); the buffer (a torch
+    tensor) is kept alive on the ledger object until the next call."""
+    names = dict(ctx.input_names())
+    n_tx, max_fee = names["fromIdx"], names["feeIdxs"]
+    n_levels = names["siblings1"] // n_tx - 1
+    if len(l1_txs) + len(l2_txs) > n_tx:
+        raise ValueError("batch full")
+    l1_txs, l2_txs = [dict(t) for t in l1_txs], [dict(t) for t in l2_txs]
+    for t in l1_txs + l2_txs:
+        if "amountF" not in t or "amount" in t:
+            t["amountF"] = fix2float(t.get("amount", 0))
+    n_l1 = len(l1_txs)
+    plan = list(fee_tokens) + [0] * (max_fee - len(fee_tokens))
+    idxs = list(fee_idxs) + [0] * (max_fee - len(fee_idxs))
+    padded = l2_txs + [{}] * (n_tx - n_l1 - len(l2_txs))
+    rows = l1_txs + l2_txs
+    for i, t in enumerate(l2_txs, n_l1):   # the rq fields a signer commits to, as _ledger_batch_inputs derives them
+        k = t.get("rqOffset", 0)
+        if k and "rqTxCompressedDataV2" not in t:
+            j = i + k if k <= 3 else i - (8 - k)
+            if not (n_l1 <= j < len(rows)):
+                raise ValueError("rqOffset %d of tx %d does not point at an L2 tx of this batch" % (k, i))
+            t["rqTxCompressedDataV2"] = build_tx_compressed_data_v2(rows[j])
+            t["rqToEthAddr"] = rows[j].get("toEthAddr", 0)
+            t["rqToBjjAy"] = rows[j].get("toBjjAy", 0)
+    if verify:
+        for t in padded:
+            if t.get("fromIdx", 0) and "signer" in t:
+                t.update(t["signer"].sign_msg(build_hash_sig(t, chain_id)))
+    growing = hasattr(ledger, "capacity")
+    atomic = growing or any(t.get("rqOffset", 0) for t in l2_txs)
+    old_last = db_like.last_idx
+    out = ledger.apply_resident(l1_txs, padded, plan, idxs, chain_id, db_like.num_batch + 1, n_sib=n_levels + 1, verify=verify, atomic=atomic)
+    addr, nbytes, buf = ledger.main_inputs(ctx, old_last)
+    ledger._packed_keep = buf
+    if stage:
+        ctx.stage(instance, addr, nbytes)
+    db_like.num_batch += 1
+    if growing:
+        db_like.last_idx = ledger.last_idx()
+    nullified = [(int(f) >> 1) & 1 for f in out["l1_flags"]] + [0] * (n_tx - n_l1)
+    return addr, nullified, int.from_bytes(out["new_exit_root"][0].tobytes(), "little"), db_like.last_idx
+
+
 RQ_SIGNALS = ("rqOffset", "rqTxCompressedDataV2", "rqToEthAddr", "rqToBjjAy")
 
 

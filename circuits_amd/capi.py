@@ -81,6 +81,7 @@ EXPORTS = [
     "hz_ledger_select_batch", "hz_ledger_plan_select", "hz_ledger_select_ms",
     "hz_ledger_exit_keep", "hz_ledger_exit_forget", "hz_ledger_exit_kept", "hz_ledger_exit_archive_stats", "hz_ledger_exit_root_of", "hz_ledger_withdraw_rows",
     "hz_ledger_withdraw_rows_dev", "hz_ledger_withdraw_ms", "hz_ledger_exit_keep_ms",
+    "hz_ledger_main_inputs", "hz_ledger_main_inputs_ms", "hz_ledger_plan_main_inputs",
 ]
 
 
@@ -196,6 +197,24 @@ WITHDRAW_SIGNALS = {"root_exit": "rootExit", "eth_addr": "ethAddr", "token_id": 
                     "siblings_state": "siblingsState"}
 WITHDRAW_MAX_ROWS = 1 << 20
 LEDGER_CREATE_ARRAYS = ("aux_from_idx", "is_old0_1", "old_key1", "old_value1", "out_idx_after", "new_last_idx")
+# hz_ledger_plan_main_inputs: the kind flags of the call (HZ_MI_*), a descriptor's kinds (HZ_MI_KIND_*) and sources (HZ_MI_SRC_*)
+MI_SIGS, MI_RQ, MI_EXITS, MI_CREATES, MI_AUX, MI_GROWING = 1, 2, 4, 8, 16, 32
+MI_KINDS = ("zero", "copy", "broadcast", "txCompressedData", "txCompressedDataV2", "amountF", "fromIdx", "toIdx", "toBjjAy", "toEthAddr", "maxNumBatch", "onChain",
+            "newAccount", "rqOffset", "rqTxCompressedDataV2", "rqToEthAddr", "rqToBjjAy", "s", "r8x", "r8y", "loadAmountF", "fromEthAddr", "fromBjjCompressed")
+MI_SRC_NONE, MI_SRC_OUT, MI_SRC_EXIT, MI_SRC_CREATE, MI_SRC_AUX_TO_IDX, MI_SRC_GLOBALS, MI_SRC_FEE_IDXS, MI_SRC_FEE_PLAN_TOKENS, MI_SRC_ROWS, MI_SRC_KEYS = (
+    0, 1, 32, 40, 48, 49, 50, 51, 52, 53)
+
+
+def mi_source_name(src):
+    """a descriptor's source as a word: an array of hz_ledger_out / _exit_out / _create_out by its name, or what of the request it reads"""
+    if MI_SRC_OUT <= src < MI_SRC_OUT + len(LEDGER_ARRAYS):
+        return LEDGER_ARRAYS[src - MI_SRC_OUT][0]
+    if MI_SRC_EXIT <= src < MI_SRC_EXIT + len(LEDGER_EXIT_ARRAYS):
+        return LEDGER_EXIT_ARRAYS[src - MI_SRC_EXIT]
+    if MI_SRC_CREATE <= src < MI_SRC_CREATE + len(LEDGER_CREATE_ARRAYS):
+        return LEDGER_CREATE_ARRAYS[src - MI_SRC_CREATE]
+    return {MI_SRC_NONE: None, MI_SRC_AUX_TO_IDX: "auxToIdx", MI_SRC_GLOBALS: "globals", MI_SRC_FEE_IDXS: "fee_idxs", MI_SRC_FEE_PLAN_TOKENS: "fee_plan_tokens",
+            MI_SRC_ROWS: "rows", MI_SRC_KEYS: "from_bjj"}[src]
 
 
 def from_bjj_array(l1_txs):
@@ -410,6 +429,10 @@ class Lib:
         c.hz_ledger_exit_root_of.argtypes = [vp, u32, vp]
         c.hz_ledger_withdraw_rows.argtypes = [vp, sz, vp, vp, ctypes.c_int32, vp]
         c.hz_ledger_withdraw_rows_dev.argtypes = [vp, vp]
+        c.hz_ledger_main_inputs.argtypes = [vp, vp, u64, vp, sz]
+        c.hz_ledger_plan_main_inputs.argtypes = [sz, vp, vp, vp, vp, u64, u32, u32, u32, u32, u32, vp, vp, vp, vp]
+        c.hz_ledger_main_inputs_ms.argtypes = [vp]
+        c.hz_ledger_main_inputs_ms.restype = ctypes.c_double
         for f in ("hz_ledger_device_ms", "hz_ledger_semantic_ms", "hz_ledger_sig_ms", "hz_ledger_resolve_ms", "hz_ledger_l1_ms", "hz_ledger_exit_ms", "hz_ledger_create_ms",
                   "hz_ledger_rq_ms", "hz_ledger_select_ms", "hz_ledger_withdraw_ms", "hz_ledger_exit_keep_ms"):
             getattr(c, f).argtypes = [vp]
@@ -639,6 +662,24 @@ class Lib:
         out["account"] = acct[:n_ev.value]
         out.update({n: a[:n_x.value] for n, a in ops.items()})
         return out
+
+    def ledger_plan_main_inputs(self, layout, n_tx, n_levels, max_l1, max_fee, flags=0):
+        """hz_ledger_plan_main_inputs: the descriptor table hz_ledger_main_inputs makes of a packed layout -- (total bytes, [(name, byte
+        offset, element bytes, flat length)]) as Ctx.packed_layout gives it -- for RollupMain(n_tx, n_levels, max_l1, max_fee) and a call
+        of the kind `flags` says (MI_SIGS | MI_RQ | MI_EXITS | MI_CREATES | MI_AUX | MI_GROWING)
+        -> {signal: (kind word of MI_KINDS, source word of mi_source_name, first row, rows)}"""
+        import numpy as np
+        total, sigs = layout
+        n = len(sigs)
+        names = (ctypes.c_char_p * max(n, 1))(*[nm.encode() for nm, _, _, _ in sigs])
+        offs = np.array([o for _, o, _, _ in sigs] or [0], dtype=np.uint64)
+        widths = np.array([w for _, _, w, _ in sigs] or [0], dtype=np.uint32)
+        lens = np.array([ln for _, _, _, ln in sigs] or [0], dtype=np.uint64)
+        kind, src = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32)
+        r0, rows = np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint64)
+        self._check(self.c.hz_ledger_plan_main_inputs(n, ctypes.addressof(names), offs.ctypes.data, widths.ctypes.data, lens.ctypes.data, total, n_tx, n_levels, max_l1,
+                                                      max_fee, flags, kind.ctypes.data, src.ctypes.data, r0.ctypes.data, rows.ctypes.data))
+        return {nm: (MI_KINDS[kind[i]], mi_source_name(int(src[i])), int(r0[i]), int(rows[i])) for i, (nm, _, _, _) in enumerate(sigs)}
 
     def host_alloc(self, nbytes):
         """pinned host memory for hz_inputs_upload (address as int); free with host_free"""
@@ -955,6 +996,7 @@ class _Resident:
     def _open(self, L, *args):
         self.L = L
         self.h = ctypes.c_void_p()
+        self.device = args[0] if args else 0   # every _create takes the device first
         L._check(getattr(L.c, self._create)(*args, ctypes.byref(self.h)))
 
     def close(self):
@@ -1294,6 +1336,58 @@ class Ledger(_Resident):
             rq = l2rq_array(txs)
         return self._apply_batch_creates(l1_txs, txs, fee_plan_tokens, fee_idxs, chain_id, current_num_batch, n_sib, verify, aux_to_idx, outputs, into, sigs, from_bjj,
                                          atomic=True, rq=rq if rq is not False else None)
+
+    def apply_resident(self, l1_txs, txs, fee_plan_tokens, fee_idxs, chain_id, current_num_batch, n_sib=None, verify=False, atomic=False, sigs=None, from_bjj=None,
+                       rq=None):
+        """apply_batch_atomic (atomic=True) or apply_batch_exits with every array left on the device -- what main_inputs packs -- but the
+        few bytes the caller of a packed batch still needs on the host: -> {"l1_flags": uint8 [n_l1], "new_exit_root": [1, 32]}. Rows
+        as dictionaries, or prebuilt: l1_txs an hz_l1tx array with from_bjj, txs an hz_l2tx array with sigs (False: none) and rq"""
+        import numpy as np
+        n_sib = self.k if n_sib is None else n_sib
+        prebuilt = isinstance(l1_txs, ctypes.Array)
+        l1 = l1_txs if prebuilt else l1tx_array(l1_txs)
+        n_l1, m = len(l1_txs), len(txs)
+        arr = txs if isinstance(txs, ctypes.Array) else l2tx_array(txs)
+        if not isinstance(txs, ctypes.Array):
+            sigs = l2sig_array(txs) if sigs is None else sigs
+            rq = l2rq_array(txs) if rq is None and atomic else rq
+        plan = np.ascontiguousarray(fee_plan_tokens, dtype=np.uint32)
+        idxs = np.ascontiguousarray(fee_idxs, dtype=np.uint64)
+        if idxs.size != plan.size:
+            raise ValueError("fee_plan_tokens and fee_idxs differ in length")
+        flags, root = np.zeros(max(n_l1, 1), dtype=np.uint8), np.zeros((1, 32), dtype=np.uint8)
+        exit_ptrs = (ctypes.c_void_p * len(LEDGER_EXIT_ARRAYS))()
+        exit_ptrs[len(LEDGER_EXIT_ARRAYS) - 1] = root.ctypes.data
+        p_sigs = ctypes.addressof(sigs) if sigs not in (None, False) else None
+        tail = [LEDGER_VERIFY_SIGS if verify else 0, None, chain_id, current_num_batch, plan.size, plan.ctypes.data, idxs.ctypes.data, n_sib, None, None, None,
+                flags.ctypes.data if n_l1 else None, ctypes.addressof(exit_ptrs)]
+        if atomic:
+            bjj = from_bjj if from_bjj is not None or prebuilt else from_bjj_array(l1_txs)
+            self.L._check(self.L.c.hz_ledger_apply_batch_atomic(self.h, n_l1, ctypes.addressof(l1), bjj.ctypes.data if bjj is not None else None, m, ctypes.addressof(arr),
+                                                                p_sigs, ctypes.addressof(rq) if rq not in (None, False) else None, *tail, None))
+        else:
+            self.L._check(self.L.c.hz_ledger_apply_batch_exits(self.h, n_l1, ctypes.addressof(l1), m, ctypes.addressof(arr), p_sigs, *tail))
+        return {"l1_flags": flags[:n_l1], "new_exit_root": root}
+
+    def main_inputs(self, ctx, old_last_idx, d_packed=None):
+        """hz_ledger_main_inputs: the packed input buffer of one instance of the RollupMain context `ctx` for the batch the last apply
+        call (any but apply_l2) applied, written on the device. d_packed: the address of ctx.packed_layout()[0] bytes of device memory
+        (a slot of a larger buffer, say), default a fresh torch.uint8 CUDA tensor. -> (address, bytes, the tensor or None): what
+        Ctx.stage / stage_range / upload take"""
+        nbytes = self.L.c.hz_inputs_packed_bytes(ctx.h)
+        if not nbytes:
+            raise HzError(2, self.L.c.hz_last_error().decode())
+        buf = None
+        if d_packed is None:
+            import torch
+            buf = torch.empty(nbytes, dtype=torch.uint8, device="cuda:%d" % self.device)
+            d_packed = buf.data_ptr()
+        self.L._check(self.L.c.hz_ledger_main_inputs(self.h, ctx.h, old_last_idx, d_packed, nbytes))
+        return d_packed, nbytes, buf
+
+    def main_inputs_ms(self):
+        """device time of k_ledger_main_inputs in the last main_inputs"""
+        return self.L.c.hz_ledger_main_inputs_ms(self.h)
 
     def rq_ms(self):
         """device time of the link kernel of the last apply_batch_atomic / verify_l2_atomic (0.0 when none ran)"""

@@ -1412,6 +1412,11 @@ void hz::ctx_geometry(const hz_ctx* c, CtxGeom& g) {
     g.device = c->device; g.s_main = c->s_main; g.wit = c->wit.p;
 }
 
+void hz::ctx_shape(const hz_ctx* c, CtxShape& s) {
+    const Params& p = c->lo.p;
+    s.tmpl = p.tmpl; s.n_tx = p.nTx; s.n_levels = p.L; s.max_l1 = p.maxL1; s.max_fee = p.F; s.device = c->device;
+}
+
 // gather `count` elements of the per-instance (virtual) witness of instance `inst` into a dense buffer
 struct GatherArgs { const uint4* wit; uint4* out; uint64_t first, count; uint32_t inst, nsec; SecMap sec[4]; };
 __global__ void k_gather_virtual(const GatherArgs a) {

@@ -19,6 +19,11 @@ struct CtxGeom {
     const void* wit = nullptr;
 };
 void ctx_geometry(const hz_ctx* c, CtxGeom& g);
+// what ledger.hip (hz_ledger_main_inputs) asks of a context before it writes a packed input buffer for it: the template and its parameters
+struct CtxShape {
+    int tmpl = 0, n_tx = 0, n_levels = 0, max_l1 = 0, max_fee = 0, device = 0;
+};
+void ctx_shape(const hz_ctx* c, CtxShape& s);
 // The export's scratch belongs to the CONTEXT, not to the map: two contexts that export through one map (each on its own stream) must
 // not share the derived-value buffer or the staging vector of the host deliveries (a map's device plan holds tables only).
 struct ExportScratch {

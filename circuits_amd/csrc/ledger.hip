@@ -61,7 +61,9 @@
 #include "ledger_rq.h"
 #include "ledger_select.h"
 #include "ledger_archive.h"
+#include "ledger_inputs.h"
 #include "ledger_tables.h"
+#include "ctx_internal.h"
 #include "smt_internal.h"
 #include "smt_plan.h"
 
@@ -330,6 +332,50 @@ __global__ __launch_bounds__(64) void k_ledger_rq(const hz_l2tx* __restrict__ tx
     }
 }
 
+// RollupMain's packed inputs (ledger_inputs.h): one launch over the descriptor table, a block range per signal found by
+// bisection as k_unpack_inputs does. A lane writes one 32-byte element as two 16-byte stores -- a row of a source array, one element of it,
+// zeros, or a signal packed from the uploaded rows (txs: the R rows as the per-row kernels read them, l1 / crow: the L1 run's and the create
+// rows' tables, sigs / rq: the m L2 rows') -- or, for the bit signal, sixteen one-byte elements as one 16-byte store: consecutive lanes,
+// consecutive addresses. Every destination lies inside the signal's range of the layout, which the host has checked against the buffer
+__global__ __launch_bounds__(256) void k_ledger_main_inputs(const MainInputsDesc* __restrict__ desc, uint32_t n_desc, uint8_t* __restrict__ dst,
+                                                            const hz_l2tx* __restrict__ txs, const LedgerL1Dev* __restrict__ l1,
+                                                            const LedgerCreateRow* __restrict__ crow, const hz_l2sig* __restrict__ sigs,
+                                                            const uint8_t* __restrict__ rq, const uint8_t* __restrict__ keys, uint32_t n_l1, uint32_t m,
+                                                            uint32_t chain_id) {
+    uint32_t lo = 0, hi = n_desc - 1;   // the last signal whose first block is not beyond this one: an empty signal never wins
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi + 1) >> 1;
+        if (desc[mid].first_block <= blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    const MainInputsDesc d = desc[lo];
+    const uint64_t t = (uint64_t)(blockIdx.x - d.first_block) * 256 + threadIdx.x;
+    const uint64_t elems = (uint64_t)d.outer * d.inner;
+    if (d.ebytes == 1) {   // inner == 256 bits a row, 16 lanes a row
+        if (t * 16 >= elems) return;
+        const uint32_t row = (uint32_t)(t >> 4), g = (uint32_t)t & 15u;
+        uint32_t w = 0;
+        if (keys && row < n_l1) w = ((const __attribute__((address_space(1))) uint32_t*)keys)[(size_t)row * 8 + (g >> 1)];
+        const uint32_t half = mi_half(w, g);
+        const hz_u32x4 v = {mi_bits4(half, 0), mi_bits4(half, 1), mi_bits4(half, 2), mi_bits4(half, 3)};
+        *(hz_g_u32x4*)(dst + d.dst_off + t * 16) = v;
+        return;
+    }
+    if (t >= elems) return;
+    Fc v = fc_zero();
+    if (d.kind == HZ_MI_KIND_COPY) {
+        v = load_fr(d.src + t * 32);
+    } else if (d.kind == HZ_MI_KIND_BROADCAST) {
+        v = load_fr(d.src);
+    } else if (d.kind != HZ_MI_KIND_ZERO) {   // inner == 1: t is the row
+        const uint32_t i = (uint32_t)t;
+        if (i < n_l1)
+            v = mi_l1_value(d.kind, chain_id, txs[i], l1[i], crow != nullptr && crow[i].aux_from != 0);
+        else
+            v = mi_l2_value(d.kind, chain_id, txs[i], sigs[i - n_l1], rq, i - n_l1, m);
+    }
+    store_fr(dst + d.dst_off + t * 32, v);
+}
+
 static const char* const LEDGER_REASON[HZ_LEDGER_REASONS] = {"", "the sender's token is not the transaction's", "the nonce is not the sender's current nonce",
                                              "the sender's balance is below amount + fee", "the receiver's token is not the transaction's",
                                              "a new balance reaches 2^192", "the fee account's token is not the slot's plan token",
@@ -384,6 +430,21 @@ struct LedgerArchive {
     double keep_ms = 0.0, withdraw_ms = 0.0;
     uint8_t* rows_dev[HZ_WITHDRAW_ARRAYS] = {};
     bool have_rows = false;
+};
+
+// what hz_ledger_main_inputs needs of the last successful apply call with a chain id beside what lies in device memory: the shape, the
+// kind of call, where the row tables lie in the integer block, and the part of the request no kernel of the apply reads
+struct LedgerMainCall {
+    bool valid = false;
+    size_t n_l1 = 0, m = 0, F = 0, n_sib = 0;
+    uint32_t chain_id = 0, current_num_batch = 0, flags = 0;   // HZ_MI_*
+    uint64_t last_before = 0;                                  // the ledger's last idx before the batch
+    Span<hz_l2tx> tx;
+    Span<LedgerL1Dev> l1;
+    Span<LedgerCreateRow> crow;
+    std::vector<uint8_t> keys;   // from_bjj, [n_l1][32], empty: none given
+    std::vector<uint64_t> fee_idxs;
+    std::vector<uint32_t> plan_tokens;
 };
 
 struct hz_ledger {
@@ -451,6 +512,13 @@ struct hz_ledger {
     double select_ms = 0.0;
     // exit trees of earlier batches (hz_ledger_exit_keep)
     std::unique_ptr<LedgerArchive> archive;
+    // RollupMain's packed inputs of the last apply (hz_ledger_main_inputs): what of the request the device does not hold,
+    // the descriptor table's upload
+    LedgerMainCall main_call;
+    DevBuf mi_in;
+    PinnedBuf h_mi;
+    DevSpan t_mi;   // around k_ledger_main_inputs
+    double mi_ms = 0.0;
     ~hz_ledger() {
         archive.reset();
         if (exit) hz_smt_destroy(exit);
@@ -492,6 +560,7 @@ static void ledger_forget(hz_ledger* l) {
     l->l1_ms = 0.0;
     l->create_ms = 0.0;
     if (l->archive) l->archive->have_rows = false;
+    l->main_call.valid = false;
 }
 
 // a reload starts a new history: no exit tree of the old one is kept
@@ -709,7 +778,7 @@ static hz_status ledger_open(hz_ledger* l) {
     HZ_HIP(hipSetDevice(l->device));
     HZ_HIP(l->planes.alloc((size_t)4 * l->N * 32));
     HZ_HIP(l->h_fail.grow(64));
-    for (DevSpan* t : {&l->t_semantic, &l->t_sig, &l->t_resolve, &l->t_l1, &l->t_exit_scan, &l->t_exit_rows, &l->t_create, &l->t_create_pack, &l->t_rq, &l->t_select})
+    for (DevSpan* t : {&l->t_semantic, &l->t_sig, &l->t_resolve, &l->t_l1, &l->t_exit_scan, &l->t_exit_rows, &l->t_create, &l->t_create_pack, &l->t_rq, &l->t_select, &l->t_mi})
         HZ_HIP(t->create());
     HZ_HIP(l->e_done.create());
     HZ_HIP(l->e_exit_tree.create());
@@ -1074,6 +1143,7 @@ extern "C" hz_status hz_ledger_resolve_l2(hz_ledger* l, size_t m, const hz_l2tx*
     if (hz_status e = ledger_ready(l, who)) return e;
     if (m && (!txs || !sigs || !aux_to_idx_out)) return set_err(HZ_ERR_ARG, "%s: null argument", who);
     if (m > HZ_LEDGER_MAX_TX) return set_err(HZ_ERR_ARG, "%s: %zu transactions in one call (at most %u)", who, m, HZ_LEDGER_MAX_TX);
+    l->main_call.valid = false;   // hz_ledger_main_inputs packs the batch of the ledger's LAST call (the *_dev getters are not touched here)
     return ledger_resolve(l, m, txs, sigs, false, aux_to_idx_out, l->live);
 }
 
@@ -1500,6 +1570,25 @@ static hz_status ledger_apply_copy_out(LedgerApply& a) {
     return HZ_OK;
 }
 
+// what hz_ledger_main_inputs will need of this call: host copies of a few kilobytes, no device work
+static void ledger_main_call_keep(LedgerApply& a) {
+    const LedgerCall& c = a.c;
+    LedgerMainCall& k = a.l->main_call;
+    k.n_l1 = c.n_l1, k.m = c.m, k.F = c.F, k.n_sib = c.n_sib;
+    k.chain_id = c.chain_id, k.current_num_batch = c.current_num_batch;
+    k.flags = (c.sigs ? HZ_MI_SIGS : 0u) | (a.links ? HZ_MI_RQ : 0u) | (c.exits ? HZ_MI_EXITS : 0u) | (c.creates ? HZ_MI_CREATES : 0u) | (c.by_addr ? HZ_MI_AUX : 0u) |
+              (a.growing ? HZ_MI_GROWING : 0u);
+    k.last_before = a.new_last - a.rows.n_creates;
+    k.tx = a.T.tx, k.l1 = a.T.l1, k.crow = a.T.crow;
+    if (c.from_bjj && c.n_l1)
+        k.keys.assign(c.from_bjj, c.from_bjj + c.n_l1 * 32);
+    else
+        k.keys.clear();
+    k.fee_idxs.assign(c.fee_idxs, c.fee_idxs + c.F);
+    k.plan_tokens.assign(c.plan_tokens, c.plan_tokens + c.F);
+    k.valid = true;
+}
+
 // stage 8: the trees' updates finished -- from there the created accounts exist --, the times, what the getters may hand out
 static hz_status ledger_apply_finish(LedgerApply& a) {
     hz_ledger* l = a.l;
@@ -1556,6 +1645,7 @@ static hz_status ledger_apply_finish(LedgerApply& a) {
         HZ_HIP(l->t_sig.read(l->sig_ms));
         l->have_sig_outputs = true;
     }
+    if (c.verify || c.by_addr) ledger_main_call_keep(a);   // every call but hz_ledger_apply_l2: it has a chain id, and the sigs are uploaded
     return HZ_OK;
 }
 
@@ -2290,5 +2380,138 @@ extern "C" hz_status hz_ledger_select_batch(hz_ledger* l, size_t n_l1, const hz_
     if (out->verdict && m) memcpy(out->verdict, back + (W.verdict.at - W.hdr.at), m);
     if (out->rq_offset && m) memcpy(out->rq_offset, back + (W.off.at - W.hdr.at), m);
     for (size_t i = 0; out->aux_to_idx && i < m; i++) out->aux_to_idx[i] = ledger_wants_receiver(txs[i]) ? r.eff[i].to_idx : 0;
+    return HZ_OK;
+}
+
+// ---- RollupMain's packed inputs of the applied batch -----------------------------------------------------------------------
+extern "C" double hz_ledger_main_inputs_ms(const hz_ledger* l) { return l ? l->mi_ms : 0.0; }
+
+extern "C" hz_status hz_ledger_plan_main_inputs(size_t n_signals, const char* const* names, const uint64_t* offsets, const uint32_t* widths, const uint64_t* flat_lens,
+                                                uint64_t bytes, uint32_t n_tx, uint32_t n_levels, uint32_t max_l1_tx, uint32_t max_fee_tx, uint32_t flags,
+                                                uint32_t* kind_out, uint32_t* source_out, uint64_t* first_row_out, uint64_t* rows_out) {
+    const char* who = "hz_ledger_plan_main_inputs";
+    if (!names || !offsets || !widths || !flat_lens) return set_err(HZ_ERR_ARG, "%s: null argument", who);
+    MiShape shape;
+    shape.n_tx = n_tx, shape.n_levels = n_levels, shape.max_l1 = max_l1_tx, shape.max_fee = max_fee_tx;
+    std::vector<MiSignal> sig;
+    const std::string err = mi_plan(n_signals, names, offsets, widths, flat_lens, bytes, shape, flags, sig);
+    if (!err.empty()) return set_err(HZ_ERR_ARG, "%s: %s", who, err.c_str());
+    for (size_t i = 0; i < n_signals; i++) {
+        if (kind_out) kind_out[i] = sig[i].kind;
+        if (source_out) source_out[i] = sig[i].source;
+        if (first_row_out) first_row_out[i] = sig[i].r0;
+        if (rows_out) rows_out[i] = sig[i].rows;
+    }
+    return HZ_OK;
+}
+
+// the first byte a COPY / BROADCAST descriptor reads: the array the apply left (or the call's own upload, at `up`) from row r0
+static const uint8_t* ledger_mi_source(const hz_ledger* l, const MiSignal& d, const uint8_t* up_globals, const uint8_t* up_fee_idxs, const uint8_t* up_tokens) {
+    const uint8_t* base = nullptr;
+    if (d.source >= HZ_MI_SRC_OUT && d.source < HZ_MI_SRC_OUT + HZ_LEDGER_ARRAYS)
+        base = l->out_dev.a[d.source - HZ_MI_SRC_OUT];
+    else if (d.source >= HZ_MI_SRC_EXIT && d.source < HZ_MI_SRC_EXIT + HZ_LEDGER_EXIT_ARRAYS)
+        base = l->exit_dev[d.source - HZ_MI_SRC_EXIT];
+    else if (d.source >= HZ_MI_SRC_CREATE && d.source < HZ_MI_SRC_CREATE + HZ_LEDGER_CREATE_ARRAYS)
+        base = l->create_dev[d.source - HZ_MI_SRC_CREATE];
+    else if (d.source == HZ_MI_SRC_AUX_TO_IDX)
+        base = (const uint8_t*)l->aux_rows.p;
+    else if (d.source == HZ_MI_SRC_GLOBALS)
+        base = up_globals;
+    else if (d.source == HZ_MI_SRC_FEE_IDXS)
+        base = up_fee_idxs;
+    else if (d.source == HZ_MI_SRC_FEE_PLAN_TOKENS)
+        base = up_tokens;
+    return base ? base + d.r0 * d.inner * 32 : nullptr;
+}
+
+extern "C" hz_status hz_ledger_main_inputs(hz_ledger* l, const hz_ctx* ctx, uint64_t old_last_idx, void* d_packed, size_t bytes) {
+    const char* who = "hz_ledger_main_inputs";
+    if (!l || !ctx || !d_packed) return set_err(HZ_ERR_ARG, "%s: null argument", who);
+    const LedgerMainCall& k = l->main_call;
+    if (!k.valid || !l->have_outputs)
+        return set_err(HZ_ERR_ARG, "%s: no successful apply call with a chain id (every one but hz_ledger_apply_l2) since the ledger's last other call", who);
+    CtxShape cs;
+    ctx_shape(ctx, cs);
+    if (cs.tmpl != HZ_T_ROLLUP_MAIN) return set_err(HZ_ERR_ARG, "%s: the context is not a rollup-main context", who);
+    if (cs.device != l->device) return set_err(HZ_ERR_ARG, "%s: the context lies on device %d, the ledger on device %d", who, cs.device, l->device);
+    if (k.n_l1 + k.m != (size_t)cs.n_tx || k.n_l1 > (size_t)cs.max_l1 || k.F != (size_t)cs.max_fee || k.n_sib != (size_t)cs.n_levels + 1)
+        return set_err(HZ_ERR_ARG, "%s: the applied batch (n_l1 = %zu, m = %zu, F = %zu, n_sib = %zu) does not fill RollupMain(%d, %d, %d, %d)", who, k.n_l1, k.m, k.F,
+                       k.n_sib, cs.n_tx, cs.n_levels, cs.max_l1, cs.max_fee);
+    const uint64_t packed = hz_inputs_packed_bytes(ctx);
+    if (!packed) return HZ_ERR_HIP;   // (its own message stands)
+    if (bytes != packed) return set_err(HZ_ERR_ARG, "%s: bytes = %zu, the packed inputs of the context take %llu", who, bytes, (unsigned long long)packed);
+    if ((uintptr_t)d_packed & 31u) return set_err(HZ_ERR_ARG, "%s: d_packed is not 32-byte aligned", who);
+    if ((k.flags & HZ_MI_GROWING) && old_last_idx != k.last_before)
+        return set_err(HZ_ERR_ARG, "%s: old_last_idx = %llu, the ledger's last idx before the batch was %llu", who, (unsigned long long)old_last_idx,
+                       (unsigned long long)k.last_before);
+    // the layout through the context's own getters, then the table
+    const int32_t n = hz_input_count(ctx);
+    std::vector<const char*> names(n);
+    std::vector<uint64_t> offsets(n), lens(n);
+    std::vector<uint32_t> widths(n);
+    for (int32_t i = 0; i < n; i++) {
+        names[i] = hz_input_name(ctx, i, &lens[i]);
+        offsets[i] = hz_input_packed_offset(ctx, i);
+        widths[i] = (uint32_t)hz_input_packed_width(ctx, i);
+    }
+    MiShape shape;
+    shape.n_tx = (uint32_t)cs.n_tx, shape.n_levels = (uint32_t)cs.n_levels, shape.max_l1 = (uint32_t)cs.max_l1, shape.max_fee = (uint32_t)cs.max_fee;
+    std::vector<MiSignal> sig;
+    const std::string err = mi_plan((size_t)n, names.data(), offsets.data(), widths.data(), lens.data(), packed, shape, k.flags, sig);
+    if (!err.empty()) return set_err(HZ_ERR_ARG, "%s: the context's packed layout: %s", who, err.c_str());
+    // one upload: the descriptors | old_last_idx, chain id, current_num_batch | fee_idxs | fee_plan_tokens as elements | the keys
+    const size_t F = k.F, at_glob = ((size_t)n * sizeof(MainInputsDesc) + 31) & ~(size_t)31, at_idx = at_glob + 96, at_tok = at_idx + F * 32, at_keys = at_tok + F * 32;
+    const size_t up = at_keys + k.keys.size();
+    HZ_HIP(hipSetDevice(l->device));
+    HZ_HIP(l->h_mi.grow(up));
+    HZ_HIP(l->mi_in.grow(up));
+    uint8_t* h = (uint8_t*)l->h_mi.p;
+    const uint8_t* dv = (const uint8_t*)l->mi_in.p;
+    memset(h + at_glob, 0, at_keys - at_glob);
+    memcpy(h + at_glob, &old_last_idx, 8);
+    memcpy(h + at_glob + 32, &k.chain_id, 4);
+    memcpy(h + at_glob + 64, &k.current_num_batch, 4);
+    for (size_t j = 0; j < F; j++) {
+        memcpy(h + at_idx + j * 32, &k.fee_idxs[j], 8);
+        memcpy(h + at_tok + j * 32, &k.plan_tokens[j], 4);
+    }
+    if (!k.keys.empty()) memcpy(h + at_keys, k.keys.data(), k.keys.size());
+    MainInputsDesc* hd = (MainInputsDesc*)h;
+    uint32_t blocks = 0;
+    for (int32_t i = 0; i < n; i++) {
+        const MiSignal& d = sig[i];
+        MainInputsDesc o{};
+        o.dst_off = offsets[i];
+        o.src = ledger_mi_source(l, d, dv + at_glob, dv + at_idx, dv + at_tok);
+        o.kind = d.kind, o.ebytes = d.width, o.outer = (uint32_t)d.rows, o.inner = d.inner, o.first_block = blocks;
+        if ((d.kind == HZ_MI_KIND_COPY || d.kind == HZ_MI_KIND_BROADCAST) && !o.src) return set_err(HZ_ERR_ARG, "%s: signal %s has no source", who, names[i]);
+        hd[i] = o;
+        blocks += mi_blocks(d);
+    }
+    hipStream_t s = ledger_stream(l);
+    HZ_HIP(hipMemcpyAsync(l->mi_in.p, h, up, hipMemcpyHostToDevice, s));
+    {   // what no signal covers: the layout's alignment gaps and its tail
+        std::vector<std::pair<uint64_t, uint64_t>> range;
+        for (int32_t i = 0; i < n; i++) range.push_back({offsets[i], offsets[i] + lens[i] * widths[i]});
+        std::sort(range.begin(), range.end());
+        uint64_t at = 0;
+        for (size_t q = 0; q <= range.size(); q++) {
+            const uint64_t next = q < range.size() ? range[q].first : packed;
+            if (next > at) HZ_HIP(hipMemsetAsync((uint8_t*)d_packed + at, 0, next - at, s));
+            if (q < range.size()) at = std::max(at, range[q].second);
+        }
+    }
+    const uint8_t* db = (const uint8_t*)l->ints.p;
+    HZ_HIP(l->t_mi.begin(s));
+    if (blocks) {
+        hipLaunchKernelGGL(k_ledger_main_inputs, dim3(blocks), dim3(256), 0, s, (const MainInputsDesc*)dv, (uint32_t)n, (uint8_t*)d_packed, k.tx.dev((void*)db),
+                           k.l1.dev((void*)db), (k.flags & HZ_MI_CREATES) ? k.crow.dev((void*)db) : nullptr, (const hz_l2sig*)l->sig_in.p,
+                           (k.flags & HZ_MI_RQ) ? (const uint8_t*)l->rq_in.p : nullptr, k.keys.empty() ? nullptr : dv + at_keys, (uint32_t)k.n_l1, (uint32_t)k.m, k.chain_id);
+        HZ_HIP(hipGetLastError());
+    }
+    HZ_HIP(l->t_mi.end(s));
+    HZ_HIP(hipStreamSynchronize(s));
+    HZ_HIP(l->t_mi.read(l->mi_ms));
     return HZ_OK;
 }

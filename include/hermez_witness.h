@@ -706,10 +706,42 @@ hz_status hz_smt_plan(size_t m, const uint64_t* key, size_t n_sib, uint32_t* dep
  *                       account is given with its auxFromIdx in from_idx's place, from_idx == 0 is HZ_ERR_ARG); and, given kept_in[m], the closure step alone --
  *                       forced_out[m] and rq_offset_out[m] -- by the routine the kernel runs. Every output may be NULL
  *   hz_ledger_select_ms device time of k_ledger_select in the last hz_ledger_select_batch
+ * MAIN INPUTS. After a successful apply call that carried a chain id -- every one but hz_ledger_apply_l2 -- and before the
+ * ledger's next call, hz_ledger_main_inputs writes the PACKED input buffer (hz_inputs_packed_bytes, above) of one instance of a
+ * RollupMain(nTx, nLevels, maxL1Tx, maxFeeTx) context on the ledger's device into device memory of the caller: every input signal, in
+ * hz_input_name order and at hz_input_packed_offset, byte for byte what the host route builds from the same request and the apply's
+ * host outputs. The state-dependent signals are copied from where the apply left them (imStateRoot / imAccFeeOut / imExitRoot / imOutIdx
+ * the first nTx - 1 rows of their arrays, imInitStateRootFee row nTx - 1 of state_root_after, imStateRootFee the first maxFeeTx - 1 rows;
+ * zeros for the exit signals of a call without exits, zeros and old_last_idx in every imOutIdx row for a call without creates); oldLastIdx
+ * is old_last_idx, oldStateRoot, globalChainID, currentNumBatch, feeIdxs and feePlanTokens are the call's; the transaction-only signals
+ * are packed from the uploaded rows: an L1 row has onChain 1, the caller's fromIdx (0 and newAccount 1 on a create row), toIdx,
+ * amountF, loadAmountF, fromEthAddr, txCompressedData = the signature constant | chain id << 32 | fromIdx << 48 | toIdx << 96 | tokenID
+ * << 144, and the 256 bits of from_bjj[i] in fromBjjCompressed (zeros for from_bjj == NULL); an L2 row has txCompressedData and
+ * txCompressedDataV2 as the signature kernels pack them, the caller's amountF, fromIdx and toIdx, toBjjAy, toEthAddr, maxNumBatch, s, r8x
+ * and r8y of its hz_l2sig entry (zeros for sigs == NULL), rqOffset and the three rq fields of its hz_l2rq entry (zeros for rq == NULL); a NOP row is
+ * zero but for the constant and the chain id; imOnChain is onChain without its last row.
+ *   hz_ledger_main_inputs  bytes == hz_inputs_packed_bytes(ctx); d_packed is device memory, 32-byte aligned. Every byte of [0, bytes) is
+ *                       written. HZ_ERR_ARG: a null argument; no successful apply call with a chain id since the ledger's last other
+ *                       call (none yet, a refused one, hz_ledger_apply_l2, or a call that invalidates the *_dev outputs); ctx is no
+ *                       rollup-main context or lies on another device; n_l1 + m != nTx, n_l1 > maxL1Tx, F != maxFeeTx, n_sib !=
+ *                       nLevels + 1; bytes is not the packed size; on a growing ledger, old_last_idx is not the ledger's last idx
+ *                       before the batch. The target buffer is untouched then.
+ *                       CONTRACT. The call changes nothing resident, invalidates no *_dev output and refuses nothing but arguments. It
+ *                       returns once its kernel has finished (one synchronise on the ledger's stream): d_packed may then go to
+ *                       hz_inputs_stage / _stage_range / _upload on any stream, and an element >= r in it is reported by the next
+ *                       hz_witness_check. It may be called again for another buffer
+ *   hz_ledger_main_inputs_ms  device time of its kernel in the last such call
+ *   hz_ledger_plan_main_inputs  DIAGNOSTIC, no device: the descriptor table of a layout given as plain arrays (names, offsets, widths,
+ *                       flat lengths; bytes its size), a shape and the call's HZ_MI_* flags, by the routine the device call uses: per
+ *                       signal kind_out (HZ_MI_KIND_*), source_out (HZ_MI_SRC_*), first_row_out and rows_out. HZ_ERR_ARG: an unknown
+ *                       or repeated signal name, a missing one, a width or flat length that does not fit the shape, a range that is
+ *                       not 32-byte aligned, overlaps another or ends beyond bytes
  * OUT OF SCOPE: L1 transactions that create accounts or exit through a call other than hz_ledger_apply_batch_exits (creates:
  * hz_ledger_apply_batch_creates on a growing ledger), an L1 amount with
  * to_idx == 0 (no receiver), persisting, or carrying across a reload, the exit trees of earlier batches kept resident, a resident address index kept across
- * calls, batch (random linear combination) verification of signatures, more than one device per ledger. One thread at a time. */
+ * calls, batch (random linear combination) verification of signatures, more than one device per ledger, the packed inputs of
+ * hz_ledger_apply_l2 (it has no chain id) or of more than one batch per hz_ledger_main_inputs call (K applies go into K consecutive
+ * slots of one buffer, staged with hz_inputs_stage_range), writing straight into the witness layout. One thread at a time. */
 typedef struct hz_ledger hz_ledger;
 typedef struct {
     uint64_t from_idx, to_idx, amount_f /* float40 */, nonce;
@@ -880,6 +912,36 @@ hz_status hz_ledger_plan_select(size_t n_l1, const hz_l1tx* l1, size_t m, const 
                                 int32_t* slot_receiver_out /* [n_l1 + m] */, size_t* n_slots_out, uint64_t* slot_account_out /* [n_slots] */,
                                 uint8_t* forced_out /* [m] */, uint8_t* rq_offset_out /* [m] */);
 double hz_ledger_select_ms(const hz_ledger* l);
+/* the kind flags of the call hz_ledger_plan_main_inputs plans for: hz_l2sig entries were given; hz_l2rq entries were given; the call
+ * takes exits; it takes creates; it leaves auxToIdx rows (every call with a chain id but hz_ledger_apply_l2_signed); the ledger grows
+ * (the table does not depend on it: the device call checks old_last_idx there) */
+#define HZ_MI_SIGS 1u
+#define HZ_MI_RQ 2u
+#define HZ_MI_EXITS 4u
+#define HZ_MI_CREATES 8u
+#define HZ_MI_AUX 16u
+#define HZ_MI_GROWING 32u
+/* what a descriptor does: zeros; rows first_row .. of a source array; one element of it in every row; then the signals packed from the
+ * uploaded rows, one kind each */
+enum {
+    HZ_MI_KIND_ZERO = 0, HZ_MI_KIND_COPY = 1, HZ_MI_KIND_BROADCAST = 2, HZ_MI_KIND_TX_COMPRESSED_DATA = 3, HZ_MI_KIND_TX_COMPRESSED_DATA_V2 = 4,
+    HZ_MI_KIND_AMOUNT_F = 5, HZ_MI_KIND_FROM_IDX = 6, HZ_MI_KIND_TO_IDX = 7, HZ_MI_KIND_TO_BJJ_AY = 8, HZ_MI_KIND_TO_ETH_ADDR = 9,
+    HZ_MI_KIND_MAX_NUM_BATCH = 10, HZ_MI_KIND_ON_CHAIN = 11, HZ_MI_KIND_NEW_ACCOUNT = 12, HZ_MI_KIND_RQ_OFFSET = 13, HZ_MI_KIND_RQ_V2 = 14,
+    HZ_MI_KIND_RQ_TO_ETH_ADDR = 15, HZ_MI_KIND_RQ_TO_BJJ_AY = 16, HZ_MI_KIND_S = 17, HZ_MI_KIND_R8X = 18, HZ_MI_KIND_R8Y = 19,
+    HZ_MI_KIND_LOAD_AMOUNT_F = 20, HZ_MI_KIND_FROM_ETH_ADDR = 21, HZ_MI_KIND_KEY_BITS = 22, HZ_MI_KINDS = 23
+};
+/* where a descriptor reads: nothing; array q of hz_ledger_out, as HZ_MI_SRC_OUT + q, of hz_ledger_exit_out, of hz_ledger_create_out; the
+ * auxToIdx rows; the call's scalars as elements (old_last_idx, chain id, current_num_batch); fee_idxs; fee_plan_tokens; the uploaded
+ * rows (hz_l1tx / hz_l2tx / hz_l2sig / hz_l2rq); from_bjj */
+enum {
+    HZ_MI_SRC_NONE = 0, HZ_MI_SRC_OUT = 1, HZ_MI_SRC_EXIT = 32, HZ_MI_SRC_CREATE = 40, HZ_MI_SRC_AUX_TO_IDX = 48, HZ_MI_SRC_GLOBALS = 49,
+    HZ_MI_SRC_FEE_IDXS = 50, HZ_MI_SRC_FEE_PLAN_TOKENS = 51, HZ_MI_SRC_ROWS = 52, HZ_MI_SRC_KEYS = 53
+};
+hz_status hz_ledger_main_inputs(hz_ledger* l, const hz_ctx* ctx, uint64_t old_last_idx, void* d_packed, size_t bytes);
+double hz_ledger_main_inputs_ms(const hz_ledger* l);
+hz_status hz_ledger_plan_main_inputs(size_t n_signals, const char* const* names, const uint64_t* offsets, const uint32_t* widths, const uint64_t* flat_lens,
+                                     uint64_t bytes, uint32_t n_tx, uint32_t n_levels, uint32_t max_l1_tx, uint32_t max_fee_tx, uint32_t flags,
+                                     uint32_t* kind_out /* [n_signals] */, uint32_t* source_out, uint64_t* first_row_out, uint64_t* rows_out);
 
 /* Poseidon batch: n independent permutations of width t = n_inputs + 1 (2..7). ----------------
  * `in`  : [n][t-1] canonical elements; `out`: [n] digests (state[0] after the last round).
