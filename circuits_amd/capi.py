@@ -246,6 +246,54 @@ def l2tx_array(txs):
     return arr
 
 
+# The arguments of the ledger's apply and verify calls, each with its ctype, and every call's list of them in the order of its prototype in
+# include/hermez_witness.h. Lib takes the argtypes from here, Ledger._call the order in which it hands over what it has built.
+LEDGER_ARG_TYPES = {"l": ctypes.c_void_p, "n_l1": ctypes.c_size_t, "l1": ctypes.c_void_p, "from_bjj": ctypes.c_void_p, "m": ctypes.c_size_t, "txs": ctypes.c_void_p,
+                    "sigs": ctypes.c_void_p, "rq": ctypes.c_void_p, "flags": ctypes.c_uint32, "aux_to_idx": ctypes.c_void_p, "chain_id": ctypes.c_uint32,
+                    "current_num_batch": ctypes.c_uint32, "F": ctypes.c_size_t, "fee_plan_tokens": ctypes.c_void_p, "fee_idxs": ctypes.c_void_p, "n_sib": ctypes.c_size_t,
+                    "out": ctypes.c_void_p, "sig_out": ctypes.c_void_p, "aux_to_idx_out": ctypes.c_void_p, "l1_flags_out": ctypes.c_void_p, "exit_out": ctypes.c_void_p,
+                    "create_out": ctypes.c_void_p, "verdict_out": ctypes.c_void_p}
+_ADDR_TAIL = "flags aux_to_idx chain_id current_num_batch F fee_plan_tokens fee_idxs n_sib out sig_out aux_to_idx_out"   # hz_ledger_apply_l2_addr's, every later form's
+LEDGER_CALLS = {fn: tuple(args.split()) for fn, args in {
+    "hz_ledger_apply_l2": "l m txs F fee_plan_tokens fee_idxs n_sib out",
+    "hz_ledger_apply_l2_signed": "l m txs sigs chain_id current_num_batch F fee_plan_tokens fee_idxs n_sib out sig_out",
+    "hz_ledger_verify_l2": "l m txs sigs chain_id current_num_batch verdict_out sig_out",
+    "hz_ledger_verify_l2_atomic": "l m txs sigs rq chain_id current_num_batch verdict_out sig_out",
+    "hz_ledger_apply_l2_addr": "l m txs sigs " + _ADDR_TAIL,
+    "hz_ledger_apply_batch": "l n_l1 l1 m txs sigs " + _ADDR_TAIL + " l1_flags_out",
+    "hz_ledger_apply_batch_exits": "l n_l1 l1 m txs sigs " + _ADDR_TAIL + " l1_flags_out exit_out",
+    "hz_ledger_apply_batch_creates": "l n_l1 l1 from_bjj m txs sigs " + _ADDR_TAIL + " l1_flags_out exit_out create_out",
+    "hz_ledger_apply_batch_atomic": "l n_l1 l1 from_bjj m txs sigs rq " + _ADDR_TAIL + " l1_flags_out exit_out create_out"}.items()}
+
+
+def _rows_and_fees(l1_txs, txs, fee_plan_tokens, fee_idxs):
+    """the rows and the fee plan of a ledger call as C takes them: dictionaries become hz_l1tx / hz_l2tx arrays, prebuilt arrays pass as they
+    are, the plan becomes uint32 [F] and uint64 [F] -> (l1 or None for l1_txs None, txs, fee_plan_tokens, fee_idxs)"""
+    import numpy as np
+    l1 = l1_txs if l1_txs is None or isinstance(l1_txs, ctypes.Array) else l1tx_array(l1_txs)
+    arr = txs if isinstance(txs, ctypes.Array) else l2tx_array(txs)
+    plan = np.ascontiguousarray(fee_plan_tokens, dtype=np.uint32)
+    idxs = np.ascontiguousarray(fee_idxs, dtype=np.uint64)
+    if idxs.size != plan.size:
+        raise ValueError("fee_plan_tokens and fee_idxs differ in length")
+    return l1, arr, plan, idxs
+
+
+def _host_arrays(got, into, shapes, dtype, strict=False, only=None):
+    """the host arrays a call writes into, for shapes [(name, shape)]: into[name] where `into` has it (strict: it must), a fresh zero array
+    otherwise, each checked for its shape, dtype (a numpy.dtype) and contiguity and entered in `got` by its name -> their addresses in
+    order; only: the names that are wanted at all, the others' addresses are None"""
+    import numpy as np
+    ptrs = []
+    for name, shape in shapes:
+        if only is not None and name not in only:
+            ptrs.append(None)
+            continue
+        a = got[name] = into[name] if into is not None and (strict or name in into) else np.zeros(shape, dtype=dtype)
+        assert a.shape == shape and a.dtype == dtype and a.flags.c_contiguous
+        ptrs.append(a.ctypes.data)
+    return ptrs
+
 
 class Lib:
     """Loaded libhermez_witness.so. Raises if the HIP library has not been built."""
@@ -387,20 +435,16 @@ class Lib:
         c.hz_ledger_accounts.argtypes = [vp, sz, vp, vp]
         c.hz_ledger_tree.argtypes = [vp]
         c.hz_ledger_tree.restype = vp
-        c.hz_ledger_apply_l2.argtypes = [vp, sz, vp, sz, vp, vp, sz, vp]
+        for f, names in LEDGER_CALLS.items():
+            getattr(c, f).argtypes = [LEDGER_ARG_TYPES[name] for name in names]
         c.hz_ledger_outputs_dev.argtypes = [vp, vp]
         c.hz_ledger_plan_l2.argtypes = [sz, vp, sz, vp, vp, ctypes.c_int32, u64, vp, vp, vp, vp, ctypes.POINTER(sz), vp, vp]
         u32 = ctypes.c_uint32
-        c.hz_ledger_apply_l2_signed.argtypes = [vp, sz, vp, vp, u32, u32, sz, vp, vp, sz, vp, vp]
-        c.hz_ledger_verify_l2.argtypes = [vp, sz, vp, vp, u32, u32, vp, vp]
         c.hz_ledger_sig_outputs_dev.argtypes = [vp, vp]
-        c.hz_ledger_apply_l2_addr.argtypes = [vp, sz, vp, vp, u32, vp, u32, u32, sz, vp, vp, sz, vp, vp, vp]
         c.hz_ledger_resolve_l2.argtypes = [vp, sz, vp, vp, vp]
         c.hz_ledger_aux_to_idx_dev.argtypes = [vp, ctypes.POINTER(vp)]
-        c.hz_ledger_apply_batch.argtypes = [vp, sz, vp, sz, vp, vp, u32, vp, u32, u32, sz, vp, vp, sz, vp, vp, vp, vp]
         c.hz_ledger_plan_batch.argtypes = [sz, vp, sz, vp, sz, vp, vp, ctypes.c_int32, u64, vp, vp, vp, vp, ctypes.POINTER(sz), vp, vp, vp, vp, ctypes.POINTER(sz), vp]
         c.hz_ledger_l1_flags_dev.argtypes = [vp, ctypes.POINTER(vp)]
-        c.hz_ledger_apply_batch_exits.argtypes = [vp, sz, vp, sz, vp, vp, u32, vp, u32, u32, sz, vp, vp, sz, vp, vp, vp, vp, vp]
         c.hz_ledger_exit_outputs_dev.argtypes = [vp, vp]
         c.hz_ledger_exit_tree.argtypes = [vp]
         c.hz_ledger_exit_tree.restype = vp
@@ -414,11 +458,8 @@ class Lib:
             getattr(c, f).restype = u64
         c.hz_ledger_state_smt.argtypes = [vp]
         c.hz_ledger_state_smt.restype = vp
-        c.hz_ledger_apply_batch_creates.argtypes = [vp, sz, vp, vp, sz, vp, vp, u32, vp, u32, u32, sz, vp, vp, sz, vp, vp, vp, vp, vp, vp]
         c.hz_ledger_create_outputs_dev.argtypes = [vp, vp]
         c.hz_ledger_plan_creates.argtypes = [sz, vp, vp, sz, vp, sz, vp, vp, ctypes.c_int32, u64, u64, u64, vp, vp, ctypes.POINTER(sz)]
-        c.hz_ledger_apply_batch_atomic.argtypes = [vp, sz, vp, vp, sz, vp, vp, vp, u32, vp, u32, u32, sz, vp, vp, sz, vp, vp, vp, vp, vp, vp]
-        c.hz_ledger_verify_l2_atomic.argtypes = [vp, sz, vp, vp, vp, u32, u32, vp, vp]
         c.hz_ledger_plan_atomic.argtypes = [sz, sz, vp, vp, vp, vp, vp]
         c.hz_ledger_select_batch.argtypes = [vp, sz, vp, vp, sz, vp, vp, vp, vp, u32, u32, u32, sz, vp]
         c.hz_ledger_plan_select.argtypes = [sz, vp, sz, vp, vp, vp, vp, vp, vp, ctypes.POINTER(sz), vp, vp, vp]
@@ -538,11 +579,9 @@ class Lib:
         argument errors of apply_batch_creates but the depth, for a ledger of `capacity` that holds `size` accounts; no device needed.
         -> {"aux_from_idx": [rows], "out_idx_after": [rows], "n_creates": int}"""
         import numpy as np
-        l1, arr = l1tx_array(l1_txs), l2tx_array(txs)
+        l1, arr, plan, idxs = _rows_and_fees(l1_txs, txs, fee_plan_tokens, fee_idxs)
         bjj = from_bjj_array(l1_txs)
         n_l1, m = len(l1_txs), len(txs)
-        plan = np.ascontiguousarray(fee_plan_tokens, dtype=np.uint32)
-        idxs = np.ascontiguousarray(fee_idxs, dtype=np.uint64)
         aux, after = np.zeros(max(n_l1 + m, 1), dtype=np.uint64), np.zeros(max(n_l1 + m, 1), dtype=np.uint64)
         n = ctypes.c_size_t(0)
         self._check(self.c.hz_ledger_plan_creates(n_l1, ctypes.addressof(l1), bjj.ctypes.data if bjj is not None else None, m, ctypes.addressof(arr), plan.size,
@@ -596,13 +635,8 @@ class Lib:
         hz_l2tx array. -> dictionary of numpy arrays: ev_sender / ev_receiver / fee_slot / last_event [m] (-1: none), account / prev_same
         [events]"""
         import numpy as np
-        arr = txs if isinstance(txs, ctypes.Array) else l2tx_array(txs)
-        m = len(txs)
-        plan = np.ascontiguousarray(fee_plan_tokens, dtype=np.uint32)
-        idxs = np.ascontiguousarray(fee_idxs, dtype=np.uint64)
-        F = plan.size
-        if idxs.size != F:
-            raise ValueError("fee_plan_tokens and fee_idxs differ in length")
+        _, arr, plan, idxs = _rows_and_fees(None, txs, fee_plan_tokens, fee_idxs)
+        m, F = len(txs), plan.size
         out = {n: np.zeros(m, dtype=np.int32) for n in ("ev_sender", "ev_receiver", "fee_slot", "last_event")}
         acct, prev, n_ev = np.zeros(2 * m + F, dtype=np.uint64), np.zeros(2 * m + F, dtype=np.int32), ctypes.c_size_t(0)
         self._check(self.c.hz_ledger_plan_l2(m, ctypes.addressof(arr), F, plan.ctypes.data, idxs.ctypes.data, k, first_idx, out["ev_sender"].ctypes.data,
@@ -615,14 +649,8 @@ class Lib:
         """hz_ledger_plan_batch, a diagnostic: ledger_plan_l2 over the n_l1 + m rows of a batch (L1 first), plus the local slots of the L1
         run: l1_slot_sender / l1_slot_receiver [n_l1] (-1: no receiver) and slot_account [slots]"""
         import numpy as np
-        l1 = l1_txs if isinstance(l1_txs, ctypes.Array) else l1tx_array(l1_txs)
-        arr = txs if isinstance(txs, ctypes.Array) else l2tx_array(txs)
-        n_l1, m = len(l1_txs), len(txs)
-        plan = np.ascontiguousarray(fee_plan_tokens, dtype=np.uint32)
-        idxs = np.ascontiguousarray(fee_idxs, dtype=np.uint64)
-        F = plan.size
-        if idxs.size != F:
-            raise ValueError("fee_plan_tokens and fee_idxs differ in length")
+        l1, arr, plan, idxs = _rows_and_fees(l1_txs, txs, fee_plan_tokens, fee_idxs)
+        n_l1, m, F = len(l1_txs), len(txs), plan.size
         R = n_l1 + m
         out = {n: np.zeros(R, dtype=np.int32) for n in ("ev_sender", "ev_receiver", "fee_slot", "last_event")}
         out.update({n: np.zeros(n_l1, dtype=np.int32) for n in ("l1_slot_sender", "l1_slot_receiver")})
@@ -641,14 +669,8 @@ class Lib:
         ev_sender / ev_receiver / last_event / ev_exit / last_exit [rows] (-1: none), account [events], and per exit operation exit_row,
         exit_key, exit_prev (-1: the operation is the insert), exit_perm (grouped by key), exit_insert, exit_is_old0, exit_old_key"""
         import numpy as np
-        l1 = l1_txs if isinstance(l1_txs, ctypes.Array) else l1tx_array(l1_txs)
-        arr = txs if isinstance(txs, ctypes.Array) else l2tx_array(txs)
-        n_l1, m = len(l1_txs), len(txs)
-        plan = np.ascontiguousarray(fee_plan_tokens, dtype=np.uint32)
-        idxs = np.ascontiguousarray(fee_idxs, dtype=np.uint64)
-        F = plan.size
-        if idxs.size != F:
-            raise ValueError("fee_plan_tokens and fee_idxs differ in length")
+        l1, arr, plan, idxs = _rows_and_fees(l1_txs, txs, fee_plan_tokens, fee_idxs)
+        n_l1, m, F = len(l1_txs), len(txs), plan.size
         R = n_l1 + m
         out = {n: np.zeros(R, dtype=np.int32) for n in ("ev_sender", "ev_receiver", "last_event", "ev_exit", "last_exit")}
         acct, n_ev, n_x = np.zeros(2 * R + F, dtype=np.uint64), ctypes.c_size_t(0), ctypes.c_size_t(0)
@@ -1118,97 +1140,106 @@ class Ledger(_Resident):
         cols = {"sib": n_sib, "fee": F}
         return [(name, (rows[r], 32) if c is None else (rows[r], cols[c], 32)) for name, r, c in LEDGER_ARRAYS]
 
-    def _l2_args(self, txs, fee_plan_tokens, fee_idxs, n_sib, outputs, into, n_l1=0):
-        """what apply_l2 and apply_l2_signed pass on: the hz_l2tx array, the fee arrays, the output arrays by name and their pointers
-        (n_l1: rows of an L1 run in front of the m of the transactions)"""
+    def _call(self, fn, txs, fee_plan_tokens=(), fee_idxs=(), chain_id=0, current_num_batch=0, n_sib=None, verify=False, aux_to_idx=None, outputs=True, into=None,
+              sigs=None, l1_txs=None, from_bjj=None, rq=None, verdict=None, only=None):
+        """the one path of every apply and verify form to C: builds each argument LEDGER_CALLS[fn] names, once, and calls fn with them in
+        its row's order. What a form's row does not name it does not get, so the public methods say which form they are and pass on what
+        they were given. sigs None: built from the dictionaries, False: null. rq and from_bjj None: built from the dictionaries, null
+        beside a prebuilt array of their rows; rq False: null. verdict: the verify forms' [max(m, 1)] bytes. only: the names wanted on
+        the host (apply_resident) -- every other array's pointer stays null, and so does a group without a wanted one.
+        -> the host arrays by name: hz_ledger_out's, the signature arrays (a form with a verify flag: when verified), auxToIdx, l1_flags,
+        the exit arrays, the create arrays; `into` must hold the first two groups and may hold the rest."""
         import numpy as np
-        arr = txs if isinstance(txs, ctypes.Array) else l2tx_array(txs)
-        m = len(txs)
-        plan = np.ascontiguousarray(fee_plan_tokens, dtype=np.uint32)
-        idxs = np.ascontiguousarray(fee_idxs, dtype=np.uint64)
-        F = plan.size
-        if idxs.size != F:
-            raise ValueError("fee_plan_tokens and fee_idxs differ in length")
-        out, ptrs = {}, (ctypes.c_void_p * len(LEDGER_ARRAYS))()
+        row = LEDGER_CALLS[fn]
+        named = frozenset(row)
+        n_sib = self.k if n_sib is None else n_sib
+        l1, arr, plan, idxs = _rows_and_fees(l1_txs, txs, fee_plan_tokens, fee_idxs)
+        n_l1, m = 0 if l1_txs is None else len(l1_txs), len(txs)
+        if "from_bjj" in named and from_bjj is None and not isinstance(l1_txs, ctypes.Array):
+            from_bjj = from_bjj_array(l1_txs)
+        if "sigs" in named and sigs is None:
+            sigs = l2sig_array(txs)
+        if "rq" in named and rq is None and not isinstance(txs, ctypes.Array):
+            rq = l2rq_array(txs)
+        aux = None
+        if aux_to_idx is not None:
+            aux = np.ascontiguousarray(aux_to_idx, dtype=np.uint64)
+            if aux.size != m:
+                raise ValueError("aux_to_idx: one entry per %stransaction" % ("L2 " if "l1" in named else ""))
+        addr = lambda a: None if a is None or a is False else ctypes.addressof(a)   # noqa: E731
+        data = lambda a: None if a is None else a.ctypes.data                        # noqa: E731
+        args = {"l": self.h, "n_l1": n_l1, "l1": addr(l1), "from_bjj": data(from_bjj), "m": m, "txs": addr(arr), "sigs": addr(sigs), "rq": addr(rq),
+                "flags": LEDGER_VERIFY_SIGS if verify else 0, "aux_to_idx": data(aux), "chain_id": chain_id, "current_num_batch": current_num_batch, "F": plan.size,
+                "fee_plan_tokens": plan.ctypes.data, "fee_idxs": idxs.ctypes.data, "n_sib": n_sib, "verdict_out": data(verdict)}
+        got, structs = {}, []   # structs: the structs of pointers, alive until C has returned like every local above
         if outputs:
-            for i, (name, shape) in enumerate(self.shapes(n_l1 + m, F, min(max(n_sib, 0), 64))):
-                out[name] = into[name] if into is not None else np.zeros(shape, dtype=np.uint8)
-                assert out[name].shape == shape and out[name].dtype == np.uint8 and out[name].flags.c_contiguous
-                ptrs[i] = out[name].ctypes.data
-        return arr, m, plan, idxs, F, out, ptrs
+            R, u8 = n_l1 + m, np.dtype(np.uint8)
+            for arg in ("out", "sig_out", "aux_to_idx_out", "l1_flags_out", "exit_out", "create_out"):
+                if arg not in named or (arg == "sig_out" and "flags" in named and not verify):   # C refuses sig_out without its verify flag
+                    continue
+                if arg == "out":
+                    shapes = self.shapes(R, plan.size, min(max(n_sib, 0), 64))
+                elif arg == "sig_out":
+                    shapes = [(name, (m, 32)) for name in LEDGER_SIG_ARRAYS]
+                elif arg == "aux_to_idx_out":
+                    shapes = [("auxToIdx", (R, 32))]
+                elif arg == "l1_flags_out":
+                    shapes = [("l1_flags", (n_l1,))]
+                else:   # [rows, 32] each, the last [1, 32]
+                    names = LEDGER_EXIT_ARRAYS if arg == "exit_out" else LEDGER_CREATE_ARRAYS
+                    shapes = [(name, (R, 32)) for name in names[:-1]] + [(names[-1], (1, 32))]
+                ptrs = _host_arrays(got, into, shapes, u8, arg in ("out", "sig_out"), only)
+                if arg in ("aux_to_idx_out", "l1_flags_out"):   # plain pointers, handed over only where there is a row to write
+                    args[arg] = ptrs[0] if shapes[0][1][0] else None
+                elif any(ptrs):
+                    structs.append((ctypes.c_void_p * len(ptrs))(*ptrs))
+                    args[arg] = ctypes.addressof(structs[-1])
+        self.L._check(getattr(self.L.c, fn)(*[args.get(name) for name in row]))
+        return got
+
+    def _dev(self, fn, names):
+        """{name: device pointer} of the struct of pointers the getter fn fills"""
+        ptrs = (ctypes.c_void_p * len(names))()
+        self.L._check(getattr(self.L.c, fn)(self.h, ctypes.addressof(ptrs)))
+        return dict(zip(names, ptrs))
 
     def apply_l2(self, txs, fee_plan_tokens, fee_idxs, n_sib=None, outputs=True, into=None):
         """txs: transaction dictionaries (fromIdx, toIdx, amountF, nonce, tokenID, userFee) or an hz_l2tx array; fee_plan_tokens /
         fee_idxs: [F]. Returns a dictionary of numpy arrays named as hz_ledger_out's members (outputs=False: nothing is copied to the
         host, outputs_dev has them; into: a dictionary of arrays to fill instead of fresh ones)."""
-        n_sib = self.k if n_sib is None else n_sib
-        arr, m, plan, idxs, F, out, ptrs = self._l2_args(txs, fee_plan_tokens, fee_idxs, n_sib, outputs, into)
-        self.L._check(self.L.c.hz_ledger_apply_l2(self.h, m, ctypes.addressof(arr), F, plan.ctypes.data, idxs.ctypes.data, n_sib,
-                                                  ctypes.addressof(ptrs) if outputs else None))
-        return out
+        return self._call("hz_ledger_apply_l2", txs, fee_plan_tokens, fee_idxs, n_sib=n_sib, outputs=outputs, into=into)
 
     def outputs_dev(self):
         """device pointers of the last successful apply_l2's arrays, by name; valid until the ledger's next call"""
-        ptrs = (ctypes.c_void_p * len(LEDGER_ARRAYS))()
-        self.L._check(self.L.c.hz_ledger_outputs_dev(self.h, ctypes.addressof(ptrs)))
-        return {name: ptrs[i] for i, (name, _, _) in enumerate(LEDGER_ARRAYS)}
-
-    def _sig_out(self, m, outputs, into):
-        import numpy as np
-        out, ptrs = {}, (ctypes.c_void_p * len(LEDGER_SIG_ARRAYS))()
-        if outputs:
-            for i, name in enumerate(LEDGER_SIG_ARRAYS):
-                out[name] = into[name] if into is not None else np.zeros((m, 32), dtype=np.uint8)
-                assert out[name].shape == (m, 32) and out[name].dtype == np.uint8 and out[name].flags.c_contiguous
-                ptrs[i] = out[name].ctypes.data
-        return out, ptrs
+        return self._dev("hz_ledger_outputs_dev", [name for name, _, _ in LEDGER_ARRAYS])
 
     def apply_l2_signed(self, txs, fee_plan_tokens, fee_idxs, chain_id, current_num_batch, n_sib=None, outputs=True, into=None):
         """apply_l2 with every L2 signature verified on the device first, against the senders' resident keys. txs: transaction
         dictionaries that also hold s, r8x, r8y and optionally toEthAddr, toBjjAy, toBjjSign, maxNumBatch. Returns apply_l2's
         dictionary with tx_compressed_data, tx_compressed_data_v2 and sig_l2_hash ([m, 32]) added. A rejected signature refuses the
         batch with reason 7, an expired maxNumBatch with reason 8."""
-        n_sib = self.k if n_sib is None else n_sib
-        arr, m, plan, idxs, F, out, ptrs = self._l2_args(txs, fee_plan_tokens, fee_idxs, n_sib, outputs, into)
-        sigs = l2sig_array(txs)
-        sig_out, sig_ptrs = self._sig_out(m, outputs, into)
-        self.L._check(self.L.c.hz_ledger_apply_l2_signed(self.h, m, ctypes.addressof(arr), ctypes.addressof(sigs), chain_id, current_num_batch, F, plan.ctypes.data,
-                                                         idxs.ctypes.data, n_sib, ctypes.addressof(ptrs) if outputs else None,
-                                                         ctypes.addressof(sig_ptrs) if outputs else None))
-        out.update(sig_out)
-        return out
+        return self._call("hz_ledger_apply_l2_signed", txs, fee_plan_tokens, fee_idxs, chain_id, current_num_batch, n_sib, outputs=outputs, into=into)
 
     def verify_l2(self, txs, chain_id, current_num_batch, outputs=False):
         """the mempool filter: one verdict per transaction against the resident keys -- 0 accepted (or a NOP), 7 signature rejected, 8
         maxNumBatch expired -- as a uint8 array; nothing resident changes. outputs=True: (verdicts, the three signature arrays)"""
-        return self._verify_l2(txs, chain_id, current_num_batch, outputs, False)
+        return self._verify("hz_ledger_verify_l2", txs, chain_id, current_num_batch, outputs, False)
 
     def verify_l2_atomic(self, txs, chain_id, current_num_batch, outputs=False, rq=None):
         """verify_l2 over transactions that carry atomic links (rqOffset, rqTxCompressedDataV2, rqToEthAddr, rqToBjjAy): the list is a
         batch of its own, row i is transaction i, and 13 marks a transaction whose rq fields are not the link fields of the row its offset
         names; 7 and 8 come first where they hold. The message hashed is the one with the rq fields. rq: a prebuilt hz_l2rq array."""
-        return self._verify_l2(txs, chain_id, current_num_batch, outputs, True, rq)
+        return self._verify("hz_ledger_verify_l2_atomic", txs, chain_id, current_num_batch, outputs, rq)
 
-    def _verify_l2(self, txs, chain_id, current_num_batch, outputs, atomic, rq=None):
+    def _verify(self, fn, txs, chain_id, current_num_batch, outputs, rq):
         import numpy as np
-        arr, sigs = l2tx_array(txs), l2sig_array(txs)
-        m = len(txs)
-        verdict = np.zeros(max(m, 1), dtype=np.uint8)
-        sig_out, sig_ptrs = self._sig_out(m, outputs, None)
-        if atomic:
-            rq = l2rq_array(txs) if rq is None else rq
-            self.L._check(self.L.c.hz_ledger_verify_l2_atomic(self.h, m, ctypes.addressof(arr), ctypes.addressof(sigs), ctypes.addressof(rq) if rq is not None else None,
-                                                              chain_id, current_num_batch, verdict.ctypes.data, ctypes.addressof(sig_ptrs) if outputs else None))
-        else:
-            self.L._check(self.L.c.hz_ledger_verify_l2(self.h, m, ctypes.addressof(arr), ctypes.addressof(sigs), chain_id, current_num_batch, verdict.ctypes.data,
-                                                       ctypes.addressof(sig_ptrs) if outputs else None))
-        return (verdict[:m], sig_out) if outputs else verdict[:m]
+        verdict = np.zeros(max(len(txs), 1), dtype=np.uint8)
+        sig_out = self._call(fn, txs, chain_id=chain_id, current_num_batch=current_num_batch, outputs=outputs, rq=rq, verdict=verdict)
+        return (verdict[:len(txs)], sig_out) if outputs else verdict[:len(txs)]
 
     def sig_outputs_dev(self):
         """device pointers of the three signature arrays of the last successful apply_l2_signed / verify_l2, by name"""
-        ptrs = (ctypes.c_void_p * len(LEDGER_SIG_ARRAYS))()
-        self.L._check(self.L.c.hz_ledger_sig_outputs_dev(self.h, ctypes.addressof(ptrs)))
-        return {name: ptrs[i] for i, name in enumerate(LEDGER_SIG_ARRAYS)}
+        return self._dev("hz_ledger_sig_outputs_dev", LEDGER_SIG_ARRAYS)
 
     def apply_l2_addr(self, txs, fee_plan_tokens, fee_idxs, chain_id, current_num_batch, n_sib=None, verify=False, aux_to_idx=None, outputs=True, into=None, sigs=None):
         """apply_l2 over transactions whose toIdx may be 0: a receiver named by toEthAddr, or by the "any" address 2^160 - 1 plus toBjjAy /
@@ -1216,29 +1247,7 @@ class Ledger(_Resident):
         verify=True: every signature is checked first as in apply_l2_signed, and its three arrays are returned as well. Returns
         apply_l2's dictionary plus auxToIdx ([m, 32]). Reasons 9 (no such account), 10 and 11 (a supplied receiver does not hold the
         signed address / key) refuse the batch. sigs: a prebuilt hz_l2sig array to go with a prebuilt hz_l2tx array."""
-        import numpy as np
-        n_sib = self.k if n_sib is None else n_sib
-        arr, m, plan, idxs, F, out, ptrs = self._l2_args(txs, fee_plan_tokens, fee_idxs, n_sib, outputs, into)
-        sigs = l2sig_array(txs) if sigs is None else sigs
-        sig_out, sig_ptrs = self._sig_out(m, outputs and verify, into)
-        aux = None
-        if aux_to_idx is not None:
-            aux = np.ascontiguousarray(aux_to_idx, dtype=np.uint64)
-            if aux.size != m:
-                raise ValueError("aux_to_idx: one entry per transaction")
-        aux_out = None
-        if outputs:
-            aux_out = into["auxToIdx"] if into is not None and "auxToIdx" in into else np.zeros((m, 32), dtype=np.uint8)
-            assert aux_out.shape == (m, 32) and aux_out.dtype == np.uint8 and aux_out.flags.c_contiguous
-        self.L._check(self.L.c.hz_ledger_apply_l2_addr(self.h, m, ctypes.addressof(arr), ctypes.addressof(sigs), LEDGER_VERIFY_SIGS if verify else 0,
-                                                       aux.ctypes.data if aux is not None else None, chain_id, current_num_batch, F, plan.ctypes.data,
-                                                       idxs.ctypes.data, n_sib, ctypes.addressof(ptrs) if outputs else None,
-                                                       ctypes.addressof(sig_ptrs) if outputs and verify else None,
-                                                       aux_out.ctypes.data if outputs and m else None))
-        out.update(sig_out)
-        if outputs:
-            out["auxToIdx"] = aux_out
-        return out
+        return self._call("hz_ledger_apply_l2_addr", txs, fee_plan_tokens, fee_idxs, chain_id, current_num_batch, n_sib, verify, aux_to_idx, outputs, into, sigs)
 
     def apply_batch(self, l1_txs, txs, fee_plan_tokens, fee_idxs, chain_id, current_num_batch, n_sib=None, verify=False, aux_to_idx=None, outputs=True, into=None,
                     sigs=None):
@@ -1247,34 +1256,7 @@ class Ledger(_Resident):
         transactions txs exactly as apply_l2_addr takes them. Every per-transaction array has len(l1_txs) + len(txs) rows, L1 first.
         Returns apply_l2_addr's dictionary plus l1_flags (uint8 [n_l1]: bit 0 nullifyLoadAmount, bit 1 isAmountNullified). sigs=False: no
         hz_l2sig array is passed at all (allowed when nothing is verified and no L2 transaction names its receiver by address)."""
-        import numpy as np
-        n_sib = self.k if n_sib is None else n_sib
-        l1 = l1_txs if isinstance(l1_txs, ctypes.Array) else l1tx_array(l1_txs)
-        n_l1 = len(l1_txs)
-        arr, m, plan, idxs, F, out, ptrs = self._l2_args(txs, fee_plan_tokens, fee_idxs, n_sib, outputs, into, n_l1=n_l1)
-        if sigs is None:
-            sigs = l2sig_array(txs)
-        sig_out, sig_ptrs = self._sig_out(m, outputs and verify, into)
-        aux = None
-        if aux_to_idx is not None:
-            aux = np.ascontiguousarray(aux_to_idx, dtype=np.uint64)
-            if aux.size != m:
-                raise ValueError("aux_to_idx: one entry per L2 transaction")
-        aux_out = flags = None
-        if outputs:
-            aux_out = into["auxToIdx"] if into is not None and "auxToIdx" in into else np.zeros((n_l1 + m, 32), dtype=np.uint8)
-            assert aux_out.shape == (n_l1 + m, 32) and aux_out.dtype == np.uint8 and aux_out.flags.c_contiguous
-            flags = into["l1_flags"] if into is not None and "l1_flags" in into else np.zeros(n_l1, dtype=np.uint8)
-            assert flags.shape == (n_l1,) and flags.dtype == np.uint8 and flags.flags.c_contiguous
-        self.L._check(self.L.c.hz_ledger_apply_batch(self.h, n_l1, ctypes.addressof(l1), m, ctypes.addressof(arr), ctypes.addressof(sigs) if sigs is not False else None,
-                                                     LEDGER_VERIFY_SIGS if verify else 0, aux.ctypes.data if aux is not None else None, chain_id, current_num_batch,
-                                                     F, plan.ctypes.data, idxs.ctypes.data, n_sib, ctypes.addressof(ptrs) if outputs else None,
-                                                     ctypes.addressof(sig_ptrs) if outputs and verify else None,
-                                                     aux_out.ctypes.data if outputs and n_l1 + m else None, flags.ctypes.data if outputs and n_l1 else None))
-        out.update(sig_out)
-        if outputs:
-            out["auxToIdx"], out["l1_flags"] = aux_out, flags
-        return out
+        return self._call("hz_ledger_apply_batch", txs, fee_plan_tokens, fee_idxs, chain_id, current_num_batch, n_sib, verify, aux_to_idx, outputs, into, sigs, l1_txs)
 
     def apply_batch_exits(self, l1_txs, txs, fee_plan_tokens, fee_idxs, chain_id, current_num_batch, n_sib=None, verify=False, aux_to_idx=None, outputs=True,
                           into=None, sigs=None):
@@ -1282,40 +1264,8 @@ class Ledger(_Resident):
         key fromIdx, an insert the first time and an update after. Returns apply_batch's dictionary plus new_exit, is_old0_2, old_key2,
         old_value2, exit_root_after ([rows, 32]) and new_exit_root ([1, 32]). exit_tree() and exit_accounts() read the tree and its leaves
         until the ledger's next batch."""
-        import numpy as np
-        n_sib = self.k if n_sib is None else n_sib
-        l1 = l1_txs if isinstance(l1_txs, ctypes.Array) else l1tx_array(l1_txs)
-        n_l1 = len(l1_txs)
-        arr, m, plan, idxs, F, out, ptrs = self._l2_args(txs, fee_plan_tokens, fee_idxs, n_sib, outputs, into, n_l1=n_l1)
-        if sigs is None:
-            sigs = l2sig_array(txs)
-        sig_out, sig_ptrs = self._sig_out(m, outputs and verify, into)
-        aux = None
-        if aux_to_idx is not None:
-            aux = np.ascontiguousarray(aux_to_idx, dtype=np.uint64)
-            if aux.size != m:
-                raise ValueError("aux_to_idx: one entry per L2 transaction")
-        R = n_l1 + m
-        aux_out = flags = None
-        exit_out, exit_ptrs = {}, (ctypes.c_void_p * len(LEDGER_EXIT_ARRAYS))()
-        if outputs:
-            shapes = {"auxToIdx": (R, 32), "l1_flags": (n_l1,)}
-            shapes.update({name: (R if name != "new_exit_root" else 1, 32) for name in LEDGER_EXIT_ARRAYS})
-            for name, shape in shapes.items():
-                exit_out[name] = into[name] if into is not None and name in into else np.zeros(shape, dtype=np.uint8)
-                assert exit_out[name].shape == shape and exit_out[name].dtype == np.uint8 and exit_out[name].flags.c_contiguous
-            aux_out, flags = exit_out["auxToIdx"], exit_out["l1_flags"]
-            for i, name in enumerate(LEDGER_EXIT_ARRAYS):
-                exit_ptrs[i] = exit_out[name].ctypes.data
-        self.L._check(self.L.c.hz_ledger_apply_batch_exits(self.h, n_l1, ctypes.addressof(l1), m, ctypes.addressof(arr), ctypes.addressof(sigs) if sigs is not False else None,
-                                                           LEDGER_VERIFY_SIGS if verify else 0, aux.ctypes.data if aux is not None else None, chain_id, current_num_batch,
-                                                           F, plan.ctypes.data, idxs.ctypes.data, n_sib, ctypes.addressof(ptrs) if outputs else None,
-                                                           ctypes.addressof(sig_ptrs) if outputs and verify else None,
-                                                           aux_out.ctypes.data if outputs and R else None, flags.ctypes.data if outputs and n_l1 else None,
-                                                           ctypes.addressof(exit_ptrs) if outputs else None))
-        out.update(sig_out)
-        out.update(exit_out)
-        return out
+        return self._call("hz_ledger_apply_batch_exits", txs, fee_plan_tokens, fee_idxs, chain_id, current_num_batch, n_sib, verify, aux_to_idx, outputs, into, sigs,
+                          l1_txs)
 
     def apply_batch_creates(self, l1_txs, txs, fee_plan_tokens, fee_idxs, chain_id, current_num_batch, n_sib=None, verify=False, aux_to_idx=None, outputs=True,
                             into=None, sigs=None, from_bjj=None):
@@ -1323,7 +1273,8 @@ class Ledger(_Resident):
         account last_idx + 1 for each, in row order, and every later row may name it. Returns apply_batch_exits' dictionary plus
         aux_from_idx, is_old0_1, old_key1, old_value1, out_idx_after ([rows, 32]) and new_last_idx ([1, 32]). from_bjj: the keys as a
         prebuilt [n_l1, 32] array (from_bjj_array) to go with a prebuilt hz_l1tx array."""
-        return self._apply_batch_creates(l1_txs, txs, fee_plan_tokens, fee_idxs, chain_id, current_num_batch, n_sib, verify, aux_to_idx, outputs, into, sigs, from_bjj)
+        return self._call("hz_ledger_apply_batch_creates", txs, fee_plan_tokens, fee_idxs, chain_id, current_num_batch, n_sib, verify, aux_to_idx, outputs, into, sigs,
+                          l1_txs, from_bjj)
 
     def apply_batch_atomic(self, l1_txs, txs, fee_plan_tokens, fee_idxs, chain_id, current_num_batch, n_sib=None, verify=False, aux_to_idx=None, outputs=True,
                            into=None, sigs=None, from_bjj=None, rq=None):
@@ -1332,42 +1283,18 @@ class Ledger(_Resident):
         and signed destination, or be zero where the offset is 0 or names an L1 row, a NOP or a place outside the batch. A mismatch refuses
         the batch with reason 13, verified or not; sig_l2_hash is the message with the rq fields. rq: a prebuilt hz_l2rq array
         (l2rq_array), False: none at all. Returns apply_batch_creates' dictionary."""
-        if rq is None and not isinstance(txs, ctypes.Array):
-            rq = l2rq_array(txs)
-        return self._apply_batch_creates(l1_txs, txs, fee_plan_tokens, fee_idxs, chain_id, current_num_batch, n_sib, verify, aux_to_idx, outputs, into, sigs, from_bjj,
-                                         atomic=True, rq=rq if rq is not False else None)
+        return self._call("hz_ledger_apply_batch_atomic", txs, fee_plan_tokens, fee_idxs, chain_id, current_num_batch, n_sib, verify, aux_to_idx, outputs, into, sigs,
+                          l1_txs, from_bjj, rq)
 
     def apply_resident(self, l1_txs, txs, fee_plan_tokens, fee_idxs, chain_id, current_num_batch, n_sib=None, verify=False, atomic=False, sigs=None, from_bjj=None,
                        rq=None):
         """apply_batch_atomic (atomic=True) or apply_batch_exits with every array left on the device -- what main_inputs packs -- but the
         few bytes the caller of a packed batch still needs on the host: -> {"l1_flags": uint8 [n_l1], "new_exit_root": [1, 32]}. Rows
         as dictionaries, or prebuilt: l1_txs an hz_l1tx array with from_bjj, txs an hz_l2tx array with sigs (False: none) and rq"""
-        import numpy as np
-        n_sib = self.k if n_sib is None else n_sib
-        prebuilt = isinstance(l1_txs, ctypes.Array)
-        l1 = l1_txs if prebuilt else l1tx_array(l1_txs)
-        n_l1, m = len(l1_txs), len(txs)
-        arr = txs if isinstance(txs, ctypes.Array) else l2tx_array(txs)
-        if not isinstance(txs, ctypes.Array):
-            sigs = l2sig_array(txs) if sigs is None else sigs
-            rq = l2rq_array(txs) if rq is None and atomic else rq
-        plan = np.ascontiguousarray(fee_plan_tokens, dtype=np.uint32)
-        idxs = np.ascontiguousarray(fee_idxs, dtype=np.uint64)
-        if idxs.size != plan.size:
-            raise ValueError("fee_plan_tokens and fee_idxs differ in length")
-        flags, root = np.zeros(max(n_l1, 1), dtype=np.uint8), np.zeros((1, 32), dtype=np.uint8)
-        exit_ptrs = (ctypes.c_void_p * len(LEDGER_EXIT_ARRAYS))()
-        exit_ptrs[len(LEDGER_EXIT_ARRAYS) - 1] = root.ctypes.data
-        p_sigs = ctypes.addressof(sigs) if sigs not in (None, False) else None
-        tail = [LEDGER_VERIFY_SIGS if verify else 0, None, chain_id, current_num_batch, plan.size, plan.ctypes.data, idxs.ctypes.data, n_sib, None, None, None,
-                flags.ctypes.data if n_l1 else None, ctypes.addressof(exit_ptrs)]
-        if atomic:
-            bjj = from_bjj if from_bjj is not None or prebuilt else from_bjj_array(l1_txs)
-            self.L._check(self.L.c.hz_ledger_apply_batch_atomic(self.h, n_l1, ctypes.addressof(l1), bjj.ctypes.data if bjj is not None else None, m, ctypes.addressof(arr),
-                                                                p_sigs, ctypes.addressof(rq) if rq not in (None, False) else None, *tail, None))
-        else:
-            self.L._check(self.L.c.hz_ledger_apply_batch_exits(self.h, n_l1, ctypes.addressof(l1), m, ctypes.addressof(arr), p_sigs, *tail))
-        return {"l1_flags": flags[:n_l1], "new_exit_root": root}
+        if sigs is None and isinstance(txs, ctypes.Array):   # prebuilt rows have no dictionaries to build signatures from
+            sigs = False
+        return self._call("hz_ledger_apply_batch_atomic" if atomic else "hz_ledger_apply_batch_exits", txs, fee_plan_tokens, fee_idxs, chain_id, current_num_batch,
+                          n_sib, verify, sigs=sigs, l1_txs=l1_txs, from_bjj=from_bjj, rq=rq, only=("l1_flags", "new_exit_root"))
 
     def main_inputs(self, ctx, old_last_idx, d_packed=None):
         """hz_ledger_main_inputs: the packed input buffer of one instance of the RollupMain context `ctx` for the batch the last apply
@@ -1429,57 +1356,9 @@ class Ledger(_Resident):
         """device time of k_ledger_select in the last select_batch"""
         return self.L.c.hz_ledger_select_ms(self.h)
 
-    def _apply_batch_creates(self, l1_txs, txs, fee_plan_tokens, fee_idxs, chain_id, current_num_batch, n_sib, verify, aux_to_idx, outputs, into, sigs, from_bjj,
-                             atomic=False, rq=None):
-        import numpy as np
-        n_sib = self.k if n_sib is None else n_sib
-        prebuilt = isinstance(l1_txs, ctypes.Array)
-        l1 = l1_txs if prebuilt else l1tx_array(l1_txs)
-        bjj = from_bjj if from_bjj is not None or prebuilt else from_bjj_array(l1_txs)
-        n_l1 = len(l1_txs)
-        arr, m, plan, idxs, F, out, ptrs = self._l2_args(txs, fee_plan_tokens, fee_idxs, n_sib, outputs, into, n_l1=n_l1)
-        if sigs is None:
-            sigs = l2sig_array(txs)
-        sig_out, sig_ptrs = self._sig_out(m, outputs and verify, into)
-        aux = None
-        if aux_to_idx is not None:
-            aux = np.ascontiguousarray(aux_to_idx, dtype=np.uint64)
-            if aux.size != m:
-                raise ValueError("aux_to_idx: one entry per L2 transaction")
-        R = n_l1 + m
-        aux_out = flags = None
-        more, exit_ptrs, create_ptrs = {}, (ctypes.c_void_p * len(LEDGER_EXIT_ARRAYS))(), (ctypes.c_void_p * len(LEDGER_CREATE_ARRAYS))()
-        if outputs:
-            shapes = {"auxToIdx": (R, 32), "l1_flags": (n_l1,)}
-            shapes.update({name: (R if name != "new_exit_root" else 1, 32) for name in LEDGER_EXIT_ARRAYS})
-            shapes.update({name: (R if name != "new_last_idx" else 1, 32) for name in LEDGER_CREATE_ARRAYS})
-            for name, shape in shapes.items():
-                more[name] = into[name] if into is not None and name in into else np.zeros(shape, dtype=np.uint8)
-                assert more[name].shape == shape and more[name].dtype == np.uint8 and more[name].flags.c_contiguous
-            aux_out, flags = more["auxToIdx"], more["l1_flags"]
-            for i, name in enumerate(LEDGER_EXIT_ARRAYS):
-                exit_ptrs[i] = more[name].ctypes.data
-            for i, name in enumerate(LEDGER_CREATE_ARRAYS):
-                create_ptrs[i] = more[name].ctypes.data
-        head = [self.h, n_l1, ctypes.addressof(l1), bjj.ctypes.data if bjj is not None else None, m, ctypes.addressof(arr),
-                ctypes.addressof(sigs) if sigs is not False else None]
-        tail = [LEDGER_VERIFY_SIGS if verify else 0, aux.ctypes.data if aux is not None else None, chain_id, current_num_batch, F, plan.ctypes.data, idxs.ctypes.data,
-                n_sib, ctypes.addressof(ptrs) if outputs else None, ctypes.addressof(sig_ptrs) if outputs and verify else None,
-                aux_out.ctypes.data if outputs and R else None, flags.ctypes.data if outputs and n_l1 else None, ctypes.addressof(exit_ptrs) if outputs else None,
-                ctypes.addressof(create_ptrs) if outputs else None]
-        if atomic:   # hz_ledger_apply_batch_creates' argument list with rq behind sigs
-            self.L._check(self.L.c.hz_ledger_apply_batch_atomic(*head, ctypes.addressof(rq) if rq is not None else None, *tail))
-        else:
-            self.L._check(self.L.c.hz_ledger_apply_batch_creates(*head, *tail))
-        out.update(sig_out)
-        out.update(more)
-        return out
-
     def create_outputs_dev(self):
         """device pointers of the six create arrays of the last successful apply_batch_creates, by name; valid until the ledger's next call"""
-        ptrs = (ctypes.c_void_p * len(LEDGER_CREATE_ARRAYS))()
-        self.L._check(self.L.c.hz_ledger_create_outputs_dev(self.h, ctypes.addressof(ptrs)))
-        return {name: ptrs[i] for i, name in enumerate(LEDGER_CREATE_ARRAYS)}
+        return self._dev("hz_ledger_create_outputs_dev", LEDGER_CREATE_ARRAYS)
 
     def create_ms(self):
         """device time of the two create kernels of the last apply_batch_creates"""
@@ -1495,9 +1374,7 @@ class Ledger(_Resident):
 
     def exit_outputs_dev(self):
         """device pointers of the six exit arrays of the last successful apply_batch_exits, by name; valid until the ledger's next call"""
-        ptrs = (ctypes.c_void_p * len(LEDGER_EXIT_ARRAYS))()
-        self.L._check(self.L.c.hz_ledger_exit_outputs_dev(self.h, ctypes.addressof(ptrs)))
-        return {name: ptrs[i] for i, name in enumerate(LEDGER_EXIT_ARRAYS)}
+        return self._dev("hz_ledger_exit_outputs_dev", LEDGER_EXIT_ARRAYS)
 
     def exit_tree(self):
         """the exit tree of the last batch as a capi.SparseTree, borrowed: proofs / root / size"""
@@ -1568,9 +1445,7 @@ class Ledger(_Resident):
 
     def withdraw_rows_dev(self):
         """device pointers of the nine arrays of the last withdraw_rows, by name; valid until the ledger's next call"""
-        ptrs = (ctypes.c_void_p * len(WITHDRAW_ARRAYS))()
-        self.L._check(self.L.c.hz_ledger_withdraw_rows_dev(self.h, ctypes.addressof(ptrs)))
-        return {name: ptrs[i] for i, name in enumerate(WITHDRAW_ARRAYS)}
+        return self._dev("hz_ledger_withdraw_rows_dev", WITHDRAW_ARRAYS)
 
     def withdraw_ms(self):
         """device time of the two kernels of the last withdraw_rows"""

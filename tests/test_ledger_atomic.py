@@ -340,3 +340,31 @@ def test_verify_l2_atomic(hz, base):
         assert got.tobytes() == exp.tobytes()
         _same_bytes(arrays, exp_arrays)
     lg.close()
+
+
+# ---- 9 -----------------------------------------------------------------------------------------------------------------------------------
+def test_into_fills_the_callers_arrays_with_what_a_fresh_call_returns(hz, base):
+    """a create, a deposit, a linked pair of transfers and an exit, verified, on a growing ledger of capacity 32 that holds 16 accounts, 7
+    siblings: once into fresh arrays, then on the reloaded ledger into arrays of the caller's that hold 0xAA everywhere, one optional
+    name missing among them -- the same arrays come back, the missing one beside them, every byte as in the fresh call"""
+    acc = K.Accounts.of(base)
+    lg = acc.to_ledger(hz, 32, n_sib_max=7)
+    l1_txs = [K.create_for(K.account(0), load=50), Q.deposits(base, 1)[0]]
+    txs = Q.transfers(base, 3, offsets={0: 1, 1: 7})
+    txs[2]["toIdx"] = B.EXIT_IDX
+    l2_txs = Q.sign_all(base, Q.derive(len(l1_txs), txs))
+
+    def call(**kw):
+        return lg.apply_batch_atomic(l1_txs, l2_txs, PLAN, IDXS, S.CHAIN_ID, 1, n_sib=7, verify=True, **kw)
+    fresh = call()
+    root = lg.root()
+    every = [name for name, _, _ in capi.LEDGER_ARRAYS] + list(capi.LEDGER_SIG_ARRAYS) + ["auxToIdx", "l1_flags"] + list(capi.LEDGER_EXIT_ARRAYS + capi.LEDGER_CREATE_ARRAYS)
+    assert list(fresh) == every and fresh["siblings1"].shape == (5, 7, 32)
+    assert fresh["new_exit"][4].any() and fresh["aux_from_idx"][0].any() and fresh["sig_l2_hash"].any() and lg.rq_ms() > 0.0   # each kind of row did its work
+    lg.load_accounts(*acc.cols())
+    into = {name: np.full_like(a, 0xAA) for name, a in fresh.items() if name != "exit_root_after"}
+    got = call(into=into)
+    assert lg.root() == root and list(got) == every
+    assert all(got[name] is into[name] for name in into) and got["exit_root_after"].shape == (5, 32)
+    _same_bytes(got, fresh)
+    lg.close()
