@@ -1,7 +1,8 @@
-// hz_ctx: one "compiled circuit" -- layout, HBM-resident witness buffer, input upload, kernel
-// schedule, constraint-failure reporting, symbol table. Implements the context part of
+// hz_ctx: one "compiled circuit" -- layout, HBM-resident witness buffer, the masked-stream pool, input upload and staging,
+// constraint-failure reporting, reads and gathers, symbol table. Implements the context part of
 // include/hermez_witness.h (the calls that replace circom's tester()/calculateWitness()/assertOut(),
-// reference test/helpers/helpers.js:139-155).
+// reference test/helpers/helpers.js:139-155). The struct itself is in ctx_internal.h; the kernel schedule of a step
+// (hz_witness_enqueue and what it launches, the sharded tail, profiling) is ctx_step.hip.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -18,160 +19,27 @@
 using namespace hz;
 using namespace hzl;
 
-struct hz_ctx {
-    // optional per-kernel timing (HIP events on the launch stream)
-    bool profiling = false;
-    struct Prof { std::string name; uint64_t bytes; uint64_t units; hipEvent_t e0, e1; float ms; };
-    std::vector<Prof> prof;
-    size_t prof_used = 0;
-    Layout lo;
-    int device = 0;
-    DevBuf wit, sc_tx, sc_fee, err, msg, chain, stage;
-    DevBuf ed_side;   // the small-launch signature ladder's parked numerators (eddsa_side_bytes), allocated by the first launch that needs it
-    // per-instance failure report (hz_witness_failures): every instance's lowest failing key, kept by report_fail beside the
-    // launch-wide minimum, and -- allocated by the first call that finds failures -- the operands of each
-    DevBuf inst_min, inst_rec;
-    bool inst_min_dirty = false;          // a failure was seen (or no check told otherwise) since inst_min was last reset
-    unsigned long long last_minkey = ~0ull;
-    bool checked = false;                 // hz_witness_check has completed for the last enqueue
-    std::vector<uint8_t> input_set;
-    std::vector<uint8_t> host_stage;
-    hipStream_t last_stream = nullptr;
-    // multi-GPU intra-batch shard (RollupMain): this context evaluates transactions [sh_first, sh_first + sh_count);
-    // only meaningful when `sharded`. The fee transactions and HashInputs of a sharded context run in hz_witness_enqueue_tail.
-    uint32_t sh_first = 0, sh_count = 0;
-    bool sharded = false;   // hz_ctx_set_shard with count >= 0 (an empty range is a legal shard: more ranks than transactions)
-    bool sh_tail = true;
-    // device-side input writes (hz_set_input_dev, hz_copy_instance_inputs, hz_inputs_upload) are asynchronous on the stream they were
-    // given; the next enqueue waits for this event on ITS stream, whichever that is
-    hipEvent_t ev_inputs = nullptr;
-    bool inputs_pending = false;
-    // bulk upload (hz_inputs_upload): one packed buffer per instance -> device staging -> k_unpack_inputs into the witness layout
-    DevBuf upl, upl_desc, upl_bad;
-    uint64_t upl_bytes = 0;                 // packed bytes of one instance
-    std::vector<uint64_t> upl_off;          // per input: byte offset inside the packed buffer
-    uint32_t upl_blocks = 0;
-    bool upl_used = false;                  // hz_witness_check also reads the range-check flag of the unpack kernel
-    // hz_inputs_stage: the H2D half alone, ahead of time (while the previous step still computes on the old inputs); the unpack
-    // kernels of the staged instances run at the head of the next enqueue
-    std::vector<uint8_t> staged;
-    bool any_staged = false;
-    hipStream_t stage_stream = nullptr;     // the stream of the stage calls since the last enqueue (ev_staged is recorded on it)
-    hipStream_t s_copy = nullptr;
-    hipEvent_t ev_staged = nullptr, ev_unpacked = nullptr;
-    // independent chains of one batch run concurrently: the EdDSA ladders and the fee transactions on
-    // their own streams, joined by events before HashInputs (DESIGN.md "Kernel schedule")
-    bool exclusive = false;   // hz_ctx_set_profiling(ctx, 2)
-    bool partitioned = false; // latency-bound context: CU-masked internal streams (hz_ctx_create)
-    hipEvent_t ev_user_in = nullptr, ev_user_out = nullptr;
-    hipStream_t s_ed = nullptr, s_fee = nullptr, s_main = nullptr;   // s_main replaces a NULL caller stream
-    hipEvent_t ev_reset = nullptr, ev_front = nullptr, ev_ed = nullptr, ev_fee = nullptr, ev_fix = nullptr;
-    hipEvent_t ev_sha[9] = {};   // HashInputs: chain group g done (0..7), expansion done (8)
-    hipStream_t s_fix = nullptr;   // the fixed-base half of the signature check
-    hipStream_t s_sha = nullptr;   // SHA-256 expansion groups behind the chain when HashInputs runs early on the fee stream
-    // Constant marks. The witness buffer is persistent: what the previous step left in it is still there when the next one starts,
-    // and more than a third of what a step of the headline shape used to store does not depend on its inputs -- the S-box block of
-    // Poseidon(0, 0) in the hash slots of every SMT level above a proof's leaf (HZ_POSEIDON3_ZERO_WIT, 243 signals per level and
-    // chain: 36.7 of 100 GB per step), zeros in the switcher / state-machine signals of those levels. k_smt keeps two bytes per
-    // (chain, unit) -- from which level up the buffer holds that content -- stores an empty level only below the mark and leaves
-    // the mark of what the buffer holds after the step (smt_kernels.hip). Nothing but k_smt writes those slots; the marks are cleared
-    // (0xFF: "nothing held") at creation and by hz_clear_inputs. HZ_NO_ZMARK=1: no marks, every level stored every step.
-    DevBuf zm_tx, zm_fee;
-    DevBuf zm_skip;                // profiling: elements not stored by [0] the transaction launch, [1] the fee launch, [2] the early-tail launch
-    bool zm_reset = false;         // hz_clear_inputs: the next enqueue clears the marks first
-    hz::ExportScratch exp_scratch; // export.hip's per-context buffers (ctx_internal.h)
-    DevBuf smt_trace;              // experiments: HZ_SMT_TRACE=<file> -- per-wavefront start / end / placement of the transaction k_smt launch
-    DevBuf pos3;                   // poseidon_quad.h's constants (C, M R, M R^2): the latency form of k_smt
-    bool smt_lat = false;          // this context's chain launches take the latency form (hz_ctx_create)
-    bool smt_lat_few = false;      // ... while at most two partitioned contexts are alive on the device (HZ_FLAG_LATENCY, one batch)
-    hipEvent_t ev_hash4 = nullptr, ev_tail = nullptr, ev_sighash = nullptr;
-    void release_masked();
-    ~hz_ctx() {
-        if (partitioned) {   // CU-masked streams go back to the process's pool (masked_stream_pool below)
-            release_masked();
-            s_ed = s_fee = s_main = s_fix = nullptr;
-        }
-        if (s_ed) (void)hipStreamDestroy(s_ed);
-        if (s_fee) (void)hipStreamDestroy(s_fee);
-        if (s_main) (void)hipStreamDestroy(s_main);
-        if (s_fix) (void)hipStreamDestroy(s_fix);
-        if (s_copy) (void)hipStreamDestroy(s_copy);
-        if (s_sha) (void)hipStreamDestroy(s_sha);
-        for (hipEvent_t e : {ev_hash4, ev_tail, ev_sighash})
-            if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : {ev_staged, ev_unpacked})
-            if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : {ev_reset, ev_front, ev_ed, ev_fee, ev_fix, ev_user_in, ev_user_out, ev_inputs})
-            if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : ev_sha)
-            if (e) (void)hipEventDestroy(e);
-        for (auto& p : prof) { (void)hipEventDestroy(p.e0); (void)hipEventDestroy(p.e1); }
+hz_ctx::~hz_ctx() {
+    if (partitioned) {   // CU-masked streams go back to the process's pool (masked_pool below)
+        release_masked();
+        s_ed = s_fee = s_main = s_fix = nullptr;
     }
-    unsigned long long filter_stage = ~0ull;
-    bool enqueued = false;
-    // symbol enumeration index: cumulative symbol counts per (section, block)
-    struct BlkRef { int sec, blk; uint64_t first; uint32_t units; };
-    std::vector<BlkRef> sym_index;
-    uint64_t sym_total = 0;
-    std::string sym_name;
-};
-
-// which kernel writes a block of the tx / fee / hash-inputs sections (for algorithmic byte counts)
-static const char* block_owner(const Layout& lo, int sec, const Block& b) {
-    const std::string& n = b.name;
-    auto has = [&](const char* t) { return n.find(t) != std::string::npos; };
-    if (sec == lo.sec_hi && lo.p.tmpl != T_WITHDRAW) return "hash_inputs";
-    const bool fee = (sec == lo.sec_fee);
-    if (has(".hash1Old.") || has(".hash1New.") || has("St1Hash.") || has("St2Hash.") || has("StFeePck.") || has("s1OldValue") || has("s2OldValue"))
-        return fee ? "fee_hash" : "hash4";
-    if (has(".topSwitcher.") || has(".checkOldInput.") || has(".areKeyEquals.") || has(".keysOk.") || (has(".processor") && n.size() > 8 && n.compare(n.size() - 8, 8, ".newRoot") == 0))
-        return fee ? "fee_back" : "rtx_back";
-    if (has(".processor")) return fee ? "fee_smt" : "smt";
-    if (!fee && lo.p.tmpl == T_ROLLUP_MAIN && has(".hashSig.")) return "sig_hash";
-    if (has(".sigVerifier.mulFix.") || has(".sigVerifier.snum2bits") || has(".sigVerifier.compConstant")) return "eddsa_fix";
-    if (has(".sigVerifier.eqCheck")) return "eddsa_final";
-    if (has(".getAx.") || has(".sigVerifier.")) return "eddsa";
-    if (has(".s3.out") || has(".s4.out") || has(".s5.out") || n == "main.hasherInputs.L1L2TxsData") return "rtx_back";
-    if (!fee && lo.p.tmpl == T_ROLLUP_MAIN && has(".feeAccumulator.")) return "fee_acc";   // (standalone RollupTx: part of its front kernel)
-    return fee ? "fee_front" : "front";
+    if (s_ed) (void)hipStreamDestroy(s_ed);
+    if (s_fee) (void)hipStreamDestroy(s_fee);
+    if (s_main) (void)hipStreamDestroy(s_main);
+    if (s_fix) (void)hipStreamDestroy(s_fix);
+    if (s_copy) (void)hipStreamDestroy(s_copy);
+    if (s_sha) (void)hipStreamDestroy(s_sha);
+    for (hipEvent_t e : {ev_hash4, ev_tail, ev_sighash})
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {ev_staged, ev_unpacked})
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {ev_reset, ev_front, ev_ed, ev_fee, ev_fix, ev_user_in, ev_user_out, ev_inputs})
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ev_sha)
+        if (e) (void)hipEventDestroy(e);
+    for (auto& p : prof) { (void)hipEventDestroy(p.e0); (void)hipEventDestroy(p.e1); }
 }
-static uint64_t owner_bytes(const hz_ctx* c, const char* owner) {
-    uint64_t n = 0;
-    const Layout& lo = c->lo;
-    if (!strcmp(owner, "withdraw") || !strcmp(owner, "withdraw_sha")) {   // the SHA part owns the sha256 blocks and the bit decompositions
-        uint64_t sha = 0;
-        for (size_t si = 0; si < lo.sections.size(); si++)
-            for (const Block& b : lo.sections[si].blocks)
-                if (b.name.find("main.hasherInputs.") == 0) sha += (uint64_t)b.count * lo.sections[si].n_units;
-        return (!strcmp(owner, "withdraw_sha") ? sha : lo.total - sha) * 32;
-    }
-    for (size_t si = 0; si < lo.sections.size(); si++)
-        for (const Block& b : lo.sections[si].blocks)
-            if (!strcmp(block_owner(lo, (int)si, b), owner)) n += (uint64_t)b.count * lo.sections[si].n_units;
-    return n * 32;
-}
-struct ProfScope {
-    hz_ctx* c;
-    hipStream_t s;
-    bool on;
-    ProfScope(hz_ctx* c_, hipStream_t s_, const char* name, uint64_t units) : c(c_), s(s_), on(c_->profiling) {
-        if (!on) return;
-        if (c->prof_used == c->prof.size()) {
-            hz_ctx::Prof p;
-            p.name = name; p.bytes = owner_bytes(c, name); p.units = units; p.ms = 0;
-            (void)hipEventCreate(&p.e0);
-            (void)hipEventCreate(&p.e1);
-            c->prof.push_back(p);
-        }
-        (void)hipEventRecord(c->prof[c->prof_used].e0, s);
-    }
-    ~ProfScope() {
-        if (!on) return;
-        (void)hipEventRecord(c->prof[c->prof_used].e1, s);
-        c->prof_used++;
-    }
-};
-
 
 // Every CU-masked stream owns a hardware queue, and the runtime does not hand a destroyed one's queue back soon enough: a process that
 // creates and destroys HZ_FLAG_LATENCY contexts in a loop (a benchmark's sweep, a test suite) ran out of queues after a few dozen
@@ -185,17 +53,10 @@ struct ProfScope {
 // (tools/experiments/scratch_env_probe.sh: the only one of six runtime knobs that does) and costs 10-50 % of every step (the headline
 // 36.2 -> 39.9 ms, 16 batches x 2 contexts 20.9 -> 45.9 ms): not a default. A fresh process with up to four such contexts has not
 // failed; bench.py runs those sweep points in child processes. The cure proper is kernels without scratch.
-namespace {
 #ifndef HZ_MAX_PARTITIONED
 #define HZ_MAX_PARTITIONED 4   // (2 until round 6: with k_main_front at 7.7 KB of scratch per lane four flagged contexts in flight aborted in the runtime)
 #endif
-struct MaskedPool {
-    std::mutex mu;
-    std::vector<hipStream_t> idle[16][4];
-    int alive[16] = {};   // partitioned contexts per device
-};
-MaskedPool& masked_pool() { static MaskedPool* p = new MaskedPool(); return *p; }   // (never destroyed: streams outlive static teardown order)
-}  // namespace
+MaskedPool& hz::masked_pool() { static MaskedPool* p = new MaskedPool(); return *p; }   // (never destroyed: streams outlive static teardown order)
 void hz_ctx::release_masked() {
     if (device < 0 || device >= 16) return;
     hipStream_t st[4] = {s_ed, s_fix, s_fee, s_main};
@@ -211,8 +72,6 @@ void hz_ctx::release_masked() {
         P.idle[device][k].push_back(st[k]);
     }
 }
-
-static uint8_t* sec_ptr(hz_ctx* c, int sec) { return (uint8_t*)c->wit.p + c->lo.sections[sec].base * 32; }
 
 static uint32_t block_units(const Layout&, const Section& s, const Block& b) {
     return (b.max_units >= 0) ? (uint32_t)b.max_units : s.upi;   // symbols describe one instance
@@ -729,448 +588,22 @@ extern "C" hz_status hz_inputs_stage_range(hz_ctx* c, int32_t first, int32_t cou
     for (int32_t j = 1; j < count; j++) c->staged[first + j] = 1;
     return HZ_OK;
 }
-
-// ---- kernel schedule ---------------------------------------------------------------------------------
-static SmtProcDesc make_proc(const SmtProcOff& o, uint32_t siblings, int which /*0: p1, 1: p2, 2: fee, 3: SMTProcessor main*/) {
-    SmtProcDesc d;
-    d.o = o;
-    d.siblings = siblings;
-    if (which == 1) {
-        d.sc_oldkey = SC_KEY_S2OLD; d.sc_newkey = SC_KEY_2; d.sc_fnc0 = SC_P2_FNC0; d.sc_fnc1 = SC_P2_FNC1; d.sc_isold0 = SC_ISOLD0_2;
-        d.sc_leaf_old = SC_LEAF_P2OLD; d.sc_leaf_new = SC_LEAF_P2NEW; d.sc_root_old = SC_ROOT_P2OLD; d.sc_root_new = SC_ROOT_P2NEW;
-        d.cid_alias_old = C_RTX_P2_ALIAS_OLD; d.cid_alias_new = C_RTX_P2_ALIAS_NEW; d.cid_levins = C_RTX_P2_LEVINS; d.cid_sm_final = C_RTX_P2_SM_FINAL;
-    } else {
-        d.sc_oldkey = SC_KEY_S1OLD; d.sc_newkey = SC_KEY_1; d.sc_fnc0 = SC_P1_FNC0; d.sc_fnc1 = SC_P1_FNC1; d.sc_isold0 = SC_ISOLD0_1;
-        d.sc_leaf_old = SC_LEAF_P1OLD; d.sc_leaf_new = SC_LEAF_P1NEW; d.sc_root_old = SC_ROOT_P1OLD; d.sc_root_new = SC_ROOT_P1NEW;
-        if (which == 0) {
-            d.cid_alias_old = C_RTX_P1_ALIAS_OLD; d.cid_alias_new = C_RTX_P1_ALIAS_NEW; d.cid_levins = C_RTX_P1_LEVINS; d.cid_sm_final = C_RTX_P1_SM_FINAL;
-        } else if (which == 3) {
-            d.cid_alias_old = C_SMTP_ALIAS_OLD; d.cid_alias_new = C_SMTP_ALIAS_NEW; d.cid_levins = C_SMTP_LEVINS; d.cid_sm_final = C_SMTP_SM_FINAL;
-        } else {
-            d.cid_alias_old = C_FEE_P_ALIAS_OLD; d.cid_alias_new = C_FEE_P_ALIAS_NEW; d.cid_levins = C_FEE_P_LEVINS; d.cid_sm_final = C_FEE_P_SM_FINAL;
-        }
-    }
-    return d;
-}
-
-static Hash4Args make_hash4_rtx(uint8_t* base, Fr* sc, uint32_t n_units, const RtxOff& r) {
-    Hash4Args h;
-    memset(&h, 0, sizeof h);
-    h.base = base; h.scratch = sc; h.n_units = n_units; h.n_jobs = 4;
-    const PoseidonOff hs[4] = {r.oldSt1Hash, r.oldSt2Hash, r.newSt1Hash, r.newSt2Hash};
-    const PoseidonOff h1[4] = {r.p1.hash1Old, r.p2.hash1Old, r.p1.hash1New, r.p2.hash1New};
-    const uint32_t key[4] = {SC_KEY_S1OLD, SC_KEY_S2OLD, SC_KEY_1, SC_KEY_2};
-    const uint32_t leaf[4] = {SC_LEAF_P1OLD, SC_LEAF_P2OLD, SC_LEAF_P1NEW, SC_LEAF_P2NEW};
-    for (int j = 0; j < 4; j++) {
-        HashJob& J = h.job[j];
-        J.hs = hs[j]; J.h1 = h1[j]; J.sc_in = SC_HS_IN + 4 * j; J.sc_key = key[j]; J.sc_leaf = leaf[j];
-        J.mux_off = ~0u; J.sc_ins = 0; J.sc_oldvalue = 0; J.out_sig = ~0u;
-    }
-    h.job[0].mux_off = r.mux16 + MX_S1OLDVALUE; h.job[0].sc_ins = SC_ISP1INSERT; h.job[0].sc_oldvalue = SC_OLDVALUE1;
-    h.job[1].mux_off = r.mux16 + MX_S2OLDVALUE; h.job[1].sc_ins = SC_ISP2INSERT; h.job[1].sc_oldvalue = SC_OLDVALUE2;
-    return h;
-}
-
-// the SMT chain kernel: one launch, one profile entry
-static hipError_t enqueue_smt_chain(hz_ctx* c, const SmtArgs& sa0, const char* name, hipStream_t s) {
-    SmtArgs sa = sa0;
-    bool lat = c->smt_lat;
-    if (!lat && c->smt_lat_few && c->partitioned && c->device >= 0 && c->device < 16) {
-        MaskedPool& P = masked_pool();
-        std::lock_guard<std::mutex> g(P.mu);
-        lat = P.alive[c->device] <= 2;
-    }
-    sa.pos3_dense = lat ? (const Fr*)c->pos3.p : nullptr;
-    const bool fee = sa.scratch == (Fr*)c->sc_fee.p;
-    sa.zmark = (uint16_t*)(fee ? c->zm_fee.p : c->zm_tx.p);
-    sa.skipped = (c->profiling && c->zm_skip.p) ? (unsigned long long*)c->zm_skip.p + (fee ? 1 : 0) : nullptr;
-    if (!fee && getenv("HZ_SMT_TRACE")) {   // tools/experiments/smt_trace.py
-        const uint32_t nl = sa.ucnt ? sa.ucnt : sa.n_units;
-        const size_t waves = (size_t)((nl + 127) / 128) * 2 * 2 * sa.n_proc;
-        if (c->smt_trace.bytes < waves * 32) { if (c->smt_trace.alloc(waves * 32) != hipSuccess) return hipErrorOutOfMemory; }
-        (void)hipMemsetAsync(c->smt_trace.p, 0, waves * 32, s);
-        sa.trace = (unsigned long long*)c->smt_trace.p;
-    }
-    ProfScope ps(c, s, name, sa.n_units);
-    return launch_smt(sa, s);
-}
-
-static HashInputsArgs make_hi(hz_ctx* c, bool is_main);
-
-// early_tail (RollupMain, whole batch): HashInputs does not wait for the SMT chains of every transaction. Its SHA-256 message needs
-// the data-availability bits (front kernel), the last fee transaction's root (fee chain, own stream from the start) and ONE value
-// of the chains: the LAST transaction's exit root. That transaction's four chains are evaluated first, as a launch of their own
-// (4 lanes per batch) on the fee stream right after the hash-state kernel, then the message, the sequential chain and the
-// expansion follow there while the main stream hashes the other 2047 transactions of every batch (its chain and back kernels leave
-// the last one out: `skip_mod`, so no signal is written twice and a failing constraint of that transaction is recorded once).
-// The 3.6 ms of one-wavefront chain latency and the expansion leave the end of the step.
-static hz_status enqueue_rtx_tail(hz_ctx* c, uint8_t* base, uint32_t n_units, bool is_main, uint32_t sib1, uint32_t sib2, hipStream_t s, bool early_tail = false,
-                                  bool early_prep = false, const MainFrontArgs* feeacc = nullptr) {
+// the head of a step (ctx_step.hip enqueue_impl): scatter the staged inputs into the witness layout
+hz_status hz::scatter_staged_inputs(hz_ctx* c, hipStream_t s) {
     const Layout& lo = c->lo;
-    Fr* sc = (Fr*)c->sc_tx.p;
-    ErrBuf* err = (ErrBuf*)c->err.p;
-    EddsaArgs ea;
-    memset(&ea, 0, sizeof ea);
-    ea.base = base; ea.scratch = sc; ea.err = err; ea.n_units = n_units; ea.upi = lo.sections[lo.sec_tx].upi; ea.ed = lo.rtx.ed;
-    const uint32_t u0 = is_main ? c->sh_first : 0, ucnt = is_main ? c->sh_count : 0;
-    ea.u0 = u0; ea.ucnt = ucnt;
-    ea.in_onChain = ~0u;
-    if (is_main && !getenv("HZ_ED_NO_PRE_SPLIT")) {
-        const auto& mi = lo.mi;
-        ea.in_onChain = mi.onChain; ea.in_newAccount = mi.newAccount; ea.in_auxFromIdx = mi.auxFromIdx; ea.in_sign1 = mi.sign1; ea.in_ay1 = mi.ay1;
-        ea.in_txCompressedData = mi.txCompressedData; ea.in_fromBjjCompressed = mi.fromBjjCompressed;
+    HZ_HIP(hipStreamWaitEvent(s, c->ev_staged, 0));
+    for (uint32_t b = 0; b < lo.n_inst;) {   // one launch per run of consecutive staged instances (usually: all of them)
+        if (!c->staged[b]) { b++; continue; }
+        uint32_t e = b;
+        while (e < lo.n_inst && c->staged[e] && e - b < 65535u) c->staged[e++] = 0;
+        const hz_status st = launch_unpack(c, b, s, e - b);
+        if (st != HZ_OK) return st;
+        b = e;
     }
-    {
-        // the split form (launches of <= HZ_ED_SPLIT_MAX signatures) parks its numerators in a side buffer: 84.7 KB per signature,
-        // allocated by the first launch that takes that form and sized for it (a shard: its own range, not the section); the throughput
-        // form keeps the lane state of the fixed-base kernel there (1.7 KB per eight signatures)
-        const size_t need = eddsa_side_bytes(ucnt ? ucnt : n_units);
-        if (need > c->ed_side.bytes || (need && !c->ed_side.p)) {
-            HZ_HIP(hipStreamSynchronize(c->s_ed));
-            HZ_HIP(hipStreamSynchronize(c->exclusive ? c->s_ed : c->s_fix));
-            HZ_HIP(c->ed_side.alloc(need));
-        }
-    }
-    ea.side = (uint32_t*)c->ed_side.p;
-    {
-        // the signature ladders only need the front step: run them beside the hash/SMT chain
-        // the two halves of the check (S*B8 and R8 + h*8A) are independent: two kernels on two streams, then the equality
-        hipStream_t sfix = c->exclusive ? c->s_ed : c->s_fix;
-        HZ_HIP(hipStreamWaitEvent(sfix, c->ev_front, 0));
-        { ProfScope ps(c, sfix, "eddsa_fix", n_units); HZ_HIP(launch_eddsa_fix(ea, sfix)); }
-        // RollupMain's fee accumulators (k_main_feeacc) need the front step only and feed nothing downstream: they follow the fixed-base
-        // half on its stream -- 10 + 1.5 ms against the 16.6 ms of the ladder beside it (one batch: 4.5 + 0.6 against 6.8) -- and are
-        // joined with it (ev_fix -> the signature stream -> the launch stream)
-        if (feeacc) { ProfScope ps(c, sfix, "fee_acc", n_units); HZ_HIP(launch_main_feeacc(*feeacc, sfix)); }
-        HZ_HIP(hipEventRecord(c->ev_fix, sfix));
-        // the signature stream waits for the front step INSIDE launch_eddsa: a RollupMain launch small enough for the split form starts
-        // the point half of its prologue before that (k_eddsa_pre_a reads inputs only; ev_reset: the error buffer, the inputs' scatter)
-        HZ_HIP(hipStreamWaitEvent(c->s_ed, c->ev_reset, 0));
-        // (RollupMain: DecodeTx's sigL2Hash comes from k_main_sighash at the head of the fee stream -- ev_sighash; the hash half of the
-        // prologue waits for it, the point half and the ladder's head do not)
-        { ProfScope ps(c, c->s_ed, "eddsa", n_units); HZ_HIP(launch_eddsa(ea, c->s_ed, c->ev_front, feeacc ? c->ev_sighash : nullptr)); }
-        HZ_HIP(hipStreamWaitEvent(c->s_ed, c->ev_fix, 0));
-        { ProfScope ps(c, c->s_ed, "eddsa_final", n_units); HZ_HIP(launch_eddsa_final(ea, c->s_ed)); }
-        HZ_HIP(hipEventRecord(c->ev_ed, c->s_ed));
-    }
-    {
-        Hash4Args h4 = make_hash4_rtx(base, sc, n_units, lo.rtx);
-        h4.u0 = u0; h4.ucnt = ucnt;
-        ProfScope ps(c, s, "hash4", n_units);
-        HZ_HIP(launch_hash4(h4, s));
-    }
-    SmtArgs sa;
-    memset(&sa, 0, sizeof sa);
-    sa.base = base; sa.scratch = sc; sa.err = err; sa.n_units = n_units; sa.n_levels = (uint32_t)lo.p.L + 1; sa.n_proc = 2; sa.upi = lo.sections[lo.sec_tx].upi;
-    sa.p[0] = make_proc(lo.rtx.p1, sib1, 0);
-    sa.p[1] = make_proc(lo.rtx.p2, sib2, 1);
-    sa.u0 = u0; sa.ucnt = ucnt;
-    RtxBackArgs ba;
-    memset(&ba, 0, sizeof ba);
-    ba.base = base; ba.glob_base = is_main ? sec_ptr(c, lo.sec_glob) : nullptr; ba.scratch = sc; ba.err = err; ba.n_units = n_units; ba.L = (uint32_t)lo.p.L;
-    ba.is_main = is_main ? 1 : 0;
-    ba.upi = lo.sections[lo.sec_tx].upi; ba.B = lo.n_inst;
-    ba.u0 = u0; ba.ucnt = ucnt;
-    ba.p[0] = sa.p[0]; ba.p[1] = sa.p[1];
-    ba.s3 = lo.rtx.s3; ba.s4 = lo.rtx.s4; ba.s5 = lo.rtx.s5;
-    if (is_main) {
-        ba.im_stateroot = lo.mi.imStateRoot; ba.im_exitroot = lo.mi.imExitRoot; ba.g_initfeeroot = lo.g.imInitStateRootFee;
-        ba.main_l1l2amt = lo.rtx.main_l1l2amt; ba.n2bAmount = lo.dec.n2bAmount;
-    } else {
-        ba.o_newStateRoot = lo.rtxi.o_newStateRoot; ba.o_newExitRoot = lo.rtxi.o_newExitRoot;
-    }
-    if (early_tail) {
-        hipStream_t st = c->s_fee;   // the fee chain was enqueued on it before: newStateRoot is ready when these run
-        HZ_HIP(hipEventRecord(c->ev_hash4, s));
-        HZ_HIP(hipStreamWaitEvent(st, c->ev_hash4, 0));
-        SmtArgs sl = sa;
-        sl.u0 = (uint32_t)lo.p.nTx - 1; sl.ucnt = lo.n_inst; sl.ustride = (uint32_t)lo.p.nTx;
-        sl.p[0].sc_root_old = SC_EROOT_P1OLD; sl.p[0].sc_root_new = SC_EROOT_P1NEW; sl.p[1].sc_root_old = SC_EROOT_P2OLD; sl.p[1].sc_root_new = SC_EROOT_P2NEW;
-        sl.zmark = (uint16_t*)c->zm_tx.p;   // (marks are per unit: these units are nobody else's this step)
-        sl.skipped = (c->profiling && c->zm_skip.p) ? (unsigned long long*)c->zm_skip.p + 2 : nullptr;
-        HZ_HIP(launch_smt(sl, st));
-        RtxBackArgs bl = ba;
-        bl.u0 = sl.u0; bl.ucnt = sl.ucnt; bl.ustride = sl.ustride;
-        bl.p[0] = sl.p[0]; bl.p[1] = sl.p[1];
-        bl.skip_h = 1;
-        HZ_HIP(launch_rtx_back(bl, st));
-        HZ_HIP(launch_da_mask(ba, st));
-        // the main stream leaves these units (and phase H of every unit: k_da_mask has it) to the launches above
-        sa.skip_mod = ba.skip_mod = (uint32_t)lo.p.nTx;
-        ba.skip_h = 1;
-        {
-            ProfScope ps(c, st, "hash_inputs", (uint64_t)lo.hi.sha.nblocks);
-            HZ_HIP(launch_hash_inputs(make_hi(c, true), st, c->exclusive ? nullptr : c->s_sha, c->ev_sha, 9));
-        }
-        HZ_HIP(hipEventRecord(c->ev_tail, st));
-    }
-    if (early_prep) {
-        // CU-partitioned contexts (a few batches, latency): the chain cannot start before the roots are known (they sit in the first
-        // block), but the rest of the message can be laid out while the SMT chains run
-        hipStream_t st = c->s_fee;
-        HZ_HIP(hipStreamWaitEvent(st, c->ev_front, 0));
-        HZ_HIP(launch_da_mask(ba, st));
-        ba.skip_h = 1;
-        HZ_HIP(launch_hi_prep_body(make_hi(c, true), st));
-        HZ_HIP(hipEventRecord(c->ev_tail, st));
-    }
-    HZ_HIP(enqueue_smt_chain(c, sa, "smt", s));
-    { ProfScope ps(c, s, "rtx_back", n_units); HZ_HIP(launch_rtx_back(ba, s)); }
-    return HZ_OK;   // the caller joins the signature stream (ev_ed) after whatever else it launches on `s`
-}
-
-static hz_status enqueue_fee(hz_ctx* c, uint8_t* base, uint32_t n_units, bool is_main, hipStream_t s) {
-    const Layout& lo = c->lo;
-    Fr* sc = (Fr*)c->sc_fee.p;
-    ErrBuf* err = (ErrBuf*)c->err.p;
-    FeeFrontArgs fa;
-    memset(&fa, 0, sizeof fa);
-    fa.base = base; fa.glob_base = is_main ? sec_ptr(c, lo.sec_glob) : nullptr; fa.scratch = sc; fa.err = err; fa.n_units = n_units; fa.is_main = is_main;
-    fa.upi = lo.sections[lo.sec_fee].upi; fa.B = lo.n_inst;
-    fa.fee = lo.fee;
-    uint32_t sib;
-    if (is_main) {
-        const MainFeeInOff& f = lo.fi;
-        fa.in_feePlanToken = f.feePlanTokens; fa.in_feeIdx = f.feeIdxs; fa.in_accFee = f.imFinalAccFee; fa.in_tokenID = f.tokenID3; fa.in_nonce = f.nonce3;
-        fa.in_sign = f.sign3; fa.in_balance = f.balance3; fa.in_ay = f.ay3; fa.in_ethAddr = f.ethAddr3; fa.im_stateRootFee = f.imStateRootFee;
-        fa.g_initfeeroot = lo.g.imInitStateRootFee;
-        sib = f.siblings3;
-    } else {
-        const FeeTxInOff& f = lo.feei;
-        fa.in_feePlanToken = f.feePlanToken; fa.in_feeIdx = f.feeIdx; fa.in_accFee = f.accFee; fa.in_tokenID = f.tokenID; fa.in_nonce = f.nonce;
-        fa.in_sign = f.sign; fa.in_balance = f.balance; fa.in_ay = f.ay; fa.in_ethAddr = f.ethAddr; fa.in_oldStateRoot = f.oldStateRoot;
-        sib = f.siblings;
-    }
-    { ProfScope ps(c, s, "fee_front", n_units); HZ_HIP(launch_fee_front(fa, s)); }
-    Hash4Args h;
-    memset(&h, 0, sizeof h);
-    h.base = base; h.scratch = sc; h.n_units = n_units; h.n_jobs = 2;
-    h.job[0] = HashJob{lo.fee.oldHash, lo.fee.p.hash1Old, SC_HS_IN + 0, SC_KEY_S1OLD, SC_LEAF_P1OLD, ~0u, 0, 0, ~0u};
-    h.job[1] = HashJob{lo.fee.newHash, lo.fee.p.hash1New, SC_HS_IN + 8, SC_KEY_1, SC_LEAF_P1NEW, ~0u, 0, 0, ~0u};
-    { ProfScope ps(c, s, "fee_hash", n_units); HZ_HIP(launch_hash4(h, s)); }
-    SmtArgs sa;
-    memset(&sa, 0, sizeof sa);
-    sa.base = base; sa.scratch = sc; sa.err = err; sa.n_units = n_units; sa.n_levels = (uint32_t)lo.p.L + 1; sa.n_proc = 1; sa.upi = lo.sections[lo.sec_fee].upi;
-    sa.p[0] = make_proc(lo.fee.p, sib, 2);
-    HZ_HIP(enqueue_smt_chain(c, sa, "fee_smt", s));
-    FeeBackArgs fb;
-    memset(&fb, 0, sizeof fb);
-    fb.base = base; fb.scratch = sc; fb.err = err; fb.n_units = n_units; fb.is_main = is_main; fb.upi = lo.sections[lo.sec_fee].upi; fb.p = sa.p[0];
-    fb.im_stateRootFee = is_main ? lo.fi.imStateRootFee : 0; fb.o_newStateRoot = lo.fee.o_newStateRoot;
-    { ProfScope ps(c, s, "fee_back", n_units); HZ_HIP(launch_fee_back(fb, s)); }
+    HZ_HIP(hipEventRecord(c->ev_unpacked, s));
+    c->any_staged = false;
     return HZ_OK;
 }
-
-static HashInputsArgs make_hi(hz_ctx* c, bool is_main) {
-    const Layout& lo = c->lo;
-    HashInputsArgs a;
-    memset(&a, 0, sizeof a);
-    a.hi_base = sec_ptr(c, lo.sec_hi);
-    a.err = (ErrBuf*)c->err.p;
-    a.nTx = (uint32_t)lo.p.nTx; a.L = (uint32_t)lo.p.L; a.maxL1 = (uint32_t)lo.p.maxL1; a.F = (uint32_t)lo.p.F; a.is_main = is_main; a.B = lo.n_inst;
-    a.hi = lo.hi;
-    a.msg = (uint8_t*)c->msg.p; a.chain = (uint32_t*)c->chain.p;
-    if (is_main) {
-        a.glob_base = sec_ptr(c, lo.sec_glob); a.tx_base = sec_ptr(c, lo.sec_tx); a.fee_base = sec_ptr(c, lo.sec_fee);
-        a.tx_scratch = (Fr*)c->sc_tx.p; a.fee_scratch = (Fr*)c->sc_fee.p;
-        a.g = lo.g; a.mi_onChain = lo.mi.onChain; a.fi_feeIdxs = lo.fi.feeIdxs; a.dec = lo.dec; a.rtx_s5 = lo.rtx.s5; a.rtx_main_l1l2amt = lo.rtx.main_l1l2amt;
-    }
-    return a;
-}
-
-// error buffer header: minkey = ~0, filter (= ~0 unless this is a second pass), count = 0
-static hz_status reset_err(hz_ctx* c, hipStream_t s, unsigned long long filter) {
-    HZ_HIP(hipMemsetAsync(c->err.p, 0xFF, 16, s));
-    HZ_HIP(hipMemsetAsync((uint8_t*)c->err.p + 16, 0, 8, s));
-    if (filter != ~0ull) {
-        c->filter_stage = filter;
-        HZ_HIP(hipMemcpyAsync((uint8_t*)c->err.p + 8, &c->filter_stage, 8, hipMemcpyHostToDevice, s));
-    } else {
-        // the per-instance minima are reset only when the last pass lowered one (or nobody checked): a clean serving loop pays nothing
-        if (c->inst_min_dirty || !c->checked) HZ_HIP(hipMemsetAsync(c->inst_min.p, 0xFF, c->inst_min.bytes, s));
-        c->inst_min_dirty = false;
-        c->checked = false;
-    }
-    return HZ_OK;
-}
-
-// filter != ~0: a second pass over the SAME inputs for the operands of failures the first pass found (hz_witness_check after an
-// overflow of the record list; hz_witness_failures): inputs staged for the next step stay staged, the per-instance minima stay.
-static hz_status enqueue_impl(hz_ctx* c, void* stream, unsigned long long filter) {
-    const bool rerun = filter != ~0ull;
-    if (!c) return set_err(HZ_ERR_ARG, "hz_witness_enqueue: null context");
-    const Layout& lo = c->lo;
-    for (size_t i = 0; i < c->input_set.size(); i++)
-        if (!c->input_set[i]) return set_err(HZ_ERR_INPUT, "Not all inputs have been set: %s", lo.inputs[i].name.c_str());
-    HZ_HIP(hipSetDevice(c->device));
-    // the legacy default stream has implicit-synchronisation semantics that do not mix with the
-    // context's non-blocking side streams: a NULL stream means "the context's own stream"
-    hipStream_t s = stream ? (hipStream_t)stream : c->s_main;
-    if (c->any_staged && !rerun) {   // scatter the staged inputs (hz_inputs_stage) into the witness layout
-        HZ_HIP(hipStreamWaitEvent(s, c->ev_staged, 0));
-        for (uint32_t b = 0; b < lo.n_inst;) {   // one launch per run of consecutive staged instances (usually: all of them)
-            if (!c->staged[b]) { b++; continue; }
-            uint32_t e = b;
-            while (e < lo.n_inst && c->staged[e] && e - b < 65535u) c->staged[e++] = 0;
-            const hz_status st = launch_unpack(c, b, s, e - b);
-            if (st != HZ_OK) return st;
-            b = e;
-        }
-        HZ_HIP(hipEventRecord(c->ev_unpacked, s));
-        c->any_staged = false;
-    }
-    if (c->inputs_pending) {
-        HZ_HIP(hipStreamWaitEvent(s, c->ev_inputs, 0));
-        c->inputs_pending = false;
-    }
-    // partitioned contexts run their main sequence on the CU-masked stream, ordered after / before the caller's stream by two events
-    hipStream_t s_user = s;
-    if (c->partitioned && s != c->s_main) {
-        HZ_HIP(hipEventRecord(c->ev_user_in, s_user));
-        s = c->s_main;
-        HZ_HIP(hipStreamWaitEvent(s, c->ev_user_in, 0));
-    }
-    // profiling mode 2: every kernel alone on the device (the side streams alias the launch stream)
-    struct StreamAlias {
-        hz_ctx* c; hipStream_t ed, fee;
-        StreamAlias(hz_ctx* c_, hipStream_t s_) : c(c_), ed(c_->s_ed), fee(c_->s_fee) { if (c->exclusive) c->s_ed = c->s_fee = s_; }
-        ~StreamAlias() { c->s_ed = ed; c->s_fee = fee; }
-    } alias(c, s);
-    { const hz_status st = reset_err(c, s, filter); if (st != HZ_OK) return st; }
-    if (c->zm_reset) {   // (before ev_reset: every side stream waits for it before its first kernel)
-        if (c->zm_tx.p) HZ_HIP(hipMemsetAsync(c->zm_tx.p, 0xFF, c->zm_tx.bytes, s));
-        if (c->zm_fee.p) HZ_HIP(hipMemsetAsync(c->zm_fee.p, 0xFF, c->zm_fee.bytes, s));
-        c->zm_reset = false;
-    }
-    if (c->profiling && c->zm_skip.p) HZ_HIP(hipMemsetAsync(c->zm_skip.p, 0, c->zm_skip.bytes, s));
-    HZ_HIP(hipEventRecord(c->ev_reset, s));
-    ErrBuf* err = (ErrBuf*)c->err.p;
-    c->prof_used = 0;
-    switch (lo.p.tmpl) {
-        case T_ROLLUP_MAIN: {
-            MainFrontArgs fa;
-            memset(&fa, 0, sizeof fa);
-            fa.tx_base = sec_ptr(c, lo.sec_tx); fa.fee_base = sec_ptr(c, lo.sec_fee); fa.glob_base = sec_ptr(c, lo.sec_glob);
-            fa.scratch = (Fr*)c->sc_tx.p; fa.err = err; fa.nTx = (uint32_t)lo.p.nTx; fa.L = (uint32_t)lo.p.L; fa.F = (uint32_t)lo.p.F; fa.B = lo.n_inst;
-            fa.g = lo.g; fa.mi = lo.mi; fa.fi = lo.fi; fa.dec = lo.dec; fa.rtx = lo.rtx;
-            hz_status st = HZ_OK;
-            const bool tail_now = !c->sharded;   // sharded contexts run the tail separately (hz_witness_enqueue_tail)
-            if (c->sharded && c->sh_count == 0) break;   // an empty shard (more ranks than transactions): nothing to evaluate
-            fa.u0 = c->sh_first; fa.ucnt = c->sh_count;
-            // DecodeTx's sigL2Hash (k_main_sighash: one Poseidon of width 7 over INPUTS; read by the signature prologue's hash half only)
-            // heads the fee stream -- beside the front kernel and the prologue's point half, in front of a chain that has time to spare
-            HZ_HIP(hipStreamWaitEvent(c->s_fee, c->ev_reset, 0));
-            { ProfScope ps(c, c->s_fee, "sig_hash", (uint64_t)fa.nTx * fa.B); HZ_HIP(launch_main_sighash(fa, c->s_fee)); }
-            HZ_HIP(hipEventRecord(c->ev_sighash, c->s_fee));
-            if (tail_now) {
-                st = enqueue_fee(c, fa.fee_base, lo.sections[lo.sec_fee].n_units, true, c->s_fee);   // independent of the transactions
-                if (st != HZ_OK) return st;
-                HZ_HIP(hipEventRecord(c->ev_fee, c->s_fee));
-            }
-            fa.u0 = c->sh_first; fa.ucnt = c->sh_count;
-            { ProfScope ps(c, s, "front", (uint64_t)fa.nTx * fa.B); HZ_HIP(launch_main_front(fa, s)); }
-            HZ_HIP(hipEventRecord(c->ev_front, s));
-            const bool early = tail_now && !c->partitioned;   // CU-partitioned contexts keep the tail on the main stream
-            const bool early_prep = tail_now && c->partitioned;
-            st = enqueue_rtx_tail(c, fa.tx_base, lo.sections[lo.sec_tx].n_units, true, lo.mi.siblings1, lo.mi.siblings2, s, early, early_prep, &fa);
-            if (st != HZ_OK) return st;
-            if (early) {
-                HZ_HIP(hipStreamWaitEvent(s, c->ev_tail, 0));
-            } else if (tail_now) {
-                // HashInputs needs the roots and the data-availability bits, not the signatures: it runs beside the ladders
-                // (partitioned contexts: chain and expansion on this stream, one launch each -- the expansion piped over the fee stream
-                // in eight groups, as the throughput schedule does, costs a single batch 1.25 ms: 9.1 against 7.86 ms)
-                HZ_HIP(hipStreamWaitEvent(s, c->ev_fee, 0));
-                if (early_prep) HZ_HIP(hipStreamWaitEvent(s, c->ev_tail, 0));
-                { ProfScope ps(c, s, "hash_inputs", (uint64_t)lo.hi.sha.nblocks); HZ_HIP(launch_hash_inputs(make_hi(c, true), s, c->partitioned ? nullptr : c->s_fee, c->ev_sha, 9, early_prep)); }
-            }
-            HZ_HIP(hipStreamWaitEvent(s, c->ev_ed, 0));   // join the signature stream
-            break;
-        }
-        case T_ROLLUP_TX: {
-            RtxFrontArgs fa;
-            memset(&fa, 0, sizeof fa);
-            fa.base = sec_ptr(c, 0); fa.scratch = (Fr*)c->sc_tx.p; fa.err = err; fa.N = lo.sections[0].n_units; fa.L = (uint32_t)lo.p.L; fa.F = (uint32_t)lo.p.F;
-            fa.in = lo.rtxi; fa.rtx = lo.rtx;
-            { ProfScope ps(c, s, "front", fa.N); HZ_HIP(launch_rtx_front(fa, s)); }
-            HZ_HIP(hipEventRecord(c->ev_front, s));
-            hz_status st = enqueue_rtx_tail(c, fa.base, fa.N, false, lo.rtxi.siblings1, lo.rtxi.siblings2, s);
-            if (st != HZ_OK) return st;
-            HZ_HIP(hipStreamWaitEvent(s, c->ev_ed, 0));   // join the signature stream
-            break;
-        }
-        case T_DECODE_TX: {
-            DecMainArgs da;
-            memset(&da, 0, sizeof da);
-            da.base = sec_ptr(c, 0); da.err = err; da.N = lo.sections[0].n_units; da.L = (uint32_t)lo.p.L; da.in = lo.deci; da.dec = lo.dec;
-            HZ_HIP(launch_dec_main(da, s));
-            break;
-        }
-        case T_FEE_TX: {
-            hz_status st = enqueue_fee(c, sec_ptr(c, 0), lo.sections[0].n_units, false, s);
-            if (st != HZ_OK) return st;
-            break;
-        }
-        case T_HASH_STATE:
-            HZ_HIP(launch_hash_state_main(sec_ptr(c, 0), lo.sections[0].n_units, lo.hs, s));
-            break;
-        case T_WITHDRAW: {
-            WithdrawArgs wa;
-            memset(&wa, 0, sizeof wa);
-            wa.base = sec_ptr(c, 0); wa.err = err; wa.N = lo.sections[0].n_units; wa.L = (uint32_t)lo.p.L; wa.wd = lo.wd;
-            // the SHA-256 bit witness (store bound) runs beside the Poseidon / SMT part (integer bound) on a side stream
-            HZ_HIP(hipStreamWaitEvent(c->s_ed, c->ev_reset, 0));
-            { ProfScope ps(c, c->s_ed, "withdraw_sha", wa.N); HZ_HIP(launch_withdraw_sha(wa, c->s_ed)); }
-            HZ_HIP(hipEventRecord(c->ev_ed, c->s_ed));
-            { ProfScope ps(c, s, "withdraw", wa.N); HZ_HIP(launch_withdraw(wa, s)); }
-            HZ_HIP(hipStreamWaitEvent(s, c->ev_ed, 0));
-            break;
-        }
-        case T_HASH_INPUTS:
-            HZ_HIP(launch_hash_inputs(make_hi(c, false), s, c->s_fee, c->ev_sha, 9));
-            break;
-        case T_SMT_PROCESSOR: case T_SMT_VERIFIER: {
-            SmtMainArgs ma;
-            memset(&ma, 0, sizeof ma);
-            ma.base = sec_ptr(c, 0); ma.scratch = (Fr*)c->sc_fee.p; ma.err = err; ma.N = lo.sections[0].n_units; ma.n_levels = (uint32_t)lo.p.L;
-            if (lo.p.tmpl == T_SMT_VERIFIER) {
-                ma.vin = lo.smtvi; ma.ver = lo.smtv;
-                HZ_HIP(launch_smtver_main(ma, s));
-                break;
-            }
-            ma.pin = lo.smtpi; ma.proc = make_proc(lo.smtp, lo.smtpi.siblings, 3);
-            HZ_HIP(launch_smtproc_front(ma, s));
-            SmtArgs sa;
-            memset(&sa, 0, sizeof sa);
-            sa.base = ma.base; sa.scratch = ma.scratch; sa.err = err; sa.n_units = ma.N; sa.n_levels = ma.n_levels; sa.n_proc = 1; sa.upi = 1;
-            sa.p[0] = ma.proc;
-            HZ_HIP(enqueue_smt_chain(c, sa, "smt", s));
-            HZ_HIP(launch_smtproc_back(ma, s));
-            break;
-        }
-        case T_DECODE_FLOAT: case T_COMPUTE_FEE: case T_FEE_ACCUMULATOR: case T_BALANCE_UPDATER: case T_ROLLUP_TX_STATES: case T_RQ_TX_VERIFIER:
-        case T_MUX256: case T_BITS2AYSIGN: case T_AYSIGN2AX: {
-            GadgetArgs ga;
-            memset(&ga, 0, sizeof ga);
-            ga.base = sec_ptr(c, 0); ga.err = err; ga.N = lo.sections[0].n_units; ga.F = (uint32_t)lo.p.F; ga.io = lo.gad;
-            ga.n2b40 = lo.rtx.n2bLoadAmountF; ga.df = lo.rtx.dfLoadAmount; ga.bu = lo.rtx.bu; ga.feeAcc = lo.rtx.feeAcc; ga.st = lo.rtx.st;
-            ga.rq_n2b = lo.rtx.rq_n2b;
-            for (int m = 0; m < 3; m++) ga.rq_mux[m] = lo.rtx.rq_mux[m];
-            if (lo.p.tmpl == T_AYSIGN2AX) HZ_HIP(launch_ay_sign_2_ax_main(ga, lo.rtx.ed, s));
-            else HZ_HIP(launch_gadget(lo.p.tmpl, ga, s));
-            break;
-        }
-    }
-    if (s != s_user) {
-        HZ_HIP(hipEventRecord(c->ev_user_out, s));
-        HZ_HIP(hipStreamWaitEvent(s_user, c->ev_user_out, 0));
-    }
-    c->last_stream = s_user;
-    c->enqueued = true;
-    return HZ_OK;
-}
-
-extern "C" hz_status hz_witness_enqueue(hz_ctx* c, void* stream) { return enqueue_impl(c, stream, ~0ull); }
 
 static void fill_error(hz_error* out, unsigned long long key, const ErrRec* r) {
     if (!out) return;
@@ -1282,121 +715,12 @@ extern "C" hz_status hz_ctx_set_shard(hz_ctx* c, int32_t first, int32_t count, i
     c->sh_tail = tail != 0;
     return HZ_OK;
 }
+// (what a sharded step launches -- hz_da_export / hz_da_import, hz_witness_enqueue_tail*, hz_sha_export / hz_sha_expand -- is ctx_step.hip)
 extern "C" uint64_t hz_da_record_bytes(const hz_ctx*) { return HZ_DA_RECORD_BYTES; }
-static DaArgs make_da(hz_ctx* c, uint32_t first, uint32_t count, void* buf) {
-    const Layout& lo = c->lo;
-    DaArgs a;
-    memset(&a, 0, sizeof a);
-    a.tx_base = sec_ptr(c, lo.sec_tx); a.tx_scratch = (Fr*)c->sc_tx.p; a.buf = (uint8_t*)buf;
-    a.nTx = (uint32_t)lo.p.nTx; a.L = (uint32_t)lo.p.L; a.u0 = first; a.ucnt = count;
-    a.l1full = lo.dec.l1full; a.n2bData = lo.dec.n2bData; a.n2bFinalToIdx = lo.dec.n2bFinalToIdx; a.l1l2amt = lo.rtx.main_l1l2amt;
-    a.l1l2Fee = lo.dec.l1l2Fee; a.s5 = lo.rtx.s5;
-    return a;
-}
-extern "C" hz_status hz_da_export(hz_ctx* c, void* d_buf, void* stream) {
-    if (!c || c->lo.p.tmpl != T_ROLLUP_MAIN || !d_buf) return set_err(HZ_ERR_ARG, "hz_da_export: bad argument");
-    HZ_HIP(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->s_main;
-    const uint32_t cnt = c->sharded ? c->sh_count : (uint32_t)c->lo.p.nTx;
-    HZ_HIP(launch_da_export(make_da(c, c->sh_first, cnt, d_buf), s));
-    return HZ_OK;
-}
-extern "C" hz_status hz_da_import(hz_ctx* c, int32_t first, int32_t count, const void* d_buf, void* stream) {
-    if (!c || c->lo.p.tmpl != T_ROLLUP_MAIN || !d_buf || first < 0 || count < 0 || first > c->lo.p.nTx || count > c->lo.p.nTx - first)
-        return set_err(HZ_ERR_ARG, "hz_da_import: bad argument");
-    HZ_HIP(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->s_main;
-    HZ_HIP(launch_da_import(make_da(c, (uint32_t)first, (uint32_t)count, const_cast<void*>(d_buf)), s));
-    return HZ_OK;
-}
-// fee transactions + HashInputs of a sharded context, after the other ranks' records were imported
-extern "C" hz_status hz_witness_enqueue_tail(hz_ctx* c, void* stream) {
-    if (!c || c->lo.p.tmpl != T_ROLLUP_MAIN) return set_err(HZ_ERR_ARG, "hz_witness_enqueue_tail: RollupMain contexts only");
-    HZ_HIP(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->s_main;
-    const Layout& lo = c->lo;
-    hz_status st = enqueue_fee(c, sec_ptr(c, lo.sec_fee), lo.sections[lo.sec_fee].n_units, true, s);
-    if (st != HZ_OK) return st;
-    { ProfScope ps(c, s, "hash_inputs", (uint64_t)lo.hi.sha.nblocks); HZ_HIP(launch_hash_inputs(make_hi(c, true), s, c->s_fee, c->ev_sha, 9)); }
-    c->last_stream = s;
-    c->enqueued = true;
-    return HZ_OK;
-}
-
-extern "C" hz_status hz_witness_enqueue_tail_chain(hz_ctx* c, void* stream) {
-    if (!c || c->lo.p.tmpl != T_ROLLUP_MAIN) return set_err(HZ_ERR_ARG, "hz_witness_enqueue_tail_chain: RollupMain contexts only");
-    HZ_HIP(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->s_main;
-    const Layout& lo = c->lo;
-    hz_status st = enqueue_fee(c, sec_ptr(c, lo.sec_fee), lo.sections[lo.sec_fee].n_units, true, s);
-    if (st != HZ_OK) return st;
-    { ProfScope ps(c, s, "hash_inputs", (uint64_t)lo.hi.sha.nblocks); HZ_HIP(launch_hi_chain_only(make_hi(c, true), s)); }
-    c->last_stream = s;
-    c->enqueued = true;
-    return HZ_OK;
-}
 extern "C" uint64_t hz_sha_blocks(const hz_ctx* c) { return (c && c->lo.sec_hi >= 0) ? (uint64_t)c->lo.hi.sha.nblocks : 0; }
 extern "C" uint64_t hz_sha_state_bytes(const hz_ctx* c) {
     return (c && c->lo.sec_hi >= 0) ? ((uint64_t)c->lo.hi.sha.nblocks * 64 + ((uint64_t)c->lo.hi.sha.nblocks + 1) * 32) * c->lo.n_inst : 0;
 }
-extern "C" hz_status hz_sha_export(hz_ctx* c, void* d_buf, void* stream) {
-    if (!c || !d_buf || c->lo.sec_hi < 0) return set_err(HZ_ERR_ARG, "hz_sha_export: needs a context with a HashInputs section and a buffer");
-    HZ_HIP(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->s_main;
-    const size_t mb = (size_t)c->lo.hi.sha.nblocks * 64 * c->lo.n_inst, cb = ((size_t)c->lo.hi.sha.nblocks + 1) * 32 * c->lo.n_inst;
-    HZ_HIP(hipMemcpyAsync(d_buf, c->msg.p, mb, hipMemcpyDeviceToDevice, s));
-    HZ_HIP(hipMemcpyAsync((uint8_t*)d_buf + mb, c->chain.p, cb, hipMemcpyDeviceToDevice, s));
-    return HZ_OK;
-}
-extern "C" hz_status hz_sha_expand(hz_ctx* c, int32_t first, int32_t count, const void* d_buf, void* stream) {
-    if (!c || c->lo.sec_hi < 0) return set_err(HZ_ERR_ARG, "hz_sha_expand: needs a context with a HashInputs section");
-    const int64_t nb = c->lo.hi.sha.nblocks;
-    if (first < 0 || count < 0 || (int64_t)first + count > nb) return set_err(HZ_ERR_ARG, "hz_sha_expand: blocks %d..%d out of range (%lld blocks)", first, first + count - 1, (long long)nb);
-    HZ_HIP(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->s_main;
-    if (d_buf) {
-        const size_t mb = (size_t)nb * 64 * c->lo.n_inst, cb = ((size_t)nb + 1) * 32 * c->lo.n_inst;
-        HZ_HIP(hipMemcpyAsync(c->msg.p, d_buf, mb, hipMemcpyDeviceToDevice, s));
-        HZ_HIP(hipMemcpyAsync(c->chain.p, (const uint8_t*)d_buf + mb, cb, hipMemcpyDeviceToDevice, s));
-    }
-    if (!c->enqueued) {   // a rank with an empty transaction shard has not reset its failure record this step
-        const hz_status st = reset_err(c, s, ~0ull);
-        if (st != HZ_OK) return st;
-    }
-    HZ_HIP(launch_sha_expand_range(make_hi(c, true), (uint32_t)first, (uint32_t)count, s));
-    c->last_stream = s;
-    c->enqueued = true;
-    return HZ_OK;
-}
-
-extern "C" hz_status hz_ctx_set_profiling(hz_ctx* c, int32_t on) {
-    if (!c) return set_err(HZ_ERR_ARG, "hz_ctx_set_profiling: null context");
-    c->profiling = on != 0;
-    c->exclusive = on == 2;
-    return HZ_OK;
-}
-extern "C" int32_t hz_profile_count(const hz_ctx* c) { return c ? (int32_t)c->prof_used : 0; }
-extern "C" hz_status hz_profile_get(hz_ctx* c, int32_t i, const char** kernel, float* ms, uint64_t* algorithmic_bytes, uint64_t* units) {
-    if (!c || i < 0 || (size_t)i >= c->prof_used) return set_err(HZ_ERR_ARG, "hz_profile_get: bad index");
-    hz_ctx::Prof& p = c->prof[i];
-    HZ_HIP(hipSetDevice(c->device));
-    HZ_HIP(hipEventSynchronize(p.e1));
-    HZ_HIP(hipEventElapsedTime(&p.ms, p.e0, p.e1));
-    if (kernel) *kernel = p.name.c_str();
-    if (ms) *ms = p.ms;
-    uint64_t bytes = p.bytes;
-    if (c->zm_skip.p && (p.name == "smt" || p.name == "fee_smt")) {
-        // what the launch left in place because the buffer held it already (constant marks) is not among the bytes it is responsible for
-        unsigned long long sk[3] = {0, 0, 0};
-        HZ_HIP(hipMemcpy(sk, c->zm_skip.p, sizeof sk, hipMemcpyDeviceToHost));
-        const uint64_t left = (uint64_t)sk[p.name == "smt" ? 0 : 1] * 32ull;
-        bytes = bytes > left ? bytes - left : 0;
-    }
-    if (algorithmic_bytes) *algorithmic_bytes = bytes;
-    if (units) *units = p.units;
-    return HZ_OK;
-}
-
 extern "C" hz_status hz_witness_run(hz_ctx* c, hz_error* err) {
     hz_status st = hz_witness_enqueue(c, nullptr);
     if (st != HZ_OK) return st;

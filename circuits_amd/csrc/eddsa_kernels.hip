@@ -1290,31 +1290,36 @@ __global__ __launch_bounds__(HZ_BLOCK) void k_eddsa_final(const EddsaArgs a) {
     io.chk_zero(C_RTX_SIG_EQY, fr_mul(fr_sub(one, ey), enabled));
 }
 
+// ---- launchers: arguments and a stream in, launches out. What a launch waits for and who waits for it is the schedule's (ctx_step.hip) ----
 // Signatures per lane: sharing an inversion among G signatures cuts the instruction count (throughput) but leaves 1/G of the
 // wavefronts, each G times as long (latency). Few units (a single batch or a handful): the device is far from full and
 // latency is what counts; many units per launch: the integer pipe is the limit.
-template <int G>
-static hipError_t launch_eddsa_split(const EddsaArgs& a0, uint32_t n, hipStream_t s, hipEvent_t front_done, hipEvent_t hash_done) {
+// A launch the device does not fill is latency bound and takes the SPLIT form: the two segments of every signature as independent lanes
+// (148 / 106 dependent steps instead of 254), one signature per lane; the doubling chain between the segments is the second lane's.
+static uint32_t ed_units(const EddsaArgs& a) { return a.ucnt ? a.ucnt : a.n_units; }
+bool eddsa_split_form(const EddsaArgs& a) { return ed_units(a) <= HZ_ED_SPLIT_MAX; }
+static EddsaArgs ed_formed(const EddsaArgs& a0) {   // every kernel of a launch reads the form from its arguments
     EddsaArgs a = a0;
-    a.chain_in_ladder = 1;
-    if (a.in_onChain != ~0u && front_done) {   // RollupMain: the point half of the prologue beside the front kernel, the hash half after it
-        hipLaunchKernelGGL(k_eddsa_pre_a, dim3((n + HZ_BLOCK - 1) / HZ_BLOCK), dim3(HZ_BLOCK), 0, s, a);
-        hipError_t e = hipStreamWaitEvent(s, front_done, 0);
-        if (e == hipSuccess && hash_done) e = hipStreamWaitEvent(s, hash_done, 0);   // sigL2Hash (k_main_sighash, on another stream)
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_eddsa_pre_b, dim3((n + HZ_BLOCK - 1) / HZ_BLOCK), dim3(HZ_BLOCK), 0, s, a);
-    } else {
-        if (front_done) { const hipError_t e = hipStreamWaitEvent(s, front_done, 0); if (e != hipSuccess) return e; }
-        if (hash_done) { const hipError_t e = hipStreamWaitEvent(s, hash_done, 0); if (e != hipSuccess) return e; }
-        hipLaunchKernelGGL(k_eddsa_pre, dim3((n + HZ_BLOCK - 1) / HZ_BLOCK), dim3(HZ_BLOCK), 0, s, a);
-    }
-    const uint32_t nl = (n + G - 1) / G;
-    hipLaunchKernelGGL(k_eddsa_ladder<G>, dim3((nl + HZ_BLOCK - 1) / HZ_BLOCK, 2), dim3(HZ_BLOCK), 0, s, a);
+    a.chain_in_ladder = eddsa_split_form(a0) ? 1 : 0;
+    return a;
+}
+static dim3 ed_grid(uint32_t n) { return dim3((n + HZ_BLOCK - 1) / HZ_BLOCK); }
+// the prologue whole (k_eddsa_pre), or -- split form of a RollupMain launch, in_onChain set -- its point half (k_eddsa_pre_a: reads
+// inputs only) and its hash half (k_eddsa_pre_b: reads the front step's scratch and SC_SIGL2HASH)
+hipError_t launch_eddsa_pre(const EddsaArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(k_eddsa_pre, ed_grid(ed_units(a)), dim3(HZ_BLOCK), 0, s, ed_formed(a));
+    return hipGetLastError();
+}
+hipError_t launch_eddsa_pre_point(const EddsaArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(k_eddsa_pre_a, ed_grid(ed_units(a)), dim3(HZ_BLOCK), 0, s, ed_formed(a));
+    return hipGetLastError();
+}
+hipError_t launch_eddsa_pre_hash(const EddsaArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(k_eddsa_pre_b, ed_grid(ed_units(a)), dim3(HZ_BLOCK), 0, s, ed_formed(a));
     return hipGetLastError();
 }
 template <int G>
 static hipError_t launch_eddsa_seg(const EddsaArgs& a, uint32_t n, hipStream_t s) {
-    hipLaunchKernelGGL(k_eddsa_pre, dim3((n + HZ_BLOCK - 1) / HZ_BLOCK), dim3(HZ_BLOCK), 0, s, a);
     const uint32_t nl = (n + G - 1) / G;
     constexpr size_t lds = (size_t)ls_slots<G>() * 9 * HZ_BLOCK * sizeof(uint32_t);
     if (lds > 64 * 1024) {   // beyond the default limit of dynamic LDS per workgroup (gfx950 has 160 KB per CU); the attribute is per device
@@ -1342,13 +1347,14 @@ size_t eddsa_side_bytes(uint32_t n) {
     const size_t lanes = (((size_t)n + HZ_ED_FIX_G - 1) / HZ_ED_FIX_G + 63) & ~(size_t)63;
     return lanes * FixMem<HZ_ED_FIX_G>::SLOTS * 9 * sizeof(uint32_t);
 }
-hipError_t launch_eddsa(const EddsaArgs& a, hipStream_t s, hipEvent_t front_done, hipEvent_t hash_done) {
-    const uint32_t n = a.ucnt ? a.ucnt : a.n_units;
-    // a launch the device does not fill is latency bound: the two segments of every signature as independent lanes (148 / 106
-    // dependent steps instead of 254), one signature per lane
-    if (n <= HZ_ED_SPLIT_MAX) return launch_eddsa_split<1>(a, n, s, front_done, hash_done);
-    if (front_done) { const hipError_t e = hipStreamWaitEvent(s, front_done, 0); if (e != hipSuccess) return e; }
-    if (hash_done) { const hipError_t e = hipStreamWaitEvent(s, hash_done, 0); if (e != hipSuccess) return e; }
+// the variable-base ladder behind the prologue: k_eddsa_ladder<1> in the split form, k_eddsa_seg<HZ_ED_G> in the throughput form
+hipError_t launch_eddsa_ladder(const EddsaArgs& a0, hipStream_t s) {
+    const EddsaArgs a = ed_formed(a0);
+    const uint32_t n = ed_units(a);
+    if (eddsa_split_form(a)) {
+        hipLaunchKernelGGL(k_eddsa_ladder<1>, dim3((n + HZ_BLOCK - 1) / HZ_BLOCK, 2), dim3(HZ_BLOCK), 0, s, a);
+        return hipGetLastError();
+    }
     return launch_eddsa_seg<HZ_ED_G>(a, n, s);
 }
 hipError_t launch_eddsa_fix(const EddsaArgs& a, hipStream_t s) {

@@ -586,64 +586,23 @@ hipError_t launch_hash_state_main(uint8_t* base, uint32_t N, const HashStateOff&
     hipLaunchKernelGGL(k_hash_state_main, grid1(N), dim3(HZ_BLOCK), 0, s, a);
     return hipGetLastError();
 }
-// The chain is sequential, the expansion (a 0.7 GB store stream per batch) is not: the blocks are split into groups, group g's
-// expansion runs on the side stream while the main stream chains group g + 1, and the main stream joins at the end. The tail
-// of a step is then about chain + expansion / groups instead of chain + expansion. side == s (or no events): one after the other.
-#ifndef HZ_SHA_GROUPS
-#define HZ_SHA_GROUPS 8
-#endif
-hipError_t launch_hi_prep_body(const HashInputsArgs& a0, hipStream_t s) {
+// HashInputs in the three pieces a schedule orders (ctx_step.hip enqueue_hash_inputs: whole, in piped groups, chain only):
+// the message (k_hi_prep; `part` as HashInputsArgs::prep_part -- HI_WHOLE and HI_BODY clear the message buffer first, it is ORed into;
+// HI_HEADER follows an HI_BODY launch once the roots are known), the sequential chain over blocks [blk0, blk1), their expansion
+hipError_t launch_hi_prep(const HashInputsArgs& a0, uint32_t part, hipStream_t s) {
     HashInputsArgs a = a0;
-    const hipError_t e = hipMemsetAsync(a.msg, 0, (size_t)a.hi.sha.nblocks * 64 * a.B, s);
-    if (e != hipSuccess) return e;
-    a.prep_part = 1;
-    hipLaunchKernelGGL(k_hi_prep, grid1((1 + a.maxL1 + a.nTx + a.F) * a.B), dim3(HZ_BLOCK), 0, s, a);
-    return hipGetLastError();
-}
-hipError_t launch_hash_inputs(const HashInputsArgs& a0, hipStream_t s, hipStream_t side, hipEvent_t* ev, int n_ev, bool body_done) {
-    HashInputsArgs a = a0;
-    hipError_t e = hipSuccess;
-    if (body_done) {
-        a.prep_part = 2;
-        hipLaunchKernelGGL(k_hi_prep, grid1(a.B), dim3(HZ_BLOCK), 0, s, a);
-    } else {
-        const size_t msg_bytes = (size_t)a.hi.sha.nblocks * 64 * a.B;
-        e = hipMemsetAsync(a.msg, 0, msg_bytes, s);
+    a.prep_part = part;
+    if (part != HI_HEADER) {
+        const hipError_t e = hipMemsetAsync(a.msg, 0, (size_t)a.hi.sha.nblocks * 64 * a.B, s);
         if (e != hipSuccess) return e;
-        a.prep_part = 0;
-        hipLaunchKernelGGL(k_hi_prep, grid1((1 + a.maxL1 + a.nTx + a.F) * a.B), dim3(HZ_BLOCK), 0, s, a);
     }
-    const uint32_t nb = (uint32_t)a.hi.sha.nblocks;
-    const bool piped = side && side != s && ev && n_ev >= 2 && nb >= 64;
-    const uint32_t groups = piped ? (uint32_t)std::min<int>(HZ_SHA_GROUPS, n_ev - 1) : 1u;
-    const uint32_t per = (nb + groups - 1) / groups;
-    for (uint32_t g = 0, b0 = 0; b0 < nb; g++, b0 += per) {
-        a.blk0 = b0;
-        a.blk1 = std::min(nb, b0 + per);
-        if (a.B <= 2 * HZ_SHAW_BATCH) hipLaunchKernelGGL(k_sha_chain_w, dim3((a.B + HZ_SHAW_BATCH - 1) / HZ_SHAW_BATCH), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL(k_sha_chain, dim3((a.B + 63) / 64), dim3(256), 0, s, a);
-        hipStream_t sx = s;
-        if (piped) {
-            if ((e = hipEventRecord(ev[g], s)) != hipSuccess) return e;
-            if ((e = hipStreamWaitEvent(side, ev[g], 0)) != hipSuccess) return e;
-            sx = side;
-        }
-        hipLaunchKernelGGL(k_sha_expand, grid1((a.blk1 - a.blk0) * a.B * HZ_SHA_PARTS), dim3(HZ_BLOCK), 0, sx, a);
-    }
-    if (piped) {
-        if ((e = hipEventRecord(ev[n_ev - 1], side)) != hipSuccess) return e;
-        if ((e = hipStreamWaitEvent(s, ev[n_ev - 1], 0)) != hipSuccess) return e;
-    }
+    hipLaunchKernelGGL(k_hi_prep, grid1(part == HI_HEADER ? a.B : (1 + a.maxL1 + a.nTx + a.F) * a.B), dim3(HZ_BLOCK), 0, s, a);
     return hipGetLastError();
 }
-hipError_t launch_hi_chain_only(const HashInputsArgs& a0, hipStream_t s) {
+hipError_t launch_sha_chain(const HashInputsArgs& a0, uint32_t blk0, uint32_t blk1, hipStream_t s) {
     HashInputsArgs a = a0;
-    hipError_t e = hipMemsetAsync(a.msg, 0, (size_t)a.hi.sha.nblocks * 64 * a.B, s);
-    if (e != hipSuccess) return e;
-    a.prep_part = 0;
-    hipLaunchKernelGGL(k_hi_prep, grid1((1 + a.maxL1 + a.nTx + a.F) * a.B), dim3(HZ_BLOCK), 0, s, a);
-    a.blk0 = 0;
-    a.blk1 = (uint32_t)a.hi.sha.nblocks;
+    a.blk0 = blk0;
+    a.blk1 = blk1;
     if (a.B <= 2 * HZ_SHAW_BATCH) hipLaunchKernelGGL(k_sha_chain_w, dim3((a.B + HZ_SHAW_BATCH - 1) / HZ_SHAW_BATCH), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(k_sha_chain, dim3((a.B + 63) / 64), dim3(256), 0, s, a);
     return hipGetLastError();

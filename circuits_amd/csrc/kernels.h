@@ -96,7 +96,7 @@ struct SmtArgs {
     uint32_t n_proc;
     uint32_t upi;
     uint32_t skip_mod;            // != 0: units u with u % skip_mod == skip_mod - 1 belong to another launch of the step (early tail)
-    // Constant marks (ctx.hip "constant marks"): two bytes per (chain, unit) that say from which level up the persistent witness buffer
+    // Constant marks (ctx_internal.h "constant marks"): two bytes per (chain, unit) that say from which level up the persistent witness buffer
     // ALREADY holds what an empty level gets -- low byte: the constant S-box block of the level hash (HZ_POSEIDON3_ZERO_WIT), high byte: zeros
     // in the per-level switcher / state-machine signals. k_smt stores such a level only below the mark and leaves the new mark behind.
     // NULL: every level is stored (HZ_NO_ZMARK, experiments).
@@ -137,8 +137,8 @@ struct EddsaArgs {
     uint32_t n_units, upi;
     EddsaOff ed;
     uint32_t* side;      // seg_any_proj's parked numerators (eddsa_side_bytes(n)); nullptr: the inversion-per-step ladder
-    uint32_t chain_in_ladder;   // set by launch_eddsa for small launches: the doubling chain between the segments is the second segment lane's
-    // RollupMain, small launches (set by ctx.hip; in_onChain == ~0u: off): the prologue in two kernels. k_eddsa_pre_a -- AySign2Ax, 8A,
+    uint32_t chain_in_ladder;   // set by the launchers for the split form: the doubling chain between the segments is the second segment lane's
+    // RollupMain, small launches (set by ctx_step.hip; in_onChain == ~0u: off): the prologue in two kernels. k_eddsa_pre_a -- AySign2Ax, 8A,
     // the zero checks -- takes what it needs of the front step straight from the INPUTS (five signals and, for a new account, the key
     // bits) and so runs beside the front kernel instead of behind it; k_eddsa_pre_b -- the message hash and its bits -- follows both.
     uint32_t in_onChain, in_newAccount, in_auxFromIdx, in_sign1, in_ay1, in_txCompressedData, in_fromBjjCompressed;
@@ -184,7 +184,7 @@ struct HashInputsArgs {
     uint32_t fee_newRoot_sc;   // scratch field holding feeTx newStateRoot
     uint8_t* msg;              // device byte buffer for the padded message (nblocks * 64)
     uint32_t* chain;           // device buffer: (nblocks + 1) * 8 chaining words
-    uint32_t blk0, blk1;       // SHA-256 blocks handled by one k_sha_chain / k_sha_expand launch (set by launch_hash_inputs)
+    uint32_t blk0, blk1;       // SHA-256 blocks handled by one k_sha_chain / k_sha_expand launch (set by launch_sha_chain / launch_sha_expand_range)
     uint32_t prep_part;        // k_hi_prep: 0 = the whole message, 1 = everything but the header lane, 2 = the header lane alone
 };
 
@@ -230,22 +230,29 @@ size_t pos3_dense_bytes();
 hipError_t upload_pos3_dense(Fr* dst);   // synchronous; dst holds pos3_dense_bytes()
 hipError_t launch_rtx_back(const RtxBackArgs& a, hipStream_t s);
 hipError_t launch_da_mask(const RtxBackArgs& a, hipStream_t s);   // RollupMain phase H alone (amount bits of L1L2TxData times 1 - isAmountNullified), every unit
-hipError_t launch_eddsa(const EddsaArgs& a, hipStream_t s, hipEvent_t front_done = nullptr, hipEvent_t hash_done = nullptr);   // hash_done: SC_SIGL2HASH is written (RollupMain: k_main_sighash on the fee stream)   // front_done: waited for where the front step's scratch is first read (NULL: the caller has ordered the stream already)         // AySign2Ax, message hash, variable-base ladder, R8 + h*8A
+// The variable-base half of the signature check -- AySign2Ax, message hash, ladder, R8 + h*8A -- in the pieces the schedule orders
+// (ctx_step.hip enqueue_sig_check): the prologue whole, or (split form with in_onChain set) its point half, which reads INPUTS only, and
+// its hash half, which reads the front step's scratch and SC_SIGL2HASH; then the ladder of the launch's form
+bool eddsa_split_form(const EddsaArgs& a);   // a launch of at most HZ_ED_SPLIT_MAX signatures: one signature per lane, two lanes per signature
+hipError_t launch_eddsa_pre(const EddsaArgs& a, hipStream_t s);
+hipError_t launch_eddsa_pre_point(const EddsaArgs& a, hipStream_t s);
+hipError_t launch_eddsa_pre_hash(const EddsaArgs& a, hipStream_t s);
+hipError_t launch_eddsa_ladder(const EddsaArgs& a, hipStream_t s);
 hipError_t launch_eddsa_fix(const EddsaArgs& a, hipStream_t s);     // S bits / range, S*B8 (independent of the above)
 hipError_t launch_eddsa_final(const EddsaArgs& a, hipStream_t s);   // the equality of the two sides
 hipError_t launch_fee_front(const FeeFrontArgs& a, hipStream_t s);
 hipError_t launch_fee_back(const FeeBackArgs& a, hipStream_t s);
-hipError_t launch_hash_inputs(const HashInputsArgs& a, hipStream_t s, hipStream_t side = nullptr, hipEvent_t* ev = nullptr, int n_ev = 0, bool body_done = false);
-// the part of the message that does not wait for the roots (the data-availability bits: front kernel + k_da_mask); launch_hash_inputs(body_done = true) follows
-hipError_t launch_hi_prep_body(const HashInputsArgs& a, hipStream_t s);
-// tx-sharded batches (multi-GPU): the message and the sequential chain alone (rank 0), then the bit-level witness of a range of
-// blocks on whichever rank holds the message blocks and chaining values (hz_sha_export / hz_sha_expand)
-hipError_t launch_hi_chain_only(const HashInputsArgs& a, hipStream_t s);
+// HashInputs: the message, the sequential chain over blocks [blk0, blk1), the bit-level witness of a range of blocks. A step runs them
+// whole or in groups piped over a second stream; a tx-sharded batch (multi-GPU) runs message and chain on rank 0 and the expansion of
+// a range on whichever rank holds the message blocks and chaining values (hz_sha_export / hz_sha_expand)
+enum : uint32_t { HI_WHOLE = 0, HI_BODY = 1, HI_HEADER = 2 };   // HashInputsArgs::prep_part
+hipError_t launch_hi_prep(const HashInputsArgs& a, uint32_t part, hipStream_t s);
+hipError_t launch_sha_chain(const HashInputsArgs& a, uint32_t blk0, uint32_t blk1, hipStream_t s);
 hipError_t launch_sha_expand_range(const HashInputsArgs& a, uint32_t first, uint32_t count, hipStream_t s);
 hipError_t launch_hash_state_main(uint8_t* base, uint32_t N, const HashStateOff& hs, hipStream_t s);
 hipError_t launch_withdraw(const WithdrawArgs& a, hipStream_t s);
 
-// data-availability record of one transaction (multi-GPU shard exchange), see ctx.hip hz_da_export
+// data-availability record of one transaction (multi-GPU shard exchange), see ctx_step.hip hz_da_export
 #define HZ_DA_RECORD_BYTES 160
 struct DaArgs {
     uint8_t* tx_base;

@@ -174,7 +174,7 @@ __global__ __launch_bounds__(HZ_SMT_BLOCK) __attribute__((amdgpu_waves_per_eu(LA
     const uint32_t li = LAT ? tidx >> 2 : tidx, qj = LAT ? (threadIdx.x & 3u) : 0u;
     if (li >= (a.ucnt ? a.ucnt : a.n_units)) return;
     const uint32_t i = a.u0 + li * (a.ustride > 1 ? a.ustride : 1u);
-    // the units another launch of this step evaluates (the last transaction of every batch: the early HashInputs chain, ctx.hip)
+    // the units another launch of this step evaluates (the last transaction of every batch: the early HashInputs chain, ctx_step.hip)
     if (a.skip_mod && i % a.skip_mod == a.skip_mod - 1) return;
     const uint32_t chain = a.chain_order ? ((a.chain_order >> (4u * blockIdx.y)) & 15u) : blockIdx.y, pi = chain >> 1;
     const bool new_side = chain & 1;

@@ -216,7 +216,7 @@ __global__ __launch_bounds__(HZ_BLOCK) void k_rtx_back(const RtxBackArgs a) {
     const uint32_t li = blockIdx.x * blockDim.x + threadIdx.x;
     if (li >= (a.ucnt ? a.ucnt : a.n_units)) return;
     const uint32_t u = a.u0 + li * (a.ustride > 1 ? a.ustride : 1u);
-    if (a.skip_mod && u % a.skip_mod == a.skip_mod - 1) return;   // evaluated by the early-tail launch of this step (ctx.hip)
+    if (a.skip_mod && u % a.skip_mod == a.skip_mod - 1) return;   // evaluated by the early-tail launch of this step (ctx_step.hip)
     const uint32_t b = u / a.upi, i = u % a.upi;
     const UnitIO io{a.base, a.n_units, u, b, i, a.err};
     const Scratch sc{a.scratch, a.n_units, u};
@@ -250,7 +250,7 @@ __global__ __launch_bounds__(HZ_BLOCK) void k_rtx_back(const RtxBackArgs a) {
 
 // RollupMain phase H alone (src/rollup-main.circom:456-459): the amount bits of L1L2TxData times (1 - isAmountNullified). Everything
 // it needs exists after the front kernel, and HashInputs needs it from every transaction: launched early so that the SHA-256 chain
-// does not have to wait for the SMT chains of 2048 transactions when it only depends on the last one's exit root (ctx.hip).
+// does not have to wait for the SMT chains of 2048 transactions when it only depends on the last one's exit root (ctx_step.hip).
 __global__ __launch_bounds__(HZ_BLOCK) void k_da_mask(const RtxBackArgs a) {
     const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
     if (u >= a.n_units) return;

@@ -23,7 +23,7 @@ PERIOD_FR, PERIOD_INST = 1009, 1013
 CAP = 2048 * 256                      # the element-wise launchers: 2048 workgroups of 256 lanes, a grid-stride loop beyond
 N_AT_CAP, N_PAST_CAP = CAP, CAP + 256 + 1   # no second pass; a whole workgroup and one ragged lane in the second pass
 N_FR = CAP + 257
-GRID_Y = 65535                        # enqueue_impl cuts a run of staged instances here
+GRID_Y = 65535                        # scatter_staged_inputs (the head of enqueue_impl) cuts a run of staged instances here
 B_STAGE = 2 * GRID_Y + 7              # runs of 65535, 65535 and 7
 EXPORT_CH = 32768                     # hz_witness_export_range_dev's chunk of instances
 B_EXPORT = 2 * EXPORT_CH + 5
@@ -385,7 +385,7 @@ AUDIT = [
      _T + "test_mux256_inputs_from_the_device for instance = -1. The per-instance transpose is UNREACHABLE at any shape the project runs: its "
      "largest input is RollupMain's siblings, nTx * (nLevels + 1) elements, which passes 524288 only from nTx ~ 15 900 at nLevels = 32 "
      "(the headline shape is nTx = 2048). Withdraw at instance = -1: no shape below 16 GiB (WITHDRAW_PAST_CAP)"),
-    ("ctx.hip", "while (e < lo.n_inst && c->staged[e] && e - b < 65535u)", "enqueue_impl -> launch_unpack: a run of staged instances is cut at grid.y = 65535",
+    ("ctx.hip", "while (e < lo.n_inst && c->staged[e] && e - b < 65535u)", "enqueue_impl -> scatter_staged_inputs -> launch_unpack: a run of staged instances is cut at grid.y = 65535",
      _T + "test_stage_range_across_the_grid_y_cut, test_second_step_stages_a_run_across_the_cut, test_range_check_across_the_cut"),
     ("ctx.hip", "const uint64_t chunk = std::min<uint64_t>(count, 1u << 22);", "hz_witness_read: gathers of 2^22 elements",
      "NOT CROSSED: every whole-buffer read of the suite stays below 2^22 elements per instance. It is the suite's own read path: an error "

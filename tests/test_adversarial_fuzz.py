@@ -63,7 +63,7 @@ def _fuzz(hz, template, shape, gen, n_total, chunk, ctx_kw, flags=0):
         else:
             FZ.compare_instanced(g, parts, chunk)
     if flags:
-        g.close()   # flagged contexts one after the other: how many are alive decides the form of their chain kernel (ctx.hip enqueue_smt_chain)
+        g.close()   # flagged contexts one after the other: how many are alive decides the form of their chain kernel (ctx_step.hip enqueue_smt_chain)
     return rejected, cids
 
 
@@ -115,7 +115,7 @@ def _with_signature_edges(cases, edges, seed):
 def test_hip_adversarial_fuzz_flagged(hz, template, shape, n_total, flags):
     """Garbage and the signature edges (fuzz_common.signature_edge_cases) through contexts created with HZ_FLAG_LATENCY (2) and
     HZ_FLAG_LATENCY | HZ_FLAG_SOLO (6, include/hermez_witness.h), one launch each, the same requirements as the plain rows above.
-    Which kernels that selects (ctx.hip hz_ctx_create / enqueue_smt_chain; the profile names do not tell the forms apart, so the
+    Which kernels that selects (ctx.hip hz_ctx_create / ctx_step.hip enqueue_smt_chain; the profile names do not tell the forms apart, so the
     rule is stated here): a RollupMain context with HZ_FLAG_LATENCY runs its chains on four CU-masked streams -- the split signature
     kernels (k_eddsa_pre_a beside the front kernel, k_eddsa_pre_b, k_eddsa_ladder<1>, k_eddsa_fix<1>, k_eddsa_final), k_main_feeacc
     behind the fixed-base kernel -- and, with at most 2 048 transactions per launch (512 x 4 here) and at most two such contexts alive

@@ -1,4 +1,4 @@
-"""Constant marks (csrc/ctx.hip "constant marks", smt_kernels.hip): k_smt does not store again what the persistent witness buffer
+"""Constant marks (csrc/ctx_internal.h "constant marks", smt_kernels.hip): k_smt does not store again what the persistent witness buffer
 already holds of an SMT proof's empty levels. The guard rails: batch A -> B -> A through ONE context, the WHOLE physical buffer against
 the oracle after every step -- states of different depth so that the marks move up AND down, instances that swap their batches, the
 throughput launch with a ragged last wavefront, both forms of the chain kernel, garbage in between, hz_clear_inputs -- and the count
@@ -166,7 +166,7 @@ def test_smt_processor_main_shuffled_garbage(hz, n):
 
 def test_flagged_context_switches_the_chain_kernel_form_with_the_marks_in_place(hz, batches):
     """A HZ_FLAG_LATENCY context of one batch takes k_smt's latency form while at most two such contexts are alive on the device and the plain
-    form otherwise (csrc/ctx.hip enqueue_smt_chain: decided per launch). The marks are per unit and chain, a wavefront of the latency form
+    form otherwise (csrc/ctx_step.hip enqueue_smt_chain: decided per launch). The marks are per unit and chain, a wavefront of the latency form
     holds 16 units and one of the plain form 64: steps of ONE context under alternating forms -- neighbours created and destroyed in between
     -- must leave the whole buffer equal to the oracle's after every step (states of different depth: the marks move both ways)."""
     mk = lambda: hz.ctx("rollup-main", nTx=SHAPE[0], nLevels=SHAPE[1], maxL1Tx=SHAPE[2], maxFeeTx=SHAPE[3], flags=2)   # noqa: E731

@@ -2,7 +2,7 @@
 launch sizes at which the sequential SHA-256 chain takes each of its paths, against a reference that shares nothing with the project:
 the message of reference src/hash-inputs.circom put together in Python and hashed by hashlib.
 
-Which kernel form a launch of B instances of a message of `nblocks` SHA-256 blocks runs (fee_kernels.hip launch_hash_inputs):
+Which kernel form a launch of B instances of a message of `nblocks` SHA-256 blocks runs (ctx_step.hip enqueue_hash_inputs over the launchers of fee_kernels.hip):
 
   B <= 16            k_sha_chain_w: workgroups of 8 batches (B = 9: a partial second workgroup, B = 16: a full one)
   B >= 17            k_sha_chain: workgroups of 64 batches (17 of 64 lanes, 64: exactly one workgroup, 65: a second one of one batch,

@@ -1,7 +1,7 @@
 """Garbage and signature edges through EVERY form of the signature kernels, against the oracle.
 
 The signature check (EdDSAPoseidonVerifier inside RollupTx / RollupMain) runs in one of two kernel forms chosen by the size of the
-launch (eddsa_kernels.hip launch_eddsa / launch_eddsa_fix: the split form up to HZ_ED_SPLIT_MAX = 16 384 signatures, the throughput
+launch (eddsa_kernels.hip eddsa_split_form, launch_eddsa_ladder / launch_eddsa_fix: the split form up to HZ_ED_SPLIT_MAX = 16 384 signatures, the throughput
 form -- k_eddsa_seg<4>, k_eddsa_fix<8>, what bench.py measures -- above), and flagged contexts (HZ_FLAG_LATENCY, HZ_FLAG_SOLO) run a
 third schedule around the split kernels. Which test covers which input class in which form -- a form that is added shows up here as a
 row of empty cells:

@@ -354,7 +354,7 @@ def test_constraint_failures_match_oracle(hz, batch):
 
 
 def test_failure_in_the_last_transaction_of_a_batch(hz):
-    """The last transaction of every batch is evaluated by the early HashInputs chain's own launches (ctx.hip early tail), the main
+    """The last transaction of every batch is evaluated by the early HashInputs chain's own launches (ctx_step.hip early tail), the main
     stream's chain leaves it out: a constraint that fails there is reported once, with the oracle's operands, for the right batch --
     and the whole witness is still the oracle's (nothing is written twice, nothing is left unwritten)."""
     from circuits_amd import builder as B
