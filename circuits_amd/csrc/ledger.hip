@@ -2,13 +2,14 @@
 // device (DESIGN.md 8c .. 8k).
 //
 // The split is the library's: the host does integer work on indices only (ledger_plan.h: events, their grouping by account, fee slots;
-// ledger_tables.h: the typed tables of one call), the device everything that touches a 256-bit value. Every exported apply call states
+// ledger_tables.h: the typed tables of one call; ledger_checks.h: every argument check, the ledger as five integers), the device everything
+// that touches a 256-bit value. Every exported apply call states
 // itself as a LedgerCall -- the request, the host destinations, and what it accepts: by_addr (to_idx == 0, a receiver named by address or
 // key, 8e), is_batch (an L1 run in front: the batch has n_l1 + m rows and "transaction" below reads "row", 8f), exits (to_idx == 1 into
 // the batch's exit tree, an hz_smt the ledger owns, 8g), creates (from_idx == 0 in L1 rows of a growing ledger, 8h), rq != NULL (atomic
 // links, 8i) -- and ledger_apply runs it in stages over one LedgerApply on the stack:
-//   1 plan      the argument checks in the order their errors win. A by_addr call first makes the rows the plan is made of
-//               (ledger_prepare): the L1 rows with auxFromIdx in from_idx's place; k_ledger_create, a lane per create row, the new account's
+//   1 plan      the argument checks (ledger_checks.h) in the order their errors win, run once for either kind of call (ledger_prepare). A
+//               by_addr call makes the rows the plan is made of: the L1 rows with auxFromIdx in from_idx's place; k_ledger_create, a lane per create row, the new account's
 //               static fields into its plane slot beyond `live`; the receivers -- k_ledger_resolve, a lane per account probing the table of
 //               the batch's distinct queries, k_ledger_resolve_pick, a lane per transaction, and the lookup's synchronise: the planner needs
 //               them, and a destination nobody holds is reason 9 here. Then the plan, and the exit tree's own (smt_apply_prepare)
@@ -34,7 +35,8 @@
 //               slot), k_ledger_writeback (the last leaf of every touched account into the planes); the exit tree's update on its own
 //               stream behind an event, then k_ledger_exit_pack / _gather
 //   7 copy out  to the host arrays the caller gave    8 finish   the trees' updates finished, the times, what the getters hand out
-// hz_ledger_verify_l2 runs the signature kernels alone. hz_ledger_select_batch (8j) shares ledger_prepare's pieces and runs
+// hz_ledger_verify_l2 runs the signature kernels alone (ledger_sig_links_launch: the one launch of them and of the link check, for every
+// call). The hz_ledger_plan_* exports, the host half alone, stand in one section at the end. hz_ledger_select_batch (8j) shares ledger_prepare's pieces and runs
 // k_ledger_select over a pool. hz_ledger_exit_keep (8k) freezes the exit tree a batch left into the ledger's archive -- copies, no kernel --
 // and hz_ledger_withdraw_rows answers (batch, idx) queries over the kept trees (ledger_archive.h: k_withdraw_walk, k_withdraw_fill).
 // Values are plain 256-bit integers in eight 32-bit limbs (the Fc container of fr.h, nothing is reduced modulo r); deltas are two's
@@ -63,15 +65,12 @@
 #include "ledger_archive.h"
 #include "ledger_inputs.h"
 #include "ledger_tables.h"
+#include "ledger_checks.h"
 #include "ctx_internal.h"
 #include "smt_internal.h"
 #include "smt_plan.h"
 
-#define HZ_LEDGER_MAX_EVENTS 65536u
-#define HZ_LEDGER_MAX_TX (1u << 20)
-#define HZ_LEDGER_MAX_F 64u
 #define HZ_ARCHIVE_SLAB_BYTES ((size_t)1 << 20)   // a slab of the exit archive; a snapshot larger than this gets a slab of its own size
-#define HZ_LEDGER_REASONS 17u   // refusal reasons 1 .. 13 and 16; 0 is none, 14 and 15 are verdicts of hz_ledger_select_batch
 
 namespace hz {
 
@@ -376,17 +375,6 @@ __global__ __launch_bounds__(256) void k_ledger_main_inputs(const MainInputsDesc
     store_fr(dst + d.dst_off + t * 32, v);
 }
 
-static const char* const LEDGER_REASON[HZ_LEDGER_REASONS] = {"", "the sender's token is not the transaction's", "the nonce is not the sender's current nonce",
-                                             "the sender's balance is below amount + fee", "the receiver's token is not the transaction's",
-                                             "a new balance reaches 2^192", "the fee account's token is not the slot's plan token",
-                                             "the signature is rejected", "max_num_batch has expired",
-                                              "no account holds the signed destination with the transaction's token",
-                                              "the receiver's ethAddr is not the signed to_eth_addr", "the receiver's key is not the signed to_bjj_ay / to_bjj_sign",
-                                              "the sender's nonce is 2^40 - 1: the next nonce is not a leaf field",
-                                              "the rq fields are not the link fields of the row rq_offset names", "", "",
-                                             "amount x fee factor does not fit 128 bits (src/compute-fee.circom:89-91)"};
-static_assert(HZ_LEDGER_FEE_OVERFLOW == 16 && HZ_LEDGER_FEE_OVERFLOW > HZ_SELECT_FULL, "the reason behind the select verdicts");
-
 // ledger_sig.hip
 hipError_t launch_ledger_sig(const hz_l2tx* d_txs, const hz_l2sig* d_sigs, uint32_t chain_id, uint32_t current_num_batch, uint8_t* d_tcd, uint8_t* d_v2, uint8_t* d_hash,
                              const uint8_t* planes, const void* b8_table, uint32_t N, uint64_t first_idx, uint32_t* d_fail_word, uint8_t* d_verdict, uint32_t m,
@@ -582,52 +570,8 @@ static hz_status ledger_ready(const hz_ledger* l, const char* who) {
     return HZ_OK;
 }
 
-static bool ledger_has(uint64_t first_idx, uint64_t N, uint64_t idx) { return idx >= first_idx && idx - first_idx < N; }
-
-// a dense ledger's tree has k levels; a growing one's depth is the planner's to judge (a leaf at depth >= n_sib is HZ_ERR_ARG there)
-static hz_status ledger_n_sib(const hz_ledger* l, const char* who, size_t n_sib) {
-    if (l->smt) {
-        if (n_sib < 1 || n_sib > 64 || n_sib > l->n_sib_max) return set_err(HZ_ERR_ARG, "%s: n_sib = %zu (1 .. %u, the ledger's n_sib_max)", who, n_sib, l->n_sib_max);
-        return HZ_OK;
-    }
-    if (n_sib < l->k || n_sib > 64) return set_err(HZ_ERR_ARG, "%s: n_sib = %zu (%u .. 64)", who, n_sib, l->k);
-    return HZ_OK;
-}
-
-// the per-transaction argument checks of every call that takes transactions; a NOP (from_idx == 0) is not looked at. by_addr: to_idx == 0
-// (a receiver named by address or key) passes; exits: to_idx == 1 does
-static hz_status ledger_check_txs(const char* who, size_t m, const hz_l2tx* txs, uint64_t first_idx, uint64_t N, bool by_addr = false, bool exits = false) {
-    const uint64_t last = first_idx + N - 1;
-    for (size_t i = 0; i < m; i++) {
-        const hz_l2tx& t = txs[i];
-        if (t.from_idx == 0) continue;
-        if (!ledger_has(first_idx, N, t.from_idx))
-            return set_err(HZ_ERR_ARG, "%s: tx %zu: from_idx = %llu is outside the state (%llu .. %llu)", who, i, (unsigned long long)t.from_idx,
-                           (unsigned long long)first_idx, (unsigned long long)last);
-        if ((t.to_idx == 0 && by_addr) || (t.to_idx == HZ_LEDGER_EXIT_IDX && exits)) {
-            if (t.amount_f >> 40) return set_err(HZ_ERR_ARG, "%s: tx %zu: amount_f has more than 40 bits", who, i);
-            continue;
-        }
-        if (t.to_idx <= 1)
-            return set_err(HZ_ERR_ARG, "%s: tx %zu: to_idx = %llu (%s) is not supported yet", who, i, (unsigned long long)t.to_idx,
-                           t.to_idx ? "an exit" : "a transfer to an address");
-        if (!ledger_has(first_idx, N, t.to_idx))
-            return set_err(HZ_ERR_ARG, "%s: tx %zu: to_idx = %llu is outside the state (%llu .. %llu)", who, i, (unsigned long long)t.to_idx,
-                           (unsigned long long)first_idx, (unsigned long long)last);
-        if (t.amount_f >> 40) return set_err(HZ_ERR_ARG, "%s: tx %zu: amount_f has more than 40 bits", who, i);
-    }
-    return HZ_OK;
-}
-
-// the checks of an L1 row that do not depend on which accounts exist
-static hz_status ledger_check_l1_fields(const char* who, size_t i, const hz_l1tx& t) {
-    if (t.amount_f >> 40) return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: amount_f has more than 40 bits", who, i);
-    if (t.load_amount_f >> 40) return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: load_amount_f has more than 40 bits", who, i);
-    for (int b = 20; b < 32; b++)
-        if (t.from_eth_addr[b]) return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: from_eth_addr has more than 160 bits", who, i);
-    if (ledger_mantissa(t.amount_f) != 0 && t.to_idx == 0) return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: an amount with to_idx = 0 (no receiver)", who, i);
-    return HZ_OK;
-}
+// the ledger as the checks see it (ledger_checks.h)
+static LedgerShape ledger_shape(const hz_ledger* l) { return LedgerShape{l->smt != nullptr, l->N, l->first_idx, l->live, l->smt ? l->n_sib_max : l->k}; }
 
 // one apply call, as its exported function states it
 struct LedgerCall {
@@ -654,124 +598,6 @@ struct LedgerCall {
     // L1 run, to_idx == 1 in L1 and L2 rows, from_idx == 0 in L1 rows
     bool by_addr = false, is_batch = false, exits = false, creates = false;
 };
-
-// what the checks of a by_addr call (ledger_prepare) leave: the rows as the pipeline takes them
-struct LedgerRows {
-    std::vector<hz_l1tx> eff_l1;   // a create row is a deposit on auxFromIdx, in from_idx's place
-    std::vector<uint64_t> aux_from, idx_after;   // [n_l1] the running index; aux_from 0: the row creates nothing
-    const hz_l1tx* l1 = nullptr;   // eff_l1's, or the caller's where the call creates nothing
-    size_t n_creates = 0, l1_events = 0;
-    std::vector<hz_l2sig> no_sigs;
-    const hz_l2sig* sigs = nullptr;   // the caller's, or zero entries where no destination is signed
-    std::vector<hz_l2tx> eff;      // the L2 rows with the effective receivers: what the plan is made of
-    uint64_t count = 0;            // the accounts an L2 row or a fee slot may name: live plus created
-};
-
-// the argument checks of an L1 run that may create accounts; -> the events it makes, the rows as the pipeline takes them
-// (eff: from_idx = auxFromIdx on a create row), auxFromIdx (0: the row creates nothing) and the last idx after every row
-static hz_status ledger_check_creates(const char* who, bool growing, uint64_t capacity, uint64_t first_idx, uint64_t size, size_t n_l1, const hz_l1tx* l1,
-                                      const uint8_t* from_bjj, size_t* events, std::vector<hz_l1tx>& eff, std::vector<uint64_t>& aux_from,
-                                      std::vector<uint64_t>& idx_after, size_t* n_creates) {
-    *events = 0;
-    *n_creates = 0;
-    if (n_l1 > HZ_LEDGER_MAX_L1) return set_err(HZ_ERR_ARG, "%s: n_l1 = %zu L1 transactions (at most %d)", who, n_l1, HZ_LEDGER_MAX_L1);
-    if (n_l1 && !l1) return set_err(HZ_ERR_ARG, "%s: null l1", who);
-    eff.assign(l1, l1 + n_l1);
-    aux_from.assign(n_l1, 0);
-    idx_after.assign(n_l1, 0);
-    uint64_t last = first_idx + size - 1;   // first_idx - 1 on an empty ledger
-    for (size_t i = 0; i < n_l1; i++) {
-        const hz_l1tx& t = l1[i];
-        const bool creates = t.from_idx == 0;
-        if (creates) {
-            if (!growing) return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: from_idx = 0 (creates an account) on a ledger that cannot grow (hz_ledger_create_growing)", who, i);
-            if (!from_bjj) return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: from_idx = 0 (creates an account) with from_bjj == NULL", who, i);
-            if (size + *n_creates + 1 > capacity)
-                return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: the ledger is full (capacity %llu accounts)", who, i, (unsigned long long)capacity);
-            *n_creates += 1;
-            last = create_next_idx(last, true);
-            aux_from[i] = last;
-            eff[i].from_idx = last;
-            if (t.to_idx == HZ_LEDGER_EXIT_IDX) return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: a row that creates an account with to_idx = 1 (an exit)", who, i);
-        } else if (!(t.from_idx >= first_idx && t.from_idx <= last && last >= first_idx)) {
-            return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: from_idx = %llu does not exist at its row (%llu .. %lld)", who, i, (unsigned long long)t.from_idx,
-                           (unsigned long long)first_idx, (long long)last);
-        }
-        idx_after[i] = last;
-        if (t.to_idx > HZ_LEDGER_EXIT_IDX && !(t.to_idx >= first_idx && t.to_idx <= last && last >= first_idx))
-            return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: to_idx = %llu does not exist at its row (%llu .. %lld)", who, i, (unsigned long long)t.to_idx,
-                           (unsigned long long)first_idx, (long long)last);
-        if (hz_status e = ledger_check_l1_fields(who, i, t)) return e;
-        *events += 1 + (ledger_mantissa(t.amount_f) != 0);
-    }
-    return HZ_OK;
-}
-
-// the argument checks of an L1 run; -> the events it makes
-static hz_status ledger_check_l1(const char* who, size_t n_l1, const hz_l1tx* l1, uint64_t first_idx, uint64_t N, size_t* events, bool exits = false) {
-    *events = 0;
-    if (n_l1 > HZ_LEDGER_MAX_L1) return set_err(HZ_ERR_ARG, "%s: n_l1 = %zu L1 transactions (at most %d)", who, n_l1, HZ_LEDGER_MAX_L1);
-    if (n_l1 && !l1) return set_err(HZ_ERR_ARG, "%s: null l1", who);
-    const uint64_t last = first_idx + N - 1;
-    for (size_t i = 0; i < n_l1; i++) {
-        const hz_l1tx& t = l1[i];
-        if (t.from_idx == 0) return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: from_idx = 0 (creates an account) is not supported yet", who, i);
-        if (!ledger_has(first_idx, N, t.from_idx))
-            return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: from_idx = %llu is outside the state (%llu .. %llu)", who, i, (unsigned long long)t.from_idx,
-                           (unsigned long long)first_idx, (unsigned long long)last);
-        if (t.to_idx == HZ_LEDGER_EXIT_IDX && !exits) return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: to_idx = 1 (an exit) is not supported yet", who, i);
-        if (t.to_idx > HZ_LEDGER_EXIT_IDX && !ledger_has(first_idx, N, t.to_idx))
-            return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: to_idx = %llu is outside the state (%llu .. %llu)", who, i, (unsigned long long)t.to_idx,
-                           (unsigned long long)first_idx, (unsigned long long)last);
-        if (hz_status e = ledger_check_l1_fields(who, i, t)) return e;
-        *events += 1 + (ledger_mantissa(t.amount_f) != 0);
-    }
-    return HZ_OK;
-}
-
-// the argument checks hz_ledger_apply_l2 and hz_ledger_plan_l2 share; on success the plan is made. by_addr (hz_ledger_apply_l2_addr): the
-// checks alone -- the plan is made later, on the effective receivers
-static hz_status ledger_check_plan(const char* who, size_t m, const hz_l2tx* txs, size_t F, const uint32_t* plan_tokens, const uint64_t* fee_idxs, uint64_t N,
-                                   uint64_t first_idx, LedgerPlan& plan, bool by_addr = false, size_t l1_events = 0, bool exits = false) {
-    if ((m && !txs) || (F && (!plan_tokens || !fee_idxs))) return set_err(HZ_ERR_ARG, "%s: null argument", who);
-    if (F > HZ_LEDGER_MAX_F) return set_err(HZ_ERR_ARG, "%s: F = %zu fee slots (at most %u)", who, F, HZ_LEDGER_MAX_F);
-    if (m > HZ_LEDGER_MAX_TX) return set_err(HZ_ERR_ARG, "%s: %zu transactions in one call (at most %u)", who, m, HZ_LEDGER_MAX_TX);
-    const uint64_t last = first_idx + N - 1;
-    if (hz_status e = ledger_check_txs(who, m, txs, first_idx, N, by_addr, exits)) return e;
-    for (size_t j = 0; j < F; j++)
-        if (fee_idxs[j] != 0 && !ledger_has(first_idx, N, fee_idxs[j]))
-            return set_err(HZ_ERR_ARG, "%s: fee_idxs[%zu] = %llu is outside the state (%llu .. %llu)", who, j, (unsigned long long)fee_idxs[j],
-                           (unsigned long long)first_idx, (unsigned long long)last);
-    size_t events = l1_events;
-    for (size_t i = 0; i < m; i++)
-        if (txs[i].from_idx != 0) events += 1 + (ledger_mantissa(txs[i].amount_f) != 0);
-    for (size_t j = 0; j < F; j++) events += fee_idxs[j] != 0;
-    if (events > HZ_LEDGER_MAX_EVENTS) return set_err(HZ_ERR_ARG, "%s: %zu updates in one call (at most %u)", who, events, HZ_LEDGER_MAX_EVENTS);
-    if (!by_addr) ledger_plan_l2(m, txs, F, plan_tokens, fee_idxs, plan);
-    return HZ_OK;
-}
-
-extern "C" hz_status hz_ledger_plan_l2(size_t m, const hz_l2tx* txs, size_t F, const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs, int32_t k,
-                                       uint64_t first_idx, int32_t* ev_sender_out, int32_t* ev_receiver_out, int32_t* fee_slot_out, int32_t* last_event_out,
-                                       size_t* n_events_out, uint64_t* ev_account_out, int32_t* ev_prev_out) {
-    if (k < 4 || k > 24) return set_err(HZ_ERR_ARG, "hz_ledger_plan_l2: k = %d (4 .. 24)", k);
-    LedgerPlan p;
-    if (hz_status e = ledger_check_plan("hz_ledger_plan_l2", m, txs, F, fee_plan_tokens, fee_idxs, 1ull << k, first_idx, p)) return e;
-    for (size_t i = 0; i < m; i++) {
-        if (ev_sender_out) ev_sender_out[i] = p.ev_sender[i];
-        if (ev_receiver_out) ev_receiver_out[i] = p.ev_receiver[i];
-        if (fee_slot_out) fee_slot_out[i] = p.fee_slot[i];
-        if (last_event_out) last_event_out[i] = p.last_event[i];
-    }
-    if (n_events_out) *n_events_out = p.account.size();
-    for (size_t e = 0; e < p.account.size(); e++) {
-        if (ev_account_out) ev_account_out[e] = p.account[e];
-        if (ev_prev_out) ev_prev_out[e] = p.prev_same[e];
-    }
-    return HZ_OK;
-}
-
-#define HZ_LEDGER_MAX_CAPACITY (1ull << 24)
 
 // what both kinds of ledger own once device, N and the trees are set: the planes, the failure word's pinned home, the events
 static hz_status ledger_open(hz_ledger* l) {
@@ -827,25 +653,6 @@ extern "C" void hz_ledger_destroy(hz_ledger* l) {
     (void)hipStreamSynchronize(ledger_stream(l));
     (void)hipStreamSynchronize(smt_stream(l->exit));
     delete l;
-}
-
-// any byte set from `from` to the end of a 32-byte little-endian element
-static bool ledger_bytes_from(const uint8_t* p, int from) {
-    uint8_t d = 0;
-    for (int b = from; b < 32; b++) d |= p[b];
-    return d != 0;
-}
-
-// the first account whose fields are not a leaf's, named
-static hz_status ledger_check_leaves(const char* who, uint64_t first_idx, size_t n, const uint8_t* e0, const uint8_t* balance, const uint8_t* eth_addr) {
-    for (size_t i = 0; i < n; i++) {
-        const char* bad = nullptr;
-        if (ledger_bytes_from(balance + i * 32, 24)) bad = "balance >= 2^192";
-        else if (ledger_bytes_from(e0 + i * 32, 10) || e0[i * 32 + 9] > 1) bad = "e0 >= 2^73";
-        else if (ledger_bytes_from(eth_addr + i * 32, 20)) bad = "ethAddr >= 2^160";
-        if (bad) return set_err(HZ_ERR_INPUT, "%s: account %llu (row %zu) is not a leaf: %s", who, (unsigned long long)(first_idx + i), i, bad);
-    }
-    return HZ_OK;
 }
 
 extern "C" hz_status hz_ledger_load(hz_ledger* l, const uint8_t* e0, const uint8_t* balance, const uint8_t* ay, const uint8_t* eth_addr) {
@@ -969,25 +776,6 @@ extern "C" hz_status hz_ledger_outputs_dev(hz_ledger* l, hz_ledger_out* dev) {
     return ledger_hand_out("hz_ledger_outputs_dev", l, dev, l ? &l->have_outputs : nullptr, "hz_ledger_apply_l2", l ? l->out_dev.a : nullptr, HZ_LEDGER_ARRAYS);
 }
 
-// the argument checks of the signed calls beyond those of the transactions; a NOP's entry is not looked at. verify == false
-// (hz_ledger_apply_l2_addr without HZ_LEDGER_VERIFY_SIGS): the destination fields alone, s, r8x, r8y and chain_id are not read
-static hz_status ledger_check_sigs(const char* who, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, uint32_t chain_id, bool verify = true) {
-    if (m && !sigs) return set_err(HZ_ERR_ARG, "%s: null sigs", who);
-    if (verify && chain_id >> 16) return set_err(HZ_ERR_ARG, "%s: chain_id = %u has more than 16 bits", who, chain_id);
-    for (size_t i = 0; i < m; i++) {
-        if (txs[i].from_idx == 0) continue;
-        const hz_l2sig& g = sigs[i];
-        if (g.to_bjj_sign > 1) return set_err(HZ_ERR_ARG, "%s: tx %zu: to_bjj_sign = %u", who, i, (unsigned)g.to_bjj_sign);
-        for (int b = 20; b < 32; b++)
-            if (g.to_eth_addr[b]) return set_err(HZ_ERR_ARG, "%s: tx %zu: to_eth_addr has more than 160 bits", who, i);
-        const uint8_t* f[4] = {g.s, g.r8x, g.r8y, g.to_bjj_ay};
-        static const char* const name[4] = {"s", "r8x", "r8y", "to_bjj_ay"};
-        for (int q = verify ? 0 : 3; q < 4; q++)
-            if (!canon_lt_p(f[q])) return set_err(HZ_ERR_INPUT, "%s: tx %zu: %s is not below the field's modulus", who, i, name[q]);
-    }
-    return HZ_OK;
-}
-
 // the signatures and the fixed-base table on the device, room for the three arrays and the verdict bytes; verify == false: the upload
 // alone, for the destination fields
 static hz_status ledger_sig_prepare(hz_ledger* l, size_t m, const hz_l2sig* sigs, hipStream_t s, bool verify = true) {
@@ -1007,17 +795,25 @@ static hz_status ledger_sig_prepare(hz_ledger* l, size_t m, const hz_l2sig* sigs
     return HZ_OK;
 }
 
-// the argument checks of the atomic links; a NOP's entry is not looked at
-static hz_status ledger_check_rq(const char* who, size_t m, const hz_l2tx* txs, const hz_l2rq* rq) {
-    if (!rq) return HZ_OK;
-    for (size_t i = 0; i < m; i++) {
-        if (txs[i].from_idx == 0) continue;
-        const hz_l2rq& q = rq[i];
-        if (q.rq_offset > HZ_RQ_MAX_OFFSET) return set_err(HZ_ERR_ARG, "%s: tx %zu: rq_offset = %u (0 .. 7)", who, i, (unsigned)q.rq_offset);
-        const uint8_t* f[3] = {q.rq_tx_compressed_data_v2, q.rq_to_eth_addr, q.rq_to_bjj_ay};
-        static const char* const name[3] = {"rq_tx_compressed_data_v2", "rq_to_eth_addr", "rq_to_bjj_ay"};
-        for (int a = 0; a < 3; a++)
-            if (!canon_lt_p(f[a])) return set_err(HZ_ERR_INPUT, "%s: tx %zu: %s is not below the field's modulus", who, i, name[a]);
+// the signature kernels over the m L2 rows at d_txs and, where the call has links, the link check behind them: a failure lowers the failure
+// word d_fail at unit_base + i (the rows stand behind unit_base L1 rows), or goes to the verdict bytes. verify: both signature kernels, under
+// t_sig; otherwise, for the links, the V2 rows of the message kernel's packing alone. own_link_kernel: the caller launches its own behind this
+static hz_status ledger_sig_links_launch(hz_ledger* l, const hz_l2tx* d_txs, uint32_t m, uint32_t chain_id, uint32_t current_num_batch, uint32_t* d_fail, uint8_t* d_verdict,
+                                         uint32_t unit_base, bool verify, bool links, hipStream_t s, bool own_link_kernel = false) {
+    const hz_l2sig* d_sigs = (const hz_l2sig*)l->sig_in.p;
+    const uint8_t* d_rq = links ? (const uint8_t*)l->rq_in.p : nullptr;
+    if (verify) {
+        HZ_HIP(l->t_sig.begin(s));
+        HZ_HIP(launch_ledger_sig(d_txs, d_sigs, chain_id, current_num_batch, l->sig_dev[0], l->sig_dev[1], l->sig_dev[2], (const uint8_t*)l->planes.p, l->b8_table.p, l->N,
+                                 l->first_idx, d_fail, d_verdict, m, s, unit_base, d_rq));
+        HZ_HIP(l->t_sig.end(s));
+    } else if (links) {
+        HZ_HIP(launch_ledger_sig_v2(d_txs, d_sigs, l->sig_dev[1], m, s));
+    }
+    if (links && !own_link_kernel) {
+        HZ_HIP(l->t_rq.begin(s));
+        HZ_HIP(launch_ledger_rq(d_txs, d_sigs, d_rq, (const uint8_t*)l->sig_dev[1], d_fail, d_verdict, m, unit_base, s, unit_base));
+        HZ_HIP(l->t_rq.end(s));
     }
     return HZ_OK;
 }
@@ -1068,17 +864,8 @@ static hz_status ledger_verify(hz_ledger* l, const char* who, size_t m, const hz
     HZ_HIP(l->ints.grow((m ? m : 1) * sizeof(hz_l2tx)));
     if (m) HZ_HIP(hipMemcpyAsync(l->ints.p, txs, m * sizeof(hz_l2tx), hipMemcpyHostToDevice, s));
     if (hz_status e = ledger_sig_prepare(l, m, sigs, s)) return e;
-    HZ_HIP(l->t_sig.begin(s));
-    HZ_HIP(launch_ledger_sig((const hz_l2tx*)l->ints.p, (const hz_l2sig*)l->sig_in.p, chain_id, current_num_batch, l->sig_dev[0], l->sig_dev[1], l->sig_dev[2],
-                             (const uint8_t*)l->planes.p, l->b8_table.p, l->N, l->first_idx, nullptr, l->verdict_dev, (uint32_t)m, s, 0,
-                             links ? (const uint8_t*)l->rq_in.p : nullptr));
-    HZ_HIP(l->t_sig.end(s));
-    if (links) {   // behind both signature kernels: 13 goes where the verdict is still 0
-        HZ_HIP(l->t_rq.begin(s));
-        HZ_HIP(launch_ledger_rq((const hz_l2tx*)l->ints.p, (const hz_l2sig*)l->sig_in.p, (const uint8_t*)l->rq_in.p, (const uint8_t*)l->sig_dev[1], nullptr, l->verdict_dev,
-                                (uint32_t)m, 0, s, 0));
-        HZ_HIP(l->t_rq.end(s));
-    }
+    // the link check behind both signature kernels: 13 goes where the verdict is still 0
+    if (hz_status e = ledger_sig_links_launch(l, (const hz_l2tx*)l->ints.p, (uint32_t)m, chain_id, current_num_batch, nullptr, l->verdict_dev, 0, true, links, s)) return e;
     if (m) HZ_HIP(hipMemcpyAsync(verdict_out, l->verdict_dev, m, hipMemcpyDeviceToHost, s));
     if (hz_status e = ledger_sig_copy_out(l, m, sig_out, s)) return e;
     HZ_HIP(hipStreamSynchronize(s));
@@ -1148,50 +935,8 @@ extern "C" hz_status hz_ledger_resolve_l2(hz_ledger* l, size_t m, const hz_l2tx*
 }
 
 // ---- what the by_addr apply calls and hz_ledger_select_batch share: the checks and preparations before a plan can be made -----------------
-static hz_status ledger_check_flags(const char* who, uint32_t flags) {
-    if (flags & ~HZ_LEDGER_VERIFY_SIGS) return set_err(HZ_ERR_ARG, "%s: flags = %#x", who, flags);
-    return HZ_OK;
-}
-
-// the one wording of a refusal: a fee slot (unit >= R), a row of a batch with an L1 run (L1 != 0), else a transaction
-static hz_status ledger_refused(const char* who, size_t unit, uint32_t reason, size_t R, size_t L1) {
-    char what[64];
-    if (unit >= R)
-        snprintf(what, sizeof what, "fee slot %zu", unit - R);
-    else if (L1)
-        snprintf(what, sizeof what, "%s transaction %zu", unit < L1 ? "L1" : "L2", unit < L1 ? unit : unit - L1);
-    else
-        snprintf(what, sizeof what, "transaction %zu", unit);
-    return set_err(HZ_ERR_INPUT, "%s: refused at index %zu (%s), reason %u: %s", who, unit, what, reason, LEDGER_REASON[reason < HZ_LEDGER_REASONS ? reason : 0]);
-}
-
-// the argument checks of the L1 run; -> r.l1, the rows as the pipeline takes them, the events they make, the accounts the call makes
-static hz_status ledger_effective_l1(const hz_ledger* l, const char* who, size_t n_l1, const hz_l1tx* l1, const uint8_t* from_bjj, bool creates, bool exits, LedgerRows& r) {
-    r.l1 = l1;
-    if (creates) {
-        if (hz_status e = ledger_check_creates(who, l->smt != nullptr, l->N, l->first_idx, l->live, n_l1, l1, from_bjj, &r.l1_events, r.eff_l1, r.aux_from, r.idx_after, &r.n_creates))
-            return e;
-        r.l1 = r.eff_l1.data();
-    } else if (hz_status e = ledger_check_l1(who, n_l1, l1, l->first_idx, l->live, &r.l1_events, exits)) {
-        return e;
-    }
-    r.count = l->live + r.n_creates;
-    return HZ_OK;
-}
-
-// sigs == NULL without verification: no destination is signed, zero entries stand in (the link fields of such rows are V2 and two zeros)
-static hz_status ledger_stand_in_sigs(const char* who, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, bool verify, LedgerRows& r) {
-    r.sigs = sigs;
-    if (sigs || !m || verify) return HZ_OK;
-    for (size_t i = 0; i < m; i++)
-        if (txs[i].from_idx != 0 && txs[i].to_idx == 0) return set_err(HZ_ERR_ARG, "%s: null sigs with tx %zu to an address", who, i);
-    r.no_sigs.assign(m, hz_l2sig{});
-    r.sigs = r.no_sigs.data();
-    return HZ_OK;
-}
-
 // k_ledger_create on the ledger's stream, before everything else of the call, the lookup included: the new accounts' static fields into
-// their plane slots. Every slot lies at or beyond the ledger's size and below its capacity (ledger_check_creates)
+// their plane slots. Every slot lies at or beyond the ledger's size and below its capacity (ledger_effective_l1)
 static hz_status ledger_create_launch(hz_ledger* l, size_t n_l1, const hz_l1tx* l1, const uint8_t* from_bjj, const LedgerRows& r) {
     const uint32_t n = (uint32_t)r.n_creates;
     HZ_HIP(hipSetDevice(l->device));
@@ -1240,24 +985,32 @@ static hz_status ledger_effective_receivers(hz_ledger* l, const char* who, size_
     return HZ_OK;
 }
 
-// the checks of a by_addr apply call, in the order their errors win; -> the rows the plan is made of
+// the checks of an apply call, in the order their errors win -- a plain L2 form's, then a by_addr form's; -> the rows, and the plan made of them
 static hz_status ledger_prepare(hz_ledger* l, const LedgerCall& c, LedgerRows& r) {
     if (hz_status e = ledger_ready(l, c.who)) return e;
     ledger_exit_reset(l);
+    const LedgerShape g = ledger_shape(l);
+    r.sigs = c.sigs;
+    if (!c.by_addr) {
+        if (hz_status e = ledger_n_sib(g, c.who, c.n_sib)) return e;
+        if (hz_status e = ledger_check_plan(c.who, c.m, c.txs, c.F, c.plan_tokens, c.fee_idxs, l->live, l->first_idx, l->plan)) return e;
+        return c.verify ? ledger_check_sigs(c.who, c.m, c.txs, c.sigs, c.chain_id) : HZ_OK;
+    }
     if (c.is_batch) l->l1_ms = 0.0;   // the time of THIS call, whatever becomes of it
     if (hz_status e = ledger_check_flags(c.who, c.flags)) return e;
     if (!c.verify && c.sig_out) return set_err(HZ_ERR_ARG, "%s: sig_out without HZ_LEDGER_VERIFY_SIGS", c.who);
-    if (hz_status e = ledger_n_sib(l, c.who, c.n_sib)) return e;
-    if (hz_status e = ledger_effective_l1(l, c.who, c.n_l1, c.l1, c.from_bjj, c.creates, c.exits, r)) return e;
+    if (hz_status e = ledger_n_sib(g, c.who, c.n_sib)) return e;
+    if (hz_status e = ledger_effective_l1(g, c.who, c.n_l1, c.l1, c.from_bjj, c.creates, c.exits, r)) return e;
     if (hz_status e = ledger_check_plan(c.who, c.m, c.txs, c.F, c.plan_tokens, c.fee_idxs, r.count, l->first_idx, l->plan, true, r.l1_events, c.exits)) return e;
-    r.sigs = c.sigs;
     if (c.is_batch)   // (without an L1 run the call is hz_ledger_apply_l2_addr's: null sigs is its error)
         if (hz_status e = ledger_stand_in_sigs(c.who, c.m, c.txs, c.sigs, c.verify, r)) return e;
     if (hz_status e = ledger_check_sigs(c.who, c.m, c.txs, r.sigs, c.chain_id, c.verify)) return e;
     if (hz_status e = ledger_check_rq(c.who, c.m, c.txs, c.rq)) return e;
     if (r.n_creates)
         if (hz_status e = ledger_create_launch(l, c.n_l1, c.l1, c.from_bjj, r)) return e;
-    return ledger_effective_receivers(l, c.who, c.n_l1, c.m, c.txs, c.aux_to_idx, true, r);
+    if (hz_status e = ledger_effective_receivers(l, c.who, c.n_l1, c.m, c.txs, c.aux_to_idx, true, r)) return e;
+    ledger_plan_rows(c.n_l1, r.l1, c.m, r.eff.data(), c.F, c.plan_tokens, c.fee_idxs, c.exits, l->plan);
+    return HZ_OK;
 }
 
 // ---- one apply call, in stages (the header comment names them) ----------------------------------------------------------------------------
@@ -1298,21 +1051,9 @@ static hz_status ledger_apply_plan(LedgerApply& a) {
     static_assert(sizeof(hz_ledger_out) == HZ_LEDGER_ARRAYS * sizeof(uint8_t*), "hz_ledger_out is an array of pointers");
     hz_ledger* l = a.l;
     const LedgerCall& c = a.c;
-    if (c.by_addr)
-        if (hz_status e = ledger_prepare(l, c, a.rows)) return e;
-    if (hz_status e = ledger_ready(l, c.who)) return e;
-    ledger_exit_reset(l);
+    if (hz_status e = ledger_prepare(l, c, a.rows)) return e;
     a.growing = l->smt != nullptr;
-    if (hz_status e = ledger_n_sib(l, c.who, c.n_sib)) return e;
-    LedgerPlan& p = l->plan;
-    if (c.by_addr) {
-        ledger_plan_rows(c.n_l1, a.rows.l1, c.m, a.rows.eff.data(), c.F, c.plan_tokens, c.fee_idxs, c.exits, p);
-    } else {
-        if (hz_status e = ledger_check_plan(c.who, c.m, c.txs, c.F, c.plan_tokens, c.fee_idxs, l->live, l->first_idx, p)) return e;
-        if (c.verify)
-            if (hz_status e = ledger_check_sigs(c.who, c.m, c.txs, c.sigs, c.chain_id)) return e;
-        a.rows.sigs = c.sigs;
-    }
+    const LedgerPlan& p = l->plan;
     ledger_forget(l);
     a.R = c.n_l1 + c.m;
     a.m32 = (uint32_t)c.m, a.R32 = (uint32_t)a.R, a.L32 = (uint32_t)c.n_l1, a.F32 = (uint32_t)c.F, a.S = (uint32_t)c.n_sib;
@@ -1446,18 +1187,8 @@ static hz_status ledger_apply_launch(LedgerApply& a) {
         HZ_HIP(hipGetLastError());
         HZ_HIP(l->t_exit_scan.end(s));
     }
-    if (c.verify) {   // they read the planes and the uploads only: any place before the failure-word read would do
-        HZ_HIP(l->t_sig.begin(s));
-        HZ_HIP(launch_ledger_sig(a.d_txs() + c.n_l1, d_sigs, c.chain_id, c.current_num_batch, l->sig_dev[0], l->sig_dev[1], l->sig_dev[2], a.planes(), l->b8_table.p, a.N,
-                                 l->first_idx, a.d_fail(), nullptr, a.m32, s, L32, a.links ? (const uint8_t*)l->rq_in.p : nullptr));
-        HZ_HIP(l->t_sig.end(s));
-    }
-    if (a.links) {   // reason 13, verified or not: the V2 rows are the message kernel's, or those of its packing alone
-        if (!c.verify) HZ_HIP(launch_ledger_sig_v2(a.d_txs() + c.n_l1, d_sigs, l->sig_dev[1], a.m32, s));
-        HZ_HIP(l->t_rq.begin(s));
-        HZ_HIP(launch_ledger_rq(a.d_txs() + c.n_l1, d_sigs, (const uint8_t*)l->rq_in.p, (const uint8_t*)l->sig_dev[1], a.d_fail(), nullptr, a.m32, L32, s, L32));
-        HZ_HIP(l->t_rq.end(s));
-    }
+    // the signature kernels read the planes and the uploads only: any place before the failure-word read would do. Reason 13, verified or not
+    if (hz_status e = ledger_sig_links_launch(l, a.d_txs() + c.n_l1, a.m32, c.chain_id, c.current_num_batch, a.d_fail(), nullptr, L32, c.verify, a.links, s)) return e;
     HZ_HIP(l->t_semantic.end(s));
     HZ_HIP(hipMemcpyAsync(l->h_fail.p, a.d_fail(), 4, hipMemcpyDeviceToHost, s));
     HZ_HIP(hipStreamSynchronize(s));   // the one round trip
@@ -1705,40 +1436,6 @@ extern "C" hz_status hz_ledger_apply_batch(hz_ledger* l, size_t n_l1, const hz_l
                                            uint8_t* aux_to_idx_out, uint8_t* l1_flags_out) {
     const LedgerCall l2 = ledger_call_l2("hz_ledger_apply_batch", m, txs, sigs, chain_id, current_num_batch, F, fee_plan_tokens, fee_idxs, n_sib, out, sig_out);
     return ledger_apply(l, ledger_call_batch(ledger_call_addr(l2, flags, aux_to_idx, aux_to_idx_out), n_l1, l1, l1_flags_out));
-}
-
-extern "C" hz_status hz_ledger_plan_batch(size_t n_l1, const hz_l1tx* l1, size_t m, const hz_l2tx* txs, size_t F, const uint32_t* fee_plan_tokens,
-                                          const uint64_t* fee_idxs, int32_t k, uint64_t first_idx, int32_t* ev_sender_out, int32_t* ev_receiver_out,
-                                          int32_t* fee_slot_out, int32_t* last_event_out, size_t* n_events_out, uint64_t* ev_account_out, int32_t* ev_prev_out,
-                                          int32_t* l1_slot_sender_out, int32_t* l1_slot_receiver_out, size_t* n_slots_out, uint64_t* slot_account_out) {
-    const char* who = "hz_ledger_plan_batch";
-    if (k < 4 || k > 24) return set_err(HZ_ERR_ARG, "%s: k = %d (4 .. 24)", who, k);
-    LedgerPlan p;
-    size_t l1_events = 0;
-    if (hz_status e = ledger_check_l1(who, n_l1, l1, first_idx, 1ull << k, &l1_events)) return e;
-    if (hz_status e = ledger_check_plan(who, m, txs, F, fee_plan_tokens, fee_idxs, 1ull << k, first_idx, p, true, l1_events)) return e;
-    for (size_t i = 0; i < m; i++)   // the planner is given receivers: a transfer to an address has none before the lookup
-        if (txs[i].from_idx != 0 && txs[i].to_idx == 0) return set_err(HZ_ERR_ARG, "%s: tx %zu: to_idx = 0 (a transfer to an address) is not supported yet", who, i);
-    ledger_plan_batch(n_l1, l1, m, txs, F, fee_plan_tokens, fee_idxs, p);
-    for (size_t i = 0; i < n_l1 + m; i++) {
-        if (ev_sender_out) ev_sender_out[i] = p.ev_sender[i];
-        if (ev_receiver_out) ev_receiver_out[i] = p.ev_receiver[i];
-        if (fee_slot_out) fee_slot_out[i] = p.fee_slot[i];
-        if (last_event_out) last_event_out[i] = p.last_event[i];
-    }
-    if (n_events_out) *n_events_out = p.account.size();
-    for (size_t e = 0; e < p.account.size(); e++) {
-        if (ev_account_out) ev_account_out[e] = p.account[e];
-        if (ev_prev_out) ev_prev_out[e] = p.prev_same[e];
-    }
-    for (size_t i = 0; i < n_l1; i++) {
-        if (l1_slot_sender_out) l1_slot_sender_out[i] = p.l1_slot_sender[i];
-        if (l1_slot_receiver_out) l1_slot_receiver_out[i] = p.l1_slot_receiver[i];
-    }
-    if (n_slots_out) *n_slots_out = p.slot_account.size();
-    for (size_t q = 0; q < p.slot_account.size(); q++)
-        if (slot_account_out) slot_account_out[q] = p.slot_account[q];
-    return HZ_OK;
 }
 
 extern "C" hz_status hz_ledger_l1_flags_dev(hz_ledger* l, uint8_t** dev) {
@@ -2045,51 +1742,6 @@ extern "C" hz_status hz_ledger_withdraw_rows_dev(hz_ledger* l, hz_withdraw_rows_
 extern "C" double hz_ledger_withdraw_ms(const hz_ledger* l) { return l && l->archive ? l->archive->withdraw_ms : 0.0; }
 extern "C" double hz_ledger_exit_keep_ms(const hz_ledger* l) { return l && l->archive ? l->archive->keep_ms : 0.0; }
 
-extern "C" hz_status hz_ledger_plan_exits(size_t n_l1, const hz_l1tx* l1, size_t m, const hz_l2tx* txs, size_t F, const uint32_t* fee_plan_tokens,
-                                          const uint64_t* fee_idxs, int32_t k, uint64_t first_idx, size_t n_sib, int32_t* ev_sender_out, int32_t* ev_receiver_out,
-                                          int32_t* last_event_out, size_t* n_events_out, uint64_t* ev_account_out, int32_t* ev_exit_out, int32_t* last_exit_out,
-                                          size_t* n_exits_out, uint32_t* exit_row_out, uint64_t* exit_key_out, int32_t* exit_prev_out, uint32_t* exit_perm_out,
-                                          uint8_t* exit_insert_out, uint8_t* exit_is_old0_out, uint64_t* exit_old_key_out) {
-    const char* who = "hz_ledger_plan_exits";
-    if (k < 4 || k > 24) return set_err(HZ_ERR_ARG, "%s: k = %d (4 .. 24)", who, k);
-    if (n_sib < (size_t)k || n_sib > 64) return set_err(HZ_ERR_ARG, "%s: n_sib = %zu (%d .. 64)", who, n_sib, k);
-    LedgerPlan p;
-    size_t l1_events = 0;
-    if (hz_status e = ledger_check_l1(who, n_l1, l1, first_idx, 1ull << k, &l1_events, true)) return e;
-    if (hz_status e = ledger_check_plan(who, m, txs, F, fee_plan_tokens, fee_idxs, 1ull << k, first_idx, p, true, l1_events, true)) return e;
-    for (size_t i = 0; i < m; i++)   // the planner is given receivers: a transfer to an address has none before the lookup
-        if (txs[i].from_idx != 0 && txs[i].to_idx == 0) return set_err(HZ_ERR_ARG, "%s: tx %zu: to_idx = 0 (a transfer to an address) is not supported yet", who, i);
-    ledger_plan_exits(n_l1, l1, m, txs, F, fee_plan_tokens, fee_idxs, p);
-    const size_t X = p.exit_row.size();
-    SmtShape sh;   // the exit tree of a batch starts empty
-    sh.begin();
-    for (size_t x = 0; x < X; x++)
-        if (sh.add(p.exit_key[x], (uint32_t)n_sib) != SMT_PLAN_OK)
-            return set_err(HZ_ERR_ARG, "%s: op %zu (key %llu) would have its leaf at depth >= n_sib = %zu: SMTProcessor(%zu) cannot express it", who, x,
-                           (unsigned long long)p.exit_key[x], n_sib, n_sib);
-    for (size_t i = 0; i < n_l1 + m; i++) {
-        if (ev_sender_out) ev_sender_out[i] = p.ev_sender[i];
-        if (ev_receiver_out) ev_receiver_out[i] = p.ev_receiver[i];
-        if (last_event_out) last_event_out[i] = p.last_event[i];
-        if (ev_exit_out) ev_exit_out[i] = p.ev_exit[i];
-        if (last_exit_out) last_exit_out[i] = p.last_exit[i];
-    }
-    if (n_events_out) *n_events_out = p.account.size();
-    for (size_t e = 0; e < p.account.size(); e++)
-        if (ev_account_out) ev_account_out[e] = p.account[e];
-    if (n_exits_out) *n_exits_out = X;
-    for (size_t x = 0; x < X; x++) {
-        if (exit_row_out) exit_row_out[x] = p.exit_row[x];
-        if (exit_key_out) exit_key_out[x] = p.exit_key[x];
-        if (exit_prev_out) exit_prev_out[x] = p.exit_prev[x];
-        if (exit_perm_out) exit_perm_out[x] = p.exit_perm[x];
-        if (exit_insert_out) exit_insert_out[x] = sh.fnc[x];
-        if (exit_is_old0_out) exit_is_old0_out[x] = sh.is_old0[x];
-        if (exit_old_key_out) exit_old_key_out[x] = sh.old_key[x];
-    }
-    return HZ_OK;
-}
-
 // ---- L1 rows that create accounts, on a growing ledger -------------------------------------------------------------------
 extern "C" hz_status hz_ledger_apply_batch_creates(hz_ledger* l, size_t n_l1, const hz_l1tx* l1, const uint8_t* from_bjj, size_t m, const hz_l2tx* txs,
                                                    const hz_l2sig* sigs, uint32_t flags, const uint64_t* aux_to_idx, uint32_t chain_id, uint32_t current_num_batch,
@@ -2110,28 +1762,6 @@ extern "C" hz_status hz_ledger_create_outputs_dev(hz_ledger* l, hz_ledger_create
 }
 
 extern "C" double hz_ledger_create_ms(const hz_ledger* l) { return l ? l->create_ms : 0.0; }
-
-extern "C" hz_status hz_ledger_plan_creates(size_t n_l1, const hz_l1tx* l1, const uint8_t* from_bjj, size_t m, const hz_l2tx* txs, size_t F,
-                                            const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs, int32_t growing, uint64_t capacity, uint64_t first_idx,
-                                            uint64_t size, uint64_t* aux_from_idx_out, uint64_t* out_idx_after_out, size_t* n_creates_out) {
-    const char* who = "hz_ledger_plan_creates";
-    if (capacity < 1 || capacity > HZ_LEDGER_MAX_CAPACITY || size > capacity || first_idx < 2)
-        return set_err(HZ_ERR_ARG, "%s: capacity = %llu, size = %llu, first_idx = %llu", who, (unsigned long long)capacity, (unsigned long long)size,
-                       (unsigned long long)first_idx);
-    size_t l1_events = 0, n_creates = 0;
-    std::vector<hz_l1tx> eff_l1;
-    std::vector<uint64_t> aux_from, idx_after;
-    if (hz_status e = ledger_check_creates(who, growing != 0, capacity, first_idx, size, n_l1, l1, from_bjj, &l1_events, eff_l1, aux_from, idx_after, &n_creates)) return e;
-    LedgerPlan p;
-    if (hz_status e = ledger_check_plan(who, m, txs, F, fee_plan_tokens, fee_idxs, size + n_creates, first_idx, p, true, l1_events, true)) return e;
-    const uint64_t last = first_idx + size + n_creates - 1;
-    for (size_t i = 0; i < n_l1 + m; i++) {
-        if (aux_from_idx_out) aux_from_idx_out[i] = i < n_l1 ? aux_from[i] : 0;
-        if (out_idx_after_out) out_idx_after_out[i] = i < n_l1 ? idx_after[i] : last;
-    }
-    if (n_creates_out) *n_creates_out = n_creates;
-    return HZ_OK;
-}
 
 // ---- atomic transactions: the rqOffset links ----------------------------------------------------------------------------
 extern "C" hz_status hz_ledger_apply_batch_atomic(hz_ledger* l, size_t n_l1, const hz_l1tx* l1, const uint8_t* from_bjj, size_t m, const hz_l2tx* txs,
@@ -2159,122 +1789,7 @@ extern "C" hz_status hz_ledger_verify_l2_atomic(hz_ledger* l, size_t m, const hz
 
 extern "C" double hz_ledger_rq_ms(const hz_ledger* l) { return l ? l->rq_ms : 0.0; }
 
-extern "C" hz_status hz_ledger_plan_atomic(size_t n_l1, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, const hz_l2rq* rq, int64_t* target_row_out,
-                                           uint8_t* verdict_out) {
-    const char* who = "hz_ledger_plan_atomic";
-    if (m && (!txs || !sigs)) return set_err(HZ_ERR_ARG, "%s: null argument", who);
-    if (n_l1 > HZ_LEDGER_MAX_L1) return set_err(HZ_ERR_ARG, "%s: n_l1 = %zu L1 transactions (at most %d)", who, n_l1, HZ_LEDGER_MAX_L1);
-    if (m > HZ_LEDGER_MAX_TX) return set_err(HZ_ERR_ARG, "%s: %zu transactions in one call (at most %u)", who, m, HZ_LEDGER_MAX_TX);
-    if (hz_status e = ledger_check_rq(who, m, txs, rq)) return e;
-    for (size_t i = 0; i < m; i++) {
-        int64_t row = -1;
-        bool ok = true;
-        if (rq && txs[i].from_idx != 0) {
-            row = rq_target_row(n_l1 + i, rq[i].rq_offset, n_l1, n_l1 + m);
-            if (row >= 0 && txs[row - n_l1].from_idx == 0) row = -1;   // a NOP: zeros
-            Fc v2 = fc_zero(), eth = fc_zero(), ay = fc_zero();
-            if (row >= 0) ledger_sig_link_fields_host(txs[row - n_l1], sigs[row - n_l1], &v2, &eth, &ay);
-            ok = rq_fields_match(resolve_load32(rq[i].rq_tx_compressed_data_v2), resolve_load32(rq[i].rq_to_eth_addr), resolve_load32(rq[i].rq_to_bjj_ay), v2, eth, ay);
-        }
-        if (target_row_out) target_row_out[i] = row;
-        if (verdict_out) verdict_out[i] = ok ? 0u : (uint8_t)HZ_RQ_REASON;
-    }
-    return HZ_OK;
-}
-
 // ---- a batch selected from a pool ----------------------------------------------------------------------------------------
-// the local slots of hz_ledger_select_batch: the distinct accounts the L1 rows and the pool touch, numbered by first appearance -- the
-// groups ledger_plan_rows makes, L1's first. Per row (L1 rows, then the pool): the sender's and the receiver's slot, -1: none
-struct SelectPlan {
-    std::vector<int32_t> slot_s, slot_r;
-    std::vector<uint64_t> slot_account;
-};
-
-// partner[i] names another transaction of the pool or none; a NOP's entry is not looked at
-static hz_status select_check_partner(const char* who, size_t m, const hz_l2tx* txs, const int32_t* partner) {
-    if (!partner) return HZ_OK;
-    for (size_t i = 0; i < m; i++) {
-        if (txs[i].from_idx == 0) continue;
-        if (partner[i] < -1 || (partner[i] >= 0 && (size_t)partner[i] >= m))
-            return set_err(HZ_ERR_ARG, "%s: tx %zu: partner = %d is outside the pool (-1 .. %zu)", who, i, partner[i], m ? m - 1 : 0);
-        if (partner[i] >= 0 && (size_t)partner[i] == i) return set_err(HZ_ERR_ARG, "%s: tx %zu: partner = %d is the transaction itself", who, i, partner[i]);
-    }
-    return HZ_OK;
-}
-
-// eff: the pool with the effective receivers; a row whose to_idx is still 0 has none (an unresolved destination, or none asked for).
-// More candidates or slots than k_ledger_select's LDS holds is an argument error that names the first pool index that does not fit
-static hz_status select_plan(const char* who, size_t n_l1, const hz_l1tx* l1, size_t m, const hz_l2tx* eff, LedgerPlan& p, SelectPlan& sp) {
-    if (m > HZ_SELECT_MAX_POOL)
-        return set_err(HZ_ERR_ARG, "%s: tx %d does not fit: a pool holds at most %d candidates (HZ_SELECT_MAX_POOL)", who, HZ_SELECT_MAX_POOL, HZ_SELECT_MAX_POOL);
-    std::vector<hz_l2tx> rows(eff, eff + m);
-    for (size_t i = 0; i < m; i++)
-        if (rows[i].from_idx != 0 && rows[i].to_idx == 0) rows[i].amount_f = 0;   // no receiver event
-    ledger_plan_rows(n_l1, l1, m, rows.data(), 0, nullptr, nullptr, true, p);
-    const size_t R = n_l1 + m, G = p.seg_start.size() - 1;
-    std::vector<uint32_t> group_of(p.account.size());
-    for (size_t g = 0; g < G; g++)
-        for (uint32_t q = p.seg_start[g]; q < p.seg_start[g + 1]; q++) group_of[p.perm[q]] = (uint32_t)g;
-    sp.slot_s.assign(R, -1);
-    sp.slot_r.assign(R, -1);
-    for (size_t r = 0; r < R; r++) {
-        if (p.ev_sender[r] >= 0) sp.slot_s[r] = (int32_t)group_of[p.ev_sender[r]];
-        if (p.ev_receiver[r] >= 0) sp.slot_r[r] = (int32_t)group_of[p.ev_receiver[r]];
-        if (sp.slot_s[r] >= (int32_t)HZ_SELECT_MAX_SLOTS || sp.slot_r[r] >= (int32_t)HZ_SELECT_MAX_SLOTS)   // (an L1 run alone has at most 1024)
-            return set_err(HZ_ERR_ARG, "%s: tx %zu does not fit: the L1 rows and the pool touch more than %d distinct accounts (HZ_SELECT_MAX_SLOTS)", who, r - n_l1,
-                           HZ_SELECT_MAX_SLOTS);
-    }
-    sp.slot_account.resize(G);
-    for (size_t g = 0; g < G; g++) sp.slot_account[g] = p.account[p.perm[p.seg_start[g]]];
-    return HZ_OK;
-}
-
-extern "C" hz_status hz_ledger_plan_select(size_t n_l1, const hz_l1tx* l1, size_t m, const hz_l2tx* txs, const uint64_t* aux_to_idx, const int32_t* partner,
-                                           const uint8_t* kept_in, int32_t* slot_sender_out, int32_t* slot_receiver_out, size_t* n_slots_out,
-                                           uint64_t* slot_account_out, uint8_t* forced_out, uint8_t* rq_offset_out) {
-    const char* who = "hz_ledger_plan_select";
-    if ((n_l1 && !l1) || (m && !txs)) return set_err(HZ_ERR_ARG, "%s: null argument", who);
-    if (n_l1 > HZ_LEDGER_MAX_L1) return set_err(HZ_ERR_ARG, "%s: n_l1 = %zu L1 transactions (at most %d)", who, n_l1, HZ_LEDGER_MAX_L1);
-    for (size_t i = 0; i < n_l1; i++) {
-        if (l1[i].from_idx == 0) return set_err(HZ_ERR_ARG, "%s: L1 tx %zu: from_idx = 0: the planner takes a create row with its auxFromIdx in from_idx's place", who, i);
-        if (hz_status e = ledger_check_l1_fields(who, i, l1[i])) return e;
-    }
-    if (m > HZ_SELECT_MAX_POOL)
-        return set_err(HZ_ERR_ARG, "%s: tx %d does not fit: a pool holds at most %d candidates (HZ_SELECT_MAX_POOL)", who, HZ_SELECT_MAX_POOL, HZ_SELECT_MAX_POOL);
-    if (hz_status e = select_check_partner(who, m, txs, partner)) return e;
-    std::vector<hz_l2tx> eff(txs, txs + m);
-    for (size_t i = 0; i < m; i++)
-        if (eff[i].from_idx != 0 && eff[i].to_idx == 0 && aux_to_idx && ledger_mantissa(eff[i].amount_f) != 0) eff[i].to_idx = aux_to_idx[i];
-    LedgerPlan p;
-    SelectPlan sp;
-    if (hz_status e = select_plan(who, n_l1, l1, m, eff.data(), p, sp)) return e;
-    for (size_t r = 0; r < n_l1 + m; r++) {
-        if (slot_sender_out) slot_sender_out[r] = sp.slot_s[r];
-        if (slot_receiver_out) slot_receiver_out[r] = sp.slot_r[r];
-    }
-    if (n_slots_out) *n_slots_out = sp.slot_account.size();
-    for (size_t g = 0; g < sp.slot_account.size(); g++)
-        if (slot_account_out) slot_account_out[g] = sp.slot_account[g];
-    if (kept_in) {   // the closure step alone, on the rows the kept transactions would have
-        std::vector<uint32_t> row(m, HZ_SELECT_NO_ROW);
-        uint32_t n_kept = 0;
-        for (size_t i = 0; i < m; i++)
-            if (kept_in[i] && txs[i].from_idx != 0) row[i] = n_kept++;
-        for (size_t i = 0; i < m; i++) {
-            uint32_t off = 0;
-            bool forced = false;
-            const int32_t q = partner && txs[i].from_idx != 0 ? partner[i] : -1;
-            if (q >= 0 && row[i] != HZ_SELECT_NO_ROW) {
-                off = select_link(row[q] != HZ_SELECT_NO_ROW, row[i], row[q]);
-                forced = off == 0;
-            }
-            if (forced_out) forced_out[i] = forced;
-            if (rq_offset_out) rq_offset_out[i] = (uint8_t)off;
-        }
-    }
-    return HZ_OK;
-}
-
 extern "C" double hz_ledger_select_ms(const hz_ledger* l) { return l ? l->select_ms : 0.0; }
 
 // the argument checks of hz_ledger_select_batch, in the order their errors win; -> the rows (the L1 rows as hz_ledger_apply_batch_atomic
@@ -2287,9 +1802,8 @@ static hz_status select_checks(hz_ledger* l, const char* who, size_t n_l1, const
     if (!out || (m && !txs)) return set_err(HZ_ERR_ARG, "%s: null argument", who);
     const bool verify = (flags & HZ_LEDGER_VERIFY_SIGS) != 0;
     if (hz_status e = ledger_check_flags(who, flags)) return e;
-    if (hz_status e = ledger_effective_l1(l, who, n_l1, l1, from_bjj, true, true, r)) return e;
-    if (m > HZ_SELECT_MAX_POOL)
-        return set_err(HZ_ERR_ARG, "%s: tx %d does not fit: a pool holds at most %d candidates (HZ_SELECT_MAX_POOL)", who, HZ_SELECT_MAX_POOL, HZ_SELECT_MAX_POOL);
+    if (hz_status e = ledger_effective_l1(ledger_shape(l), who, n_l1, l1, from_bjj, true, true, r)) return e;
+    if (hz_status e = select_check_pool(who, m)) return e;
     if (hz_status e = ledger_check_txs(who, m, txs, l->first_idx, r.count, true, true)) return e;
     if (hz_status e = select_check_partner(who, m, txs, partner)) return e;
     if (hz_status e = ledger_stand_in_sigs(who, m, txs, sigs, verify, r)) return e;
@@ -2344,16 +1858,9 @@ extern "C" hz_status hz_ledger_select_batch(hz_ledger* l, size_t n_l1, const hz_
         const hz_l2sig* d_sigs = (const hz_l2sig*)l->sig_in.p;
         if (links)
             if (hz_status e = ledger_rq_upload(l, m, rq_eff.data(), s)) return e;
-        if (verify) {
-            HZ_HIP(l->t_sig.begin(s));
-            HZ_HIP(launch_ledger_sig(d_txs, d_sigs, chain_id, current_num_batch, l->sig_dev[0], l->sig_dev[1], l->sig_dev[2], (const uint8_t*)l->planes.p, l->b8_table.p, l->N,
-                                     l->first_idx, nullptr, l->verdict_dev, m32, s, 0, links ? (const uint8_t*)l->rq_in.p : nullptr));
-            HZ_HIP(l->t_sig.end(s));
-        } else if (m) {   // the V2 rows alone, for the link compare; no verdict yet
-            HZ_HIP(hipMemsetAsync(l->verdict_dev, 0, m, s));
-            HZ_HIP(launch_ledger_sig_v2(d_txs, d_sigs, l->sig_dev[1], m32, s));
-        }
-        if (links) {
+        if (!verify) HZ_HIP(hipMemsetAsync(l->verdict_dev, 0, m, s));   // the V2 rows alone, for the link compare (links: m != 0); no verdict yet
+        if (hz_status e = ledger_sig_links_launch(l, d_txs, m32, chain_id, current_num_batch, nullptr, l->verdict_dev, 0, verify, links, s, true)) return e;
+        if (links) {   // the selection's own link kernel
             hipLaunchKernelGGL(k_ledger_select_rq, dim3((m32 + 63) / 64), dim3(64), 0, s, d_txs, d_sigs, (const uint8_t*)l->rq_in.p, (const uint8_t*)l->sig_dev[1],
                                partner ? T.partner.dev(db) : nullptr, l->verdict_dev, m32);
             HZ_HIP(hipGetLastError());
@@ -2385,25 +1892,6 @@ extern "C" hz_status hz_ledger_select_batch(hz_ledger* l, size_t n_l1, const hz_
 
 // ---- RollupMain's packed inputs of the applied batch -----------------------------------------------------------------------
 extern "C" double hz_ledger_main_inputs_ms(const hz_ledger* l) { return l ? l->mi_ms : 0.0; }
-
-extern "C" hz_status hz_ledger_plan_main_inputs(size_t n_signals, const char* const* names, const uint64_t* offsets, const uint32_t* widths, const uint64_t* flat_lens,
-                                                uint64_t bytes, uint32_t n_tx, uint32_t n_levels, uint32_t max_l1_tx, uint32_t max_fee_tx, uint32_t flags,
-                                                uint32_t* kind_out, uint32_t* source_out, uint64_t* first_row_out, uint64_t* rows_out) {
-    const char* who = "hz_ledger_plan_main_inputs";
-    if (!names || !offsets || !widths || !flat_lens) return set_err(HZ_ERR_ARG, "%s: null argument", who);
-    MiShape shape;
-    shape.n_tx = n_tx, shape.n_levels = n_levels, shape.max_l1 = max_l1_tx, shape.max_fee = max_fee_tx;
-    std::vector<MiSignal> sig;
-    const std::string err = mi_plan(n_signals, names, offsets, widths, flat_lens, bytes, shape, flags, sig);
-    if (!err.empty()) return set_err(HZ_ERR_ARG, "%s: %s", who, err.c_str());
-    for (size_t i = 0; i < n_signals; i++) {
-        if (kind_out) kind_out[i] = sig[i].kind;
-        if (source_out) source_out[i] = sig[i].source;
-        if (first_row_out) first_row_out[i] = sig[i].r0;
-        if (rows_out) rows_out[i] = sig[i].rows;
-    }
-    return HZ_OK;
-}
 
 // the first byte a COPY / BROADCAST descriptor reads: the array the apply left (or the call's own upload, at `up`) from row r0
 static const uint8_t* ledger_mi_source(const hz_ledger* l, const MiSignal& d, const uint8_t* up_globals, const uint8_t* up_fee_idxs, const uint8_t* up_tokens) {
@@ -2513,5 +2001,151 @@ extern "C" hz_status hz_ledger_main_inputs(hz_ledger* l, const hz_ctx* ctx, uint
     HZ_HIP(l->t_mi.end(s));
     HZ_HIP(hipStreamSynchronize(s));
     HZ_HIP(l->t_mi.read(l->mi_ms));
+    return HZ_OK;
+}
+
+// ---- the hz_ledger_plan_* exports: the host half of a call alone, no ledger -- a shape check, the checks of ledger_checks.h, the planner, ------
+// ---- the copies out ---------------------------------------------------------------------------------------------------------------------
+// a planner's vector (its first n entries) to an output array the caller may have left out
+template <class T, class V>
+static void plan_out(T* out, const V& v, size_t n) {
+    for (size_t i = 0; out && i < n; i++) out[i] = (T)v[i];
+}
+static void plan_out(size_t* out, size_t count) {
+    if (out) *out = count;
+}
+
+extern "C" hz_status hz_ledger_plan_l2(size_t m, const hz_l2tx* txs, size_t F, const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs, int32_t k,
+                                       uint64_t first_idx, int32_t* ev_sender_out, int32_t* ev_receiver_out, int32_t* fee_slot_out, int32_t* last_event_out,
+                                       size_t* n_events_out, uint64_t* ev_account_out, int32_t* ev_prev_out) {
+    const char* who = "hz_ledger_plan_l2";
+    LedgerPlan p;
+    if (hz_status e = ledger_check_k(who, k)) return e;
+    if (hz_status e = ledger_check_plan(who, m, txs, F, fee_plan_tokens, fee_idxs, 1ull << k, first_idx, p)) return e;
+    plan_out(ev_sender_out, p.ev_sender, m), plan_out(ev_receiver_out, p.ev_receiver, m), plan_out(fee_slot_out, p.fee_slot, m), plan_out(last_event_out, p.last_event, m);
+    plan_out(n_events_out, p.account.size()), plan_out(ev_account_out, p.account, p.account.size()), plan_out(ev_prev_out, p.prev_same, p.account.size());
+    return HZ_OK;
+}
+
+extern "C" hz_status hz_ledger_plan_batch(size_t n_l1, const hz_l1tx* l1, size_t m, const hz_l2tx* txs, size_t F, const uint32_t* fee_plan_tokens,
+                                          const uint64_t* fee_idxs, int32_t k, uint64_t first_idx, int32_t* ev_sender_out, int32_t* ev_receiver_out,
+                                          int32_t* fee_slot_out, int32_t* last_event_out, size_t* n_events_out, uint64_t* ev_account_out, int32_t* ev_prev_out,
+                                          int32_t* l1_slot_sender_out, int32_t* l1_slot_receiver_out, size_t* n_slots_out, uint64_t* slot_account_out) {
+    LedgerPlan p;
+    if (hz_status e = ledger_check_plan_rows("hz_ledger_plan_batch", k, first_idx, false, 0, n_l1, l1, m, txs, F, fee_plan_tokens, fee_idxs, p)) return e;
+    ledger_plan_batch(n_l1, l1, m, txs, F, fee_plan_tokens, fee_idxs, p);
+    const size_t R = n_l1 + m, M = p.account.size();
+    plan_out(ev_sender_out, p.ev_sender, R), plan_out(ev_receiver_out, p.ev_receiver, R), plan_out(fee_slot_out, p.fee_slot, R), plan_out(last_event_out, p.last_event, R);
+    plan_out(n_events_out, M), plan_out(ev_account_out, p.account, M), plan_out(ev_prev_out, p.prev_same, M);
+    plan_out(l1_slot_sender_out, p.l1_slot_sender, n_l1), plan_out(l1_slot_receiver_out, p.l1_slot_receiver, n_l1);
+    plan_out(n_slots_out, p.slot_account.size()), plan_out(slot_account_out, p.slot_account, p.slot_account.size());
+    return HZ_OK;
+}
+
+extern "C" hz_status hz_ledger_plan_exits(size_t n_l1, const hz_l1tx* l1, size_t m, const hz_l2tx* txs, size_t F, const uint32_t* fee_plan_tokens,
+                                          const uint64_t* fee_idxs, int32_t k, uint64_t first_idx, size_t n_sib, int32_t* ev_sender_out, int32_t* ev_receiver_out,
+                                          int32_t* last_event_out, size_t* n_events_out, uint64_t* ev_account_out, int32_t* ev_exit_out, int32_t* last_exit_out,
+                                          size_t* n_exits_out, uint32_t* exit_row_out, uint64_t* exit_key_out, int32_t* exit_prev_out, uint32_t* exit_perm_out,
+                                          uint8_t* exit_insert_out, uint8_t* exit_is_old0_out, uint64_t* exit_old_key_out) {
+    const char* who = "hz_ledger_plan_exits";
+    LedgerPlan p;
+    if (hz_status e = ledger_check_plan_rows(who, k, first_idx, true, n_sib, n_l1, l1, m, txs, F, fee_plan_tokens, fee_idxs, p)) return e;
+    ledger_plan_exits(n_l1, l1, m, txs, F, fee_plan_tokens, fee_idxs, p);
+    const size_t R = n_l1 + m, X = p.exit_row.size();
+    SmtShape sh;   // the exit tree of a batch starts empty
+    sh.begin();
+    for (size_t x = 0; x < X; x++)
+        if (sh.add(p.exit_key[x], (uint32_t)n_sib) != SMT_PLAN_OK)
+            return set_err(HZ_ERR_ARG, "%s: op %zu (key %llu) would have its leaf at depth >= n_sib = %zu: SMTProcessor(%zu) cannot express it", who, x,
+                           (unsigned long long)p.exit_key[x], n_sib, n_sib);
+    plan_out(ev_sender_out, p.ev_sender, R), plan_out(ev_receiver_out, p.ev_receiver, R), plan_out(last_event_out, p.last_event, R);
+    plan_out(ev_exit_out, p.ev_exit, R), plan_out(last_exit_out, p.last_exit, R);
+    plan_out(n_events_out, p.account.size()), plan_out(ev_account_out, p.account, p.account.size());
+    plan_out(n_exits_out, X), plan_out(exit_row_out, p.exit_row, X), plan_out(exit_key_out, p.exit_key, X), plan_out(exit_prev_out, p.exit_prev, X);
+    plan_out(exit_perm_out, p.exit_perm, X), plan_out(exit_insert_out, sh.fnc, X), plan_out(exit_is_old0_out, sh.is_old0, X), plan_out(exit_old_key_out, sh.old_key, X);
+    return HZ_OK;
+}
+
+extern "C" hz_status hz_ledger_plan_creates(size_t n_l1, const hz_l1tx* l1, const uint8_t* from_bjj, size_t m, const hz_l2tx* txs, size_t F,
+                                            const uint32_t* fee_plan_tokens, const uint64_t* fee_idxs, int32_t growing, uint64_t capacity, uint64_t first_idx,
+                                            uint64_t size, uint64_t* aux_from_idx_out, uint64_t* out_idx_after_out, size_t* n_creates_out) {
+    LedgerRows r;
+    if (hz_status e = ledger_check_plan_creates("hz_ledger_plan_creates", LedgerShape{growing != 0, capacity, first_idx, size, 0}, n_l1, l1, from_bjj, m, txs, F, fee_plan_tokens,
+                                                fee_idxs, r))
+        return e;
+    r.aux_from.resize(n_l1 + m, 0);   // an L2 row creates nothing and leaves the last idx where the L1 run left it
+    r.idx_after.resize(n_l1 + m, first_idx + r.count - 1);
+    plan_out(aux_from_idx_out, r.aux_from, n_l1 + m), plan_out(out_idx_after_out, r.idx_after, n_l1 + m), plan_out(n_creates_out, r.n_creates);
+    return HZ_OK;
+}
+
+extern "C" hz_status hz_ledger_plan_atomic(size_t n_l1, size_t m, const hz_l2tx* txs, const hz_l2sig* sigs, const hz_l2rq* rq, int64_t* target_row_out,
+                                           uint8_t* verdict_out) {
+    if (hz_status e = ledger_check_plan_atomic("hz_ledger_plan_atomic", n_l1, m, txs, sigs, rq)) return e;
+    for (size_t i = 0; i < m; i++) {
+        int64_t row = -1;
+        bool ok = true;
+        if (rq && txs[i].from_idx != 0) {
+            row = rq_target_row(n_l1 + i, rq[i].rq_offset, n_l1, n_l1 + m);
+            if (row >= 0 && txs[row - n_l1].from_idx == 0) row = -1;   // a NOP: zeros
+            Fc v2 = fc_zero(), eth = fc_zero(), ay = fc_zero();
+            if (row >= 0) ledger_sig_link_fields_host(txs[row - n_l1], sigs[row - n_l1], &v2, &eth, &ay);
+            ok = rq_fields_match(resolve_load32(rq[i].rq_tx_compressed_data_v2), resolve_load32(rq[i].rq_to_eth_addr), resolve_load32(rq[i].rq_to_bjj_ay), v2, eth, ay);
+        }
+        if (target_row_out) target_row_out[i] = row;
+        if (verdict_out) verdict_out[i] = ok ? 0u : (uint8_t)HZ_RQ_REASON;
+    }
+    return HZ_OK;
+}
+
+extern "C" hz_status hz_ledger_plan_select(size_t n_l1, const hz_l1tx* l1, size_t m, const hz_l2tx* txs, const uint64_t* aux_to_idx, const int32_t* partner,
+                                           const uint8_t* kept_in, int32_t* slot_sender_out, int32_t* slot_receiver_out, size_t* n_slots_out,
+                                           uint64_t* slot_account_out, uint8_t* forced_out, uint8_t* rq_offset_out) {
+    const char* who = "hz_ledger_plan_select";
+    if (hz_status e = select_check_plan(who, n_l1, l1, m, txs, partner)) return e;
+    std::vector<hz_l2tx> eff(txs, txs + m);
+    for (size_t i = 0; i < m; i++)
+        if (aux_to_idx && ledger_wants_receiver(eff[i])) eff[i].to_idx = aux_to_idx[i];
+    LedgerPlan p;
+    SelectPlan sp;
+    if (hz_status e = select_plan(who, n_l1, l1, m, eff.data(), p, sp)) return e;
+    plan_out(slot_sender_out, sp.slot_s, n_l1 + m), plan_out(slot_receiver_out, sp.slot_r, n_l1 + m);
+    plan_out(n_slots_out, sp.slot_account.size()), plan_out(slot_account_out, sp.slot_account, sp.slot_account.size());
+    if (kept_in) {   // the closure step alone, on the rows the kept transactions would have
+        std::vector<uint32_t> row(m, HZ_SELECT_NO_ROW);
+        uint32_t n_kept = 0;
+        for (size_t i = 0; i < m; i++)
+            if (kept_in[i] && txs[i].from_idx != 0) row[i] = n_kept++;
+        for (size_t i = 0; i < m; i++) {
+            uint32_t off = 0;
+            bool forced = false;
+            const int32_t q = partner && txs[i].from_idx != 0 ? partner[i] : -1;
+            if (q >= 0 && row[i] != HZ_SELECT_NO_ROW) {
+                off = select_link(row[q] != HZ_SELECT_NO_ROW, row[i], row[q]);
+                forced = off == 0;
+            }
+            if (forced_out) forced_out[i] = forced;
+            if (rq_offset_out) rq_offset_out[i] = (uint8_t)off;
+        }
+    }
+    return HZ_OK;
+}
+
+extern "C" hz_status hz_ledger_plan_main_inputs(size_t n_signals, const char* const* names, const uint64_t* offsets, const uint32_t* widths, const uint64_t* flat_lens,
+                                                uint64_t bytes, uint32_t n_tx, uint32_t n_levels, uint32_t max_l1_tx, uint32_t max_fee_tx, uint32_t flags,
+                                                uint32_t* kind_out, uint32_t* source_out, uint64_t* first_row_out, uint64_t* rows_out) {
+    const char* who = "hz_ledger_plan_main_inputs";
+    if (!names || !offsets || !widths || !flat_lens) return set_err(HZ_ERR_ARG, "%s: null argument", who);
+    MiShape shape;
+    shape.n_tx = n_tx, shape.n_levels = n_levels, shape.max_l1 = max_l1_tx, shape.max_fee = max_fee_tx;
+    std::vector<MiSignal> sig;
+    const std::string err = mi_plan(n_signals, names, offsets, widths, flat_lens, bytes, shape, flags, sig);
+    if (!err.empty()) return set_err(HZ_ERR_ARG, "%s: %s", who, err.c_str());
+    for (size_t i = 0; i < n_signals; i++) {
+        if (kind_out) kind_out[i] = sig[i].kind;
+        if (source_out) source_out[i] = sig[i].source;
+        if (first_row_out) first_row_out[i] = sig[i].r0;
+        if (rows_out) rows_out[i] = sig[i].rows;
+    }
     return HZ_OK;
 }
