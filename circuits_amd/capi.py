@@ -82,6 +82,7 @@ EXPORTS = [
     "hz_ledger_exit_keep", "hz_ledger_exit_forget", "hz_ledger_exit_kept", "hz_ledger_exit_archive_stats", "hz_ledger_exit_root_of", "hz_ledger_withdraw_rows",
     "hz_ledger_withdraw_rows_dev", "hz_ledger_withdraw_ms", "hz_ledger_exit_keep_ms",
     "hz_ledger_main_inputs", "hz_ledger_main_inputs_ms", "hz_ledger_plan_main_inputs",
+    "hz_ledger_journal", "hz_ledger_applied", "hz_ledger_rollback", "hz_ledger_journal_stats", "hz_ledger_journal_ms", "hz_ledger_rollback_ms",
 ]
 
 
@@ -474,6 +475,13 @@ class Lib:
         c.hz_ledger_plan_main_inputs.argtypes = [sz, vp, vp, vp, vp, u64, u32, u32, u32, u32, u32, vp, vp, vp, vp]
         c.hz_ledger_main_inputs_ms.argtypes = [vp]
         c.hz_ledger_main_inputs_ms.restype = ctypes.c_double
+        c.hz_ledger_journal.argtypes = [vp, u32]
+        c.hz_ledger_applied.argtypes = [vp, ctypes.POINTER(u64)]
+        c.hz_ledger_rollback.argtypes = [vp, u64]
+        c.hz_ledger_journal_stats.argtypes = [vp, ctypes.POINTER(u32), ctypes.POINTER(sz), ctypes.POINTER(u64), ctypes.POINTER(sz), ctypes.POINTER(sz)]
+        for f in (c.hz_ledger_journal_ms, c.hz_ledger_rollback_ms):
+            f.argtypes = [vp]
+            f.restype = ctypes.c_double
         for f in ("hz_ledger_device_ms", "hz_ledger_semantic_ms", "hz_ledger_sig_ms", "hz_ledger_resolve_ms", "hz_ledger_l1_ms", "hz_ledger_exit_ms", "hz_ledger_create_ms",
                   "hz_ledger_rq_ms", "hz_ledger_select_ms", "hz_ledger_withdraw_ms", "hz_ledger_exit_keep_ms"):
             getattr(c, f).argtypes = [vp]
@@ -1315,6 +1323,34 @@ class Ledger(_Resident):
     def main_inputs_ms(self):
         """device time of k_ledger_main_inputs in the last main_inputs"""
         return self.L.c.hz_ledger_main_inputs_ms(self.h)
+
+    def journal(self, depth):
+        """hz_ledger_journal: keep an undo record of each of the last `depth` applies (0: off, the default); discards the records held"""
+        self.L._check(self.L.c.hz_ledger_journal(self.h, depth))
+
+    def applied(self):
+        """hz_ledger_applied: the mark -- successful apply calls since the last load"""
+        v = ctypes.c_uint64()
+        self.L._check(self.L.c.hz_ledger_applied(self.h, ctypes.byref(v)))
+        return v.value
+
+    def rollback(self, mark):
+        """hz_ledger_rollback: the ledger as it was when applied() gave `mark`"""
+        self.L._check(self.L.c.hz_ledger_rollback(self.h, mark))
+
+    def journal_stats(self):
+        """hz_ledger_journal_stats -> {"depth", "records", "oldest_mark", "bytes_used", "bytes_reserved"}"""
+        v = (ctypes.c_uint32(), ctypes.c_size_t(), ctypes.c_uint64(), ctypes.c_size_t(), ctypes.c_size_t())
+        self.L._check(self.L.c.hz_ledger_journal_stats(self.h, *[ctypes.byref(x) for x in v]))
+        return dict(zip(("depth", "records", "oldest_mark", "bytes_used", "bytes_reserved"), (x.value for x in v)))
+
+    def journal_ms(self):
+        """device time of the journal's save kernels in the last apply (0.0 with the journal off)"""
+        return self.L.c.hz_ledger_journal_ms(self.h)
+
+    def rollback_ms(self):
+        """device time of the last rollback"""
+        return self.L.c.hz_ledger_rollback_ms(self.h)
 
     def rq_ms(self):
         """device time of the link kernel of the last apply_batch_atomic / verify_l2_atomic (0.0 when none ran)"""

@@ -66,6 +66,7 @@
 #include "ledger_inputs.h"
 #include "ledger_tables.h"
 #include "ledger_checks.h"
+#include "ledger_journal.h"
 #include "ctx_internal.h"
 #include "smt_internal.h"
 #include "smt_plan.h"
@@ -271,6 +272,31 @@ __global__ __launch_bounds__(64) void k_ledger_writeback(const LedgerPos* __rest
     store_fr(planes + ((size_t)N + ev.acct) * 32, load_fr(records + (size_t)ev.ev * 128 + 32));
 }
 
+// the undo journal's plane part (ledger_journal.h): thread f * G + g saves plane f of group g's account, consecutive lanes on
+// consecutive journal addresses, and the first G threads note the accounts. A create row's account lies at or beyond `live`, the accounts
+// the batch found: its slot holds nothing to save. Before k_ledger_writeback, on the same stream
+__global__ __launch_bounds__(256) void k_ledger_journal_save(const LedgerPos* __restrict__ pos, const uint32_t* __restrict__ seg_start, const uint8_t* __restrict__ planes,
+                                                             uint8_t* __restrict__ out, uint32_t* __restrict__ index, uint32_t N, uint32_t G, uint32_t live) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= 4 * G) return;
+    const uint32_t f = t / G, g = t - f * G;
+    const uint32_t acct = pos[seg_start[g]].acct;
+    if (f == 0) index[g] = acct;
+    if (acct >= live) return;
+    store_fr(out + (size_t)t * 32, load_fr(planes + ((size_t)f * N + acct) * 32));
+}
+
+// the same list run the other way: every account appears once in a record
+__global__ __launch_bounds__(256) void k_ledger_journal_restore(const uint32_t* __restrict__ index, const uint8_t* __restrict__ saved, uint8_t* __restrict__ planes, uint32_t N,
+                                                                uint32_t G, uint32_t live) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= 4 * G) return;
+    const uint32_t f = t / G, g = t - f * G;
+    const uint32_t acct = index[g];
+    if (acct >= live) return;
+    store_fr(planes + ((size_t)f * N + acct) * 32, load_fr(saved + (size_t)t * 32));
+}
+
 // thread (i, f): field f of account i
 __global__ __launch_bounds__(256) void k_ledger_accounts(const uint32_t* __restrict__ acct, const uint8_t* __restrict__ planes, uint8_t* __restrict__ out, uint32_t N,
                                                          uint32_t n) {
@@ -435,6 +461,17 @@ struct LedgerMainCall {
     std::vector<uint32_t> plan_tokens;
 };
 
+// the undo journal (ledger_journal.h): the ring's bookkeeping, its slabs -- one per slot, all of one capacity --, and per
+// slot what an hz_smt state tree handed out of its shape. Made by hz_ledger_journal(depth > 0): a ledger without a journal owns none of this
+struct LedgerJournal {
+    JournalRing ring;
+    std::unique_ptr<DevBuf[]> slab;        // [ring.slots()]: depth + 1, one always free for the apply in progress
+    size_t cap = 0;
+    std::vector<SmtShape::UndoLog> undo;   // [ring.slots()]
+    std::vector<uint8_t> has_undo;         // [ring.slots()]: the record's apply updated the growing ledger's tree
+    DevSpan t_tree, t_planes, t_rollback;  // around the tree's save kernel, the planes', a rollback's restores
+};
+
 struct hz_ledger {
     int32_t device = 0;
     uint32_t k = 0, N = 0;
@@ -507,7 +544,13 @@ struct hz_ledger {
     PinnedBuf h_mi;
     DevSpan t_mi;   // around k_ledger_main_inputs
     double mi_ms = 0.0;
+    // marks and the undo journal (hz_ledger_journal / _rollback)
+    uint64_t applied = 0;
+    std::unique_ptr<LedgerJournal> journal;
+    double journal_ms = 0.0, rollback_ms = 0.0;
+    bool rollback_failed = false;   // a rollback failed behind its first queued restore: tree, planes and shape may disagree until a load
     ~hz_ledger() {
+        journal.reset();
         archive.reset();
         if (exit) hz_smt_destroy(exit);
         if (smt) hz_smt_destroy(smt);
@@ -558,8 +601,18 @@ static void ledger_archive_clear(hz_ledger* l) {
     l->archive->slabs.clear();
 }
 
+// a load starts a new history of marks too: no record of the old one is kept
+static void ledger_history_reset(hz_ledger* l) {
+    l->applied = 0;
+    l->rollback_failed = false;
+    l->journal_ms = 0.0;
+    if (l->journal) l->journal->ring.clear();
+}
+
 static hz_status ledger_ready(const hz_ledger* l, const char* who) {
     if (!l) return set_err(HZ_ERR_ARG, "%s: null ledger", who);
+    if (l->rollback_failed)
+        return set_err(HZ_ERR_HIP, "%s: an earlier hz_ledger_rollback failed on the device after its first restore was queued; loading the ledger makes it usable again", who);
     if (l->smt) {
         if (!l->loaded) return set_err(HZ_ERR_ARG, "%s: the ledger has not been loaded yet (hz_ledger_load_accounts)", who);
         if (smt_poisoned(l->smt))
@@ -662,6 +715,7 @@ extern "C" hz_status hz_ledger_load(hz_ledger* l, const uint8_t* e0, const uint8
     if (hz_status e = ledger_check_leaves("hz_ledger_load", l->first_idx, l->N, e0, balance, eth_addr)) return e;
     ledger_forget(l);
     ledger_archive_clear(l);
+    ledger_history_reset(l);
     if (hz_status e = hz_state_load(l->tree, e0, balance, ay, eth_addr)) return e;   // checks every field < r
     const uint8_t* src[4] = {e0, balance, ay, eth_addr};
     hipStream_t s = ledger_stream(l);
@@ -697,6 +751,7 @@ extern "C" hz_status hz_ledger_load_accounts(hz_ledger* l, uint64_t n, const uin
     ledger_forget(l);
     ledger_exit_reset(l);
     ledger_archive_clear(l);
+    ledger_history_reset(l);
     HZ_HIP(hipSetDevice(l->device));
     if (hz_status e = hz_smt_reset(l->smt)) return e;   // synchronises the stream
     l->live = 0;
@@ -1039,6 +1094,14 @@ struct LedgerApply {
     LedgerCreateOutDev cd{};
     uint64_t new_last = 0;
     const hz_l2sig* d_dest = nullptr;   // by_addr: the signed destinations, for reasons 10 and 11 and the zero-amount rows
+    // the undo record of this call (journal on): its layout in the slab, the slot, the accounts the batch found
+    bool journal = false;
+    JournalLayout jl;
+    size_t j_tree = 0;
+    int32_t j_slot = -1;
+    uint64_t live0 = 0;
+    bool j_has_kept = false;
+    uint32_t j_last_kept = 0;
     LedgerApply(hz_ledger* l_, const LedgerCall& c_) : l(l_), c(c_) {}
     const hz_l2tx* d_txs() const { return T.tx.dev(db); }
     const uint8_t* planes() const { return (const uint8_t*)l->planes.p; }
@@ -1110,6 +1173,31 @@ static hz_status ledger_apply_buffers(LedgerApply& a) {
     return HZ_OK;
 }
 
+// the undo record of the call, journal on: the tree says how many resident entries its write-back will replace, the
+// layout follows, and the slabs get room. The only allocation of the journal: a record larger than any before doubles every slab's
+// capacity -- the records held are copied over --, so a steady run of applies allocates nothing here
+static hz_status ledger_journal_room(LedgerApply& a) {
+    hz_ledger* l = a.l;
+    LedgerJournal& J = *l->journal;
+    size_t n = 0;
+    if (a.M)
+        if (hz_status e = a.growing ? smt_journal_entries(l->smt, &n) : state_journal_entries(l->tree, a.M, &n)) return e;
+    a.j_tree = n;
+    a.jl = journal_layout(n, a.G);
+    a.journal = true;
+    if (a.jl.bytes <= J.cap) return HZ_OK;
+    const size_t cap = journal_grown_cap(J.cap, a.jl.bytes);
+    const uint32_t slots = J.ring.slots();
+    std::unique_ptr<DevBuf[]> fresh(new DevBuf[slots]);
+    for (uint32_t q = 0; q < slots; q++) HZ_HIP(fresh[q].alloc(cap));
+    for (const JournalRecord& r : J.ring.rec)
+        if (r.bytes) HZ_HIP(hipMemcpyAsync(fresh[r.slot].p, J.slab[r.slot].p, r.bytes, hipMemcpyDeviceToDevice, a.s));
+    HZ_HIP(hipStreamSynchronize(a.s));
+    J.slab.swap(fresh);
+    J.cap = cap;
+    return HZ_OK;
+}
+
 // stage 3: the tables, and the state tree's plan: hz_state's on a dense ledger; on a growing one hz_smt's, whose planner turns the first
 // event of a key the tree does not hold -- a create row's sender event -- into an INSERT and refuses a leaf at depth >= n_sib before
 // anything of the update is launched. The create rows read its integers, so they are written behind it
@@ -1130,6 +1218,9 @@ static hz_status ledger_apply_tables(LedgerApply& a) {
     }
     a.new_last = l->first_idx + l->live + a.rows.n_creates - 1;
     if (a.c.creates) a.T.fill_creates(l->h_ints.p, p, a.rows.aux_from.data(), a.rows.idx_after.data(), a.new_last, a.sb.old_key, a.sb.is_old0);
+    a.live0 = l->live;
+    if (l->journal)
+        if (hz_status e = ledger_journal_room(a)) return e;
     return HZ_OK;
 }
 
@@ -1221,9 +1312,20 @@ static hz_status ledger_apply_commit(LedgerApply& a) {
                            T.ev_r.dev(db), T.ev_fee.dev(db), T.acct.dev(db), a.W.before.dev(wb), a.planes(), a.N, R32, F32, a.L32);
         HZ_HIP(hipGetLastError());
     }
+    uint8_t* jbase = nullptr;   // the undo record's slab: the ring's free slot, beside every record held -- the ring changes in the last stage
+    if (a.journal) {
+        LedgerJournal& J = *l->journal;
+        a.j_slot = J.ring.free_slot();
+        jbase = (uint8_t*)J.slab[a.j_slot].p;
+        a.j_has_kept = l->archive && !l->archive->snaps.empty();
+        a.j_last_kept = a.j_has_kept ? l->archive->snaps.back().batch_num : 0u;
+    }
     const uint8_t* root0 = nullptr;
     if (M) {
-        if (hz_status e = a.growing ? smt_apply_launch(l->smt, M, S, true) : state_apply_launch(l->tree, M, S, false)) return e;
+        const SmtJournalDst sj{jbase + a.jl.tree.values, (uint32_t*)(jbase + a.jl.tree.index), a.journal ? &l->journal->t_tree : nullptr};
+        const StateJournalDst tj{sj.values, sj.index, sj.span};
+        if (hz_status e = a.growing ? smt_apply_launch(l->smt, M, S, true, a.journal ? &sj : nullptr) : state_apply_launch(l->tree, M, S, false, a.journal ? &tj : nullptr))
+            return e;
         root0 = a.tb.old_root;
     } else if (a.growing) {   // no update at all: the root as it stands, through the host
         uint8_t r32[32];
@@ -1246,6 +1348,14 @@ static hz_status ledger_apply_commit(LedgerApply& a) {
         hipLaunchKernelGGL(k_ledger_gather, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, a.od, T.ev_s.dev(db), T.ev_r.dev(db), T.ev_fee.dev(db), T.last.dev(db),
                            a.tb.siblings, a.tb.new_root, root0, a.k, S, R32, F32);
         HZ_HIP(hipGetLastError());
+    }
+    if (G && a.journal) {   // the plane elements k_ledger_writeback is about to replace
+        LedgerJournal& J = *l->journal;
+        HZ_HIP(J.t_planes.begin(s));
+        hipLaunchKernelGGL(k_ledger_journal_save, dim3((4 * G + 255) / 256), dim3(256), 0, s, T.pos.dev(db), T.seg.dev(db), a.planes(), jbase + a.jl.planes.values,
+                           (uint32_t*)(jbase + a.jl.planes.index), a.N, G, (uint32_t)a.live0);
+        HZ_HIP(hipGetLastError());
+        HZ_HIP(J.t_planes.end(s));
     }
     if (G) {
         hipLaunchKernelGGL(k_ledger_writeback, dim3((G + 63) / 64), dim3(64), 0, s, T.pos.dev(db), T.seg.dev(db), a.tb.fields, (uint8_t*)l->planes.p, a.N, G);
@@ -1327,7 +1437,7 @@ static hz_status ledger_apply_finish(LedgerApply& a) {
     const LedgerPlan& p = l->plan;
     if (a.M && a.growing) {
         a.tree_guard.t = nullptr;
-        if (hz_status e = smt_apply_finish(l->smt)) {
+        if (hz_status e = smt_apply_finish(l->smt, a.journal ? &l->journal->undo[a.j_slot] : nullptr)) {
             smt_apply_abort(l->smt);
             return e;
         }
@@ -1377,6 +1487,25 @@ static hz_status ledger_apply_finish(LedgerApply& a) {
         l->have_sig_outputs = true;
     }
     if (c.verify || c.by_addr) ledger_main_call_keep(a);   // every call but hz_ledger_apply_l2: it has a chain id, and the sigs are uploaded
+    double journal_ms = 0.0;   // the save kernels' time, read before the ring and the mark move: both move together or not at all
+    if (a.journal && a.j_tree) {
+        HZ_HIP(l->journal->t_tree.read(ms));
+        journal_ms += ms;
+    }
+    if (a.journal && a.G) {
+        HZ_HIP(l->journal->t_planes.read(ms));
+        journal_ms += ms;
+    }
+    l->journal_ms = journal_ms;
+    if (a.journal) {   // the call stands: so does its undo record
+        LedgerJournal& J = *l->journal;
+        JournalRecord r;
+        r.mark = l->applied, r.live = a.live0, r.has_kept = a.j_has_kept, r.last_kept = a.j_last_kept;
+        r.slot = (uint32_t)a.j_slot, r.tree_entries = a.j_tree, r.groups = a.G, r.bytes = a.jl.bytes;
+        J.has_undo[r.slot] = a.M && a.growing;
+        J.ring.push(r);
+    }
+    l->applied++;
     return HZ_OK;
 }
 
@@ -1616,6 +1745,12 @@ extern "C" hz_status hz_ledger_exit_keep(hz_ledger* l, uint32_t batch_num) {
     return HZ_OK;
 }
 
+// a slab no snapshot lies in any more is freed (no call is in flight: every one ends behind a synchronise)
+static void archive_free_empty_slabs(LedgerArchive* a) {
+    for (size_t i = a->slabs.size(); i-- > 0;)
+        if (a->slabs[i]->live == 0) a->slabs.erase(a->slabs.begin() + (ptrdiff_t)i);
+}
+
 extern "C" hz_status hz_ledger_exit_forget(hz_ledger* l, uint32_t below_batch) {
     const char* who = "hz_ledger_exit_forget";
     if (!l) return set_err(HZ_ERR_ARG, "%s: null ledger", who);
@@ -1628,8 +1763,7 @@ extern "C" hz_status hz_ledger_exit_forget(hz_ledger* l, uint32_t below_batch) {
     for (size_t i = 0; i < drop; i++)
         if (ArchiveSlab* slab = a->snaps[i].slab) slab->live--;
     a->snaps.erase(a->snaps.begin(), a->snaps.begin() + (ptrdiff_t)drop);
-    for (size_t i = a->slabs.size(); i-- > 0;)
-        if (a->slabs[i]->live == 0) a->slabs.erase(a->slabs.begin() + (ptrdiff_t)i);   // (no call is in flight: every one ends behind a synchronise)
+    archive_free_empty_slabs(a);
     std::vector<ArchiveDesc> host_table;
     hipStream_t s = ledger_stream(l);
     HZ_HIP(archive_upload_table(a->snaps, a->table.p, host_table, s));
@@ -2001,6 +2135,129 @@ extern "C" hz_status hz_ledger_main_inputs(hz_ledger* l, const hz_ctx* ctx, uint
     HZ_HIP(l->t_mi.end(s));
     HZ_HIP(hipStreamSynchronize(s));
     HZ_HIP(l->t_mi.read(l->mi_ms));
+    return HZ_OK;
+}
+
+// ---- marks, the undo journal, rollback (ledger_journal.h) ------------------------------------------------------------------------
+extern "C" hz_status hz_ledger_journal(hz_ledger* l, uint32_t depth) {
+    const char* who = "hz_ledger_journal";
+    if (!l) return set_err(HZ_ERR_ARG, "%s: null ledger", who);
+    if (hz_status e = journal_check_depth(who, depth)) return e;
+    HZ_HIP(hipSetDevice(l->device));
+    l->journal.reset();   // (no call is in flight: every one ends behind a synchronise)
+    l->journal_ms = 0.0;
+    if (depth == 0) return HZ_OK;
+    std::unique_ptr<LedgerJournal> j(new LedgerJournal);
+    j->ring.set_depth(depth);
+    j->slab.reset(new DevBuf[j->ring.slots()]);
+    j->undo.resize(j->ring.slots());
+    j->has_undo.assign(j->ring.slots(), 0);
+    for (DevSpan* t : {&j->t_tree, &j->t_planes, &j->t_rollback}) HZ_HIP(t->create());
+    l->journal = std::move(j);
+    return HZ_OK;
+}
+
+extern "C" hz_status hz_ledger_applied(const hz_ledger* l, uint64_t* mark) {
+    if (!l || !mark) return set_err(HZ_ERR_ARG, "hz_ledger_applied: null argument");
+    *mark = l->applied;
+    return HZ_OK;
+}
+
+extern "C" hz_status hz_ledger_journal_stats(const hz_ledger* l, uint32_t* depth, size_t* records, uint64_t* oldest_mark, size_t* bytes_used, size_t* bytes_reserved) {
+    if (!l) return set_err(HZ_ERR_ARG, "hz_ledger_journal_stats: null ledger");
+    const LedgerJournal* j = l->journal.get();
+    if (depth) *depth = j ? j->ring.depth : 0u;
+    if (records) *records = j ? j->ring.records() : 0;
+    if (oldest_mark) *oldest_mark = j ? j->ring.oldest_mark(l->applied) : l->applied;
+    if (bytes_used) *bytes_used = j ? j->ring.bytes_used() : 0;
+    if (bytes_reserved) *bytes_reserved = j ? j->cap * j->ring.slots() : 0;
+    return HZ_OK;
+}
+
+extern "C" double hz_ledger_journal_ms(const hz_ledger* l) { return l ? l->journal_ms : 0.0; }
+extern "C" double hz_ledger_rollback_ms(const hz_ledger* l) { return l ? l->rollback_ms : 0.0; }
+
+// the exit trees kept after the mark was reached go, from the archive's end. Two steps, as hz_ledger_exit_keep works on `next`: plan -- how
+// many snapshots stay, and the table of those uploaded on s, the archive itself untouched --, and once the rollback's synchronise has
+// succeeded, commit: the snapshots popped, the counters of their slabs as a keep left them, the emptied slabs freed
+static hz_status ledger_archive_cut_plan(const hz_ledger* l, bool has_kept, uint32_t last_kept, std::vector<ArchiveDesc>& host_table, hipStream_t s, size_t* stay) {
+    const LedgerArchive* a = l->archive.get();
+    *stay = a ? a->snaps.size() : 0;
+    if (!a || a->snaps.empty()) return HZ_OK;
+    std::vector<uint32_t> kept;
+    for (const ArchiveSnap& sn : a->snaps) kept.push_back(sn.batch_num);
+    *stay = journal_archive_keep(kept.data(), kept.size(), has_kept, last_kept);
+    if (*stay == a->snaps.size()) return HZ_OK;
+    const std::vector<ArchiveSnap> next(a->snaps.begin(), a->snaps.begin() + (ptrdiff_t)*stay);
+    HZ_HIP(archive_upload_table(next, a->table.p, host_table, s));
+    return HZ_OK;
+}
+
+static void ledger_archive_cut_commit(hz_ledger* l, size_t stay) {
+    LedgerArchive* a = l->archive.get();
+    if (!a || stay >= a->snaps.size()) return;
+    while (a->snaps.size() > stay) {
+        const ArchiveSnap& sn = a->snaps.back();   // the last snapshot of its slab: its bytes are the slab's last
+        if (sn.slab) {
+            sn.slab->live--;
+            sn.slab->used -= sn.bytes;
+        }
+        a->snaps.pop_back();
+    }
+    archive_free_empty_slabs(a);
+}
+
+extern "C" hz_status hz_ledger_rollback(hz_ledger* l, uint64_t mark) {
+    const char* who = "hz_ledger_rollback";
+    if (hz_status e = ledger_ready(l, who)) return e;
+    LedgerJournal* J = l->journal.get();
+    if (hz_status e = journal_check_mark(who, l->applied, J ? J->ring.depth : 0u, J ? J->ring.records() : 0, mark)) return e;
+    if (mark == l->applied) return HZ_OK;   // nothing changes, nothing is invalidated
+    HZ_HIP(hipSetDevice(l->device));
+    hipStream_t s = ledger_stream(l);
+    const size_t n = J->ring.undone_by(mark);   // == applied - mark: the verdict says the ring reaches that far
+    std::vector<ArchiveDesc> host_table;
+    bool queued = false;
+    size_t stay = 0;
+    const hz_status st = [&]() -> hz_status {
+        HZ_HIP(J->t_rollback.begin(s));
+        for (size_t i = 0; i < n; i++) {   // newest first: where two batches touched an element the oldest saved value is written last
+            const JournalRecord r = J->ring.rec.back();
+            const JournalLayout lay = journal_layout(r.tree_entries, r.groups);
+            const uint8_t* base = (const uint8_t*)J->slab[r.slot].p;
+            if (r.groups) {
+                const uint32_t G = (uint32_t)r.groups;
+                queued = true;
+                hipLaunchKernelGGL(k_ledger_journal_restore, dim3((4 * G + 255) / 256), dim3(256), 0, s, (const uint32_t*)(base + lay.planes.index), base + lay.planes.values,
+                                   (uint8_t*)l->planes.p, l->N, G, (uint32_t)r.live);
+                HZ_HIP(hipGetLastError());
+            }
+            if (l->smt && J->has_undo[r.slot]) {
+                queued = true;
+                if (hz_status e = smt_journal_restore(l->smt, base + lay.tree.values, (const uint32_t*)(base + lay.tree.index), r.tree_entries, J->undo[r.slot])) return e;
+            } else if (l->tree && r.tree_entries) {
+                queued = true;
+                if (hz_status e = state_journal_restore(l->tree, base + lay.tree.values, (const uint32_t*)(base + lay.tree.index), r.tree_entries)) return e;
+            }
+            l->live = r.live;
+            if (i + 1 == n)
+                if (hz_status e = ledger_archive_cut_plan(l, r.has_kept, r.last_kept, host_table, s, &stay)) return e;
+            J->ring.pop_newest();
+        }
+        HZ_HIP(J->t_rollback.end(s));
+        HZ_HIP(hipStreamSynchronize(s));   // the one synchronise
+        HZ_HIP(J->t_rollback.read(l->rollback_ms));
+        return HZ_OK;
+    }();
+    if (st) {
+        (void)hipStreamSynchronize(s);
+        l->rollback_failed = queued;
+        return st;
+    }
+    ledger_archive_cut_commit(l, stay);
+    ledger_exit_reset(l);   // the batch's exit tree is empty, as after a load
+    ledger_forget(l);
+    l->applied = mark;
     return HZ_OK;
 }
 

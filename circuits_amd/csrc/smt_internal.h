@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/hermez_witness.h"
+#include "smt_plan.h"
 
 namespace hz {
 
@@ -22,10 +23,24 @@ struct SmtCallBufs {
 // tree's stream. A key the planner refuses leaves the tree as it was: HZ_ERR_INPUT, or depth_status for a leaf at depth >= n_sib.
 // The tree must be usable and 1 <= M <= 65536, 1 <= n_sib <= n_sib_max (the callers check).
 hz_status smt_apply_prepare(hz_smt* t, const char* who, hz_status depth_status, uint32_t M, const uint64_t* key, uint32_t n_sib, bool want_siblings, SmtCallBufs* out);
-// the kernels, on the tree's stream: leaf, one level launch per depth, gather, write-back
-hz_status smt_apply_launch(hz_smt* t, uint32_t M, uint32_t n_sib, bool want_siblings);
-// synchronises the tree's stream, records the device time of the launch and lets the call stand
-hz_status smt_apply_finish(hz_smt* t);
+// Undo for an owner that journals its applies (ledger.hip). A prepared call tells how many resident pool entries its
+// write-back will replace (entries at or above the pools' old counts are new and are not counted); the owner gives room for them -- n
+// 32-byte elements and n uint32 entries, pool kind << 29 | index -- and the launch saves them there, between the level kernels and the
+// write-back, under `span`. Entries, never addresses: a pool reallocated later does not matter
+struct DevSpan;
+struct SmtJournalDst {
+    uint8_t* values;
+    uint32_t* index;
+    DevSpan* span;
+};
+hz_status smt_journal_entries(hz_smt* t, size_t* n);
+// the kernels, on the tree's stream: leaf, one level launch per depth, gather, (the journal's save,) write-back
+hz_status smt_apply_launch(hz_smt* t, uint32_t M, uint32_t n_sib, bool want_siblings, const SmtJournalDst* journal = nullptr);
+// synchronises the tree's stream, records the device time of the launch and lets the call stand; undo: what it changed of the shape
+hz_status smt_apply_finish(hz_smt* t, SmtShape::UndoLog* undo = nullptr);
+// the call that left (values, index, undo) did not happen: the n saved elements back into the pools on the tree's stream -- no
+// synchronise --, the shape reverted at once. Every later call has been restored already
+hz_status smt_journal_restore(hz_smt* t, const uint8_t* values, const uint32_t* index, size_t n, const SmtShape::UndoLog& undo);
 // the prepared call did not happen, or failed: nothing stays in flight, the shape is rolled back; after a queued write-back the tree
 // is poisoned (hz_smt_apply's rule)
 void smt_apply_abort(hz_smt* t);

@@ -230,6 +230,37 @@ struct SmtShape {
         begin();
     }
 
+    // what a call that stands changed of the shape, for an owner that may want the call undone later (ledger_journal.h): the references it
+    // replaced in slots the tree already had, and the counts it found
+    struct UndoLog {
+        std::vector<Undo> undo;
+        size_t nodes0 = 0, leaves0 = 0;
+    };
+
+    // commit(), but hand me the undo
+    void commit_undo(UndoLog& out) {
+        out.undo.clear();
+        for (const Undo& u : undo)
+            if (u.at < 0 || (size_t)u.at < nodes0 * 2) out.undo.push_back(u);
+        out.nodes0 = nodes0;
+        out.leaves0 = leaves0;
+        commit();
+    }
+
+    // revert this undo: the shape as it was before the call that handed it out. No call is in progress, and every later call has been
+    // reverted already (newest first): the entries the call added are the pools' last
+    void revert(const UndoLog& u) {
+        for (size_t i = u.undo.size(); i-- > 0;) {
+            if (u.undo[i].at < 0) root = u.undo[i].ref;
+            else child[(size_t)u.undo[i].at] = u.undo[i].ref;
+        }
+        child.resize(u.nodes0 * 2);
+        node_ver.resize(u.nodes0);
+        leaf_key.resize(u.leaves0);
+        leaf_op.resize(u.leaves0);
+        begin();
+    }
+
     // a walk for a proof against the resident tree (no call in progress): the find depth, what the walk met (0 nothing, else a leaf
     // reference), and the sibling sources of depths 0 .. f - 1 in sib[]
     uint32_t find(uint64_t key, int32_t* met, uint32_t* sib) const {

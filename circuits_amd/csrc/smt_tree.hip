@@ -79,6 +79,28 @@ __global__ __launch_bounds__(256) void k_smt_writeback(const SmtCopy* __restrict
     store_fr(const_cast<uint8_t*>(bases[c.dst >> 29]) + (size_t)(c.dst & 0x1FFFFFFFu) * 32, smt_load(bases, c.src));
 }
 
+// the undo journal of an owner (smt_internal.h): a lane per 32-byte element, moved as 16-byte accesses, consecutive lanes on consecutive
+// journal addresses; the entry names the pool (SMT_NODE / SMT_LEAF / SMT_VALUE) and the element's index there
+template <class T>   // uint8_t to restore, const uint8_t to save
+__device__ __forceinline__ T* smt_journal_at(uint32_t e, T* node, T* leaf, T* value) {
+    const uint32_t kind = e >> 29;
+    T* pool = kind == SMT_NODE ? node : kind == SMT_LEAF ? leaf : value;
+    return pool + (size_t)(e & 0x1FFFFFFFu) * 32;
+}
+__global__ __launch_bounds__(256) void k_smt_journal_save(const uint32_t* __restrict__ index, const uint8_t* node, const uint8_t* leaf, const uint8_t* value,
+                                                          uint8_t* __restrict__ out, uint32_t n) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    store_fr(out + (size_t)t * 32, load_fr(smt_journal_at(index[t], node, leaf, value)));
+}
+// the write-back run the other way: every destination appears once in a record
+__global__ __launch_bounds__(256) void k_smt_journal_restore(const uint32_t* __restrict__ index, const uint8_t* __restrict__ saved, uint8_t* node, uint8_t* leaf,
+                                                             uint8_t* value, uint32_t n) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    store_fr(smt_journal_at(index[t], node, leaf, value), load_fr(saved + (size_t)t * 32));
+}
+
 }  // namespace hz
 
 using namespace hz;
@@ -88,7 +110,8 @@ struct hz_smt {
     SmtShape shape;
     DevBuf node, leaf, value, pos3;                      // resident pools, the quad form's constants
     DevBuf fields, lv, lh, ver, out, sib, ints;          // per call, grown on demand
-    PinnedBuf h_ints;
+    PinnedBuf h_ints, h_journal;                         // h_journal: the entries of a journalled call, made only for an owner that asks
+    size_t n_journal = 0;
     std::vector<SmtCopy> copies;
     Resident r;               // device, stream, device time of the last apply
     bool wb_queued = false;   // the call in progress has queued its write-back: the pools may have changed
@@ -267,7 +290,30 @@ hz_status hz::smt_apply_prepare(hz_smt* t, const char* who, hz_status depth_stat
     return HZ_OK;
 }
 
-hz_status hz::smt_apply_launch(hz_smt* t, uint32_t M, uint32_t n_sib, bool want_siblings) {
+// the resident entries the prepared call's write-back replaces, into the pinned entry list
+hz_status hz::smt_journal_entries(hz_smt* t, size_t* n_out) {
+    const SmtShape& sh = t->shape;
+    t->n_journal = 0;
+    size_t n = 0;
+    for (uint32_t x : sh.touched_nodes) n += x < sh.nodes0;
+    for (uint32_t l : sh.touched_leaves) n += l < sh.leaves0 ? 2 : 0;
+    *n_out = n;
+    if (n == 0) return HZ_OK;
+    HZ_HIP(t->h_journal.grow(n * 4));
+    uint32_t* h = (uint32_t*)t->h_journal.p;
+    size_t w = 0;
+    for (uint32_t x : sh.touched_nodes)
+        if (x < sh.nodes0) h[w++] = smt_src(SMT_NODE, x);
+    for (uint32_t l : sh.touched_leaves)
+        if (l < sh.leaves0) {
+            h[w++] = smt_src(SMT_LEAF, l);
+            h[w++] = smt_src(SMT_VALUE, l);
+        }
+    t->n_journal = n;
+    return HZ_OK;
+}
+
+hz_status hz::smt_apply_launch(hz_smt* t, uint32_t M, uint32_t n_sib, bool want_siblings, const SmtJournalDst* journal) {
     const SmtShape& sh = t->shape;
     const uint32_t* first = t->first;
     const size_t G = t->n_gather, W = t->n_wb;
@@ -287,6 +333,15 @@ hz_status hz::smt_apply_launch(hz_smt* t, uint32_t M, uint32_t n_sib, bool want_
     }
     hipLaunchKernelGGL(k_smt_gather, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, s, (const SmtCopy*)(db + t->o_gather), d_bases, (uint8_t*)t->out.p, (uint32_t)G);
     HZ_HIP(hipGetLastError());
+    if (journal && t->n_journal) {   // what the write-back is about to replace
+        const uint32_t n = (uint32_t)t->n_journal;
+        HZ_HIP(hipMemcpyAsync(journal->index, t->h_journal.p, (size_t)n * 4, hipMemcpyHostToDevice, s));
+        HZ_HIP(journal->span->begin(s));
+        hipLaunchKernelGGL(k_smt_journal_save, dim3((n + 255) / 256), dim3(256), 0, s, (const uint32_t*)journal->index, (const uint8_t*)t->node.p, (const uint8_t*)t->leaf.p,
+                           (const uint8_t*)t->value.p, journal->values, n);
+        HZ_HIP(hipGetLastError());
+        HZ_HIP(journal->span->end(s));
+    }
     t->wb_queued = true;
     hipLaunchKernelGGL(k_smt_writeback, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, s, (const SmtCopy*)(db + t->o_wb), d_bases, (uint32_t)W);
     HZ_HIP(hipGetLastError());
@@ -294,9 +349,23 @@ hz_status hz::smt_apply_launch(hz_smt* t, uint32_t M, uint32_t n_sib, bool want_
     return HZ_OK;
 }
 
-hz_status hz::smt_apply_finish(hz_smt* t) {
+hz_status hz::smt_apply_finish(hz_smt* t, SmtShape::UndoLog* undo) {
     if (hz_status e = t->r.finish()) return e;
-    t->shape.commit();
+    if (undo)
+        t->shape.commit_undo(*undo);
+    else
+        t->shape.commit();
+    return HZ_OK;
+}
+
+hz_status hz::smt_journal_restore(hz_smt* t, const uint8_t* values, const uint32_t* index, size_t n, const SmtShape::UndoLog& undo) {
+    HZ_HIP(hipSetDevice(t->r.device));
+    if (n) {
+        hipLaunchKernelGGL(k_smt_journal_restore, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, t->r.s, index, values, (uint8_t*)t->node.p, (uint8_t*)t->leaf.p,
+                           (uint8_t*)t->value.p, (uint32_t)n);
+        HZ_HIP(hipGetLastError());
+    }
+    t->shape.revert(undo);
     return HZ_OK;
 }
 

@@ -105,6 +105,26 @@ __global__ __launch_bounds__(256) void k_state_writeback(const uint32_t* __restr
     if (d == k) store_fr(value + (size_t)(keys[j] - first_idx) * 32, load_fr(uval + (size_t)j * 32));
 }
 
+// the undo journal of an owner (state_internal.h): a lane per 32-byte element, moved as 16-byte accesses, consecutive lanes on consecutive
+// journal addresses. The entry names the element: 1 << 29 | account in the state hashes, else the node's element in the level buffer
+#define HZ_STATE_JOURNAL_VALUE (1u << 29)
+static_assert(2ull << HZ_STATE_MAX_K <= 1ull << 29, "a level-buffer element, up to 2N - 2, and an account fit below the entry's kind bit");
+__global__ __launch_bounds__(256) void k_state_journal_save(const uint32_t* __restrict__ index, const uint8_t* levels, const uint8_t* value, uint8_t* __restrict__ out,
+                                                            uint32_t n) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const uint32_t e = index[t];
+    store_fr(out + (size_t)t * 32, load_fr((e >> 29 ? value : levels) + (size_t)(e & 0x1FFFFFFFu) * 32));
+}
+// the write-back run the other way: every destination appears once in a record
+__global__ __launch_bounds__(256) void k_state_journal_restore(const uint32_t* __restrict__ index, const uint8_t* __restrict__ saved, uint8_t* levels, uint8_t* value,
+                                                               uint32_t n) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const uint32_t e = index[t];
+    store_fr((e >> 29 ? value : levels) + (size_t)(e & 0x1FFFFFFFu) * 32, load_fr(saved + (size_t)t * 32));
+}
+
 // proofs: a pure gather. Thread (i, d): sibling d of key i; thread (i, k): its state hash
 __global__ __launch_bounds__(256) void k_state_proofs(const uint64_t* __restrict__ keys, const uint8_t* __restrict__ levels, const uint8_t* __restrict__ value,
                                                       uint8_t* __restrict__ sib_out, uint8_t* __restrict__ value_out, uint64_t first_idx, uint32_t k,
@@ -178,7 +198,8 @@ struct hz_state {
     bool loaded = false;
     DevBuf levels, value, pos3;                  // resident: (2N - 1) x 32, N x 32, the quad form's constants
     DevBuf fields, uval, oldval, ver, sib, ints;  // per call, grown on demand
-    PinnedBuf h_ints;
+    PinnedBuf h_ints, h_journal;   // h_journal: the entries of a journalled call, made only for an owner that asks
+    size_t n_journal = 0;
     NodeTable table;
     Resident r;   // device, stream, device time of the last load / apply
     uint8_t* level(uint32_t d) const { return (uint8_t*)levels.p + (((size_t)1 << d) - 1) * 32; }
@@ -313,7 +334,32 @@ hz_status hz::state_apply_prepare(hz_state* st, uint32_t M, const uint64_t* idx,
     return HZ_OK;
 }
 
-hz_status hz::state_apply_launch(hz_state* st, uint32_t M, uint32_t n_sib, bool clear_siblings) {
+// the resident elements the prepared call's write-back replaces, from the call's own `last` flags, into the pinned entry list
+hz_status hz::state_journal_entries(hz_state* st, uint32_t M, size_t* n_out) {
+    const uint32_t k = st->k;
+    const StateInts o(k, M);
+    const uint8_t* hb = (const uint8_t*)st->h_ints.p;
+    const uint64_t* h_keys = (const uint64_t*)hb;
+    const uint32_t* h_res = (const uint32_t*)(hb + o.res);
+    const uint8_t* h_last = hb + o.last;
+    st->n_journal = 0;
+    size_t n = 0;
+    for (size_t t = 0; t < (size_t)(k + 1) * M; t++) n += h_last[t] ? (t >= (size_t)k * M ? 2 : 1) : 0;
+    *n_out = n;
+    if (n == 0) return HZ_OK;
+    HZ_HIP(st->h_journal.grow(n * 4));
+    uint32_t* h = (uint32_t*)st->h_journal.p;
+    size_t w = 0;
+    for (uint32_t d = 0; d <= k; d++)
+        for (uint32_t j = 0; j < M; j++)
+            if (h_last[(size_t)d * M + j]) h[w++] = ((1u << d) - 1u) + (h_res[j] & ((1u << d) - 1u));
+    for (uint32_t j = 0; j < M; j++)
+        if (h_last[(size_t)k * M + j]) h[w++] = HZ_STATE_JOURNAL_VALUE | (uint32_t)(h_keys[j] - st->first_idx);
+    st->n_journal = n;
+    return HZ_OK;
+}
+
+hz_status hz::state_apply_launch(hz_state* st, uint32_t M, uint32_t n_sib, bool clear_siblings, const StateJournalDst* journal) {
     const uint32_t k = st->k;
     const StateInts o(k, M);
     uint8_t* db = (uint8_t*)st->ints.p;
@@ -338,6 +384,15 @@ hz_status hz::state_apply_launch(hz_state* st, uint32_t M, uint32_t n_sib, bool 
     }
     // the root before the first update is set aside before the write-back replaces it: old roots = (that, versions 0 .. m - 2 of the root)
     HZ_HIP(hipMemcpyAsync(st->ver.p, st->level(0), 32, hipMemcpyDeviceToDevice, s));
+    if (journal && st->n_journal) {   // what the write-back is about to replace
+        const uint32_t n = (uint32_t)st->n_journal;
+        HZ_HIP(hipMemcpyAsync(journal->index, st->h_journal.p, (size_t)n * 4, hipMemcpyHostToDevice, s));
+        HZ_HIP(journal->span->begin(s));
+        hipLaunchKernelGGL(k_state_journal_save, dim3((n + 255) / 256), dim3(256), 0, s, (const uint32_t*)journal->index, (const uint8_t*)st->levels.p,
+                           (const uint8_t*)st->value.p, journal->values, n);
+        HZ_HIP(hipGetLastError());
+        HZ_HIP(journal->span->end(s));
+    }
     const uint32_t wb = (k + 1) * M;
     hipLaunchKernelGGL(k_state_writeback, dim3((wb + 255) / 256), dim3(256), 0, s, d_res, d_keys, d_last, (const uint8_t*)ver, (const uint8_t*)st->uval.p,
                        (uint8_t*)st->levels.p, (uint8_t*)st->value.p, st->first_idx, k, M);
@@ -347,6 +402,15 @@ hz_status hz::state_apply_launch(hz_state* st, uint32_t M, uint32_t n_sib, bool 
 }
 
 hz_status hz::state_apply_finish(hz_state* st) { return st->r.finish(); }
+
+hz_status hz::state_journal_restore(hz_state* st, const uint8_t* values, const uint32_t* index, size_t n) {
+    HZ_HIP(hipSetDevice(st->r.device));
+    if (n == 0) return HZ_OK;
+    hipLaunchKernelGGL(k_state_journal_restore, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st->r.s, index, values, (uint8_t*)st->levels.p, (uint8_t*)st->value.p,
+                       (uint32_t)n);
+    HZ_HIP(hipGetLastError());
+    return HZ_OK;
+}
 
 hipStream_t hz::state_stream(const hz_state* st) { return st->r.s; }
 const uint8_t* hz::state_root_dev(const hz_state* st) { return st->level(0); }

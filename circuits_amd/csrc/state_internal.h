@@ -18,8 +18,21 @@ struct StateCallBufs {
 
 // idx[M] must lie inside the state and the state must be loaded (the callers check); 1 <= M <= 65536, k <= n_sib <= 64
 hz_status state_apply_prepare(hz_state* st, uint32_t M, const uint64_t* idx, uint32_t n_sib, StateCallBufs* out);
-hz_status state_apply_launch(hz_state* st, uint32_t M, uint32_t n_sib, bool clear_siblings);
+// Undo for an owner that journals its applies (ledger.hip). A prepared call tells how many resident elements its write-back
+// will replace -- the touched level nodes, then the touched state hashes, each once --; the owner gives room for them -- n 32-byte elements
+// and n uint32 entries (1 << 29 | account for a state hash, else the node's element in the level buffer) -- and the launch saves them there,
+// between the level kernels and the write-back, under `span`
+struct DevSpan;
+struct StateJournalDst {
+    uint8_t* values;
+    uint32_t* index;
+    DevSpan* span;
+};
+hz_status state_journal_entries(hz_state* st, uint32_t M, size_t* n);
+hz_status state_apply_launch(hz_state* st, uint32_t M, uint32_t n_sib, bool clear_siblings, const StateJournalDst* journal = nullptr);
 hz_status state_apply_finish(hz_state* st);   // synchronises and records the device time of the launch
+// the call that left (values, index) did not happen: the n saved elements back into levels and state hashes, on the state's stream, no synchronise
+hz_status state_journal_restore(hz_state* st, const uint8_t* values, const uint32_t* index, size_t n);
 hipStream_t state_stream(const hz_state* st);
 const uint8_t* state_root_dev(const hz_state* st);
 bool state_loaded(const hz_state* st);

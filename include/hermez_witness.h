@@ -736,12 +736,37 @@ hz_status hz_smt_plan(size_t m, const uint64_t* key, size_t n_sib, uint32_t* dep
  *                       signal kind_out (HZ_MI_KIND_*), source_out (HZ_MI_SRC_*), first_row_out and rows_out. HZ_ERR_ARG: an unknown
  *                       or repeated signal name, a missing one, a width or flat length that does not fit the shape, a range that is
  *                       not 32-byte aligned, overlaps another or ends beyond bytes
+ * ROLLBACK. `applied` -- a MARK -- is the number of successful apply calls since the ledger's last load: all seven forms
+ * count, hz_ledger_apply_l2 included; a refused call, hz_ledger_verify_*, _resolve_l2, _select_batch, _withdraw_rows, _main_inputs and
+ * _exit_keep do not; a load sets it to 0 and empties the journal. It counts whether or not a journal is on.
+ *   hz_ledger_journal   keeps an undo record of each of the last `depth` applies (0 .. HZ_LEDGER_JOURNAL_MAX; 0, the default of a new
+ *                       ledger, turns the journal off and frees its memory). Every call discards the records held. With the journal off
+ *                       an apply launches no kernel and allocates nothing for it. With it on, an apply saves the resident 32-byte elements its
+ *                       write-backs replace -- touched tree nodes and state hashes (pool entries of a growing ledger), the four plane
+ *                       elements of every touched account -- into a ring of depth + 1 device slabs of one capacity, grown by doubling
+ *                       when a record does not fit: an apply allocates only then
+ *   hz_ledger_applied   *mark = applied. HZ_ERR_ARG: a null argument
+ *   hz_ledger_rollback  makes the ledger what it was when hz_ledger_applied gave `mark`, byte for byte: the root, every plane element
+ *                       below the size, the size of a growing ledger, every resident entry of the state tree (levels and state hashes;
+ *                       shape and the node, leaf and value pools). The records are undone newest first on the ledger's stream, one
+ *                       synchronise at the end. Afterwards the batch's exit tree is empty, as after a load; every exit tree kept after
+ *                       `mark` was reached is dropped (a record notes the highest kept batch_num when its apply began: snapshots above it
+ *                       go, their bytes released as hz_ledger_exit_forget releases them; those kept before stay and answer
+ *                       hz_ledger_withdraw_rows as before); every *_dev output and the hz_ledger_main_inputs window are invalid;
+ *                       applied == mark and the records above mark are gone. mark == applied succeeds and changes and invalidates
+ *                       nothing. HZ_ERR_ARG, nothing changed: a null ledger, a ledger not loaded, mark > applied, mark < applied - records
+ *                       (the journal is off, or the ring has moved on); the message names both numbers. A HIP failure after the first
+ *                       restore was queued leaves the ledger answering HZ_ERR_HIP until it is loaded again
+ *   hz_ledger_journal_stats  the depth, the records held, the oldest mark hz_ledger_rollback accepts, the bytes the records fill and the
+ *                       bytes the slabs reserve; every output may be NULL
+ *   hz_ledger_journal_ms / _rollback_ms  device time of the save kernels in the last apply (0 with the journal off) / of the last rollback
  * OUT OF SCOPE: L1 transactions that create accounts or exit through a call other than hz_ledger_apply_batch_exits (creates:
  * hz_ledger_apply_batch_creates on a growing ledger), an L1 amount with
  * to_idx == 0 (no receiver), persisting, or carrying across a reload, the exit trees of earlier batches kept resident, a resident address index kept across
  * calls, batch (random linear combination) verification of signatures, more than one device per ledger, the packed inputs of
  * hz_ledger_apply_l2 (it has no chain id) or of more than one batch per hz_ledger_main_inputs call (K applies go into K consecutive
- * slots of one buffer, staged with hz_inputs_stage_range), writing straight into the witness layout. One thread at a time. */
+ * slots of one buffer, staged with hz_inputs_stage_range), writing straight into the witness layout; restoring the live exit tree of the batch rolled back to
+ * (keep it first), undo records that outlive the process or a reload. One thread at a time. */
 typedef struct hz_ledger hz_ledger;
 typedef struct {
     uint64_t from_idx, to_idx, amount_f /* float40 */, nonce;
@@ -939,6 +964,13 @@ enum {
 };
 hz_status hz_ledger_main_inputs(hz_ledger* l, const hz_ctx* ctx, uint64_t old_last_idx, void* d_packed, size_t bytes);
 double hz_ledger_main_inputs_ms(const hz_ledger* l);
+#define HZ_LEDGER_JOURNAL_MAX 64
+hz_status hz_ledger_journal(hz_ledger* l, uint32_t depth);
+hz_status hz_ledger_applied(const hz_ledger* l, uint64_t* mark);
+hz_status hz_ledger_rollback(hz_ledger* l, uint64_t mark);
+hz_status hz_ledger_journal_stats(const hz_ledger* l, uint32_t* depth, size_t* records, uint64_t* oldest_mark, size_t* bytes_used, size_t* bytes_reserved);
+double hz_ledger_journal_ms(const hz_ledger* l);  /* device time of the capture kernels in the last apply */
+double hz_ledger_rollback_ms(const hz_ledger* l); /* device time of the last rollback */
 hz_status hz_ledger_plan_main_inputs(size_t n_signals, const char* const* names, const uint64_t* offsets, const uint32_t* widths, const uint64_t* flat_lens,
                                      uint64_t bytes, uint32_t n_tx, uint32_t n_levels, uint32_t max_l1_tx, uint32_t max_fee_tx, uint32_t flags,
                                      uint32_t* kind_out /* [n_signals] */, uint32_t* source_out, uint64_t* first_row_out, uint64_t* rows_out);
